@@ -2,6 +2,7 @@
 """bench.py -- latents/s through the geodesic-codebook hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c3d32|c4|swiss|real|c5cb|c5prior|c2pam]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one child process per GPU
@@ -152,8 +153,53 @@ def hot_path_step(z, dec, cfg, timers, rank, world, group=None):
     if timers is not None:
         torch.cuda.synchronize(z.device)
         timers["assign_sweep"] = timers.get("assign_sweep", 0.0) + time.perf_counter() - t0
-    res["assign_batched"] = arg
+    res["assign_batched"], res["dmin_batched"] = arg, dmin
     return res, (float(ms[0]), int(launches[0]))
+
+
+def codebook_outputs(res):
+    """--dump-outputs of the codebook workloads: what one build hands its caller (build_codebook_device's arrays, the graph
+    it clustered, and the batched assignment stage's nearest medoid and geodesic distance per LCC node)."""
+    G = res["W_lcc"]
+    out = {"medoids": res["medoids"], "assign_flat": res["assign_flat"], "qe": np.float64(res["qe"]),
+           "z_medoid": res["z_medoid"], "mask_lcc": res["mask_lcc"], "edges_src": res["edges"][0], "edges_dst": res["edges"][1],
+           "edge_lengths": res["edge_lengths"], "W_lcc_indptr": G.indptr, "W_lcc_indices": G.indices,
+           "assign_batched": res["assign_batched"], "dmin_batched": res["dmin_batched"]}
+    if G.data is not None:
+        out["W_lcc_data"] = G.data
+    return out
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20       # under the 64 MB a dump may take, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Writes every array as out_dir/<name>.npy so that two builds of the project can be compared output for output:
+    float32 / float64 as computed, integers and flags as float64 (exact below 2^53).  When the arrays together exceed
+    `budget` bytes, every array above budget / 64 keeps the same fraction of its rows, drawn with a fixed seed (arrays of
+    one length keep the same rows), and the row numbers go beside it as <name>_rows.npy.  A directory this call creates
+    gets a .gitignore that ignores it."""
+    arrs = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > budget:
+        big = [name for name, a in arrs.items() if a.ndim and a.nbytes > budget // 64]
+        rest = total - sum(arrs[name].nbytes for name in big)
+        assert rest < budget, f"--dump-outputs: {rest} bytes of small arrays exceed the budget of {budget}"
+        frac = (budget - rest) / sum(arrs[name].nbytes + 8 * len(arrs[name]) for name in big)
+        for name in big:
+            a = arrs[name]
+            rows = np.sort(np.random.RandomState(0).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            arrs[name], arrs[name + "_rows"] = a[rows], rows.astype(np.float64)
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("*\n")
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"bench.py: wrote {len(arrs)} arrays ({sum(a.nbytes for a in arrs.values()) / 2**20:.1f} MiB) to {out_dir}")
 
 
 def cpu_baseline(res, z, dec, cfg, mode):
@@ -293,11 +339,11 @@ def prior_bench(args, rank, world, dev, json_fd):
             t = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt, float(last)
+        return dt, float(last), model.arena.detach()
 
     with contextlib.redirect_stdout(sys.stderr):
-        dt_native, loss_native = run(True)
-        dt_eager, loss_eager = run(False)
+        dt_native, loss_native, params_native = run(True)
+        dt_eager, loss_eager, _ = run(False)
     tok = B * (T - 1) * args.steps
     out = {"metric": "prior training tokens/sec (BASELINE config 5's second stage; secondary to the codebook metric)",
            "value": tok / dt_native, "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": max(args.warmup, 3),
@@ -311,6 +357,8 @@ def prior_bench(args, rank, world, dev, json_fd):
                            "tokens_per_s": tok / dt_eager, "last_loss": loss_eager},
            "speedup_over_eager": dt_eager / dt_native}
     if rank == 0:
+        if args.dump_outputs:               # the native (reported) path after its last step: parameters and that step's loss
+            dump_outputs(args.dump_outputs, {"arena": params_native, "loss": np.float64(loss_native)})
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
 
@@ -372,6 +420,9 @@ def pam_bench(args, dev, json_fd):
                         "kernel": "pam_swap_kernel", "launches_per_step": 1, "avg_launch_ms": avg_kernel,
                         "algorithmic_bytes_per_launch": bytes_per_pass},
            "best_swap": {"delta": delta, "medoid_position": i, "candidate": x, "total_cost": total}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"swap_delta": np.float64(delta), "swap_medoid_position": np.float64(i),
+                                         "swap_candidate": np.float64(x), "swap_total_cost": np.float64(total)})
     sys.stdout.flush()
     os.write(json_fd, (json.dumps(out) + "\n").encode())
 
@@ -391,7 +442,8 @@ def launch_ranks(args) -> int:
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--workload", args.workload, "--pipeline", str(args.pipeline)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + \
-          (["--replicas"] if args.replicas else [])
+          (["--replicas"] if args.replicas else []) + \
+          (["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     return subprocess.call(cmd, env=env)
 
@@ -409,7 +461,13 @@ def main():
                          "taken from the memory one warmed-up build reserved, at most 8 on one GPU and 4 per rank of a multi-GPU run)")
     ap.add_argument("--replicas", action="store_true", default=os.environ.get("GEO_BENCH_REPLICAS", "0") == "1",
                     help="N > 1: every GPU builds its own codebooks (weak scaling, no data-path collective) instead of sharding each build")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB: a seeded sample of the rows of large arrays, row numbers in <name>_rows.npy); "
+                         "inputs are seeded, so two builds of the project run with the same arguments can be compared array by array")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         n_dev = torch.cuda.device_count()                 # counting devices does not initialise the GPU
@@ -486,6 +544,7 @@ def main():
 
     from vqvae_amd.parallel import CollectiveOrder, OrderedGroup
     order = [None]                                   # sharded builds in flight: one ticket order per timed region
+    last = [None]                                    # result of the timed region's last step
 
     def one_step(i, slot):
         grp = solo
@@ -501,6 +560,8 @@ def main():
             if order[0] is not None:
                 order[0].finish(i)
         ok = bool((r["assign_batched"].cpu().numpy() == r["assign_flat"][r["mask_lcc"]]).all())   # (syncs this stream only)
+        if i == args.steps - 1:
+            last[0] = r                              # (only the last step's result outlives its step: --dump-outputs)
         return i, float(r["qe"]), pr, ok
 
     def timed_region(d):
@@ -508,6 +569,7 @@ def main():
         barrier()
         torch.cuda.synchronize(dev)
         order[0] = CollectiveOrder(args.steps, d) if (shard_world > 1 and d > 1) else None
+        last[0] = None
         t0 = time.perf_counter()
         if d > 1:
             done = run_pipelined(one_step, args.steps, d, dev, streams)
@@ -526,7 +588,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         region_prof[:] = [pr for _, _, pr, _ in done]            # per-build HIP-event sweep time measured INSIDE the timed region
-        return el, [ok for _, _, _, ok in done]
+        return el, [ok for _, _, _, ok in done], last[0]
 
     fallback_note = None
     region_prof = []
@@ -566,10 +628,10 @@ def main():
             # order is by construction, but this repository's own runs never had more than one GPU: a region with one build
             # after the other is timed first, the pipelined region runs under a watchdog, and the line reports the faster of
             # the two -- or the plain one, if the pipelined region does not come back.
-            elapsed_plain, same_plain = timed_region(1)
+            elapsed_plain, same_plain, last_plain = timed_region(1)
             prof_plain = list(region_prof)
         else:
-            elapsed, all_same = timed_region(depth)
+            elapsed, all_same, last_res = timed_region(depth)
         # one more build, alone and instrumented (NOT part of a timed region): stage times and single-build latency
         if depth > 1:                                             # this stream's workspace has not been used yet: warm it
             hot_path_step(z, dec, cfg, None, rank if not replicas else 0, shard_world, solo)
@@ -604,7 +666,7 @@ def main():
             th.start()
             th.join(limit)
             if "out" in box and box["out"][0] < elapsed_plain:
-                elapsed, all_same = box["out"]
+                elapsed, all_same, last_res = box["out"]
             else:
                 if "out" in box:
                     fallback_note = f"{depth} builds in flight were not faster ({box['out'][0] / args.steps * 1e3:.1f} ms per build)"
@@ -613,7 +675,7 @@ def main():
                 else:
                     fallback_note = f"the region with {depth} builds in flight did not come back within {limit:.0f} s"
                 log("bench.py: " + fallback_note + "; reporting the region with one build after the other")
-                elapsed, all_same, depth = elapsed_plain, same_plain, 1
+                elapsed, all_same, last_res, depth = elapsed_plain, same_plain, last_plain, 1
                 region_prof[:] = prof_plain
             hung = th.is_alive()
         else:
@@ -755,6 +817,8 @@ def main():
                 mode = "full" if os.environ.get("GEO_BENCH_CPU_FULL", "0") == "1" else "bounded"
             with contextlib.redirect_stdout(sys.stderr):
                 out["cpu_baseline"] = cpu_baseline(res, z, dec, cfg, mode)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, codebook_outputs(last_res))
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if hung:                                        # host threads parked inside the region that never came back: leave without joining

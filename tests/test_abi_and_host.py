@@ -251,3 +251,35 @@ def test_sssp_plan_keeps_32bit_row_offsets_below_2_pow_25_nodes():
     assert plan(40_000_000, 1024) == 64
     assert plan(1 << 25, 8) == 16                                # few sources: the 16-source NODE kernel (size_t indices)
     assert plan(2048, 64) == 64 and plan(0, 4) < 0
+
+
+def test_bench_dump_outputs_stays_in_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 files only, small arrays whole, large ones cut to one seeded set of rows per
+    length (the same on every call) so that the dump stays within its byte budget."""
+    # importing bench.py sets OMP_NUM_THREADS; pinned here for this test only, processes that later tests spawn must keep
+    # this process's thread count (test_distributed_cpu compares their float32 results bit for bit with the parent's)
+    monkeypatch.setenv("OMP_NUM_THREADS", os.environ.get("OMP_NUM_THREADS", str(torch.get_num_threads())))
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    r = np.random.RandomState(1)
+    arrays = {"lengths": torch.from_numpy(r.rand(50000).astype(np.float32)), "src": r.randint(0, 9000, 50000).astype(np.int32),
+              "codes": r.randint(0, 64, 300).astype(np.int64), "qe": np.float64(1.5), "mask": np.ones(300, bool)}
+    budget = 200_000
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        bench.dump_outputs(str(d), arrays, budget=budget)
+    names = sorted(f for f in os.listdir(dirs[0]) if f.endswith(".npy"))
+    assert names == ["codes.npy", "lengths.npy", "lengths_rows.npy", "mask.npy", "qe.npy", "src.npy", "src_rows.npy"]
+    got = {f[:-4]: np.load(dirs[0] / f) for f in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= budget
+    assert got["lengths"].dtype == np.float32 and got["codes"].dtype == np.float64 and got["qe"].shape == () and float(got["qe"]) == 1.5
+    np.testing.assert_array_equal(got["codes"], arrays["codes"])                     # small: whole
+    rows = got["lengths_rows"].astype(np.int64)
+    assert 0 < len(rows) < 50000 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(got["src_rows"], got["lengths_rows"])              # one length, one sample
+    np.testing.assert_array_equal(got["lengths"], arrays["lengths"].numpy()[rows])
+    np.testing.assert_array_equal(got["src"], arrays["src"][rows])
+    for f in names:                                                                    # the same rows on every call
+        np.testing.assert_array_equal(np.load(dirs[1] / f), got[f[:-4]])
+    assert (dirs[0] / ".gitignore").read_text() == "*\n"

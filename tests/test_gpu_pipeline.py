@@ -75,15 +75,18 @@ def test_pipeline_with_disconnected_graph_vs_oracle(tmp_path):
     np.testing.assert_array_equal(res["z_medoid"].numpy(), ref["z_medoid"])
 
 
-def test_bench_prints_one_contract_line():
+def test_bench_prints_one_contract_line(tmp_path):
     """bench.py on the small c1 workload (the reference's CPU-runnable configuration), CPU baseline included: ONE JSON
-    line on stdout with the driver's fields, the roofline object of the sweep kernel and the cpu_baseline object."""
+    line on stdout with the driver's fields, the roofline object of the sweep kernel and the cpu_baseline object; with
+    --dump-outputs, the last timed build's arrays as float .npy files that agree with the line."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, GEO_BENCH_CPU_SAMPLE="1")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c1", "--steps", "2", "--warmup", "1"],
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(dump)],
                          capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -102,6 +105,13 @@ def test_bench_prints_one_contract_line():
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
     assert d["parity_selfcheck"]["batched_assign_equals_fused"] is True
+    got = {f[:-4]: np.load(dump / f) for f in os.listdir(dump) if f.endswith(".npy")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(dump / f) for f in os.listdir(dump)) <= 64 * 10 ** 6
+    assert float(got["qe"]) == d["parity_selfcheck"]["qe"] and got["medoids"].shape == (64,)
+    assert len(got["edge_lengths"]) == d["config"]["graph"]["edges_reweighted"] and got["edge_lengths"].dtype == np.float32
+    np.testing.assert_array_equal(got["assign_batched"], got["assign_flat"][got["mask_lcc"] > 0])
+    assert np.all(np.isfinite(got["dmin_batched"])) and got["dmin_batched"][got["medoids"].astype(np.int64)].max() == 0
 
 
 def test_bench_two_ranks_with_sharded_builds_in_flight():
