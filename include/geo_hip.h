@@ -179,6 +179,24 @@ int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neighbors, int3
                  int64_t row0, int64_t row1, int32_t *idx_out, double *d2_out,
                  void *ws, size_t ws_bytes, void *stream);
 
+/* The path the calling thread's last geo_knn_topk call took (host state only, no GPU call; 0 before any call, after an
+ * empty row range or an argument error):
+ *   GEO_KNN_PATH_EXACT        the exact fp64 scan of every pair (n_neighbors <= 64);
+ *   GEO_KNN_PATH_EXACT_WIDE   the exact scan with lists of two or four entries per lane (n_neighbors > 64);
+ *   GEO_KNN_PATH_FILTER_BF16  thresholds from a strided corpus subset (exact), bf16 hi/lo matrix-core scan, fp64 refinement;
+ *   GEO_KNN_PATH_FILTER_F32   the same with the float32 matrix-core scan (option knn_filter = 2);
+ *   GEO_KNN_PATH_TWO_LEVEL    the bf16 filter whose thresholds come from a filtered pass over that subset themselves
+ *                             (n >= 200 000);
+ *   | GEO_KNN_PATH_OVERFLOW   added to a filter path when some query kept more candidates than its list holds and the
+ *                             whole call was answered by the exact scan instead. */
+#define GEO_KNN_PATH_EXACT 1
+#define GEO_KNN_PATH_EXACT_WIDE 2
+#define GEO_KNN_PATH_FILTER_BF16 3
+#define GEO_KNN_PATH_FILTER_F32 4
+#define GEO_KNN_PATH_TWO_LEVEL 5
+#define GEO_KNN_PATH_OVERFLOW 16
+int geo_knn_last_path(void);
+
 /* ------------------------------------------------------------------------------------------
  * Symmetrisation.  Replaces csr_matrix(...) + W.maximum/minimum(W.T) + setdiag(0) +
  * eliminate_zeros() of src/geo/knn_graph_optimized.py:54-66.

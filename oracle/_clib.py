@@ -26,6 +26,8 @@ def lib() -> ctypes.CDLL:
         L.oracle_knn.restype = ctypes.c_int
         L.oracle_knn.argtypes = [P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                  ctypes.c_int64, ctypes.c_int64, P, P]
+        L.oracle_knn_pair_keys.restype = ctypes.c_int
+        L.oracle_knn_pair_keys.argtypes = [P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, P, P, ctypes.c_int64, P]
         L.oracle_cc.restype = ctypes.c_int32
         L.oracle_cc.argtypes = [ctypes.c_int32, P, P, P, P, P]
         _lib = L

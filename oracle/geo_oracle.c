@@ -17,7 +17,8 @@
  *                 distances.  form=1 is the brute-force expansion |x|^2 - 2 x.y + |y|^2 clamped
  *                 at 0 (sklearn _argkmin.pyx.tp:492-502, chosen by "auto" for d > 15), form=0 the
  *                 direct sum of squared differences (kd-tree rdist, chosen for d <= 15).
- *                 Ties are ordered (distance, index).
+ *                 Ties are ordered (distance, index).  oracle_knn_pair_keys gives the same key for
+ *                 arbitrary (query, corpus) pairs (oracle/knn.py check_knn_lists).
  *   oracle_cc     scipy.sparse.csgraph.connected_components(directed=False) as called from
  *                 src/geo/knn_graph_optimized.py:175,187: labels numbered in order of the lowest
  *                 node index of each component.
@@ -144,42 +145,63 @@ static void topk_insert(double *bd, int64_t *bi, int32_t kq, int32_t *cnt, doubl
     *cnt = c + 1;
 }
 
+/* fp64 squared norm: fma chain over the dimensions in ascending order */
+static double knn_sqnorm(const float *x, int32_t d) {
+    double s = 0.0;
+    for (int32_t c = 0; c < d; ++c) { double v = x[c]; s = fma(v, v, s); }
+    return s;
+}
+
+/* The ranking key of the pair (x, y).  form=1: (|x|^2 + (-2 x.y)) + |y|^2 clamped at 0, with nx / ny from
+ * knn_sqnorm; form=0: fma chain of the squared differences (nx / ny unused). */
+static double knn_key(const float *xi, const float *yj, int32_t d, int32_t form, double nx, double ny) {
+    double d2;
+    if (form) {
+        double dot = 0.0;
+        for (int32_t c = 0; c < d; ++c) dot = fma((double)xi[c], (double)yj[c], dot);
+        d2 = (nx + (-2.0 * dot)) + ny;
+        if (!(d2 > 0.0)) d2 = 0.0;
+    } else {
+        d2 = 0.0;
+        for (int32_t c = 0; c < d; ++c) {
+            double t = (double)xi[c] - (double)yj[c];
+            d2 = fma(t, t, d2);
+        }
+    }
+    return d2;
+}
+
 /* z: [N][d] f32 (queries = corpus).  rows [row0,row1) are computed.  idx_out / d2_out: [row1-row0][kq] */
 int oracle_knn(const float *z, int64_t N, int32_t d, int32_t kq, int32_t form,
                int64_t row0, int64_t row1, int64_t *idx_out, double *d2_out) {
     double *nrm = (double *)malloc((size_t)(N > 0 ? N : 1) * sizeof(double));
     if (!nrm) return -1;
-    for (int64_t i = 0; i < N; ++i) {
-        double s = 0.0;
-        for (int32_t c = 0; c < d; ++c) { double x = z[i * d + c]; s = fma(x, x, s); }
-        nrm[i] = s;
-    }
+    for (int64_t i = 0; i < N; ++i) nrm[i] = knn_sqnorm(z + i * d, d);
 #pragma omp parallel for schedule(dynamic, 16)
     for (int64_t i = row0; i < row1; ++i) {
         double *bd = d2_out + (size_t)(i - row0) * kq;
         int64_t *bi = idx_out + (size_t)(i - row0) * kq;
         int32_t cnt = 0;
         const float *xi = z + i * d;
-        for (int64_t j = 0; j < N; ++j) {
-            const float *yj = z + j * d;
-            double d2;
-            if (form) {
-                double dot = 0.0;
-                for (int32_t c = 0; c < d; ++c) dot = fma((double)xi[c], (double)yj[c], dot);
-                d2 = (nrm[i] + (-2.0 * dot)) + nrm[j];
-                if (!(d2 > 0.0)) d2 = 0.0;
-            } else {
-                d2 = 0.0;
-                for (int32_t c = 0; c < d; ++c) {
-                    double t = (double)xi[c] - (double)yj[c];
-                    d2 = fma(t, t, d2);
-                }
-            }
-            topk_insert(bd, bi, kq, &cnt, d2, j);
-        }
+        for (int64_t j = 0; j < N; ++j)
+            topk_insert(bd, bi, kq, &cnt, knn_key(xi, z + j * d, d, form, nrm[i], nrm[j]), j);
     }
     free(nrm);
     return 0;
+}
+
+/* The key oracle_knn ranks the pair (qi[p], qj[p]) by, for p < m: out[p] (fp64).  Returns -2 on an index outside [0, N). */
+int oracle_knn_pair_keys(const float *z, int64_t N, int32_t d, int32_t form, const int64_t *qi, const int64_t *qj,
+                         int64_t m, double *out) {
+    int bad = 0;
+#pragma omp parallel for schedule(static) reduction(|:bad)
+    for (int64_t p = 0; p < m; ++p) {
+        const int64_t i = qi[p], j = qj[p];
+        if (i < 0 || i >= N || j < 0 || j >= N) { bad = 1; out[p] = NAN; continue; }
+        const float *xi = z + i * d, *yj = z + j * d;
+        out[p] = form ? knn_key(xi, yj, d, form, knn_sqnorm(xi, d), knn_sqnorm(yj, d)) : knn_key(xi, yj, d, form, 0.0, 0.0);
+    }
+    return bad ? -2 : 0;
 }
 
 /* ------------------------------------------------------------------ connected components */

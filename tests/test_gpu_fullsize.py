@@ -73,10 +73,17 @@ def _columns_strictly_ascending(W):
     return bool((d[inside] > 0).all())
 
 
-def _knn_rows_vs_oracle(ctx, n, d, spans):
+def _knn_rows_vs_oracle(ctx, n, d, spans, path, name):
+    """Sampled rows against the oracle's own scan, every row against the exact checker, and the path the search took
+    (geo_knn_last_path: 3 = one-level bf16 filter, 5 = two levels)."""
     from oracle import _clib
+    from oracle.knn import check_knn_lists
+    from vqvae_amd import _lib
     from vqvae_amd.geo.knn_graph_optimized import knn_search_device
     idx, d2 = knn_search_device(ctx["z"], KNN + 1)
+    assert _lib.load().geo_knn_last_path() == path
+    st = check_knn_lists(ctx["z_h"], idx, d2, KNN + 1, 1, device="cuda")
+    _record(f"{name}_knn_checker", st)
     idx_h, d2_h = idx.cpu().numpy(), d2.cpu().numpy()
     for r0, r1 in spans:
         io = np.empty((r1 - r0, KNN + 1), np.int64)
@@ -156,7 +163,7 @@ def _full_chain_vs_oracle(ctx, K):
 # ------------------------------------------------------------------------------------------------- C2
 def test_c2_knn_rows_vs_oracle_and_graph_invariants(c2, golden):
     from oracle import synthetic as syn
-    _knn_rows_vs_oracle(c2, N, D, ((0, 64), (29968, 30032), (N - 64, N)))
+    _knn_rows_vs_oracle(c2, N, D, ((0, 64), (29968, 30032), (N - 64, N)), 3, "c2")
     W = _graph_invariants(c2, N)
     g = golden("c2_formula")                                     # the reference's (sklearn) structure at C2
     assert W.nnz == int(g["meta"][5])
@@ -441,7 +448,7 @@ def c3():
 
 def test_c3_d64_knn_jvp_chain_vs_oracle(c3):
     n = 50000
-    _knn_rows_vs_oracle(c3, n, 64, ((0, 48), (25000, 25048), (n - 48, n)))
+    _knn_rows_vs_oracle(c3, n, 64, ((0, 48), (25000, 25048), (n - 48, n)), 3, "c3")
     _graph_invariants(c3, n)
     _all_chunks_vs_fp64(c3, "c3")
     _full_chain_vs_oracle(c3, KMED)
@@ -476,13 +483,22 @@ def test_c2_one_solve_assignment_equals_k_source_argmin_with_float32_ties(c2):
 def test_real_shape_960k_one_solve_assignment_equals_k_source_argmin():
     """The same at the pipeline's real node count (SURVEY finding 7: 960 000 nodes of d=16, distance-weighted k=20 union
     graph): about one float32 collision per call is expected here, so the suspect resolution runs on real data."""
+    from vqvae_amd import _lib
     from vqvae_amd._device import device, release_workspace
-    from vqvae_amd.geo.knn_graph_optimized import knn_graph_device
+    from vqvae_amd.geo.knn_graph_optimized import knn_graph_device, knn_search_device
     from oracle import synthetic as syn
+    from oracle.knn import check_knn_lists
     dev = device()
-    z = torch.from_numpy(syn.gauss_latents(960_000, D, 3)).to(dev)
+    z_h = syn.gauss_latents(960_000, D, 3)
+    z = torch.from_numpy(z_h).to(dev)
     out = knn_graph_device(z, KNN, mode="distance", sym="union")
+    assert _lib.load().geo_knn_last_path() == 5                  # two-level filter
     G = out[0] if isinstance(out, tuple) else out
+    # the graph's lists: every row exact (the same search again, with its fp64 keys and the self column)
+    idx, d2 = knn_search_device(z, KNN + 1)
+    assert torch.equal(out[2].to(idx.dtype), idx[:, 1:])
+    _record("real_knn_checker", check_knn_lists(z_h, idx, d2, KNN + 1, 1, device="cuda"))
+    del idx, d2
     log = _nearest_equals_k_source(G, KMED, range(4), dev)
     _record("real_one_solve_assignment_float32_ties", {"n": int(G.n), "nnz": int(G.nnz), "K512": log})
     assert not any(i["declined"] for i in log)
@@ -503,7 +519,7 @@ def test_c4_one_gpu_1m_latents_k1024():
     n, K = 1_000_000, 1024
     ctx = _pipeline(n, D, 1, 28, K)
     res = ctx["res"]
-    _knn_rows_vs_oracle(ctx, n, D, ((0, 32), (n - 32, n)))
+    _knn_rows_vs_oracle(ctx, n, D, ((0, 32), (n - 32, n)), 5, "c4")
     W = res["W_lcc"].to_scipy()
     assert W.shape == (n, n) and _columns_strictly_ascending(W) and np.diff(W.indptr).min() >= KNN
     assert res["n_edges"] * 2 == W.nnz

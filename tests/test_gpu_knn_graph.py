@@ -132,6 +132,19 @@ def test_lists_longer_than_one_wave_vs_oracle():
         build_knn_graph(latents(400, 8, 1), k=MAX_NEIGHBORS)
 
 
+EXACT, BF16, F32, TWO, OVERFLOW = 1, 3, 4, 5, 16       # geo_knn_last_path() (GEO_KNN_PATH_* of include/geo_hip.h)
+
+
+def _path_and_every_row(z, idx, d2, kq, path, row0=0):
+    """The path the last search took (one code or a tuple of acceptable ones), and every row of its answer against the
+    exact checker (oracle/knn.py)."""
+    from oracle.knn import check_knn_lists
+    from vqvae_amd import _lib
+    got = _lib.load().geo_knn_last_path()
+    assert got in (path if isinstance(path, tuple) else (path,)), f"geo_knn_last_path() = {got}, expected {path}"
+    check_knn_lists(z, idx, d2, kq, 1 if z.shape[1] > 15 else 0, row0=row0, device="cuda")
+
+
 def _oracle_rows(z, n_neighbors, form, r0, r1):
     import ctypes
     from oracle import _clib
@@ -144,18 +157,20 @@ def _oracle_rows(z, n_neighbors, form, r0, r1):
 
 @pytest.mark.parametrize("d,filt", [(16, "1"), (8, "1"), (24, "1"), (64, "1"), (16, "0")])
 def test_large_corpus_filter_path_vs_oracle(d, filt):
-    """Above 40 000 rows the search runs behind the float32 matrix-core filter (subset thresholds, MFMA scan, exact
+    """Above 40 000 rows (80 000 at d <= 8) the search runs behind the matrix-core filter (subset thresholds, MFMA scan, exact
     fp64 refinement of the kept candidates); lists and fp64 keys must equal the oracle's, as without the filter --
-    expansion form (d > 15), direct form (d <= 15) and a padded dimension (24 -> 32)."""
+    expansion form (d > 15), direct form (d = 8: dp = 8, bf16 parts padded to 16 columns) and a padded dimension (24 -> 32);
+    knn_filter = 0 switches the filter off."""
     import torch
     from vqvae_amd._device import device
     from vqvae_amd.geo.knn_graph_optimized import knn_search_device
     from vqvae_amd import _lib
-    n, kq = 45000, 21
+    n, kq = (80000 if d <= 8 else 45000), 21
     z = latents(n, d, 21)
     _lib.check(_lib.load().geo_set_option(b"knn_filter", int(filt)), "geo_set_option")
     try:
         idx, d2 = knn_search_device(torch.from_numpy(z).to(device()), kq)
+        _path_and_every_row(z, idx, d2, kq, BF16 if filt == "1" else EXACT)
     finally:
         _lib.load().geo_set_option(b"knn_filter", 1)
     idx, d2 = idx.cpu().numpy(), d2.cpu().numpy()
@@ -176,6 +191,7 @@ def test_filter_path_at_tile_boundaries_vs_oracle(n):
     kq = 21
     z = latents(n, 16, 31)
     idx, d2 = knn_search_device(torch.from_numpy(z).to(device()), kq)
+    _path_and_every_row(z, idx, d2, kq, BF16)
     idx, d2 = idx.cpu().numpy(), d2.cpu().numpy()
     for r0, r1 in ((0, 32), (n - 300, n - 268), (n - 32, n)):
         io, do = _oracle_rows(z, kq, 1, r0, r1)
@@ -188,17 +204,22 @@ def test_filter_path_at_tile_boundaries_vs_oracle(n):
 def test_filter_margins_hold_far_from_the_origin(filt):
     """Latents shifted by +40 in every coordinate: norms (25 600) dwarf the neighbour distances (~10), so the filter's
     rounding margin -- relative to |x|^2 + |y|^2, wider for the bf16 scan (1) than for the float32 one (2) -- decides
-    what is kept; the lists must still be the exact ones, and a coordinate scale of 1e3 must not change that either."""
+    what is kept; the lists must still be the exact ones, and a coordinate scale of 1e3 must not change that either.
+    At +40 (and at scale 1e-3 around +0.05) the bf16 margin keeps ~1 700 (~3 400) candidates per query on average, past the
+    list cap of 1 024: the call ends on the exact scan (path flag 16); +10 keeps the bf16 filter itself under that margin."""
     import torch
     from vqvae_amd._device import device
     from vqvae_amd.geo.knn_graph_optimized import knn_search_device
     from vqvae_amd import _lib
     n, kq = 42000, 21
-    for scale, shift in ((1.0, 40.0), (1000.0, 0.0), (1e-3, 0.05)):
+    p = BF16 if filt == 1 else F32
+    paths = {(1.0, 40.0): (p, p | OVERFLOW), (1000.0, 0.0): p, (1e-3, 0.05): (p, p | OVERFLOW), (1.0, 10.0): p}
+    for (scale, shift), path in paths.items():
         z = (latents(n, 16, 5) * np.float32(scale) + np.float32(shift)).astype(np.float32)
         _lib.check(_lib.load().geo_set_option(b"knn_filter", int(filt)), "geo_set_option")
         try:
             idx, d2 = knn_search_device(torch.from_numpy(z).to(device()), kq)
+            _path_and_every_row(z, idx, d2, kq, path)
         finally:
             _lib.load().geo_set_option(b"knn_filter", 1)
         idx, d2 = idx.cpu().numpy(), d2.cpu().numpy()
@@ -216,8 +237,10 @@ def test_large_corpus_row_ranges_equal_the_full_search():
     n, kq = 45000, 21
     z = torch.from_numpy(latents(n, 16, 23)).to(device())
     idx, d2 = knn_search_device(z, kq)
+    _path_and_every_row(z, idx, d2, kq, BF16)
     for r0, r1 in ((0, 11250), (11250, 30001), (30001, n)):
         i_s, d_s = knn_search_device(z, kq, r0, r1)
+        _path_and_every_row(z, i_s, d_s, kq, BF16, row0=r0)
         assert torch.equal(i_s, idx[r0:r1]) and torch.equal(d_s, d2[r0:r1])
 
 
@@ -231,6 +254,7 @@ def test_large_corpus_with_masses_of_duplicates_falls_back():
     z = latents(n, d, 22)
     z[5000:8000] = z[5000]
     idx, d2 = knn_search_device(torch.from_numpy(z).to(device()), kq)
+    _path_and_every_row(z, idx, d2, kq, BF16 | OVERFLOW)
     idx, d2 = idx.cpu().numpy(), d2.cpu().numpy()
     for r0, r1 in ((0, 32), (5000, 5032), (7968, 8000)):
         io, do = _oracle_rows(z, kq, 1, r0, r1)
@@ -254,6 +278,7 @@ def test_filter_path_with_ties_at_the_kq_th_distance(copies):
         rows = 1000 + 2000 * g + 7 * np.arange(copies)
         z[rows] = z[rows[0]]
     idx, d2 = knn_search_device(torch.from_numpy(z).to(device()), kq)
+    _path_and_every_row(z, idx, d2, kq, BF16)
     idx, d2 = idx.cpu().numpy(), d2.cpu().numpy()
     for r0, r1 in ((990, 1022), (1000 + 7 * (copies - 1) - 8, 1000 + 7 * (copies - 1) + 8), (39000, 39032), (n - 32, n)):
         io, do = _oracle_rows(z, kq, 1, r0, r1)
@@ -406,18 +431,21 @@ def test_two_level_thresholds_from_200k_rows_vs_oracle_and_one_level(d, shift):
     """From 200 000 rows on the filter's thresholds come from a filtered pass themselves (every 256th row exact, then the
     matrix-core scan + fp64 refinement over the every-16th-row subset): the lists and fp64 keys must equal the oracle's on
     sampled rows and, everywhere, those of the one-level scheme (float32 scan, `knn_filter = 2`) -- also far from the
-    origin, where the margins are wide and the lists long."""
+    origin, where the margins are wide and the lists long (there the candidate lists may pass their cap at either level, and
+    the call end on the exact scan: path flag 16)."""
     import torch
     from vqvae_amd._device import device
     from vqvae_amd.geo.knn_graph_optimized import knn_search_device
     from vqvae_amd import _lib
     n, kq = 210000, 21
     z = (latents(n, d, 33) + np.float32(shift)).astype(np.float32)
+    paths = {1: (TWO,), 2: (F32,)} if shift == 0.0 else {1: (TWO, TWO | OVERFLOW, BF16 | OVERFLOW), 2: (F32, F32 | OVERFLOW)}
     out = {}
     try:
         for filt in (1, 2):
             _lib.check(_lib.load().geo_set_option(b"knn_filter", filt), "geo_set_option")
             idx, d2 = knn_search_device(torch.from_numpy(z).to(device()), kq)
+            _path_and_every_row(z, idx, d2, kq, paths[filt])
             out[filt] = (idx.cpu().numpy(), d2.cpu().numpy())
     finally:
         _lib.load().geo_set_option(b"knn_filter", 1)
@@ -425,6 +453,7 @@ def test_two_level_thresholds_from_200k_rows_vs_oracle_and_one_level(d, shift):
     np.testing.assert_array_equal(out[1][1], out[2][1])
     # a rank's share of the query rows (sharded kNN): the same rows of the full answer
     ia, da = knn_search_device(torch.from_numpy(z).to(device()), kq, 70001, 140777)
+    _path_and_every_row(z, ia, da, kq, paths[1], row0=70001)
     np.testing.assert_array_equal(ia.cpu().numpy(), out[1][0][70001:140777])
     np.testing.assert_array_equal(da.cpu().numpy(), out[1][1][70001:140777])
     for r0, r1 in ((0, 24), (104000, 104024), (n - 24, n)):

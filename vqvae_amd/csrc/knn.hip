@@ -157,15 +157,19 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ zp32
 }
 
 // ---- exact search behind a float32 matrix-core filter (large corpora) -----------------------------------------------
-// 1. tau[i] = the kq-th smallest exact distance from query i to every FILTER_STRIDE-th corpus row: an upper bound of
-//    the kq-th smallest over the whole corpus (knn_kernel on the subset).
+// 1. tau[i] = the kq-th smallest exact distance from query i to every S-th corpus row: an upper bound of the kq-th
+//    smallest over the whole corpus (knn_kernel on the subset).  S = filter_stride(kq) (FILTER_STRIDE for short lists).
 // 2. knn_scan_kernel: approximate squared distances of ALL pairs on the matrix cores (v_mfma_f32_32x32x2_f32, expansion
 //    form with the fp64 norms); pair (i, j) is kept when  approx <= tau[i] + eps * (|x_i|^2 + |x_j|^2),  eps far above
-//    the rounding of a d-term float32 dot product -- every true neighbour is kept, plus ~FILTER_STRIDE * kq others.
+//    the rounding of a d-term float32 dot product -- every true neighbour is kept, plus ~S * kq others.
 // 3. knn_refine_kernel: the kept candidates are re-evaluated with the same fp64 fma chains as knn_kernel and ranked
 //    by (distance, index): the result is the one knn_kernel gives.  A query whose list overflows FILTER_CAP (heavily
 //    duplicated points) is reported and the caller falls back to knn_kernel.
-constexpr int FILTER_STRIDE = 16, FILTER_CAP = 1024;
+constexpr int FILTER_STRIDE = 16, FILTER_STRIDE_MIN = 4, FILTER_CAP = 1024;
+// A query keeps ~S * kq candidates on average (about S kq corpus rows lie at or below the kq-th distance to every S-th row),
+// with a tail of a few hundred more: at S = 16 and kq = 64 the mean was the cap itself, half the queries overflowed and the
+// whole call fell back to the exact scan.  Denser subsets for longer lists keep S * kq <= 384 (kq <= 64 here).
+constexpr int filter_stride(int kq) { return kq <= 24 ? FILTER_STRIDE : kq <= 40 ? 8 : FILTER_STRIDE_MIN; }
 constexpr int64_t TWO_LEVEL_MIN = 200000;      // from here on the thresholds themselves come from a filtered pass (below)
 typedef float f32x16v __attribute__((ext_vector_type(16)));
 
@@ -779,6 +783,9 @@ int launch_knn_wide(bool expansion, const float *zp32, const double *zq64, const
     return launch_knn<DCH, 4, 4>(expansion, zp32, zq64, nrm, nrm, n, nch, kq, row0, row1, idx_out, d2_out, s);
 }
 
+// the path the calling thread's last geo_knn_topk took (GEO_KNN_PATH_* of include/geo_hip.h), for tests and profiles
+thread_local int32_t g_last_path = 0;
+
 bool filter_applies(int64_t n, int dp) {
     if (geo::options().knn_filter == 0) return false;
     // worth it from ~40 000 rows at 16 dimensions; the exact scan costs in proportion to the dimension
@@ -794,13 +801,13 @@ extern "C" size_t geo_knn_workspace_bytes(int64_t n, int32_t d) {
     size_t b = geo::align_up((size_t)n * p.dp * sizeof(float)) + geo::align_up((size_t)n * p.dp * sizeof(double)) +
                geo::align_up((size_t)n * sizeof(double)) + 1024;
     if (filter_applies(n, p.dp)) {
-        const size_t m = ((size_t)n + FILTER_STRIDE - 1) / FILTER_STRIDE;
+        const size_t m = ((size_t)n + FILTER_STRIDE_MIN - 1) / FILTER_STRIDE_MIN;     // the densest subset (longest lists)
         const size_t dpb = p.dp < 16 ? 16 : p.dp;
         const size_t n_pad = ((size_t)n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;   // the scan reads whole tiles
         b += geo::align_up(m * p.dp * sizeof(float)) + geo::align_up(m * sizeof(double)) + geo::align_up((size_t)n * 8) +
              geo::align_up((size_t)n * 4) + geo::align_up((size_t)n * FILTER_CAP * 4) + 256 +
              geo::align_up(n_pad * 2 * dpb * sizeof(unsigned short)) + geo::align_up(n_pad * sizeof(float));
-        const size_t m0 = (m + FILTER_STRIDE - 1) / FILTER_STRIDE;
+        const size_t m0 = (m + FILTER_STRIDE_MIN - 1) / FILTER_STRIDE_MIN;
         b += geo::align_up(m0 * p.dp * sizeof(float)) + geo::align_up(m0 * sizeof(double)) +
              geo::align_up(m_pad * 2 * dpb * sizeof(unsigned short)) + geo::align_up(m_pad * sizeof(float));   // two-level thresholds
     }
@@ -811,6 +818,7 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
                             int64_t row1, int32_t *idx_out, double *d2_out, void *ws, size_t ws_bytes,
                             void *stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    g_last_path = 0;
     GEO_REQUIRE(z && idx_out && d2_out && ws, "geo_knn_topk: null pointer");
     GEO_REQUIRE(n > 0 && n < (int64_t)1 << 31, "geo_knn_topk: n=%lld out of range", (long long)n);
     GEO_REQUIRE(d > 0 && d <= 128, "geo_knn_topk: d=%d not in [1,128]", d);
@@ -832,12 +840,14 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
     const bool ex = form != 0;
     const int64_t rows = row1 - row0;
     if (n_neighbors > 64) {                       // no float32 filter here: its candidate lists are sized for kq <= 64
+        g_last_path = GEO_KNN_PATH_EXACT_WIDE;
         if (p.dch == 8) return launch_knn_wide<8>(ex, zp32, zq64, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
         if (p.dch == 16) return launch_knn_wide<16>(ex, zp32, zq64, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
         return launch_knn_wide<32>(ex, zp32, zq64, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
     }
-    if (filter_applies(n, p.dp) && (n + FILTER_STRIDE - 1) / FILTER_STRIDE >= n_neighbors) {
-        const int64_t m = (n + FILTER_STRIDE - 1) / FILTER_STRIDE;
+    const int S = filter_stride(n_neighbors);
+    if (filter_applies(n, p.dp) && (n + S - 1) / S >= n_neighbors) {
+        const int64_t m = (n + S - 1) / S;
         float *zs32 = ar.take<float>((size_t)m * p.dp);
         double *nrm_s = ar.take<double>((size_t)m);
         double *u = ar.take<double>((size_t)n);
@@ -849,7 +859,7 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
         const int64_t n_pad = (n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;      // the scan reads whole tiles
         unsigned short *zb = ar.take<unsigned short>((size_t)n_pad * 2 * dpb);
         float *negn = ar.take<float>((size_t)n_pad);
-        const size_t m0w = ((size_t)m + FILTER_STRIDE - 1) / FILTER_STRIDE;
+        const size_t m0w = ((size_t)m + S - 1) / S;
         float *zs0 = ar.take<float>(m0w * p.dp);
         double *nrm_s0 = ar.take<double>(m0w);
         unsigned short *zb_s = ar.take<unsigned short>((size_t)m_pad * 2 * dpb);
@@ -864,7 +874,7 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
         // (the bf16 scan keeps 16 bits of every coordinate: its products err by < 2^-16 (|x|^2 + |y|^2) on top, 4x margin)
         const double eps = 16.0 * (p.dp + 2) * 5.9604644775390625e-08 + (bf16_scan ? 4.0 * 1.52587890625e-05 : 0.0);
         GEO_HIP_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
-        knn_subset_kernel<<<geo::grid_for(m * p.dp, 256, 4096), 256, 0, stream>>>(zp32, nrm, n, p.dp, FILTER_STRIDE, m, zs32, nrm_s);
+        knn_subset_kernel<<<geo::grid_for(m * p.dp, 256, 4096), 256, 0, stream>>>(zp32, nrm, n, p.dp, S, m, zs32, nrm_s);
         GEO_LAUNCH_CHECK();
         if (bf16_scan) {
             knn_split_kernel<<<geo::grid_for(n_pad * dpb, 256, 4096), 256, 0, stream>>>(zp32, nrm, n, n_pad, p.dp, dpb, eps, zb, negn);
@@ -896,9 +906,10 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
         // Large inputs: the exact pass over every 16th row is itself N^2 / 16 fp64 work (100 ms of 255 at a million latents).
         // Two levels instead: thresholds from every 256th row (exact), with them the SAME filter + refinement over the
         // every-16th-row subset gives the exact kq-th distance to that subset -- the threshold the one-level scheme uses.
-        const int64_t m0 = (m + FILTER_STRIDE - 1) / FILTER_STRIDE;
+        // (Every S-th row of every S-th row for longer lists: the same candidate counts at both levels.)
+        const int64_t m0 = (m + S - 1) / S;
         if (bf16_scan && zs0 && n >= TWO_LEVEL_MIN && m0 >= n_neighbors) {
-            knn_subset_kernel<<<geo::grid_for(m0 * p.dp, 256, 4096), 256, 0, stream>>>(zs32, nrm_s, m, p.dp, FILTER_STRIDE, m0, zs0, nrm_s0);
+            knn_subset_kernel<<<geo::grid_for(m0 * p.dp, 256, 4096), 256, 0, stream>>>(zs32, nrm_s, m, p.dp, S, m0, zs0, nrm_s0);
             GEO_LAUNCH_CHECK();
             rc = GEO_EXACT_SUBSET(zs0, nrm_s0, m0);
             if (rc) return rc;
@@ -918,9 +929,11 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
             GEO_HIP_CHECK(hipMemcpyAsync(&h_over0, overflow, 4, hipMemcpyDeviceToHost, stream));
             GEO_HIP_CHECK(hipStreamSynchronize(stream));
             tau_done = h_over0 == 0;
+            if (tau_done) g_last_path = GEO_KNN_PATH_TWO_LEVEL;
             if (!tau_done) GEO_HIP_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
         }
         if (!tau_done) {
+            g_last_path = bf16_scan ? GEO_KNN_PATH_FILTER_BF16 : GEO_KNN_PATH_FILTER_F32;
             rc = GEO_EXACT_SUBSET(zs32, nrm_s, m);
             if (rc) return rc;
         }
@@ -948,6 +961,9 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
         GEO_HIP_CHECK(hipStreamSynchronize(stream));
         if (h_over == 0) return GEO_OK;
         // some query kept more than FILTER_CAP candidates (masses of near-duplicates): exact scan for everything
+        g_last_path |= GEO_KNN_PATH_OVERFLOW;
+    } else {
+        g_last_path = GEO_KNN_PATH_EXACT;
     }
     const bool small = rows < 16384;              // fewer queries per wave keeps the chip busy on small inputs
     int rc;
@@ -962,3 +978,5 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
                    : launch_knn<32, 16>(ex, zp32, zq64, nrm, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
     return rc;
 }
+
+extern "C" int geo_knn_last_path(void) { return g_last_path; }
