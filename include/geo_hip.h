@@ -322,6 +322,35 @@ int geo_prior_attention_bwd(const float *qkv, const float *probs, const uint8_t 
 int geo_prior_adamw(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev,
                     const int64_t *step_dev, float beta1, float beta2, float eps, float weight_decay, void *stream);
 
+/* ---- sampling from the code prior (src/scripts/generate_samples.py:12-31: sample, top_k_logits) ----
+ * The model: dims, the flat f32 parameter arena (vqvae_amd/prior/transformer.py, Transformer.layout) and the float offsets of
+ * its tensors.  Every weight matrix starts on 16 bytes.  class_emb = -1 for an unconditional model. */
+typedef struct {
+    int32_t num_tokens, embed_dim, n_layers, n_head, max_seq_len, num_classes;
+    const float *arena;
+    int64_t pos_emb, token_emb, class_emb, ln_f_w, ln_f_b, head_w;
+    /* [host] n_layers x 12 offsets: ln1.weight, ln1.bias, ln2.weight, ln2.bias, attn.c_attn.weight, attn.c_attn.bias,
+     * attn.c_proj.weight, attn.c_proj.bias, mlp.0.weight, mlp.0.bias, mlp.2.weight, mlp.2.bias */
+    const int64_t *block;
+} geo_prior_desc;
+
+/* Workspace of geo_prior_sample for B rows and n_positions = T0 + steps - 1 decoded positions (KV cache, activations,
+ * logits).  0 for invalid arguments. */
+size_t geo_prior_sample_workspace_bytes(const geo_prior_desc *model, int32_t B, int32_t n_positions);
+
+/* KV-cached autoregressive decode of B rows: tokens_out i64 [B][T0 + steps] = the prompt i64 [B][T0] followed by `steps`
+ * drawn tokens, the standard causal mask, dropout off (eval).  y i64 [B] class labels or NULL.  uniforms f32 [B][steps] in
+ * [0, 1) pick the tokens by the draw rule: l = logits / temperature; with top_k > 0 keep every l_i >= the k-th largest
+ * (ties kept); p = exp(l - max l) over the kept set; the token is the smallest i whose prefix sum exceeds u * sum(p), else
+ * the last kept index.  top_k = 0: no filter.  logits_out f32 [B][T0 + steps - 1][V] or NULL receives the logits of every
+ * position (teacher-forced over the prompt).  Covered: max_seq_len <= 16, head_dim in {16, 32, 64}, embed_dim a multiple
+ * of 64 and <= 512, num_tokens <= 1024; T0 >= 1, T0 + steps - 1 <= max_seq_len.  Prompt tokens and labels must be in
+ * range (the caller checks; the kernels clamp their embedding lookups).  No global state: concurrent calls on different
+ * streams with their own workspaces and outputs are independent.  Asynchronous on `stream`. */
+int geo_prior_sample(const geo_prior_desc *model, const int64_t *prompt, int32_t T0, int32_t steps, const int64_t *y,
+                     const float *uniforms, float temperature, int32_t top_k, int64_t *tokens_out, float *logits_out,
+                     int32_t B, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,14 @@ class DecoderDesc(ctypes.Structure):
                 + [("update_running", i32), ("momentum", ctypes.c_float)])
 
 
+class PriorDesc(ctypes.Structure):
+    """geo_prior_desc of include/geo_hip.h."""
+    _fields_ = ([(n, i32) for n in ("num_tokens", "embed_dim", "n_layers", "n_head", "max_seq_len", "num_classes")]
+                + [("arena", c_p)]
+                + [(n, i64) for n in ("pos_emb", "token_emb", "class_emb", "ln_f_w", "ln_f_b", "head_w")]
+                + [("block", ctypes.POINTER(i64))])
+
+
 _SIGNATURES = {
     "geo_version": (ctypes.c_int, []),
     "geo_last_error": (ctypes.c_char_p, []),
@@ -63,6 +71,9 @@ _SIGNATURES = {
     "geo_decoder_jvp_edges": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, i64, c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
     "geo_decoder_jvp_pairs": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
     "geo_gather_edge_weights": (ctypes.c_int, [c_p, c_p, i64, c_p, c_p]),
+    "geo_prior_sample_workspace_bytes": (sz, [ctypes.POINTER(PriorDesc), i32, i32]),
+    "geo_prior_sample": (ctypes.c_int, [ctypes.POINTER(PriorDesc), c_p, i32, i32, c_p, c_p, ctypes.c_float, i32, c_p, c_p, i32,
+                                        c_p, sz, c_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
