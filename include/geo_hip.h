@@ -351,6 +351,42 @@ int geo_prior_sample(const geo_prior_desc *model, const int64_t *prompt, int32_t
                      const float *uniforms, float temperature, int32_t top_k, int64_t *tokens_out, float *logits_out,
                      int32_t B, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Euclidean k-means (sklearn.cluster.KMeans, lloyd, k-means++; the reference's demos/codebook_comparison.py:73-77) ----
+ * X f32 [n][d] (row-major, 1 <= d <= 128), centres f32 [K][d], 1 <= K <= min(n, 4096).  The key of row x and centre c is the
+ * fp64 fma chain of (x_k - c_k)^2 over k ascending; labels are argmin_j key with ties to the lowest j.  One workspace query
+ * serves all three calls (n_starts / n_trials as given to geo_kmeans_pp; 1 / 1 for the other two).  No float atomics: every
+ * output is bit-identical across runs, streams and workspace sizes.  0 for invalid arguments. */
+size_t geo_kmeans_workspace_bytes(int64_t n, int32_t d, int32_t K, int32_t n_starts, int32_t n_trials);
+
+/* labels_out i32 [n], keys_out f64 [n] (may be NULL) = the key of the chosen centre.  A float32 matrix-core screen decides
+ * most rows; rows within its proven error margin (kmeans.hip) are re-keyed exactly against every centre ("fallback rows"):
+ * n_fallback_out [host, may be NULL] receives their number (synchronises when given). */
+int geo_kmeans_assign(const float *X, int64_t n, int32_t d, const float *C, int32_t K, int32_t *labels_out, double *keys_out,
+                      int64_t *n_fallback_out, void *ws, size_t ws_bytes, void *stream);
+
+/* k-means++ seeding of n_starts starts at once (sklearn _kmeans_plusplus, unit weights).  first_host [host] i32 [n_starts]
+ * = the first centre of each start (rs.choice), u_host [host] f64 [n_starts][K-1][n_trials] = the uniforms of each later
+ * step.  Step c: closest = f32(key) min-folded over the chosen centres; candidate t = the first row i whose fp64 cumulative
+ * sum of closest (fixed association: 1024-row segments) reaches u * pot, clipped to n - 1; candidate pots = f32 of the
+ * fixed-order fp64 sum of min(closest, f32(key to the candidate)); the first minimum wins and becomes pot.  pot of step 1
+ * = f32 of the fp64 sum of closest.  indices_out i32 [n_starts][K] (device), centers_out f32 [n_starts][K][d] or NULL.
+ * 1 <= n_trials <= 64, n <= 7 000 000.  Synchronises once, after taking the host arrays; the rest is asynchronous. */
+int geo_kmeans_pp(const float *X, int64_t n, int32_t d, int32_t K, int32_t n_starts, int32_t n_trials, const int32_t *first_host,
+                  const double *u_host, int32_t *indices_out, float *centers_out, void *ws, size_t ws_bytes, void *stream);
+
+/* Lloyd iterations of sklearn _kmeans_single_lloyd for each of n_starts starts, init f32 [n_starts][K][d].  Iteration: exact
+ * labels; per-cluster fp64 sums in ascending row order; empty clusters (ascending) take the rows farthest from their old
+ * centre by (key descending, row ascending) unless every key is 0; centre = f32(sum / count), a cluster left empty takes the
+ * row sklearn's _average_centers gives it (the biggest cluster's, kmeans.hip); shift2 = fp64 |new - old|^2.
+ * Stops on unchanged labels (strict; never in the first iteration), else when the fp64 sum of shift2 <= tol, else at
+ * max_iter; without strict convergence the rows are relabelled once with the final centres.  centers_out f32
+ * [n_starts][K][d], labels_out i32 [n_starts][n] (device); inertia_out f64 (fp64 sum of the keys), n_iter_out i32,
+ * strict_out i32 (may be NULL) [host] [n_starts]; n_fallback_out [host, may be NULL] = fallback rows over all assignments.
+ * Synchronises once per batch of iterations. */
+int geo_kmeans_lloyd(const float *X, int64_t n, int32_t d, int32_t K, int32_t n_starts, const float *init, int32_t max_iter,
+                     double tol, float *centers_out, int32_t *labels_out, double *inertia_out, int32_t *n_iter_out,
+                     int32_t *strict_out, int64_t *n_fallback_out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,11 @@ _SIGNATURES = {
     "geo_prior_sample_workspace_bytes": (sz, [ctypes.POINTER(PriorDesc), i32, i32]),
     "geo_prior_sample": (ctypes.c_int, [ctypes.POINTER(PriorDesc), c_p, i32, i32, c_p, c_p, ctypes.c_float, i32, c_p, c_p, i32,
                                         c_p, sz, c_p]),
+    "geo_kmeans_workspace_bytes": (sz, [i64, i32, i32, i32, i32]),
+    "geo_kmeans_assign": (ctypes.c_int, [c_p, i64, i32, c_p, i32, c_p, c_p, c_p, c_p, sz, c_p]),
+    "geo_kmeans_pp": (ctypes.c_int, [c_p, i64, i32, i32, i32, i32, c_p, c_p, c_p, c_p, c_p, sz, c_p]),
+    "geo_kmeans_lloyd": (ctypes.c_int, [c_p, i64, i32, i32, i32, c_p, i32, ctypes.c_double, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                        sz, c_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
