@@ -387,6 +387,13 @@ int geo_kmeans_lloyd(const float *X, int64_t n, int32_t d, int32_t K, int32_t n_
                      double tol, float *centers_out, int32_t *labels_out, double *inertia_out, int32_t *n_iter_out,
                      int32_t *strict_out, int64_t *n_fallback_out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Evaluation metrics: per-image pair moments (the reductions of PSNR and SSIM; reference src/eval/metrics.py) ----
+ * x, y f32 [n_images][n_pix] (device, contiguous), 1 <= n_pix <= 16384, 0 <= n_images < 2^31.  mom_out f64 [n_images][6] =
+ * mean_x, mean_y, var_x, var_y, cov_xy (biased, centred on the fp64 means in a second pass), sse = sum (x - y)^2, all
+ * accumulated in fp64.  Fixed reduction order that depends on n_pix alone, no atomics: bit-identical across runs, streams,
+ * batch sizes and positions in the batch.  Asynchronous on `stream`. */
+int geo_image_pair_moments(const float *x, const float *y, int64_t n_images, int64_t n_pix, double *mom_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 stack with the reference's parameter names, so the `decoder.*` entries of a reference checkpoint load unchanged.  The legacy
 Riemannian builder differentiates this module -- Linear-first, so edge_lengths_riemannian takes its autograd path on the GPU
 (riemannian_metric.py:18-22).  Encoder, loss and sampling of the reference's VAE are not part of the hot path and not built."""
-from typing import Dict, Sequence
+import os
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -38,3 +39,37 @@ def decoder_from_vae_checkpoint(state: Dict[str, torch.Tensor], in_channels: int
     own = {k[len("decoder."):]: v for k, v in state.items() if k.startswith("decoder.")}
     dec.load_state_dict(own if own else state)           # (a bare decoder state dict is accepted too)
     return dec
+
+
+def auto_detect_vae_config(state: Dict[str, torch.Tensor]) -> Dict:
+    """The architecture of a vanilla-VAE state dict, as the reference's checkpoint loader detects it
+    (src/utils/checkpoint_utils.py auto_detect_vae_config and load_vae_from_checkpoint): in_channels from the first encoder
+    convolution, enc_channels from every third encoder layer (dec_channels reversed), batch norm iff the first norm layer has
+    running statistics, 32 px for 3 channels else 28, latent_dim from encoder.fc_mu (128 when absent)."""
+    first = state.get("encoder.conv_layers.0.weight")
+    in_channels = int(first.shape[1]) if first is not None else 1
+    enc, i = [], 0
+    while f"encoder.conv_layers.{i * 3}.weight" in state:
+        enc.append(int(state[f"encoder.conv_layers.{i * 3}.weight"].shape[0]))
+        i += 1
+    enc = enc or [32, 64, 128]
+    mu = state.get("encoder.fc_mu.weight")
+    return {"in_channels": in_channels, "enc_channels": tuple(enc), "dec_channels": tuple(reversed(enc)),
+            "norm_type": "batch" if "encoder.conv_layers.1.running_mean" in state else "none",
+            "output_image_size": 32 if in_channels == 3 else 28,
+            "latent_dim": int(mu.shape[0]) if mu is not None else 128}
+
+
+def load_vae_decoder(checkpoint_path: str, device="cpu", latent_dim: Optional[int] = None) -> Tuple[Decoder, Dict]:
+    """(decoder in eval mode, detected config) of a vanilla-VAE checkpoint: the decoder half of the reference's
+    load_vae_from_checkpoint.  The state dict is the checkpoint's 'model_state_dict', else its 'model', else the checkpoint
+    itself.  Raises FileNotFoundError for a missing file (the reference prints and returns None)."""
+    if not os.path.exists(checkpoint_path):
+        raise FileNotFoundError(f"Checkpoint not found: {checkpoint_path}")
+    ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
+    state = ckpt.get("model_state_dict") or ckpt.get("model") or ckpt
+    cfg = auto_detect_vae_config(state)
+    if latent_dim is not None:
+        cfg["latent_dim"] = int(latent_dim)
+    dec = decoder_from_vae_checkpoint(state, **cfg)
+    return dec.to(device).eval(), cfg
