@@ -63,7 +63,7 @@ fetch_raw = sum(x for _, x in sw_f) * 1024.0 / len(sw_f)
 wr = sum(x for _, x in sw_w) * 1024.0 / len(sw_w)
 traffic = {
     "source": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes), bench.py --steps 1 "
-              f"--warmup 0 --no-cpu-baseline, workload c2, MI355X ({tag}; profiles/collect.sh)",
+              f"--warmup 0 --no-cpu-baseline --full, workload c2, MI355X ({tag}; profiles/collect.sh)",
     "units": "FETCH_SIZE/WRITE_SIZE are reported in KiB; gfx950 FETCH_SIZE counts half of the bytes of coalesced row "
              "reads (MI355X_MICROARCH.md, HBM section)",
     "calibration": {"kernel": cal_kernel, "known_read_bytes": known, "fetch_size_bytes_raw": raw,

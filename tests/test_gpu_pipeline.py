@@ -76,7 +76,7 @@ def test_pipeline_with_disconnected_graph_vs_oracle(tmp_path):
 
 
 def test_bench_prints_one_contract_line(tmp_path):
-    """bench.py on the small c1 workload (the reference's CPU-runnable configuration), CPU baseline included: ONE JSON
+    """bench.py --full on the small c1 workload (the reference's CPU-runnable configuration), CPU baseline included: ONE JSON
     line on stdout with the driver's fields, the roofline object of the sweep kernel and the cpu_baseline object; with
     --dump-outputs, the last timed build's arrays as float .npy files that agree with the line."""
     import json
@@ -86,7 +86,7 @@ def test_bench_prints_one_contract_line(tmp_path):
     env = dict(os.environ, GEO_BENCH_CPU_SAMPLE="1")
     dump = tmp_path / "dump"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c1", "--steps", "2", "--warmup", "1",
-                          "--dump-outputs", str(dump)],
+                          "--dump-outputs", str(dump), "--full"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -112,6 +112,45 @@ def test_bench_prints_one_contract_line(tmp_path):
     assert len(got["edge_lengths"]) == d["config"]["graph"]["edges_reweighted"] and got["edge_lengths"].dtype == np.float32
     np.testing.assert_array_equal(got["assign_batched"], got["assign_flat"][got["mask_lcc"] > 0])
     assert np.all(np.isfinite(got["dmin_batched"])) and got["dmin_batched"][got["medoids"].astype(np.int64)].max() == 0
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_what_a_full_run_dumps(tmp_path):
+    """bench.py without --full: the same ONE line with the headline fields and the timed builds' self-check, none of what
+    --full measures after the timed steps (instrumented build, rooflines, CPU baseline), and with --dump-outputs exactly the
+    arrays a --full run of the same arguments writes."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for mode in ("plain", "full"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / mode)] + (["--full", "--no-cpu-baseline"] if mode == "full" else []),
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(js) == 1, out.stdout[-2000:]
+        lines[mode] = json.loads(js[0])
+    plain, full = lines["plain"], lines["full"]
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "parity_selfcheck"):
+        assert key in plain, key
+    for key in ("roofline", "roofline_knn", "roofline_jvp", "stages_ms", "latency_ms_single_build", "serial_fraction", "cpu_baseline"):
+        assert key not in plain, key
+    assert "roofline" in full and "stages_ms" in full and "cpu_baseline" not in full
+    assert "one_solve_assignment" not in plain["parity_selfcheck"] and full["parity_selfcheck"]["one_solve_assignment"]
+    for key in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "dtype", "data"):
+        assert plain[key] == full[key], key
+    assert plain["config"]["graph"] == full["config"]["graph"]
+    assert plain["config"]["pipeline_depth"] == full["config"]["pipeline_depth"]
+    assert abs(plain["value"] - 2048 / (plain["ms_per_step"] * 1e-3)) < 1e-6 * plain["value"]
+    assert plain["parity_selfcheck"]["batched_assign_equals_fused"] is True
+    assert plain["parity_selfcheck"]["qe"] == full["parity_selfcheck"]["qe"]
+    names = sorted(f for f in os.listdir(tmp_path / "plain") if f.endswith(".npy"))
+    assert names and names == sorted(f for f in os.listdir(tmp_path / "full") if f.endswith(".npy"))
+    for f in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f), err_msg=f)
+    assert float(np.load(tmp_path / "plain" / "qe.npy")) == plain["parity_selfcheck"]["qe"]
 
 
 def test_bench_two_ranks_with_sharded_builds_in_flight():
