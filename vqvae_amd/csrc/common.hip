@@ -30,6 +30,7 @@ const OptionName kOptionNames[] = {
     {"jvp_per_node", "GEO_JVP_PER_NODE", &Options::jvp_per_node},
     {"jvp_node_jacobian", "GEO_JVP_NODE_JACOBIAN", &Options::jvp_node_jacobian},
     {"jvp_pipe_grid", "GEO_JVP_PIPE_GRID", &Options::jvp_pipe_grid},
+    {"jvp_start_dedup", "GEO_JVP_START_DEDUP", &Options::jvp_start_dedup},
 };
 Options from_environment() {
     Options o;

@@ -1045,6 +1045,25 @@ __global__ __launch_bounds__(512, 2) void mid_all_kernel(const float *__restrict
 #endif
 }
 
+// BN2 partial sums of one lane of a ConvT2 wave (mid_pipe_kernel's layout): bn2_add over rows (q & 3) + 8 (q >> 2) + 4 h of the
+// tile, the wave's four chunks in order (lc outer, q inner), then bn2_store adds the two row halves, one [tile][wave slot][channel]
+// entry per lane < 32.  The primal comes from the accumulators (mid_pipe_kernel) or is gathered from the start side's compact rows
+// (mid_start_kernel): the same terms in the same order, bit-identical sums.
+struct Bn2Sums { double sx = 0, sxx = 0, st = 0, sxt = 0; };
+__device__ __forceinline__ void bn2_add(Bn2Sums &a, float x, float t, bool live) {
+    // (no branch per element: rows beyond the chunk's edges contribute zeros; all but a batch's last tile are full)
+    const double xd = live ? (double)x : 0.0, td = live ? (double)t : 0.0;
+    a.sx += xd; a.sxx = fma(xd, xd, a.sxx); a.st += td; a.sxt = fma(xd, td, a.sxt);
+}
+__device__ __forceinline__ void bn2_store(Bn2Sums a, double *__restrict__ partial2, int tile, int wslot, int co, int lane) {
+    a.sx += __shfl_xor(a.sx, 32, 64); a.sxx += __shfl_xor(a.sxx, 32, 64);
+    a.st += __shfl_xor(a.st, 32, 64); a.sxt += __shfl_xor(a.sxt, 32, 64);
+    if (lane < 32) {                                           // wave slot = (chunk group, column half): channels (wq & 1) * 32 + lane
+        double *pp = partial2 + (((size_t)tile * 4 + wslot) * 64 + co) * 4;
+        pp[0] = a.sx; pp[1] = a.sxx; pp[2] = a.st; pp[3] = a.sxt;
+    }
+}
+
 // ---- ConvT2, persistent and skewed (dec_channels 128 -> 64, BatchNorm or no norm): the default for the shipped decoder ------
 // In-kernel stamps of mid_all_kernel (one tile per workgroup, -DGEO_MID_PROF): the four pixel intervals keep the matrix pipe 85 %
 // busy, but the tile's prologue (constants, first staging: 9 100 cycles) and epilogue (128 stores per wave + fp64 statistics:
@@ -1058,6 +1077,7 @@ __global__ __launch_bounds__(512, 2) void mid_all_kernel(const float *__restrict
 // staging always run beside the other group's MFMAs.  The statistics leave per wave (partial2 [tile][4 wave slots][channel],
 // finalize_batch_kernel adds them: npx_stored = 4), so no epilogue needs a workgroup barrier.  Same products in the same order as
 // mid_all_kernel: pre-activations are bit-identical; the fp64 statistic sums associate differently (last-bit differences).
+template <bool END_ONLY>
 __global__ __launch_bounds__(512, 2) void mid_pipe_kernel(const float *__restrict__ pre1, const float *__restrict__ tpre1,
                                                          const NormConst *__restrict__ consts1, int consts_per_group,
                                                          int tiles_per_group, int n_tiles, int /*c2 == 64*/,
@@ -1065,6 +1085,7 @@ __global__ __launch_bounds__(512, 2) void mid_pipe_kernel(const float *__restric
                                                          float *__restrict__ pre2, float *__restrict__ tpre2,
                                                          double *__restrict__ partial2, int want_stats, int64_t e_base,
                                                          int64_t n_edges, int batch) {
+    // END_ONLY: the n_tiles work tiles are the END-side tiles of the pass (the start side runs in mid_start_kernel)
     constexpr int C1 = 128, LDK = C1 + 8, KS = C1 / 16, NL = 4, c2 = 64;
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     __shared__ __attribute__((aligned(16))) unsigned short A3[2][3][2][TS][LDK];   // double buffered over input pixels
@@ -1092,7 +1113,9 @@ __global__ __launch_bounds__(512, 2) void mid_pipe_kernel(const float *__restric
     // staging state of this wave: constants of the tile it stages next, and raw pre-activations in flight
     NormConst kA, kB;
     f32x2 rp[4], rt[4];
+    auto phys = [&](int t) { return END_ONLY ? ((t / tiles_per_group) * 2 + 1) * tiles_per_group + t % tiles_per_group : t; };
     auto load_consts = [&](int tile) {
+        tile = phys(tile);
         const NormConst *kp = consts1 + (size_t)(consts_per_group ? tile / tiles_per_group : 0) * C1 + k0p;
         kA = kp[0];
         kB = kp[1];
@@ -1102,7 +1125,7 @@ __global__ __launch_bounds__(512, 2) void mid_pipe_kernel(const float *__restric
     const unsigned v_pair = (unsigned)k0p * 4u;
     auto fetch = [&](int tile, int px, int sample0, auto ns_tag) {
         constexpr int NS = decltype(ns_tag)::value;
-        const size_t tbase = (size_t)tile * TS * n1;
+        const size_t tbase = (size_t)phys(tile) * TS * n1;
         const __amdgpu_buffer_rsrc_t rp_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pre1 + tbase), 0, TS * n1 * 4, 0x00020000);
         const __amdgpu_buffer_rsrc_t rt_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tpre1 + tbase), 0, TS * n1 * 4, 0x00020000);
         const int soff = (sample0 * n1 + MidGeom::pix(px) * C1) * 4;      // (px = position in the tile's pixel sequence)
@@ -1154,6 +1177,7 @@ __global__ __launch_bounds__(512, 2) void mid_pipe_kernel(const float *__restric
     };
     // stores + statistics of one tile's accumulators (this wave's four chunks), then the accumulators start over
     auto epilogue = [&](int tile) {
+        tile = phys(tile);
         const int group = tile / tiles_per_group;
         int64_t cnt_g = n_edges - (e_base + (int64_t)(group >> 1) * batch);
         if (cnt_g > batch) cnt_g = batch;
@@ -1161,7 +1185,7 @@ __global__ __launch_bounds__(512, 2) void mid_pipe_kernel(const float *__restric
         const size_t tbase = (size_t)tile * TS * n2;
         const __amdgpu_buffer_rsrc_t p_dst = __builtin_amdgcn_make_buffer_rsrc(pre2 + tbase, 0, TS * n2 * 4, 0x00020000);
         const __amdgpu_buffer_rsrc_t t_dst = __builtin_amdgcn_make_buffer_rsrc(tpre2 + tbase, 0, TS * n2 * 4, 0x00020000);
-        double sx = 0, sxx = 0, st_ = 0, sxt = 0;
+        Bn2Sums sums;
 #pragma unroll
         for (int lc = 0; lc < NL; ++lc) {
             const int ch = wg == 0 ? MidGeom::chunk_of(0, lc) : MidGeom::chunk_of(1, lc);
@@ -1173,19 +1197,10 @@ __global__ __launch_bounds__(512, 2) void mid_pipe_kernel(const float *__restric
                 const int soff = (((q & 3) + 8 * (q >> 2)) * n2 + op * c2) * 4;          // scalar; the lane adds v_out
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), p_dst, v_out, soff, 0);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(t), t_dst, v_out, soff, 0);
-                // (no branch per element: rows beyond the chunk's edges contribute zeros; all but a batch's last tile are full)
-                const double xd = row < n_valid ? (double)x : 0.0, td = row < n_valid ? (double)t : 0.0;
-                sx += xd; sxx = fma(xd, xd, sxx); st_ += td; sxt = fma(xd, td, sxt);
+                bn2_add(sums, x, t, row < n_valid);
             }
         }
-        if (want_stats) {
-            sx += __shfl_xor(sx, 32, 64); sxx += __shfl_xor(sxx, 32, 64);
-            st_ += __shfl_xor(st_, 32, 64); sxt += __shfl_xor(sxt, 32, 64);
-            if (lane < 32) {                                   // wave slot = (chunk group, column half): channels (wq & 1) * 32 + lane
-                double *pp = partial2 + (((size_t)tile * 4 + (wg * 2 + (wq >> 1))) * c2 + co) * 4;
-                pp[0] = sx; pp[1] = sxx; pp[2] = st_; pp[3] = sxt;
-            }
-        }
+        if (want_stats) bn2_store(sums, partial2, tile, wg * 2 + (wq >> 1), co, lane);
         zero_acc();
     };
 
@@ -1269,6 +1284,214 @@ __global__ __launch_bounds__(512, 2) void mid_pipe_kernel(const float *__restric
 #undef GEO_PIPE_SEP
 #undef GEO_PB
 #undef GEO_PIPE_PIXEL
+}
+
+// ---- start side of train-mode BatchNorm, graph edges (jvp_start_dedup) ------------------------------------------------------
+// The edge list is row-major (src ascending), so a chunk's start-side slots hold runs of one latent.  Their primal rows are the same
+// function of (latent, the group's BatchNorm constants): ConvT2 / ConvT3 run them once per run.  Per start group (= chunk):
+//   row_map[slot]      absolute index of the slot's compact primal row (compact row k of group g lives at slot position g * spg + k,
+//                      where the start side no longer keeps per-slot primal rows; padding slots: compact row 0)
+//   rep[g * spg + k]   the slot whose pre-activations feed compact row k (the first slot of its run); rows k in [cnt, cnt rounded up
+//                      to TS) repeat the group's first slot (padding of the last compact tile)
+//   n_compact[chunk]   cnt, the number of runs
+// No sorting: an unsorted list only has shorter runs.
+__global__ __launch_bounds__(256) void start_runs_kernel(const int32_t *__restrict__ src, int64_t e_base, int64_t n_edges, int batch,
+                                                        int slots_per_group, int32_t *__restrict__ row_map, int32_t *__restrict__ rep,
+                                                        int32_t *__restrict__ n_compact) {
+    __shared__ int wsum[4];
+    __shared__ int carry_s;
+    const int chunk = blockIdx.x;
+    const size_t g0 = (size_t)chunk * 2 * slots_per_group;     // first slot of the start group
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;                                             // runs before this block of 256 slots
+    for (int w0 = 0; w0 < slots_per_group; w0 += 256) {
+        const int within = w0 + (int)threadIdx.x;
+        const int64_t e = e_base + (int64_t)chunk * batch + within;
+        const bool valid = within < slots_per_group && within < batch && e < n_edges;
+        const bool head = valid && (within == 0 || src[e] != src[e - 1]);
+        const unsigned long long m = __ballot(head);
+        const int below = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wave] = __popcll(m);
+        __syncthreads();
+        int before = carry, total = carry;
+        for (int w = 0; w < 4; ++w) { if (w < wave) before += wsum[w]; total += wsum[w]; }
+        const int k = before + below + (head ? 1 : 0) - 1;     // index of the run this slot belongs to
+        if (within < slots_per_group) {
+            row_map[g0 + within] = (int32_t)(g0 + (valid ? k : 0));
+            if (head) rep[g0 + k] = (int32_t)(g0 + within);
+        }
+        carry = total;
+        __syncthreads();                                       // wsum reused
+    }
+    if (threadIdx.x == 0) { carry_s = carry; n_compact[chunk] = carry; }
+    __syncthreads();
+    const int cnt = carry_s, padded = (cnt + TS - 1) / TS * TS;
+    for (int k = cnt + (int)threadIdx.x; k < padded; k += 256) rep[g0 + k] = (int32_t)g0;
+}
+
+// ConvT2 of the start side in full 64-row tiles of two independent 32-row halves, both of one start group (one set of constants):
+//   TT = true   halves = the tangents of start tiles 2j and 2j + 1 of the group (their own pre1 rows give the BN1 / ReLU terms);
+//               tangent rows -> tpre2, and the tiles' BN2 partial sums with the primal gathered from the compact rows (bn2_partial),
+//               so this launch follows the TT = false one
+//   TT = false  halves = compact primal tiles 2j and 2j + 1 (rows gathered through rep) -> the compact rows of pre2
+// Same staging arithmetic, products (mid_products) and order as mid_all_kernel / mid_pipe_kernel: every row is bit-identical to the
+// row those kernels compute for the same inputs.  grid = (ceil(tiles_per_group / 2), chunks of the pass), 512 threads.
+template <bool TT>
+__global__ __launch_bounds__(512, 2) void mid_start_kernel(const float *__restrict__ pre1, const float *__restrict__ tpre1,
+                                                          const NormConst *__restrict__ consts1, int tiles_per_group,
+                                                          const unsigned short *__restrict__ B3, const float *__restrict__ b2,
+                                                          float *__restrict__ pre2, float *__restrict__ tpre2,
+                                                          double *__restrict__ partial2, const int32_t *__restrict__ row_map,
+                                                          const int32_t *__restrict__ rep, const int32_t *__restrict__ n_compact,
+                                                          int64_t e_base, int64_t n_edges, int batch) {
+    constexpr int C1 = 128, LDK = C1 + 8, KS = C1 / 16, NL = 4, c2 = 64, n1 = 4 * C1, n2 = 16 * c2;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    __shared__ __attribute__((aligned(16))) unsigned short A3[2][3][2][TS][LDK];   // [buf][part][half][row][k]
+    const int chunk = blockIdx.y, group = 2 * chunk;
+    const int ncomp = TT ? 0 : n_compact[chunk];
+    // (the compact launch runs one workgroup per chunk over its few tile pairs: empty workgroups are not free -- a launch is bound by
+    // the wave dispatch rate, ~25 ns per wave across the chip, and a per-pair grid is 8 mostly empty 8-wave workgroups per chunk)
+    auto run = [&](int item) {
+    const int lt0 = 2 * item;                                   // local tile of half 0 (half 1: lt0 + 1)
+    const bool live1 = TT ? lt0 + 1 < tiles_per_group : (lt0 + 1) * TS < ncomp;
+    const int tile0 = group * tiles_per_group + lt0, tile1 = live1 ? tile0 + 1 : tile0;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wq = wave & 3, wg = wave >> 2;
+    const int r = lane & 31, h = lane >> 5;
+    f32x16 accp[NL], acct[NL];
+#pragma unroll
+    for (int lc = 0; lc < NL; ++lc)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { accp[lc][i] = 0.f; acct[lc][i] = 0.f; }
+
+    // staging (mid_all_kernel's channel-pair layout): lane -> channels 2 lane, 2 lane + 1; wave -> rows 4 wave .. 4 wave + 3 of both halves
+    const int k0p = 2 * lane, s0p = 4 * wave;
+    const NormConst *kp = consts1 + (size_t)group * C1 + k0p;
+    const NormConst kA = kp[0], kB = kp[1];
+    size_t xrow[2][4];                                          // pre1 rows feeding the wave's staging rows (wave-uniform)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const size_t s0 = (size_t)tile0 * TS + s0p + i, s1 = (size_t)tile1 * TS + s0p + i;
+        xrow[0][i] = TT ? s0 : (size_t)__builtin_amdgcn_readfirstlane(rep[s0]);
+        xrow[1][i] = TT ? s1 : (size_t)__builtin_amdgcn_readfirstlane(rep[s1]);
+    }
+    f32x2 rx[2][4], rt[2][4];
+    auto fetch = [&](int nx) {
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const size_t off = xrow[hh][i] * n1 + (size_t)MidGeom::pix(nx) * C1 + k0p;
+                rx[hh][i] = *reinterpret_cast<const f32x2 *>(pre1 + off);
+                if (TT) rt[hh][i] = *reinterpret_cast<const f32x2 *>(tpre1 + off);
+            }
+    };
+    fetch(0);
+    auto stage_px = [&](int buf, int nx) {
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float a0, t0, a1, t1;
+                norm_relu(kA, rx[hh][i].x, TT ? rt[hh][i].x : 0.f, &a0, &t0);
+                norm_relu(kB, rx[hh][i].y, TT ? rt[hh][i].y : 0.f, &a1, &t1);
+                unsigned w[3];
+                if (TT) split3_pair(t0, t1, w[0], w[1], w[2]);
+                else split3_pair(a0, a1, w[0], w[1], w[2]);
+#pragma unroll
+                for (int part = 0; part < 3; ++part) *reinterpret_cast<unsigned *>(&A3[buf][part][hh][s0p + i][k0p]) = w[part];
+            }
+        if (nx < 4) {
+            fetch(nx);
+            __builtin_amdgcn_sched_group_barrier(0x020, TT ? 16 : 8, 0);
+        }
+    };
+    bf16x8 ring[3][3];
+    const unsigned b_lane = (unsigned)(h * 3 * NC * 8 + (wq * 32 + r) * 8) * 2u;      // bytes
+    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned short *>(B3), 0, (int)((size_t)8 * MAX_BLOCKS * C1 * NC * 3 * 2), 0x00020000);
+    {
+        const int cb0 = wg == 0 ? MidGeom::prod_cb(0, MidGeom::pix(0), 0) : MidGeom::prod_cb(1, MidGeom::pix(0), 0);
+        const int cb1 = wg == 0 ? MidGeom::prod_cb(0, MidGeom::pix(0), 1) : MidGeom::prod_cb(1, MidGeom::pix(0), 1);
+#pragma unroll
+        for (int part = 0; part < 3; ++part) {
+            ring[0][part] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, b_lane, (cb0 * KS * 2 * 3 + part) * NC * 8 * 2, 0));
+            ring[1][part] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, b_lane, (cb1 * KS * 2 * 3 + part) * NC * 8 * 2, 0));
+        }
+    }
+    stage_px(0, 1);
+    if (wg == 1) __builtin_amdgcn_s_setprio(1);
+    lds_barrier();
+    const unsigned short *a3 = &A3[0][0][0][0][0];
+    const unsigned a_lane = (unsigned)(r * LDK + h * 8);
+    constexpr unsigned A_BUF = 3u * 2u * TS * LDK;
+#define GEO_MID_PIXEL(WGV, IPV) mid_products<C1, false, WGV, IPV>(a3, a_lane + ((IPV) & 1) * A_BUF, b_rsrc, b_lane, accp, acct, ring)
+    if (wg == 0) {
+        GEO_MID_PIXEL(0, 0); stage_px(1, 2); lds_barrier();
+        GEO_MID_PIXEL(0, 1); stage_px(0, 3); lds_barrier();
+        GEO_MID_PIXEL(0, 2); stage_px(1, 4); lds_barrier();
+        GEO_MID_PIXEL(0, 3);
+    } else {
+        stage_px(1, 2); GEO_MID_PIXEL(1, 0); lds_barrier();
+        stage_px(0, 3); GEO_MID_PIXEL(1, 1); lds_barrier();
+        stage_px(1, 4); GEO_MID_PIXEL(1, 2); lds_barrier();
+        GEO_MID_PIXEL(1, 3);
+    }
+#undef GEO_MID_PIXEL
+
+    // epilogue: C[row = (q & 3) + 8 (q >> 2) + 4 h][col = lane & 31]; column -> (output pixel lo of the chunk, channel co)
+    const int lo = wq >> 1, co = (wq & 1) * 32 + r;
+    const float bias = TT ? 0.f : b2[co];                       // (the primal rows carry the bias, the tangents do not)
+    float *dst = TT ? tpre2 : pre2;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        if (hh == 1 && !live1) break;
+        const size_t tbase = (size_t)(hh ? tile1 : tile0) * TS;
+#pragma unroll
+        for (int lc = 0; lc < NL; ++lc) {
+            const int ch = wg == 0 ? MidGeom::chunk_of(0, lc) : MidGeom::chunk_of(1, lc);
+            const int op = lo == 0 ? MidGeom::opix(ch, 0) : MidGeom::opix(ch, 1);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int row = (q & 3) + 8 * (q >> 2) + 4 * h;
+                const float v = hh ? acct[lc][q] : accp[lc][q];
+                dst[(tbase + row) * n2 + (size_t)op * c2 + co] = TT ? v : v + bias;
+            }
+        }
+    }
+    if (TT) {                                                  // BN2 partial sums of both tiles, primal from the compact rows
+        int64_t cnt_g = n_edges - (e_base + (int64_t)chunk * batch);
+        if (cnt_g > batch) cnt_g = batch;
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            if (hh == 1 && !live1) break;
+            const int tile = hh ? tile1 : tile0;
+            const size_t tbase = (size_t)tile * TS;
+            const int n_valid = (int)cnt_g - (tile - group * tiles_per_group) * TS;
+            Bn2Sums sums;
+#pragma unroll
+            for (int lc = 0; lc < NL; ++lc) {
+                const int ch = wg == 0 ? MidGeom::chunk_of(0, lc) : MidGeom::chunk_of(1, lc);
+                const int op = lo == 0 ? MidGeom::opix(ch, 0) : MidGeom::opix(ch, 1);
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int row = (q & 3) + 8 * (q >> 2) + 4 * h;
+                    const float x = pre2[(size_t)row_map[tbase + row] * n2 + (size_t)op * c2 + co];
+                    bn2_add(sums, x, hh ? acct[lc][q] : accp[lc][q], row < n_valid);
+                }
+            }
+            bn2_store(sums, partial2, tile, wg * 2 + (wq >> 1), co, lane);
+        }
+    }
+    };
+    if (TT) {
+        run((int)blockIdx.x);
+    } else {
+        for (int item = 0; 2 * item * TS < ncomp; ++item) {
+            if (item > 0) { __builtin_amdgcn_s_setprio(0); __syncthreads(); }   // (A3 is staged again by the next pair)
+            run(item);
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void slot_valid_kernel(int64_t e_base, int64_t n_edges, int batch, int tiles_per_group,
@@ -1404,6 +1627,9 @@ __global__ __launch_bounds__(256) void pack_back_bf16_kernel(const float *__rest
 }
 
 // MODE 0: primal + tangent of every slot -> |J dz| per slot.
+// Start side with compact primal rows (jvp_start_dedup, start_runs_kernel): MODE 2 runs over the compact tiles (n_compact), MODE 1 over the start tiles with row_map as the slot -> primal row map; sg_node is then indexed by the
+// compact row.  side_only: 0 = every tile of the pass, 1 = start-side tiles only, 2 = end-side tiles only (grid = half the tiles);
+// with n_compact the grid is one workgroup per chunk.
 // Per-node primal (decoders with fixed statistics; run_jvp): MODE 2 runs over the LATENTS, primal only, and stores the
 // sigmoid of every output (sg_node [node][NP]); MODE 1 runs over the edge slots, tangent only: the ReLU mask comes from the
 // slot's node row of pre2 (gathered), sigmoid' from sg_node -- the same products in the same order as MODE 0.
@@ -1417,12 +1643,20 @@ __global__ __launch_bounds__(256, 2) void back_mfma_kernel(const float *__restri
                                                        const int32_t *__restrict__ src = nullptr,
                                                        const int32_t *__restrict__ dst = nullptr, int64_t e_base = 0,
                                                        int64_t n_edges = 0, int batch = 1, float *__restrict__ jac_node = nullptr,
-                                                       int unit_d = 0) {
+                                                       int unit_d = 0, const int32_t *__restrict__ row_map = nullptr,
+                                                       const int32_t *__restrict__ n_compact = nullptr, int side_only = 0) {
     constexpr int C2 = 64, KB = 128, LDK = KB + 8, NP = NT * 32;
     __shared__ __attribute__((aligned(16))) unsigned short A3[3][2][TS][LDK];     // 52 KB, reused for the reduction
     __shared__ NormConst kc[C2];
     __shared__ float4 gsl[GN ? TS : 1][32];                                       // GroupNorm: per (sample, group)
-    const int tile = blockIdx.x;
+    // (n_compact: one workgroup per chunk walks the chunk's compact tiles -- see mid_start_kernel on empty workgroups)
+    const int n_iter = MODE == 2 && n_compact ? (n_compact[blockIdx.x] + TS - 1) / TS : 1;
+    for (int it = 0; it < n_iter; ++it) {
+    if (it > 0) __syncthreads();                               // (LDS staged again)
+    const int tile = MODE == 2 && n_compact ? (int)blockIdx.x * 2 * tiles_per_group + it
+                   : side_only ? (((int)blockIdx.x / tiles_per_group) * 2 + side_only - 1) * tiles_per_group +
+                                     (int)blockIdx.x % tiles_per_group
+                               : (int)blockIdx.x;
     const int group = tile / tiles_per_group;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n2 = 16 * C2, P = co_n * s_out * s_out;
@@ -1449,7 +1683,7 @@ __global__ __launch_bounds__(256, 2) void back_mfma_kernel(const float *__restri
         const int64_t e = edge_of(sample);
         return e < 0 ? 0 : (size_t)((group & 1) ? dst[e] : src[e]);
     };
-    const size_t prow = MODE == 1 ? node_of(ss) : slot0 + ss;      // row of the primal pre-activations this thread stages
+    const size_t prow = MODE == 1 ? (row_map ? (size_t)row_map[slot0 + ss] : node_of(ss)) : slot0 + ss;   // row of the primal this thread stages
     for (int kb = 0; kb < 8; ++kb) {
         __syncthreads();
         {
@@ -1510,7 +1744,7 @@ __global__ __launch_bounds__(256, 2) void back_mfma_kernel(const float *__restri
     // sum the four waves' partial tiles through LDS (one 32-column tile at a time), then sigmoid' and the norm
     float *red = reinterpret_cast<float *>(&A3[0][0][0][0]);     // [wave 4][p|t 2][32 rows][33]
     const int row = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
-    const size_t nrow = MODE == 1 ? node_of(row) : slot0 + row;    // sg_node row: the slot's latent (1) / this latent (2)
+    const size_t nrow = MODE == 1 ? (row_map ? (size_t)row_map[slot0 + row] : node_of(row)) : slot0 + row;   // sg_node row: the slot's latent / compact row (1), this row (2)
     // unit tangents: this slot's outputs are column e % unit_d of its latent's Jacobian, kept as jac_node[latent][dimension][NP]
     float *jrow = nullptr;
     if (MODE == 1 && jac_node) {
@@ -1550,6 +1784,7 @@ __global__ __launch_bounds__(256, 2) void back_mfma_kernel(const float *__restri
     sumsq += __shfl_xor(sumsq, 2, 64);
     sumsq += __shfl_xor(sumsq, 4, 64);
     if (MODE != 2 && (threadIdx.x & 7) == 0) norms[slot0 + row] = (float)sqrt(sumsq);
+    }
 }
 
 __global__ __launch_bounds__(256) void combine_kernel(const float *__restrict__ norms, int64_t e_base, int64_t e_count,
@@ -1918,6 +2153,20 @@ int run_jvp(const geo_decoder_desc *dc, const float *z, int64_t n_nodes, const i
                              mid_opt != 2;
         // the shipped widths with BatchNorm / no norm, primal + tangent: the persistent skewed kernel (jvp_mid = 3: mid_all_kernel)
         const bool mid_pipe = mid_all && !per_node && !gs1 && s.c1 == 128 && s.c2 == 64 && mid_opt != 3;
+        // Train-mode BatchNorm over graph edges: the start side's primal rows once per run of equal src (start_runs_kernel).  The
+        // maps live in part1 (dead after finalize_batch_kernel), the compact rows' output sigmoids in pre1 (dead after ConvT2).
+        const size_t np_back = (size_t)back_nt * 32;
+        const bool dedup = batch_stats && src && dst && mid_pipe && back_mfma && !jac_node && !gs2 &&
+                           geo::options().jvp_start_dedup != 0 && (2 * slots + groups) * 4 <= tiles * s.n1 * 4 * 8 &&
+                           np_back <= (size_t)s.n1;
+        int32_t *row_map = reinterpret_cast<int32_t *>(part1), *rep = row_map + slots, *n_compact = rep + slots;
+        float *sg_compact = pre1;
+        const int64_t side_tiles = nch * pl.tiles_per_group;
+        if (dedup) {
+            start_runs_kernel<<<(unsigned)nch, 256, 0, stream>>>(src, e_base, n_edges, batch, pl.slots_per_group, row_map, rep,
+                                                                 n_compact);
+            GEO_LAUNCH_CHECK();
+        }
         if (mid_all && per_node) {
 #define GEO_MIDA_T(C1V, GNV)                                                                                       \
     mid_all_kernel<C1V, GNV, true><<<(unsigned)p_tiles, 512, 0, stream>>>(pre1, tpre1, k1, 0, pl.tiles_per_group,       \
@@ -1938,10 +2187,23 @@ int run_jvp(const geo_decoder_desc *dc, const float *z, int64_t n_nodes, const i
                 n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
             }
             const int per_cu = geo::options().jvp_pipe_grid > 0 ? geo::options().jvp_pipe_grid : 1;
-            const unsigned pgrid = (unsigned)std::min<int64_t>(p_tiles, (int64_t)n_cu * per_cu);   // persistent workgroups, one resident per CU
-            mid_pipe_kernel<<<pgrid, 512, 0, stream>>>(pre1, tpre1, k1, batch_stats ? 1 : 0, pl.tiles_per_group, (int)p_tiles,
-                                                       s.c2, B3, dc->b2, pre2, tpre2, part2, batch_stats ? 1 : 0, e_base,
-                                                       n_edges, batch);
+            const int64_t pipe_tiles = dedup ? side_tiles : p_tiles;                               // (dedup: the end side only)
+            const unsigned pgrid = (unsigned)std::min<int64_t>(pipe_tiles, (int64_t)n_cu * per_cu);   // persistent workgroups, one resident per CU
+#define GEO_PIPE(EO)                                                                                               \
+    mid_pipe_kernel<EO><<<pgrid, 512, 0, stream>>>(pre1, tpre1, k1, batch_stats ? 1 : 0, pl.tiles_per_group, (int)pipe_tiles, \
+                                                   s.c2, B3, dc->b2, pre2, tpre2, part2, batch_stats ? 1 : 0, e_base,  \
+                                                   n_edges, batch)
+            if (dedup) GEO_PIPE(true);
+            else GEO_PIPE(false);
+#undef GEO_PIPE
+            if (dedup) {                                        // compact primal rows first: the tangent launch gathers them
+                const dim3 sgrid((unsigned)((pl.tiles_per_group + 1) / 2), (unsigned)nch);
+                mid_start_kernel<false><<<dim3(1, (unsigned)nch), 512, 0, stream>>>(pre1, tpre1, k1, pl.tiles_per_group, B3, dc->b2, pre2, tpre2,
+                                                                   part2, row_map, rep, n_compact, e_base, n_edges, batch);
+                GEO_LAUNCH_CHECK();
+                mid_start_kernel<true><<<sgrid, 512, 0, stream>>>(pre1, tpre1, k1, pl.tiles_per_group, B3, dc->b2, pre2, tpre2,
+                                                                  part2, row_map, rep, n_compact, e_base, n_edges, batch);
+            }
         } else if (mid_all) {
 #define GEO_MIDA(C1V, GNV)                                                                                         \
     mid_all_kernel<C1V, GNV><<<(unsigned)p_tiles, 512, 0, stream>>>(pre1, tpre1, k1, batch_stats ? 1 : 0,           \
@@ -1996,7 +2258,21 @@ int run_jvp(const geo_decoder_desc *dc, const float *z, int64_t n_nodes, const i
     back_mfma_kernel<NTV, GNV, 1><<<(unsigned)p_tiles, 256, 0, stream>>>(pre2_node, tpre2, k2, 0, pl.tiles_per_group, s.co, \
                                                                          s.s_out, W3b, dc->b3, norms, gs2, sg_node, src,   \
                                                                          dst, e_base, n_edges, batch, jac_node, unit_d)
-        if (per_node && back_nt == 1) { if (gs2) GEO_BACK_T(1, true); else GEO_BACK_T(1, false); }
+#define GEO_BACK_D(NTV)                                                                                            \
+    do {                                                                                                            \
+    back_mfma_kernel<NTV, false, 0><<<(unsigned)side_tiles, 256, 0, stream>>>(                                      \
+        pre2, tpre2, k2, 1, pl.tiles_per_group, s.co, s.s_out, W3b, dc->b3, norms, nullptr, nullptr, nullptr, nullptr, \
+        0, 0, 1, nullptr, 0, nullptr, nullptr, 2);                                                                  \
+    back_mfma_kernel<NTV, false, 2><<<(unsigned)nch, 256, 0, stream>>>(                                      \
+        pre2, tpre2, k2, 1, pl.tiles_per_group, s.co, s.s_out, W3b, dc->b3, norms, nullptr, sg_compact, nullptr,     \
+        nullptr, 0, 0, 1, nullptr, 0, nullptr, n_compact, 1);                                                       \
+    back_mfma_kernel<NTV, false, 1><<<(unsigned)side_tiles, 256, 0, stream>>>(                                      \
+        pre2, tpre2, k2, 1, pl.tiles_per_group, s.co, s.s_out, W3b, dc->b3, norms, nullptr, sg_compact, nullptr,     \
+        nullptr, 0, 0, 1, nullptr, 0, row_map, nullptr, 1);                                                        \
+    } while (0)
+        if (dedup) { if (back_nt == 1) GEO_BACK_D(1); else GEO_BACK_D(6); }
+#undef GEO_BACK_D
+        else if (per_node && back_nt == 1) { if (gs2) GEO_BACK_T(1, true); else GEO_BACK_T(1, false); }
         else if (per_node) { if (gs2) GEO_BACK_T(6, true); else GEO_BACK_T(6, false); }
 #undef GEO_BACK_T
         else if (back_mfma && back_nt == 1) { if (gs2) GEO_BACK(1, true); else GEO_BACK(1, false); }
