@@ -360,7 +360,8 @@ size_t geo_kmeans_workspace_bytes(int64_t n, int32_t d, int32_t K, int32_t n_sta
 
 /* labels_out i32 [n], keys_out f64 [n] (may be NULL) = the key of the chosen centre.  A float32 matrix-core screen decides
  * most rows; rows within its proven error margin (kmeans.hip) are re-keyed exactly against every centre ("fallback rows"):
- * n_fallback_out [host, may be NULL] receives their number (synchronises when given). */
+ * n_fallback_out [host, may be NULL] receives their number (synchronises when given).  Non-finite input is outside the
+ * covered envelope; the fallback still ranks a NaN key first, so every label is in [0, K). */
 int geo_kmeans_assign(const float *X, int64_t n, int32_t d, const float *C, int32_t K, int32_t *labels_out, double *keys_out,
                       int64_t *n_fallback_out, void *ws, size_t ws_bytes, void *stream);
 
@@ -393,6 +394,26 @@ int geo_kmeans_lloyd(const float *X, int64_t n, int32_t d, int32_t K, int32_t n_
  * accumulated in fp64.  Fixed reduction order that depends on n_pix alone, no atomics: bit-identical across runs, streams,
  * batch sizes and positions in the batch.  Asynchronous on `stream`. */
 int geo_image_pair_moments(const float *x, const float *y, int64_t n_images, int64_t n_pix, double *mom_out, void *stream);
+
+/* ---- EMA vector quantizer (the reference's baseline VQ-VAE, VectorQuantizerEMA) ----
+ * z_e [B][C][HW] (NCHW, contiguous) f32 (half = 0) or f16 (half = 1), 1 <= C <= 128, 1 <= K <= 4096, any n = B HW >= 1 (K > n
+ * allowed).  Rows are z_e's positions (b, h, w) in that order, upcast to f32.  idx_out i64 [n] = geo_kmeans_assign's labels
+ * of the rows against embed f32 [K][C] (fp64 key, ties to the lowest code; a NaN key comes first, so a row holding a NaN or
+ * an infinity -- every key NaN or +inf -- gets code 0, and every label is in [0, K)).  z_q_out f32 NCHW = embed[idx] before the
+ * update; z_q_st_out f32 NCHW = fl32(z_e + fl32(z_q - z_e)).  loss_out f32 [1] = fl32(beta) * fl32(mean (z_q_st - z_e)^2);
+ * stats_out f32 [4] = q_mse (mean (z_q - z_e)^2), perplexity exp(-sum p log(p + 1e-12)), usage, dead of the batch's counts;
+ * the means are fp64 sums in a fixed association.  counts_out i32 [K] or NULL.  training != 0: the EMA update of
+ * cluster_size f32 [K], embed_avg f32 [K][C] and embed, in place, from the integer counts and the fp64 per-code sums in
+ * ascending row order.  No float atomics: bit-identical across runs, streams and workspace sizes.  Asynchronous. */
+size_t geo_vq_workspace_bytes(int64_t n, int32_t d, int32_t K);
+int geo_vq_forward(const void *z_e, int32_t half, int32_t B, int32_t C, int32_t HW, float *embed, float *cluster_size,
+                   float *embed_avg, int32_t K, int32_t training, double decay, double eps, double beta, float *z_q_out,
+                   float *z_q_st_out, int64_t *idx_out, float *loss_out, float *stats_out, int32_t *counts_out, void *ws,
+                   size_t ws_bytes, void *stream);
+/* grad_out (z_e's dtype) = cast(g_st + fl32(fl32(g_loss beta) fl32(2 / numel)) (z_e - z_q_st)), evaluated in f32 and rounded
+ * once.  g_st f32 [numel] and g_loss f32 [1] (device) may be NULL (zero).  Asynchronous. */
+int geo_vq_backward(const float *g_st, const float *g_loss, double beta, const void *z_e, int32_t half, const float *z_q_st,
+                    int64_t numel, void *grad_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,8 @@
 //   geo_kmeans_pp      k-means++ seeding, all n_init starts at once, from host-supplied draws (sklearn's _kmeans_plusplus).
 //   geo_kmeans_lloyd   the Lloyd loop of sklearn's _kmeans_single_lloyd for each start: exact labels, per-cluster fp64 sums in
 //                      ascending row order, empty-cluster relocation, centre shift, strict / tol / max_iter stopping.
+// and the EMA vector quantizer of the baseline VQ-VAE (geo_vq_forward / geo_vq_backward, end of the file), built on the same
+// assignment and cluster-sum kernels.
 //
 // Screening margin (geo_kmeans_assign).  Let u = 2^-24, x and c float32 vectors of dimension d, X = |x|^2, C = max_j |c_j|^2.
 //   screen  s_j = fl(fma(-2, dot_j, n_j)), dot_j the f32 fma chain of x.c_j (the MFMA is bit-for-bit that chain), n_j the f32
@@ -32,6 +34,7 @@
 // that depends on the shapes alone.
 #include "geo_common.h"
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -51,6 +54,16 @@ __device__ __forceinline__ double exact_key(const float *__restrict__ x, const f
         acc = fma(t, t, acc);
     }
     return acc;
+}
+
+// Order of (key, index) in the exact fallback: ascending key, ties to the lower index, a NaN key before every number (the
+// rule of torch.argmin).  On finite keys it is the plain (key, index) order; it also gives a row whose keys are all +inf or
+// NaN (a non-finite row or centre) a real index -- the first one -- instead of the loop's start value.
+__device__ __forceinline__ bool key_before(double a, int ia, double b, int ib) {
+    const bool na = isnan(a), nb = isnan(b);
+    if (na != nb) return na;
+    if (na) return ia < ib;
+    return a < b || (a == b && ia < ib);
 }
 
 // Loop status of one start, device resident.  The kernels of an iteration return at once when `done` is set, so the host
@@ -173,13 +186,13 @@ __global__ __launch_bounds__(256) void km_assign_kernel(const float *__restrict_
         int bj = 0x7fffffff;
         for (int j = lane; j < K; j += 64) {
             const double kj = exact_key(xr, C + (size_t)j * d, d);
-            if (kj < bk) { bk = kj; bj = j; }   // ascending j per lane: the first minimum stays
+            if (key_before(kj, j, bk, bj)) { bk = kj; bj = j; }   // ascending j per lane: the first minimum stays
         }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
             const double ok = __shfl_xor(bk, off);
             const int oj = __shfl_xor(bj, off);
-            if (ok < bk || (ok == bk && oj < bj)) { bk = ok; bj = oj; }
+            if (key_before(ok, oj, bk, bj)) { bk = ok; bj = oj; }
         }
         if (lane == rr) { label = bj; key = bk; }
     }
@@ -856,5 +869,324 @@ extern "C" int geo_kmeans_lloyd(const float *X, int64_t n, int32_t d, int32_t K,
         fallback_total += (int64_t)h2.n_fallback;
     }
     if (n_fallback_out) *n_fallback_out = fallback_total;
+    return GEO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// EMA vector quantizer (VectorQuantizerEMA of the reference's baseline VQ-VAE, models/vqvae.py:53-115), DESIGN.md section 11.
+// Same translation unit as the k-means kernels so that it launches their packing, screened assignment, counting sort and
+// cluster sums unchanged.  z_e is NCHW (f32 or f16), rows are its (b, h, w) positions in that order, d = C.
+//   forward   rows = f32(z_e) transposed; labels = geo_kmeans_assign's; z_q = embed[label] (pre-update); z_q_st =
+//             fl32(z_e + fl32(z_q - z_e)); fp64 sums of (z_q_st - z_e)^2 and (z_q - z_e)^2 per fixed block range, summed in
+//             a fixed order; counts; in training, the EMA update on the fp64 per-code sums in ascending row order (the
+//             counting sort of k-means, then tile runs summed in ascending tile order: balanced when a few codes take most
+//             rows, where k-means' one-block-per-cluster sum serialises).
+//   backward  grad = g_st + fl32(fl32(g_loss beta) fl32(2 / numel)) (z_e - z_q_st), rounded once to z_e's dtype.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int VQ_OUT_BLOCKS = 1024;   // most blocks of the fused output kernel (its fixed partition of the elements)
+
+// rows[(b HW + p) C + c] = f32(z[(b C + c) HW + p]) through a 32 x 32 LDS tile.  grid.x = B * ceil(HW / 32), grid.y = ceil(C / 32).
+template <typename T>
+__global__ __launch_bounds__(256) void vq_rows_kernel(const T *__restrict__ z, int C, int HW, int ptiles, float *__restrict__ rows) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.x / ptiles, p0 = (blockIdx.x % ptiles) * 32, c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int q = ty; q < 32; q += 8) {
+        const int c = c0 + q, p = p0 + tx;
+        if (c < C && p < HW) tile[q][tx] = (float)z[((int64_t)b * C + c) * HW + p];
+    }
+    __syncthreads();
+    for (int q = ty; q < 32; q += 8) {
+        const int p = p0 + q, c = c0 + tx;
+        if (p < HW && c < C) rows[((int64_t)b * HW + p) * C + c] = tile[tx][q];
+    }
+}
+
+// Sum of the block's per-thread values: butterfly inside each wave, then the four waves in ascending order (thread 0 returns it).
+__device__ __forceinline__ double block_sum_256(double v, double *wsum) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// z_q, z_q_st (f32 NCHW), idx (i64) and per-block fp64 partials of (z_q_st - z_e)^2 and (z_q - z_e)^2.  Block blk covers the
+// elements [blk per, (blk + 1) per), thread t the ones t, t + 256, ... ascending: the association depends on the shape alone.
+template <typename T>
+__global__ __launch_bounds__(256) void vq_out_kernel(const T *__restrict__ z, int C, int HW, int64_t total, int64_t per,
+                                                     const int32_t *__restrict__ labels, const float *__restrict__ E,
+                                                     float *__restrict__ zq_out, float *__restrict__ st_out,
+                                                     int64_t *__restrict__ idx_out, int64_t n, double *__restrict__ partial) {
+    __shared__ double wsum[2][4];
+    const int64_t e0 = (int64_t)blockIdx.x * per, e1 = min(total, e0 + per);
+    const int64_t chw = (int64_t)C * HW;
+    double a1 = 0.0, a2 = 0.0;
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) {
+        const int64_t b = e / chw, rem = e - b * chw;
+        const int c = (int)(rem / HW), p = (int)(rem - (int64_t)c * HW);
+        const float ze = (float)z[e];
+        const float zq = E[(int64_t)labels[b * HW + p] * C + c];
+        const float st = ze + (zq - ze);
+        zq_out[e] = zq;
+        st_out[e] = st;
+        const double d1 = (double)st - (double)ze, d2 = (double)zq - (double)ze;
+        a1 = fma(d1, d1, a1);
+        a2 = fma(d2, d2, a2);
+    }
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) idx_out[r] = labels[r];
+    const double s1 = block_sum_256(a1, wsum[0]);
+    const double s2 = block_sum_256(a2, wsum[1]);
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = s1;
+        partial[2 * blockIdx.x + 1] = s2;
+    }
+}
+
+// One block of 256: loss = fl32(fl32(beta) fl32(S1 / numel)); stats = (q_mse, perplexity, usage, dead) of the batch, from the
+// partials (ascending per thread, then block_sum_256) and the counts (usage = used / K, p = count / max(n, 1), perplexity =
+// exp(-sum p log(p + 1e-12)) in fp64).
+__global__ __launch_bounds__(256) void vq_metrics_kernel(const double *__restrict__ partial, int nblk, int64_t numel,
+                                                         const int32_t *__restrict__ counts, int K, int64_t n, float beta,
+                                                         float *__restrict__ loss_out, float *__restrict__ stats_out) {
+    __shared__ double wsum[4][4];
+    double a1 = 0.0, a2 = 0.0, h = 0.0, used = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 256) { a1 += partial[2 * b]; a2 += partial[2 * b + 1]; }
+    const double tot = (double)(n > 1 ? n : 1);
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const double p = (double)counts[k] / tot;
+        h += p * log(p + 1e-12);
+        used += counts[k] > 0 ? 1.0 : 0.0;
+    }
+    const double s1 = block_sum_256(a1, wsum[0]);
+    const double s2 = block_sum_256(a2, wsum[1]);
+    const double sh = block_sum_256(h, wsum[2]);
+    const double su = block_sum_256(used, wsum[3]);
+    if (threadIdx.x == 0) {
+        *loss_out = beta * (float)(s1 / (double)numel);
+        const float usage = (float)(su / (double)K);
+        stats_out[0] = (float)(s2 / (double)numel);
+        stats_out[1] = (float)exp(-sh);
+        stats_out[2] = usage;
+        stats_out[3] = 1.f - usage;
+    }
+}
+
+// Per-code fp64 sums over the rows sorted by code (order, offs from the counting sort), balanced for skewed codes: the sorted
+// rows are cut into tiles of VQ_SEG positions; vq_seg_kernel sums each code's run inside a tile in ascending row order and
+// stores it at the run's first position; vq_seg_sum_kernel adds a code's runs in ascending tile order.
+constexpr int VQ_SEG = 64;
+
+__global__ __launch_bounds__(128) void vq_seg_kernel(const float *__restrict__ X, int d, const int32_t *__restrict__ order,
+                                                     const int32_t *__restrict__ labels, int64_t n, double *__restrict__ seg) {
+    const int c = threadIdx.x;
+    const int64_t p0 = (int64_t)blockIdx.x * VQ_SEG, p1 = min(n, p0 + VQ_SEG);
+    if (c >= d || p0 >= n) return;
+    double a = 0.0;
+    int64_t start = p0;
+    int32_t cur = labels[order[p0]];
+    for (int64_t pos = p0; pos < p1; ++pos) {
+        const int32_t r = order[pos];
+        const int32_t lab = labels[r];
+        if (lab != cur) {
+            seg[start * d + c] = a;
+            a = 0.0;
+            start = pos;
+            cur = lab;
+        }
+        a += (double)X[(int64_t)r * d + c];
+    }
+    seg[start * d + c] = a;
+}
+
+__global__ __launch_bounds__(128) void vq_seg_sum_kernel(const double *__restrict__ seg, const int32_t *__restrict__ offs, int d,
+                                                         double *__restrict__ sums) {
+    const int k = blockIdx.x, c = threadIdx.x;
+    if (c >= d) return;
+    const int64_t m0 = offs[k], m1 = offs[k + 1];
+    double s = 0.0;
+    if (m1 > m0) {
+        const int64_t t0 = m0 / VQ_SEG, t1 = (m1 - 1) / VQ_SEG;
+#pragma unroll 8
+        for (int64_t t = t0; t <= t1; ++t) s += seg[max(m0, t * VQ_SEG) * d + c];
+    }
+    sums[(size_t)k * d + c] = s;
+}
+
+// EMA cluster sizes, one block of 1024: cs = fma(count, 1 - decay, fl32(cs decay)) in place; n = fl32(fp64 sum of the new cs,
+// ascending per thread then over the threads); norm[k] = max(fl32(fl32(fl32(cs + eps) / fl32(n + K eps)) n), eps).
+__global__ __launch_bounds__(1024) void vq_ema_size_kernel(float *__restrict__ cluster_size, const int32_t *__restrict__ counts,
+                                                           int K, float decay, float omd, float eps, float keps,
+                                                           float *__restrict__ norm) {
+    __shared__ double tsum[1024];
+    __shared__ float n_sh;
+    double a = 0.0;
+    for (int k = threadIdx.x; k < K; k += 1024) {
+        const float cs = fmaf((float)counts[k], omd, cluster_size[k] * decay);
+        cluster_size[k] = cs;
+        a += (double)cs;
+    }
+    tsum[threadIdx.x] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int t = 0; t < 1024; ++t) s += tsum[t];
+        n_sh = (float)s;
+    }
+    __syncthreads();
+    const float n = n_sh, denom = n + keps;
+    for (int k = threadIdx.x; k < K; k += 1024) norm[k] = fmaxf(((cluster_size[k] + eps) / denom) * n, eps);
+}
+
+// EMA embedding, one block per code: embed_avg = fma(f32(sum), 1 - decay, fl32(embed_avg decay)); embed = clamp(nan_to_num(
+// embed_avg / norm, nan 0, +inf 1, -inf -1), -2, 2).
+__global__ __launch_bounds__(128) void vq_ema_embed_kernel(const double *__restrict__ sums, const float *__restrict__ norm, int d,
+                                                           float decay, float omd, float *__restrict__ embed_avg,
+                                                           float *__restrict__ embed) {
+    const int k = blockIdx.x;
+    const float nk = norm[k];
+    for (int c = threadIdx.x; c < d; c += 128) {
+        const size_t i = (size_t)k * d + c;
+        const float ea = fmaf((float)sums[i], omd, embed_avg[i] * decay);
+        embed_avg[i] = ea;
+        float v = ea / nk;
+        if (isnan(v)) v = 0.f;
+        else if (isinf(v)) v = v > 0.f ? 1.f : -1.f;
+        embed[i] = fminf(fmaxf(v, -2.f), 2.f);
+    }
+}
+
+// grad = cast(g_st + coef (z_e - z_q_st)), coef = fl32(fl32(g_loss beta) fl32(2 / numel)); null g_st / g_loss count as zero.
+template <typename T>
+__global__ __launch_bounds__(256) void vq_backward_kernel(const float *__restrict__ g_st, const float *__restrict__ g_loss, float beta,
+                                                          float two_over_n, const T *__restrict__ z, const float *__restrict__ st,
+                                                          int64_t numel, T *__restrict__ grad) {
+    const float coef = g_loss ? (*g_loss * beta) * two_over_n : 0.f;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < numel; e += (int64_t)gridDim.x * 256) {
+        const float g = g_st ? g_st[e] : 0.f;
+        grad[e] = (T)(g + coef * ((float)z[e] - st[e]));
+    }
+}
+
+struct VqPlan {
+    Plan km;
+    float *rows, *norm;
+    int32_t *labels;
+    double *partial, *seg;
+    size_t bytes;
+};
+
+// Only what the quantizer's launches touch: the centre packing and status of the assignment, the counting sort and the sums.
+VqPlan vq_plan(int64_t n, int d, int K, void *ws) {
+    VqPlan v{};
+    Plan &p = v.km;
+    const int ns = ns_for(d), ntiles = (K + 31) / 32;
+    const int64_t nchunk = (n + CHUNK - 1) / CHUNK;
+    size_t off = 0;
+    auto take = [&](size_t bytes) -> char * {
+        char *r = ws ? static_cast<char *>(ws) + off : nullptr;
+        off += geo::align_up(bytes);
+        return r;
+    };
+    p.Ap = (float *)take((size_t)ntiles * ns * 64 * 4);
+    p.cnp = (float *)take((size_t)ntiles * 32 * 4);
+    p.st = (Status *)take(sizeof(Status));
+    p.chunk_hist = (int32_t *)take((size_t)nchunk * K * 4);
+    p.counts = (int32_t *)take((size_t)K * 4);
+    p.offs = (int32_t *)take((size_t)(K + 1) * 4);
+    p.order = (int32_t *)take((size_t)n * 4);
+    p.sums = (double *)take((size_t)K * d * 8);
+    v.rows = (float *)take((size_t)n * d * 4);
+    v.labels = (int32_t *)take((size_t)n * 4);
+    v.partial = (double *)take((size_t)VQ_OUT_BLOCKS * 2 * 8);
+    v.norm = (float *)take((size_t)K * 4);
+    v.seg = (double *)take((size_t)n * d * 8);
+    v.bytes = off;
+    return v;
+}
+
+int vq_check(const char *who, int64_t B, int C, int64_t HW, int K) {
+    GEO_REQUIRE(B >= 1 && HW >= 1 && B * HW < ((int64_t)1 << 31) - CHUNK, "%s: B=%lld HW=%lld", who, (long long)B, (long long)HW);
+    GEO_REQUIRE(C >= 1 && C <= MAX_D, "%s: C=%d (1..%d)", who, C, MAX_D);
+    GEO_REQUIRE(K >= 1 && K <= MAX_K, "%s: K=%d (1..%d)", who, K, MAX_K);
+    return GEO_OK;
+}
+
+}  // namespace
+
+extern "C" size_t geo_vq_workspace_bytes(int64_t n, int32_t d, int32_t K) {
+    if (n < 1 || n >= ((int64_t)1 << 31) - CHUNK || d < 1 || d > MAX_D || K < 1 || K > MAX_K) return 0;
+    return vq_plan(n, d, K, nullptr).bytes;
+}
+
+extern "C" int geo_vq_forward(const void *z_e, int32_t half, int32_t B, int32_t C, int32_t HW, float *embed, float *cluster_size,
+                              float *embed_avg, int32_t K, int32_t training, double decay, double eps, double beta, float *z_q_out,
+                              float *z_q_st_out, int64_t *idx_out, float *loss_out, float *stats_out, int32_t *counts_out,
+                              void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (int e = vq_check("geo_vq_forward", B, C, HW, K)) return e;
+    GEO_REQUIRE(z_e && embed && z_q_out && z_q_st_out && idx_out && loss_out && stats_out, "geo_vq_forward: null argument");
+    GEO_REQUIRE(!training || (cluster_size && embed_avg), "geo_vq_forward: training needs cluster_size and embed_avg");
+    GEO_REQUIRE(ws && ((uintptr_t)ws) % 256 == 0, "geo_vq_forward: workspace null or not 256-byte aligned");
+    const int64_t n = (int64_t)B * HW, total = n * C;
+    const VqPlan v = vq_plan(n, C, K, ws);
+    if (ws_bytes < vq_plan(n, C, K, nullptr).bytes) {
+        geo::set_error("geo_vq_forward: workspace %zu bytes too small", ws_bytes);
+        return GEO_E_WORKSPACE;
+    }
+    const Plan &p = v.km;
+    GEO_HIP_CHECK(hipMemsetAsync(p.st, 0, sizeof(Status), stream));
+    const int ptiles = (HW + 31) / 32;
+    const dim3 rgrid((unsigned)(B * ptiles), (unsigned)((C + 31) / 32));
+    if (half) vq_rows_kernel<_Float16><<<rgrid, 256, 0, stream>>>(static_cast<const _Float16 *>(z_e), C, HW, ptiles, v.rows);
+    else vq_rows_kernel<float><<<rgrid, 256, 0, stream>>>(static_cast<const float *>(z_e), C, HW, ptiles, v.rows);
+    GEO_LAUNCH_CHECK();
+    if (int e = launch_pack(embed, K, C, p, false, stream)) return e;
+    if (int e = launch_assign(v.rows, n, C, embed, K, p, v.labels, nullptr, 0, 0, stream)) return e;
+    const int nblk = (int)std::min<int64_t>(VQ_OUT_BLOCKS, (total + 2047) / 2048);
+    const int64_t per = (total + nblk - 1) / nblk;
+    if (half)
+        vq_out_kernel<_Float16><<<nblk, 256, 0, stream>>>(static_cast<const _Float16 *>(z_e), C, HW, total, per, v.labels, embed,
+                                                          z_q_out, z_q_st_out, idx_out, n, v.partial);
+    else
+        vq_out_kernel<float><<<nblk, 256, 0, stream>>>(static_cast<const float *>(z_e), C, HW, total, per, v.labels, embed, z_q_out,
+                                                       z_q_st_out, idx_out, n, v.partial);
+    GEO_LAUNCH_CHECK();
+    const int64_t nchunk = (n + CHUNK - 1) / CHUNK;
+    km_hist_kernel<<<(unsigned)nchunk, 256, (size_t)K * 4, stream>>>(v.labels, n, K, p.chunk_hist, p.st);
+    km_colscan_kernel<<<(K + 63) / 64, 1024, 0, stream>>>(p.chunk_hist, (int)nchunk, K, p.counts, p.st);
+    GEO_LAUNCH_CHECK();
+    if (training) {
+        const float decay_f = (float)decay, omd = (float)(1.0 - decay), eps_f = (float)eps, keps = (float)((double)K * eps);
+        km_offsets_kernel<<<1, 1024, 0, stream>>>(p.counts, K, p.offs, p.st);
+        km_scatter_kernel<<<(unsigned)nchunk, CHUNK, 0, stream>>>(v.labels, n, K, p.chunk_hist, p.offs, p.order, p.st);
+        vq_seg_kernel<<<(unsigned)((n + VQ_SEG - 1) / VQ_SEG), 128, 0, stream>>>(v.rows, C, p.order, v.labels, n, v.seg);
+        vq_seg_sum_kernel<<<K, 128, 0, stream>>>(v.seg, p.offs, C, p.sums);
+        vq_ema_size_kernel<<<1, 1024, 0, stream>>>(cluster_size, p.counts, K, decay_f, omd, eps_f, keps, v.norm);
+        vq_ema_embed_kernel<<<K, 128, 0, stream>>>(p.sums, v.norm, C, decay_f, omd, embed_avg, embed);
+        GEO_LAUNCH_CHECK();
+    }
+    vq_metrics_kernel<<<1, 256, 0, stream>>>(v.partial, nblk, total, p.counts, K, n, (float)beta, loss_out, stats_out);
+    GEO_LAUNCH_CHECK();
+    if (counts_out) GEO_HIP_CHECK(hipMemcpyAsync(counts_out, p.counts, (size_t)K * 4, hipMemcpyDeviceToDevice, stream));
+    return GEO_OK;
+}
+
+extern "C" int geo_vq_backward(const float *g_st, const float *g_loss, double beta, const void *z_e, int32_t half,
+                               const float *z_q_st, int64_t numel, void *grad_out, void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    GEO_REQUIRE(z_e && z_q_st && grad_out && numel >= 1, "geo_vq_backward: null argument or numel=%lld", (long long)numel);
+    const float two_over_n = (float)(2.0 / (double)numel);
+    const int grid = geo::grid_for(numel, 256, 8192);
+    if (half)
+        vq_backward_kernel<_Float16><<<grid, 256, 0, stream>>>(g_st, g_loss, (float)beta, two_over_n,
+                                                               static_cast<const _Float16 *>(z_e), z_q_st, numel,
+                                                               static_cast<_Float16 *>(grad_out));
+    else
+        vq_backward_kernel<float><<<grid, 256, 0, stream>>>(g_st, g_loss, (float)beta, two_over_n, static_cast<const float *>(z_e),
+                                                            z_q_st, numel, static_cast<float *>(grad_out));
+    GEO_LAUNCH_CHECK();
     return GEO_OK;
 }

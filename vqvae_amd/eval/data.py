@@ -3,7 +3,7 @@ root, and the transforms the reference's evaluation scripts apply (Resize, ToTen
 a missing file is a FileNotFoundError that names the paths looked for.
 
     <root>/FashionMNIST/raw/t10k-images-idx3-ubyte[.gz], t10k-labels-idx1-ubyte[.gz]
-    <root>/cifar-10-batches-py/test_batch
+    <root>/cifar-10-batches-py/test_batch, data_batch_1 .. data_batch_5
 """
 import gzip
 import os
@@ -47,16 +47,28 @@ def fashionmnist_test(root: str) -> Tuple[np.ndarray, np.ndarray]:
     return images, labels
 
 
+def _cifar10_batches(root: str, names) -> Tuple[np.ndarray, np.ndarray]:
+    images, labels = [], []
+    for name in names:
+        path = os.path.join(root, "cifar-10-batches-py", name)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"dataset file not found: {path}; nothing is downloaded, place the file there")
+        with open(path, "rb") as f:
+            entry = pickle.load(f, encoding="latin1")
+        images.append(np.asarray(entry["data"], dtype=np.uint8).reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1))
+        labels.append(np.asarray(entry["labels"] if "labels" in entry else entry["fine_labels"], dtype=np.int64))
+    return np.ascontiguousarray(np.concatenate(images)), np.concatenate(labels)
+
+
 def cifar10_test(root: str) -> Tuple[np.ndarray, np.ndarray]:
     """(images uint8 [N, 32, 32, 3], labels int64 [N]) of the CIFAR-10 test batch under `root` (torchvision's layout)."""
-    path = os.path.join(root, "cifar-10-batches-py", "test_batch")
-    if not os.path.exists(path):
-        raise FileNotFoundError(f"dataset file not found: {path}; nothing is downloaded, place the file there")
-    with open(path, "rb") as f:
-        entry = pickle.load(f, encoding="latin1")
-    images = np.asarray(entry["data"], dtype=np.uint8).reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)
-    labels = np.asarray(entry["labels"] if "labels" in entry else entry["fine_labels"], dtype=np.int64)
-    return np.ascontiguousarray(images), labels
+    return _cifar10_batches(root, ["test_batch"])
+
+
+def cifar10_train(root: str) -> Tuple[np.ndarray, np.ndarray]:
+    """(images uint8 [N, 32, 32, 3], labels int64 [N]) of the CIFAR-10 training split under `root`: data_batch_1 .. 5
+    concatenated in that order, which is torchvision's CIFAR10(train=True) order."""
+    return _cifar10_batches(root, [f"data_batch_{i}" for i in range(1, 6)])
 
 
 def load_test_split(name: str, root: str = "data") -> Tuple[np.ndarray, np.ndarray]:
