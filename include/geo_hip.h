@@ -296,6 +296,32 @@ int geo_decoder_jvp_edges(const geo_decoder_desc *dec, const float *z, int64_t n
                           const int32_t *src, const int32_t *dst, int64_t n_edges, int32_t batch_size,
                           float *len_out, void *ws, size_t ws_bytes, void *stream);
 
+/* Which kernels a geo_decoder_jvp_edges (graph_edges != 0) or geo_decoder_jvp_pairs (graph_edges = 0, n_nodes ignored) call with
+ * these sizes runs under the current options: the decision the call itself makes, host arithmetic only (no GPU call).
+ * ws_bytes = 0: a workspace as sized by the matching *_workspace_bytes query.  Negative (GEO_E_*, text in geo_last_error)
+ * where the call would refuse the decoder or the workspace. */
+#define GEO_JVP_FRONT_VALU 0        /* front_kernel */
+#define GEO_JVP_FRONT_MFMA 1        /* front_mfma_kernel */
+#define GEO_JVP_MID_PIPE 0          /* mid_pipe_kernel over every tile */
+#define GEO_JVP_MID_PIPE_DEDUP 1    /* mid_pipe_kernel over the end side + mid_start_kernel (start rows once per run of equal src) */
+#define GEO_JVP_MID_ALL 2           /* mid_all_kernel */
+#define GEO_JVP_MID_ALL_TANGENT 3   /* mid_all_kernel, tangent only, behind the per-node primal pass */
+#define GEO_JVP_MID_CHUNK 4         /* mid_bf16_kernel */
+#define GEO_JVP_BACK_MFMA 0         /* back_mfma_kernel, primal + tangent per slot */
+#define GEO_JVP_BACK_PER_NODE 1     /* back_mfma_kernel: primal once per latent, tangent per slot */
+#define GEO_JVP_BACK_DEDUP 2        /* back_mfma_kernel: end side per slot, start-side primal once per run of equal src */
+#define GEO_JVP_BACK_VALU 3         /* back_kernel */
+#define GEO_JVP_PLAN_FRONT(p) ((p) & 3)
+#define GEO_JVP_PLAN_DMAX(p) (16 << (((p) >> 2) & 3))   /* compiled latent width of the front kernel: 16, 32, 64 */
+#define GEO_JVP_PLAN_MID(p) (((p) >> 4) & 15)
+#define GEO_JVP_PLAN_BACK(p) (((p) >> 8) & 15)
+#define GEO_JVP_PER_NODE 0x1000      /* flag: primal pass once per latent */
+#define GEO_JVP_NODE_JACOBIAN 0x2000 /* flag: decoder Jacobian once per latent, edge ends from its columns */
+#define GEO_JVP_DEDUP 0x4000         /* flag: start-side primal rows once per run of equal src */
+#define GEO_JVP_PLAN_PASSES(p) ((p) >> 16)              /* passes over the (pseudo-)edges, capped at 32767 */
+int geo_jvp_plan(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size, int32_t graph_edges,
+                 size_t ws_bytes);
+
 /* Same quantity for explicit endpoint arrays (edge_lengths_riemannian's own signature):
  * z_start / z_end f32 [E][d]. */
 int geo_decoder_jvp_pairs(const geo_decoder_desc *dec, const float *z_start, const float *z_end,

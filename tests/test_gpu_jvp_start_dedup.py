@@ -26,6 +26,9 @@ def _both_modes(sd, d, cout, size, z, src, dst, bs, request):
     for mode in (1, 0):
         _lib.check(lib.geo_set_option(b"jvp_start_dedup", mode), "geo_set_option")
         ex = DecoderExport(_decoder(sd, d, cout, size, z.device), z.device)
+        r = _lib.decode_jvp_plan(lib.geo_jvp_plan(ex.desc, z.shape[0], src.numel(), bs, 1, 0))
+        assert (r["front"], r["mid"], r["back"], r["dedup"]) == (("valu", "pipe_dedup", "dedup", True) if mode else
+                                                                 ("valu", "pipe", "mfma", False))
         L = edge_lengths_graph_device(ex, z, src, dst, bs).cpu().numpy()
         stats = {k: ex.tensors[k].cpu().numpy().copy() for k in ("rm1", "rv1", "rm2", "rv2")}
         out[mode] = (L, stats)

@@ -16,6 +16,15 @@ E = 2048
 TOL = 1e-5
 
 
+def _route(ex, n_edges, bs, n_nodes=0, graph=False):
+    """The kernels the library says this call runs (geo_jvp_plan, host arithmetic): (front, mid, back, flags...), passes."""
+    from vqvae_amd import _lib
+    code = _lib.load().geo_jvp_plan(ex.desc, n_nodes, n_edges, bs, int(graph), 0)
+    assert code >= 0, _lib.load().geo_last_error()
+    r = _lib.decode_jvp_plan(code)
+    return (r["front"], r["mid"], r["back"]) + tuple(f for f in ("per_node", "node_jacobian", "dedup") if r[f]), r["passes"]
+
+
 def _decoder(name, training):
     from oracle import metric as om
     from vqvae_amd.spatial_decoder import SpatialDecoder
@@ -259,9 +268,16 @@ def test_per_node_primal_is_bit_identical_to_the_per_edge_end_path(norm, trainin
     request.addfinalizer(restore)
     _lib.check(_lib.load().geo_set_option(b"jvp_node_jacobian", 0), "geo_set_option")   # (its own test below: not bit-identical)
     out = {}
+    spg = (bs + 31) // 32 * 32                                  # slots of a (chunk, side) group; a pass holds at most 2^20 slots
+    fits = (n_nodes + 31) // 32 * 32 <= 2 * spg * min(-(-n_edges // bs), (1 << 20) // (2 * spg))
+    front = "valu" if d <= 16 else "mfma"
+    mid = "all" if norm == "group" else "pipe"
     for mode in (1, 0):
         _lib.check(_lib.load().geo_set_option(b"jvp_per_node", mode), "geo_set_option")
+        want = (front, "all_tangent", "per_node", "per_node") if mode and fits else (front, mid, "mfma")
+        assert _route(ex, n_edges, bs, n_nodes, graph=True)[0] == want
         out[mode] = edge_lengths_graph_device(ex, z, src, dst, bs).cpu().numpy()
+    assert _route(ex, n_edges, bs)[0] == (front, mid, "mfma")
     pairs = edge_lengths_device(ex, z[src.long()].contiguous(), z[dst.long()].contiguous(), bs).cpu().numpy()
     np.testing.assert_array_equal(out[1], out[0])
     np.testing.assert_array_equal(out[1], pairs)
@@ -308,8 +324,10 @@ def test_per_latent_jacobian_route_matches_the_per_edge_end_path(norm, training,
     lib = _lib.load()
     request.addfinalizer(lambda: lib.geo_set_option(b"jvp_node_jacobian", 1))
     _lib.check(lib.geo_set_option(b"jvp_node_jacobian", 0), "geo_set_option")
+    assert _route(ex, n_edges, bs, n_nodes, graph=True)[0] == ("valu", "all_tangent", "per_node", "per_node")
     per_edge_end = edge_lengths_graph_device(ex, z, src, dst, bs).cpu().numpy()
     _lib.check(lib.geo_set_option(b"jvp_node_jacobian", 2 if forced else 1), "geo_set_option")
+    assert _route(ex, n_edges, bs, n_nodes, graph=True)[0] == ("valu", "all_tangent", "per_node", "per_node", "node_jacobian")
     got = edge_lengths_graph_device(ex, z, src, dst, bs).cpu().numpy()
     assert not np.array_equal(got, per_edge_end)                 # (it did run: another summation order)
     ref64 = om.edge_lengths(sd, norm, size, z_h[src_h], z_h[dst_h], bs, training, dtype=torch.float64).numpy()
@@ -345,7 +363,9 @@ def test_per_latent_jacobian_route_over_several_passes(request):
     request.addfinalizer(lambda: lib.geo_set_option(b"jvp_node_jacobian", 1))
     _lib.check(lib.geo_set_option(b"jvp_node_jacobian", 0), "geo_set_option")
     per_edge_end = edge_lengths_graph_device(ex, z, src, dst, 512).cpu().numpy()
+    assert _route(ex, n_edges, 512, n_nodes, graph=True) == (("valu", "all_tangent", "per_node", "per_node"), 2)
     _lib.check(lib.geo_set_option(b"jvp_node_jacobian", 2), "geo_set_option")
+    assert _route(ex, n_edges, 512, n_nodes, graph=True) == (("valu", "all_tangent", "per_node", "per_node", "node_jacobian"), 2)
     got = edge_lengths_graph_device(ex, z, src, dst, 512).cpu().numpy()
     assert not np.array_equal(got, per_edge_end)
     rel = np.abs(got - per_edge_end) / per_edge_end
@@ -381,4 +401,64 @@ def test_per_latent_jacobian_route_is_not_taken_where_it_does_not_apply(request)
         off = edge_lengths_graph_device(ex, z, src, dst, 512).cpu().numpy()
         for mode in modes:
             _lib.check(lib.geo_set_option(b"jvp_node_jacobian", mode), "geo_set_option")
+            want = ("valu", "pipe_dedup", "dedup", "dedup") if training else ("valu" if d <= 16 else "mfma", "all_tangent", "per_node", "per_node")
+            assert _route(ex, n_edges, 512, n_nodes, graph=True)[0] == want
             np.testing.assert_array_equal(edge_lengths_graph_device(ex, z, src, dst, 512).cpu().numpy(), off)
+
+
+def _check_fallback(channels, cout, size, training, bs, want_route, seed=21):
+    """2 048 pairs through a route the default decoder does not take, against the fp64 closed form at the file's gate."""
+    from oracle import metric as om
+    from vqvae_amd._device import device
+    from vqvae_amd.geo.riemannian_metric import edge_lengths_device
+    from vqvae_amd.spatial_decoder import DecoderExport, SpatialDecoder, hip_kernels_cover
+    dev = device()
+    sd = om.make_decoder_state(seed, 16, cout, channels=channels, norm_type="batch")
+    dec = SpatialDecoder(cout, channels, 16, size, "batch")
+    dec.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    assert hip_kernels_cover(dec)
+    r = np.random.RandomState(100 + seed)
+    zs = r.randn(E, 16).astype(np.float32)
+    ze = (zs + 0.3 * r.randn(E, 16)).astype(np.float32)
+    ex = DecoderExport(dec.to(dev).train(training), dev)
+    assert _route(ex, E, bs)[0] == want_route
+    L = edge_lengths_device(ex, torch.from_numpy(zs).to(dev), torch.from_numpy(ze).to(dev), bs).cpu().numpy()
+    L64 = om.edge_lengths(sd, "batch", size, zs, ze, batch_size=bs, training=training, dtype=torch.float64).numpy()
+    rel64 = np.abs(L - L64) / np.abs(L64)
+    print(f"{channels} {cout}ch {size}px train={training} bs={bs} {want_route}: {np.mean(rel64 <= TOL):.4%} within {TOL}, "
+          f"max {rel64.max():.2e}, q99.9 {np.quantile(rel64, 0.999):.2e}")
+    assert np.mean(rel64 <= TOL) >= 0.999, (rel64.max(), np.quantile(rel64, 0.999))
+
+
+CHUNK_VALU, ALL_MFMA = ("valu", "chunk", "valu"), ("valu", "all", "mfma")    # mid_bf16_kernel + back_kernel; mid_all_kernel<64>
+
+
+@pytest.mark.parametrize("channels,want_route,training,bs", [
+    ((256, 128, 32), CHUNK_VALU, True, 512), ((256, 128, 32), CHUNK_VALU, True, 100),
+    ((256, 128, 32), CHUNK_VALU, False, 512), ((256, 128, 32), CHUNK_VALU, False, 100),
+    ((256, 64, 64), ALL_MFMA, True, 100), ((256, 64, 64), ALL_MFMA, False, 512), ((256, 64, 64), ALL_MFMA, False, 100),
+])
+def test_other_decoder_widths_vs_fp64(channels, want_route, training, bs):
+    """The live routes of other decoder widths: the per-chunk ConvT2 with the VALU ConvT3 (c2 != 64), the one-tile-per-workgroup
+    ConvT2 at c1 = 64.  Not in the gate: 256-64-64, train mode, batch 512 on these inputs -- 99.22 % of the 2 048 pairs within 1e-5
+    (16 beyond it, max 2.3e-3, 99.9th percentile 2.3e-5), the same figures from the library before and after the route refactor
+    (bit-identical lengths); DESIGN.md section 2."""
+    _check_fallback(channels, 1, 28, training, bs, want_route)
+
+
+@pytest.mark.parametrize("option,value,want_route", [(b"jvp_mid", 2, ("valu", "chunk", "mfma")), (b"jvp_mid", 3, ("valu", "all", "mfma")),
+                                                     (b"jvp_back_valu", 1, ("valu", "pipe", "valu"))])
+@pytest.mark.parametrize("bs", [512, 100])
+def test_default_decoder_through_the_optional_kernels_vs_fp64(option, value, want_route, bs, request):
+    """The default decoder through the kernels the A/B options select: per-chunk ConvT2, mid_all_kernel<128>, VALU ConvT3."""
+    from vqvae_amd import _lib
+    lib = _lib.load()
+    request.addfinalizer(lambda: lib.geo_set_option(option, 0))
+    _lib.check(lib.geo_set_option(option, value), "geo_set_option")
+    _check_fallback((256, 128, 64), 1, 28, True, bs, want_route)
+
+
+@pytest.mark.parametrize("bs", [512, 100])
+def test_one_channel_32px_head_vs_fp64(bs):
+    """64 outputs: the VALU ConvT3 behind the persistent ConvT2 kernel."""
+    _check_fallback((256, 128, 64), 1, 32, True, bs, ("valu", "pipe", "valu"))

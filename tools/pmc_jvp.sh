@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes over the JVP-only script (GPU box): one counter group per run, each under its own timeout.
-# usage: bash tools/pmc_jvp.sh <tag> <GEO_JVP_MID value>
+# usage: bash tools/pmc_jvp.sh <tag> <GEO_JVP_MID value: 0, c (per chunk) or a (one tile per workgroup)>
 tag=${1:-pmcjvp}; export GEO_JVP_MID=${2:-0}
 cd /tmp && export TMPDIR=/tmp
 i=0

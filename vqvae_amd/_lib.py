@@ -68,6 +68,7 @@ _SIGNATURES = {
     "geo_csr_compact_fill": (ctypes.c_int, [c_p, c_p, c_p, i32, c_p, i32, c_p, c_p, c_p, c_p, c_p]),
     "geo_jvp_workspace_bytes": (sz, [ctypes.POINTER(DecoderDesc), i64, i32]),
     "geo_jvp_edges_workspace_bytes": (sz, [ctypes.POINTER(DecoderDesc), i64, i64, i32]),
+    "geo_jvp_plan": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), i64, i64, i32, i32, sz]),
     "geo_decoder_jvp_edges": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, i64, c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
     "geo_decoder_jvp_pairs": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
     "geo_gather_edge_weights": (ctypes.c_int, [c_p, c_p, i64, c_p, c_p]),
@@ -87,6 +88,19 @@ _SIGNATURES = {
 }
 
 EXPORTS = tuple(_SIGNATURES)
+
+# geo_jvp_plan's encoding (the GEO_JVP_* constants of include/geo_hip.h)
+JVP_FRONT = ("valu", "mfma")
+JVP_MID = ("pipe", "pipe_dedup", "all", "all_tangent", "chunk")
+JVP_BACK = ("mfma", "per_node", "dedup", "valu")
+
+
+def decode_jvp_plan(code: int) -> dict:
+    """A non-negative geo_jvp_plan answer as names: front / mid / back kernels, the front's compiled width, flags, passes."""
+    assert code >= 0, code
+    return {"front": JVP_FRONT[code & 3], "dmax": 16 << ((code >> 2) & 3), "mid": JVP_MID[(code >> 4) & 15],
+            "back": JVP_BACK[(code >> 8) & 15], "per_node": bool(code & 0x1000), "node_jacobian": bool(code & 0x2000),
+            "dedup": bool(code & 0x4000), "passes": code >> 16}
 _lib = None
 
 

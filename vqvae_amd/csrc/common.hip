@@ -29,7 +29,6 @@ const OptionName kOptionNames[] = {
     {"jvp_front_valu", "GEO_JVP_FRONT_VALU", &Options::jvp_front_valu},
     {"jvp_per_node", "GEO_JVP_PER_NODE", &Options::jvp_per_node},
     {"jvp_node_jacobian", "GEO_JVP_NODE_JACOBIAN", &Options::jvp_node_jacobian},
-    {"jvp_pipe_grid", "GEO_JVP_PIPE_GRID", &Options::jvp_pipe_grid},
     {"jvp_start_dedup", "GEO_JVP_START_DEDUP", &Options::jvp_start_dedup},
 };
 Options from_environment() {
@@ -37,7 +36,7 @@ Options from_environment() {
     for (const OptionName &e : kOptionNames) {
         const char *v = getenv(e.env);
         if (!v) continue;
-        if (e.field == &Options::jvp_mid) o.jvp_mid = v[0] == 'f' ? 1 : (v[0] == 'c' ? 2 : (v[0] == 'a' ? 3 : atoi(v)));
+        if (e.field == &Options::jvp_mid) o.jvp_mid = v[0] == 'c' ? 2 : (v[0] == 'a' ? 3 : atoi(v));
         else o.*(e.field) = atoi(v);
     }
     return o;

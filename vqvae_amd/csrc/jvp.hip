@@ -12,13 +12,23 @@
 // (chunk, endpoint side) is one BatchNorm batch, exactly the batches riemannian_metric.py:50-58
 // feeds to the decoder, so train-mode batch statistics see the same samples.
 //
-// Kernels (activations are laid out [slot][pixel][channel], slot = padded sample position):
-//   front  (VALU)  pre1 = z . M01 + b01, M01 = conv_in o ConvT1 composed once in fp64 (no
-//                  nonlinearity sits between them); per-tile partial BN sums in fp64.
-//   mid    (MFMA)  v_mfma_f32_32x32x2_f32 GEMM for ConvT2 as a block-sparse product over
-//                  (input pixel -> output pixel) blocks; prologue = norm1 + ReLU on primal and
-//                  tangent while staging A into LDS; epilogue = bias, store, partial BN sums.
-//   back   (VALU)  norm2 + ReLU, ConvT3, sigmoid', squared norm per sample.
+// Kernels (activations: [slot][pixel][channel], slot = padded sample position) and the route that picks them (make_route, once
+// per call; geo_jvp_plan reports it):
+//   front  pre1 = z . M01 + b01, M01 = conv_in o ConvT1 composed once in fp64; per-tile partial BN sums in fp64.
+//            front_kernel (VALU)   d <= 16, or jvp_front_valu
+//            front_mfma_kernel     d > 16: v_mfma_f32_32x32x2_f32, the same k-ordered fmaf chain
+//   mid    ConvT2 as a block-sparse product over (input pixel -> output pixel) blocks on the bf16 matrix cores (f32 operands split
+//          exactly into three bf16 parts); prologue = norm1 + ReLU while staging A into LDS; epilogue = bias, store, BN sums.
+//            mid_pipe_kernel       PIPE: 256-128-64 with BatchNorm / no norm, persistent and skewed over the tiles; with dedup
+//                                  over the end side only, mid_start_kernel runs the start side once per run of equal src
+//            mid_all_kernel        ALL: c2 = 64 otherwise (GroupNorm, c1 = 64 / 32, jvp_mid = 3), one tile per workgroup;
+//                                  ALL_TANGENT: tangent only, behind the per-node primal pass
+//            mid_bf16_kernel       CHUNK: c2 != 64 or jvp_mid = 2, one workgroup per (tile, chunk of output pixels)
+//   back   norm2 + ReLU, ConvT3, sigmoid', squared norm per sample.
+//            back_mfma_kernel      c2 = 64 and 16 or 192 outputs: MODE 0 primal + tangent; MODE 2 then 1: the primal rows once
+//                                  (per latent: per_node; per run of equal src: dedup), then the tangents
+//            back_kernel (VALU)    every other head, or jvp_back_valu
+//   node_jacobian: the per_node kernels over unit tangents, then jacobian_lengths_kernel.
 #include "geo_common.h"
 
 #include <cmath>
@@ -435,91 +445,6 @@ __global__ __launch_bounds__(256) void group_stats_kernel(const float *__restric
         const double mt = st / n;
         const double mxt = (sxt - mu * st) * inv / n;
         out[i] = make_float4((float)mu, (float)inv, (float)mt, (float)(inv * mxt));
-    }
-}
-
-// ---------------------------------------------------------------------------------- mid (MFMA)
-// grid = (tiles, chunks).  LDS: A_p / A_t [TS][c1+1] f32 for the current input pixel.
-// Wave w computes columns [32w, 32w+32) of the chunk for the 32 primal and the 32 tangent rows.
-template <int C1>
-__global__ __launch_bounds__(256) void mid_kernel(const float *__restrict__ pre1, const float *__restrict__ tpre1,
-                                                 const NormConst *__restrict__ consts1, int consts_per_group,
-                                                 int tiles_per_group, ChunkTable tab, int opix_per_chunk, int c2,
-                                                 const float *__restrict__ B2p, const float *__restrict__ b2,
-                                                 float *__restrict__ pre2, float *__restrict__ tpre2,
-                                                 double *__restrict__ partial2, int want_stats,
-                                                 const int32_t *__restrict__ slot_valid) {
-    constexpr int LDA = C1 + 1;
-    __shared__ float Ap[TS * LDA];
-    __shared__ float At[TS * LDA];
-    __shared__ NormConst kc[C1];
-    const int tile = blockIdx.x, chunk = blockIdx.y;
-    const int group = tile / tiles_per_group;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n1 = 4 * C1, n2 = 16 * c2;
-    const size_t slot0 = (size_t)tile * TS;
-    for (int c = threadIdx.x; c < C1; c += 256) kc[c] = consts1[(size_t)(consts_per_group ? group : 0) * C1 + c];
-
-    f32x16 accp, acct;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { accp[i] = 0.f; acct[i] = 0.f; }
-
-    const int nblk = tab.nblk[chunk];
-    for (int blk = 0; blk < nblk; ++blk) {
-        const int ip = tab.ipix[chunk][blk];
-        __syncthreads();                       // previous block's MFMA reads are done (and kc is visible)
-        // stage A: thread -> (sample = tid/8, 16 consecutive channels)
-        {
-            const int s = threadIdx.x >> 3, k0 = (threadIdx.x & 7) * (C1 / 8);
-            const float *xp = pre1 + (slot0 + s) * n1 + (size_t)ip * C1 + k0;
-            const float *xt = tpre1 + (slot0 + s) * n1 + (size_t)ip * C1 + k0;
-#pragma unroll
-            for (int k = 0; k < C1 / 8; ++k) {
-                float a, ta;
-                norm_relu(kc[k0 + k], xp[k], xt[k], &a, &ta);
-                Ap[s * LDA + k0 + k] = a;
-                At[s * LDA + k0 + k] = ta;
-            }
-        }
-        // B fragment of this block: lane holds B[k = 2*st + (lane>>5)][col = 32*wave + (lane&31)]
-        float breg[C1 / 2];
-        const float *bsrc = B2p + (((size_t)chunk * MAX_BLOCKS + blk) * C1 + (lane >> 5)) * NC + wave * 32 + (lane & 31);
-#pragma unroll
-        for (int st = 0; st < C1 / 2; ++st) breg[st] = bsrc[(size_t)st * 2 * NC];
-        __syncthreads();
-        const float *ap = Ap + (lane & 31) * LDA + (lane >> 5);
-        const float *at = At + (lane & 31) * LDA + (lane >> 5);
-#pragma unroll
-        for (int st = 0; st < C1 / 2; ++st) {
-            accp = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * st], breg[st], accp, 0, 0, 0);
-            acct = __builtin_amdgcn_mfma_f32_32x32x2f32(at[2 * st], breg[st], acct, 0, 0, 0);
-        }
-    }
-
-    // epilogue: C[row = (r&3) + 8*(r>>2) + 4*(lane>>5)][col = lane&31]
-    const int col = wave * 32 + (lane & 31);
-    const int lo = col / c2, co = col % c2;
-    const bool col_ok = lo < opix_per_chunk;
-    const int op = col_ok ? tab.opix[chunk][lo] : 0;
-    const float bias = col_ok ? b2[co] : 0.f;
-    double sx = 0, sxx = 0, st_ = 0, sxt = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const float x = accp[r] + bias, t = acct[r];
-        if (col_ok) {
-            pre2[(slot0 + row) * n2 + (size_t)op * c2 + co] = x;
-            tpre2[(slot0 + row) * n2 + (size_t)op * c2 + co] = t;
-            if (slot_valid[slot0 + row]) { sx += x; sxx += (double)x * x; st_ += t; sxt += (double)x * t; }
-        }
-    }
-    if (want_stats) {
-        sx += __shfl_xor(sx, 32, 64); sxx += __shfl_xor(sxx, 32, 64);
-        st_ += __shfl_xor(st_, 32, 64); sxt += __shfl_xor(sxt, 32, 64);
-        if (lane < 32 && col_ok) {
-            double *p = partial2 + ((size_t)tile * n2 + (size_t)op * c2 + co) * 4;
-            p[0] = sx; p[1] = sxx; p[2] = st_; p[3] = sxt;
-        }
     }
 }
 
@@ -1851,7 +1776,7 @@ __global__ __launch_bounds__(256) void jacobian_lengths_kernel(const float *__re
     if (live && l == 0) len_out[e] = 0.5f * (end_norm[0] + end_norm[1]);
 }
 
-// ---------------------------------------------------------------------------------- host side
+// ---------------------------------------------------------------------------------- host side: shape, plan, route
 bool make_shape(const geo_decoder_desc *dc, Shape *s) {
     s->d = dc->latent_dim; s->c0 = dc->c0; s->c1 = dc->c1; s->c2 = dc->c2; s->co = dc->out_channels;
     if (dc->out_size == 28) { s->s_out = 4; s->pad3 = 3; }
@@ -1888,22 +1813,38 @@ void make_chunks(const Shape &s, ChunkTable *t) {
     }
 }
 
+// mid_all_kernel / mid_pipe_kernel / mid_start_kernel have the chunk table compiled in (MidGeom): it must be this table
+bool chunks_match_mid_geom(const ChunkTable &tab, int *bad_chunk) {
+    for (int ch = 0; ch < 8; ++ch) {
+        int nb = 0;
+        bool ok = true;
+        for (int ip = 0; ip < 4; ++ip) {
+            const int blk = MidGeom::blk_of(ch, ip);
+            if (blk >= 0) { ok = ok && tab.ipix[ch][blk] == ip; ++nb; }
+        }
+        ok = ok && nb == tab.nblk[ch] && tab.opix[ch][0] == MidGeom::opix(ch, 0) && tab.opix[ch][1] == MidGeom::opix(ch, 1);
+        if (!ok) { *bad_chunk = ch; return false; }
+    }
+    return true;
+}
+
 struct Plan {
     Shape sh;
     int batch, tiles_per_group, slots_per_group;
     int64_t chunks_per_pass;
     size_t bytes;
+    size_t pass_slots() const { return (size_t)chunks_per_pass * 2 * slots_per_group; }
 };
 
 constexpr int64_t MAX_SLOTS_PER_PASS = 1 << 20;      // bounds the activation workspace (~12.5 GB; the C2 graph takes two passes)
 
-// bytes of the per-node primal buffers (pre2 of every latent + the sigmoid of every output), 0 when the decoder / sizes do not
-// take that path
+size_t round_up_to_tile(int64_t n) { return n > 0 ? ((size_t)n + TS - 1) / TS * TS : 0; }
+
+// bytes of the per-node primal buffers (pre2 of every latent + the sigmoid of every output)
 size_t node_bytes(const Shape &s, int64_t n_nodes) {
     if (n_nodes <= 0) return 0;
-    const size_t node_slots = ((size_t)n_nodes + TS - 1) / TS * TS;
     const size_t np = (size_t)((s.p_out + 31) / 32) * 32;
-    return geo::align_up(node_slots * s.n2 * 4) + geo::align_up(node_slots * np * 4);
+    return geo::align_up(round_up_to_tile(n_nodes) * s.n2 * 4) + geo::align_up(round_up_to_tile(n_nodes) * np * 4);
 }
 
 bool make_plan(const geo_decoder_desc *dc, int64_t n_edges, int batch, Plan *p) {
@@ -1917,7 +1858,7 @@ bool make_plan(const geo_decoder_desc *dc, int64_t n_edges, int batch, Plan *p) 
     if (cpp > chunks) cpp = chunks > 0 ? chunks : 1;
     p->chunks_per_pass = cpp;
     const Shape &s = p->sh;
-    const size_t slots = (size_t)cpp * 2 * p->slots_per_group, tiles = slots / TS, groups = (size_t)cpp * 2;
+    const size_t slots = p->pass_slots(), tiles = slots / TS, groups = (size_t)cpp * 2;
     size_t b = 0;
     b += geo::align_up((size_t)s.d * s.n1 * 4) + geo::align_up((size_t)s.n1 * 4);          // M01, b01
     b += geo::align_up((size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC * 4);                   // B2p
@@ -1934,411 +1875,462 @@ bool make_plan(const geo_decoder_desc *dc, int64_t n_edges, int batch, Plan *p) 
     return true;
 }
 
-int run_jvp(const geo_decoder_desc *dc, const float *z, int64_t n_nodes, const int32_t *src, const int32_t *dst,
-            const float *z_start, const float *z_end, int64_t n_edges, int32_t batch, float *len_out, void *ws,
-            size_t ws_bytes, hipStream_t stream, float *jac_node = nullptr) {
-    // jac_node != nullptr (run_node_jacobian): the edges are pseudo-edges (latent pair, latent dimension), their tangents unit
-    // vectors; the outputs go to jac_node[latent][dimension][np] and no lengths are formed
-    GEO_REQUIRE(dc && (len_out || jac_node) && ws, "geo_decoder_jvp: null pointer");
-    GEO_REQUIRE(batch > 0, "geo_decoder_jvp: batch_size must be positive");
-    if (n_edges == 0) return GEO_OK;
-    Plan pl;
-    GEO_REQUIRE(make_plan(dc, n_edges, batch, &pl),
-                "geo_decoder_jvp: unsupported decoder (out_size %d, c2=%d must divide %d)", dc->out_size, dc->c2, NC);
-    const Shape &s = pl.sh;
-    GEO_REQUIRE(s.d >= 1 && s.d <= 64, "geo_decoder_jvp: latent_dim %d not in [1,64]", s.d);
-    GEO_REQUIRE(s.c1 == 128 || s.c1 == 64 || s.c1 == 32, "geo_decoder_jvp: dec_channels[1]=%d not in {32,64,128}", s.c1);
-    GEO_REQUIRE(dc->norm >= 0 && dc->norm <= 2, "geo_decoder_jvp: unknown norm code %d", dc->norm);
-    GEO_REQUIRE(s.c2 % 16 == 0, "geo_decoder_jvp: dec_channels[2]=%d must be a multiple of 16", s.c2);
-    const size_t back_lds = ((size_t)2 * BACK_TS * 16 * (s.c2 + 4) + (size_t)16 * s.co * (s.c2 + 4) +
-                             (size_t)BACK_TS * s.p_out) * 4;
-    GEO_REQUIRE(back_lds <= 160 * 1024, "geo_decoder_jvp: decoder too wide for the back kernel (%zu B LDS)", back_lds);
-    if (ws_bytes < pl.bytes) {
-        geo::set_error("geo_decoder_jvp: workspace %zu < %zu", ws_bytes, pl.bytes);
-        return GEO_E_WORKSPACE;
-    }
-    const size_t slots = (size_t)pl.chunks_per_pass * 2 * pl.slots_per_group, tiles = slots / TS;
-    const size_t groups = (size_t)pl.chunks_per_pass * 2;
-    geo::Arena ar(ws, ws_bytes);
-    float *M01 = ar.take<float>((size_t)s.d * s.n1);
-    float *b01 = ar.take<float>((size_t)s.n1);
-    float *B2p = ar.take<float>((size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC);
-    unsigned short *B3 = ar.take<unsigned short>((size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC * 3);
-    float *W3p = ar.take<float>((size_t)16 * s.co * s.c2);
-    unsigned short *W3b = ar.take<unsigned short>((size_t)16 * s.c2 * 192 * 3);
-    float *pre1 = ar.take<float>(slots * s.n1), *tpre1 = ar.take<float>(slots * s.n1);
-    float *pre2 = ar.take<float>(slots * s.n2), *tpre2 = ar.take<float>(slots * s.n2);
-    double *part1 = ar.take<double>(tiles * s.n1 * 4), *part2 = ar.take<double>(tiles * s.n2 * 4);
-    NormConst *k1 = ar.take<NormConst>((groups + 1) * s.c1), *k2 = ar.take<NormConst>((groups + 1) * s.c2);
-    float *norms = ar.take<float>(slots);
-    float2 *stats = ar.take<float2>((groups + 1) * (size_t)(s.c1 > s.c2 ? s.c1 : s.c2));
-    int32_t *slot_valid = ar.take<int32_t>(slots);
-    float4 *gs1 = nullptr, *gs2 = nullptr;
-    if (dc->norm == 2) {
-        gs1 = ar.take<float4>(slots * 32);
-        gs2 = ar.take<float4>(slots * 32);
-        GEO_REQUIRE(gs2 != nullptr, "geo_decoder_jvp: workspace carve failed");
-    }
-    GEO_REQUIRE(slot_valid != nullptr, "geo_decoder_jvp: workspace carve failed");
-    // per-node primal (see below): the buffers exist when the caller sized the workspace with geo_jvp_edges_workspace_bytes
-    const size_t node_slots = n_nodes > 0 ? ((size_t)n_nodes + TS - 1) / TS * TS : 0;
-    const size_t np_pad = (size_t)((s.p_out + 31) / 32) * 32;
-    float *pre2_node = nullptr, *sg_node = nullptr;
-    if (node_slots && node_slots <= slots && ws_bytes >= pl.bytes + node_bytes(s, n_nodes)) {
-        pre2_node = ar.take<float>(node_slots * s.n2);
-        sg_node = ar.take<float>(node_slots * np_pad);
-        if (!sg_node) pre2_node = nullptr;
-    }
+// Every decision of a call, made once by make_route (host arithmetic: no GPU call, no global): which kernels run, over what
+// tiling, in how much workspace.  The sizing queries, the run and geo_jvp_plan all read it from here.
+//   per_node       Fixed statistics (no norm layer, BatchNorm in eval mode, GroupNorm's primal) over graph edges: the primal is a
+//                  function of the latent, not of the edge -- 60 000 rows instead of 1.89 M edge ends.  One launch sequence over
+//                  the latents keeps pre2 and the output sigmoids per node; the edge slots carry the tangent alone and take the
+//                  ReLU masks and sigmoid' from their node's rows.  Same products in the same order: bit-identical to per slot.
+//                  (GroupNorm: the primal's statistics per latent, the tangent's own per slot.)
+//   node_jacobian  per_node and d <= 16: the passes run over pseudo-edges (latent pair, latent dimension) with unit tangents and
+//                  leave the Jacobian's columns per latent; each edge end is then |J(z_node) dz| from those columns.
+//   dedup          Train-mode BatchNorm over graph edges: the start side's primal rows once per run of equal src.  The maps live
+//                  in part1 (dead after finalize_batch_kernel), the compact rows' output sigmoids in pre1 (dead after ConvT2).
+enum { BACK_NODE_PRIMAL = 15 };      // launch_back only: ConvT3 of the per-node primal pass (never a route's `back`)
 
-    ChunkTable tab;
-    make_chunks(s, &tab);
-    if (s.n_chunks == 8 && s.opix_per_chunk == 2) {          // mid_all_kernel's compiled-in geometry must be this table
-        for (int ch = 0; ch < 8; ++ch) {
-            int nb = 0;
-            for (int ip = 0; ip < 4; ++ip) {
-                const int blk = MidGeom::blk_of(ch, ip);
-                if (blk >= 0) { GEO_REQUIRE(tab.ipix[ch][blk] == ip, "geo_decoder_jvp: chunk table / MidGeom mismatch (chunk %d)", ch); ++nb; }
-            }
-            GEO_REQUIRE(nb == tab.nblk[ch] && tab.opix[ch][0] == MidGeom::opix(ch, 0) && tab.opix[ch][1] == MidGeom::opix(ch, 1),
-                        "geo_decoder_jvp: chunk table / MidGeom mismatch (chunk %d)", ch);
-        }
-    }
-    compose_front_kernel<<<geo::grid_for((int64_t)(s.d + 1) * s.n1, 256), 256, 0, stream>>>(
-        dc->w_in, dc->b_in, dc->w1, dc->b1, s.d, s.c0, s.c1, M01, b01);
-    GEO_LAUNCH_CHECK();
-    pack_mid_kernel<<<geo::grid_for((int64_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC, 256), 256, 0, stream>>>(
-        dc->w2, s.c1, s.c2, tab, s.n_chunks, s.opix_per_chunk, B2p);
-    GEO_LAUNCH_CHECK();
-    pack_back_kernel<<<geo::grid_for(16 * s.co * s.c2, 256), 256, 0, stream>>>(dc->w3, s.c2, s.co, W3p);
-    GEO_LAUNCH_CHECK();
-    // ConvT2 on the matrix cores: bf16 x 3 split by default, exact-f32 MFMA with GEO_JVP_MID=f32
-    const int mid_opt = geo::options().jvp_mid;
-    const bool mid_split = mid_opt != 1 && s.c1 % 16 == 0;
-    const int back_nt = (s.p_out + 31) / 32;
-    const bool back_mfma = mid_split && s.c2 == 64 && (back_nt == 1 || back_nt == 6) && !geo::options().jvp_back_valu;
-    if (back_mfma) {
-        pack_back_bf16_kernel<<<geo::grid_for((int64_t)16 * s.c2 * back_nt * 32, 256), 256, 0, stream>>>(
-            dc->w3, s.c2, s.co, s.s_out, s.pad3, back_nt * 32, W3b);
-        GEO_LAUNCH_CHECK();
-    }
-    if (mid_split) {
-        pack_mid_bf16_kernel<<<geo::grid_for((int64_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC, 256), 256, 0, stream>>>(
-            B2p, s.c1, s.n_chunks, B3);
-        GEO_LAUNCH_CHECK();
-    }
-    if (dc->norm == 2) {
-        // the GroupNorm path exists for the 32-group layouts of the matrix-core kernels (reference default decoder)
-        GEO_REQUIRE(dc->groups1 == 32 && dc->groups2 == 32 && s.c2 == 64 && back_mfma && mid_split && s.n_chunks == 8 &&
-                        s.opix_per_chunk == 2 && mid_opt != 2,
-                    "geo_decoder_jvp: GroupNorm needs 32 groups per layer and dec_channels[2] == 64 (got %d/%d groups, c2=%d)",
-                    dc->groups1, dc->groups2, s.c2);
-    }
-    const bool batch_stats = dc->norm == 1 && dc->bn_train;
-    // train-mode BatchNorm with tracked statistics: the batches are folded into running_mean / running_var in call order
-    const bool track = batch_stats && dc->update_running && dc->rm1 && dc->rv1 && dc->rm2 && dc->rv2;
-    if (!batch_stats) {
-        finalize_fixed_kernel<<<1, 256, 0, stream>>>(s.c1, dc->norm, dc->g1, dc->be1, dc->rm1, dc->rv1, dc->eps, k1);
-        GEO_LAUNCH_CHECK();
-        finalize_fixed_kernel<<<1, 256, 0, stream>>>(s.c2, dc->norm, dc->g2, dc->be2, dc->rm2, dc->rv2, dc->eps, k2);
-        GEO_LAUNCH_CHECK();
-    }
-    // Per-node primal (round-2 review: "pre-activations depend on the node only"): with FIXED statistics (no norm layer,
-    // BatchNorm in eval mode) the whole primal pass is a function of the latent, not of the edge -- 60 000 rows instead of
-    // 1.89 M edge ends.  One launch sequence over the latents keeps pre2 and the output sigmoids per node; the edge slots then
-    // carry the tangent alone (ConvT2 and ConvT3 at half the matrix work, no primal stores), taking the ReLU masks and
-    // sigmoid' from their node's rows.  Same products in the same order: lengths are bit-identical to the per-slot path
-    // (`jvp_per_node = 0`).  GroupNorm's statistics are per sample, hence per latent for the primal; the tangent's own group
-    // statistics stay per slot (group_stats_kernel with the slot -> latent map).  Train-mode BatchNorm (batch statistics change
-    // with the chunk) keeps the per-slot path.
-    const bool mid_all_path = mid_split && s.n_chunks == 8 && s.opix_per_chunk == 2 && s.c1 >= 32 && mid_opt != 2;
-    const bool per_node = !batch_stats && src && dst && pre2_node && mid_all_path && back_mfma &&
-                          geo::options().jvp_per_node != 0;
-    GEO_REQUIRE(!jac_node || (per_node && s.d <= 16), "geo_decoder_jvp: per-latent Jacobians need the per-node primal path");
-    const int unit_d = jac_node ? s.d : 0;
-    if (per_node) {
-        const int64_t nt_node = (int64_t)(node_slots / TS);
-        const int big_batch = (int)node_slots;                  // one group: every latent on the "start" side
-#define GEO_FRONT_N(DM)                                                                                            \
-    front_kernel<DM><<<(unsigned)nt_node, 256, 0, stream>>>(nullptr, nullptr, nullptr, z, z, 0, n_nodes, big_batch,   \
-                                                            (int)nt_node, s.d, s.n1, M01, b01, pre1, tpre1, part1, 0)
-#define GEO_FRONT_MFMA_N(DM)                                                                                       \
-    front_mfma_kernel<DM><<<(unsigned)nt_node, 256, 0, stream>>>(nullptr, nullptr, nullptr, z, z, 0, n_nodes,         \
-                                                                 big_batch, (int)nt_node, s.d, s.n1, M01, b01, pre1,  \
-                                                                 tpre1, part1, 0)
-        const bool front_mfma_n = s.d > 16 && s.n1 % 32 == 0 && geo::options().jvp_front_valu == 0;
-        if (s.d <= 16) GEO_FRONT_N(16);
-        else if (s.d <= 32) { if (front_mfma_n) GEO_FRONT_MFMA_N(32); else GEO_FRONT_N(32); }
-        else { if (front_mfma_n) GEO_FRONT_MFMA_N(64); else GEO_FRONT_N(64); }
-#undef GEO_FRONT_MFMA_N
-#undef GEO_FRONT_N
-        GEO_LAUNCH_CHECK();
-        if (gs1) {
-            group_stats_kernel<<<geo::grid_for((int64_t)node_slots * 32, 256), 256, 0, stream>>>(pre1, tpre1, (int64_t)node_slots, 4,
-                                                                                                 s.c1, 32, dc->eps, gs1);
-            GEO_LAUNCH_CHECK();
-        }
-#define GEO_MIDA_N(C1V, GNV)                                                                                       \
-    mid_all_kernel<C1V, GNV><<<(unsigned)nt_node, 512, 0, stream>>>(pre1, tpre1, k1, 0, (int)nt_node, s.c2, B3,         \
-                                                                    dc->b2, pre2_node, tpre2, part2, 0, slot_valid,   \
-                                                                    gs1, 0, n_nodes, big_batch)
-        if (gs1) { if (s.c1 == 128) GEO_MIDA_N(128, true); else if (s.c1 == 64) GEO_MIDA_N(64, true); else GEO_MIDA_N(32, true); }
-        else if (s.c1 == 128) GEO_MIDA_N(128, false);
-        else if (s.c1 == 64) GEO_MIDA_N(64, false);
-        else GEO_MIDA_N(32, false);
-#undef GEO_MIDA_N
-        GEO_LAUNCH_CHECK();
-        if (gs2) {
-            group_stats_kernel<<<geo::grid_for((int64_t)node_slots * 32, 256), 256, 0, stream>>>(pre2_node, tpre2, (int64_t)node_slots,
-                                                                                                 16, s.c2, 32, dc->eps, gs2);
-            GEO_LAUNCH_CHECK();
-        }
-#define GEO_BACK_N(NTV, GNV)                                                                                       \
-    back_mfma_kernel<NTV, GNV, 2><<<(unsigned)nt_node, 256, 0, stream>>>(pre2_node, tpre2, k2, 0, (int)nt_node, s.co,   \
-                                                                         s.s_out, W3b, dc->b3, norms, gs2, sg_node)
-        if (back_nt == 1) { if (gs2) GEO_BACK_N(1, true); else GEO_BACK_N(1, false); }
-        else { if (gs2) GEO_BACK_N(6, true); else GEO_BACK_N(6, false); }
-#undef GEO_BACK_N
-        GEO_LAUNCH_CHECK();
-    }
-    const int64_t total_chunks = (n_edges + batch - 1) / batch;
-    for (int64_t c0 = 0; c0 < total_chunks; c0 += pl.chunks_per_pass) {
-        int64_t nch = total_chunks - c0;
-        if (nch > pl.chunks_per_pass) nch = pl.chunks_per_pass;
-        const int64_t e_base = c0 * batch;
-        int64_t e_count = n_edges - e_base;
-        if (e_count > nch * batch) e_count = nch * batch;
-        const int64_t p_groups = nch * 2, p_tiles = p_groups * pl.tiles_per_group, p_slots = p_tiles * TS;
-        slot_valid_kernel<<<geo::grid_for(p_slots, 256), 256, 0, stream>>>(e_base, n_edges, batch, pl.tiles_per_group,
-                                                                          p_slots, slot_valid);
-        GEO_LAUNCH_CHECK();
-#define GEO_FRONT(DM)                                                                                              \
-    front_kernel<DM><<<(unsigned)p_tiles, 256, 0, stream>>>(z, src, dst, z_start, z_end, e_base, n_edges, batch,    \
-                                                            pl.tiles_per_group, s.d, s.n1, M01, b01, pre1, tpre1,   \
-                                                            part1, batch_stats ? 1 : 0, unit_d)
-#define GEO_FRONT_MFMA(DM)                                                                                         \
-    front_mfma_kernel<DM><<<(unsigned)p_tiles, 256, 0, stream>>>(z, src, dst, z_start, z_end, e_base, n_edges, batch, \
-                                                                 pl.tiles_per_group, s.d, s.n1, M01, b01, pre1,       \
-                                                                 tpre1, part1, batch_stats ? 1 : 0)
-        const bool front_mfma = s.d > 16 && s.n1 % 32 == 0 && geo::options().jvp_front_valu == 0;
-        if (s.d <= 16) { if (geo::options().jvp_front_valu == 2 && s.n1 % 32 == 0 && !unit_d) GEO_FRONT_MFMA(16); else GEO_FRONT(16); }
-        else if (s.d <= 32) { if (front_mfma) GEO_FRONT_MFMA(32); else GEO_FRONT(32); }
-        else { if (front_mfma) GEO_FRONT_MFMA(64); else GEO_FRONT(64); }
-#undef GEO_FRONT_MFMA
-#undef GEO_FRONT
-        GEO_LAUNCH_CHECK();
-        if (batch_stats) {
-            finalize_batch_kernel<<<geo::grid_for(p_groups * s.c1, 256), 256, 0, stream>>>(
-                part1, pl.tiles_per_group, 1, 4, s.c1, e_base, n_edges, batch, dc->g1, dc->be1, dc->eps, k1, (int)p_groups,
-                track ? stats : nullptr);
-            if (track)
-                running_update_kernel<<<(unsigned)((s.c1 + 7) / 8), 256, 0, stream>>>(stats, (int)p_groups, s.c1, dc->momentum,
-                                                                          const_cast<float *>(dc->rm1), const_cast<float *>(dc->rv1));
-            GEO_LAUNCH_CHECK();
-        }
-        if (gs1) {
-            group_stats_kernel<<<geo::grid_for(p_slots * 32, 256), 256, 0, stream>>>(pre1, tpre1, p_slots, 4, s.c1, 32,
-                                                                                    dc->eps, gs1);
-            GEO_LAUNCH_CHECK();
-        }
-        const dim3 mgrid((unsigned)p_tiles, (unsigned)s.n_chunks);
-#define GEO_MID(C1V)                                                                                               \
-    mid_kernel<C1V><<<mgrid, 256, 0, stream>>>(pre1, tpre1, k1, batch_stats ? 1 : 0, pl.tiles_per_group, tab,       \
-                                               s.opix_per_chunk, s.c2, B2p, dc->b2, pre2, tpre2, part2,             \
-                                               batch_stats ? 1 : 0, slot_valid)
-#define GEO_MID3(C1V)                                                                                              \
-    mid_bf16_kernel<C1V><<<mgrid, 256, 0, stream>>>(pre1, tpre1, k1, batch_stats ? 1 : 0, pl.tiles_per_group, tab,  \
-                                                    s.opix_per_chunk, s.c2, B3, dc->b2, pre2, tpre2, part2,        \
-                                                    batch_stats ? 1 : 0, slot_valid)
-        const bool mid_all = mid_split && s.n_chunks == 8 && s.opix_per_chunk == 2 && s.c1 >= 32 &&
-                             mid_opt != 2;
-        // the shipped widths with BatchNorm / no norm, primal + tangent: the persistent skewed kernel (jvp_mid = 3: mid_all_kernel)
-        const bool mid_pipe = mid_all && !per_node && !gs1 && s.c1 == 128 && s.c2 == 64 && mid_opt != 3;
-        // Train-mode BatchNorm over graph edges: the start side's primal rows once per run of equal src (start_runs_kernel).  The
-        // maps live in part1 (dead after finalize_batch_kernel), the compact rows' output sigmoids in pre1 (dead after ConvT2).
-        const size_t np_back = (size_t)back_nt * 32;
-        const bool dedup = batch_stats && src && dst && mid_pipe && back_mfma && !jac_node && !gs2 &&
-                           geo::options().jvp_start_dedup != 0 && (2 * slots + groups) * 4 <= tiles * s.n1 * 4 * 8 &&
-                           np_back <= (size_t)s.n1;
-        int32_t *row_map = reinterpret_cast<int32_t *>(part1), *rep = row_map + slots, *n_compact = rep + slots;
-        float *sg_compact = pre1;
-        const int64_t side_tiles = nch * pl.tiles_per_group;
-        if (dedup) {
-            start_runs_kernel<<<(unsigned)nch, 256, 0, stream>>>(src, e_base, n_edges, batch, pl.slots_per_group, row_map, rep,
-                                                                 n_compact);
-            GEO_LAUNCH_CHECK();
-        }
-        if (mid_all && per_node) {
-#define GEO_MIDA_T(C1V, GNV)                                                                                       \
-    mid_all_kernel<C1V, GNV, true><<<(unsigned)p_tiles, 512, 0, stream>>>(pre1, tpre1, k1, 0, pl.tiles_per_group,       \
-                                                                          s.c2, B3, dc->b2, pre2, tpre2, part2, 0,     \
-                                                                          slot_valid, gs1, e_base, n_edges, batch)
-            if (gs1) { if (s.c1 == 128) GEO_MIDA_T(128, true); else if (s.c1 == 64) GEO_MIDA_T(64, true); else GEO_MIDA_T(32, true); }
-            else if (s.c1 == 128) GEO_MIDA_T(128, false);
-            else if (s.c1 == 64) GEO_MIDA_T(64, false);
-            else GEO_MIDA_T(32, false);
-#undef GEO_MIDA_T
-        } else if (mid_pipe) {
-            static int n_cu = 0;
-            if (n_cu == 0) {
-                int devid = 0;
-                hipDeviceProp_t prop;
-                GEO_HIP_CHECK(hipGetDevice(&devid));
-                GEO_HIP_CHECK(hipGetDeviceProperties(&prop, devid));
-                n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-            }
-            const int per_cu = geo::options().jvp_pipe_grid > 0 ? geo::options().jvp_pipe_grid : 1;
-            const int64_t pipe_tiles = dedup ? side_tiles : p_tiles;                               // (dedup: the end side only)
-            const unsigned pgrid = (unsigned)std::min<int64_t>(pipe_tiles, (int64_t)n_cu * per_cu);   // persistent workgroups, one resident per CU
-#define GEO_PIPE(EO)                                                                                               \
-    mid_pipe_kernel<EO><<<pgrid, 512, 0, stream>>>(pre1, tpre1, k1, batch_stats ? 1 : 0, pl.tiles_per_group, (int)pipe_tiles, \
-                                                   s.c2, B3, dc->b2, pre2, tpre2, part2, batch_stats ? 1 : 0, e_base,  \
-                                                   n_edges, batch)
-            if (dedup) GEO_PIPE(true);
-            else GEO_PIPE(false);
-#undef GEO_PIPE
-            if (dedup) {                                        // compact primal rows first: the tangent launch gathers them
-                const dim3 sgrid((unsigned)((pl.tiles_per_group + 1) / 2), (unsigned)nch);
-                mid_start_kernel<false><<<dim3(1, (unsigned)nch), 512, 0, stream>>>(pre1, tpre1, k1, pl.tiles_per_group, B3, dc->b2, pre2, tpre2,
-                                                                   part2, row_map, rep, n_compact, e_base, n_edges, batch);
-                GEO_LAUNCH_CHECK();
-                mid_start_kernel<true><<<sgrid, 512, 0, stream>>>(pre1, tpre1, k1, pl.tiles_per_group, B3, dc->b2, pre2, tpre2,
-                                                                  part2, row_map, rep, n_compact, e_base, n_edges, batch);
-            }
-        } else if (mid_all) {
-#define GEO_MIDA(C1V, GNV)                                                                                         \
-    mid_all_kernel<C1V, GNV><<<(unsigned)p_tiles, 512, 0, stream>>>(pre1, tpre1, k1, batch_stats ? 1 : 0,           \
-                                                                    pl.tiles_per_group, s.c2, B3, dc->b2,           \
-                                                                    pre2, tpre2, part2, batch_stats ? 1 : 0,        \
-                                                                    slot_valid, gs1, e_base, n_edges, batch)
-            if (gs1) {
-                if (s.c1 == 128) GEO_MIDA(128, true);
-                else if (s.c1 == 64) GEO_MIDA(64, true);
-                else GEO_MIDA(32, true);
-            } else if (s.c1 == 128) GEO_MIDA(128, false);
-            else if (s.c1 == 64) GEO_MIDA(64, false);
-            else GEO_MIDA(32, false);
-#undef GEO_MIDA
-        } else if (mid_split) {
-            if (s.c1 == 128) GEO_MID3(128);
-            else if (s.c1 == 64) GEO_MID3(64);
-            else GEO_MID3(32);
-        } else {
-            if (s.c1 == 128) GEO_MID(128);
-            else if (s.c1 == 64) GEO_MID(64);
-            else GEO_MID(32);
-        }
-#undef GEO_MID3
-#undef GEO_MID
-        GEO_LAUNCH_CHECK();
-        if (batch_stats) {
-            finalize_batch_kernel<<<geo::grid_for(p_groups * s.c2, 256), 256, 0, stream>>>(
-                part2, pl.tiles_per_group, mid_pipe ? 4 : (mid_all ? 1 : 16), 16, s.c2, e_base, n_edges, batch, dc->g2, dc->be2, dc->eps, k2, (int)p_groups,
-                track ? stats : nullptr);
-            if (track)
-                running_update_kernel<<<(unsigned)((s.c2 + 7) / 8), 256, 0, stream>>>(stats, (int)p_groups, s.c2, dc->momentum,
-                                                                          const_cast<float *>(dc->rm2), const_cast<float *>(dc->rv2));
-            GEO_LAUNCH_CHECK();
-        }
-        if (gs2 && per_node) {                                  // (slot_valid is not read on this path: it carries the slot -> latent map)
-            slot_node_kernel<<<geo::grid_for(p_slots, 256), 256, 0, stream>>>(src, dst, e_base, n_edges, batch, pl.tiles_per_group,
-                                                                             p_slots, slot_valid);
-            group_stats_kernel<<<geo::grid_for(p_slots * 32, 256), 256, 0, stream>>>(pre2_node, tpre2, p_slots, 16, s.c2, 32,
-                                                                                    dc->eps, gs2, slot_valid);
-            GEO_LAUNCH_CHECK();
-        } else if (gs2) {
-            group_stats_kernel<<<geo::grid_for(p_slots * 32, 256), 256, 0, stream>>>(pre2, tpre2, p_slots, 16, s.c2, 32,
-                                                                                    dc->eps, gs2);
-            GEO_LAUNCH_CHECK();
-        }
-#define GEO_BACK(NTV, GNV)                                                                                         \
-    back_mfma_kernel<NTV, GNV><<<(unsigned)p_tiles, 256, 0, stream>>>(pre2, tpre2, k2, batch_stats ? 1 : 0,         \
-                                                                      pl.tiles_per_group, s.co, s.s_out, W3b,       \
-                                                                      dc->b3, norms, gs2)
-#define GEO_BACK_T(NTV, GNV)                                                                                       \
-    back_mfma_kernel<NTV, GNV, 1><<<(unsigned)p_tiles, 256, 0, stream>>>(pre2_node, tpre2, k2, 0, pl.tiles_per_group, s.co, \
-                                                                         s.s_out, W3b, dc->b3, norms, gs2, sg_node, src,   \
-                                                                         dst, e_base, n_edges, batch, jac_node, unit_d)
-#define GEO_BACK_D(NTV)                                                                                            \
-    do {                                                                                                            \
-    back_mfma_kernel<NTV, false, 0><<<(unsigned)side_tiles, 256, 0, stream>>>(                                      \
-        pre2, tpre2, k2, 1, pl.tiles_per_group, s.co, s.s_out, W3b, dc->b3, norms, nullptr, nullptr, nullptr, nullptr, \
-        0, 0, 1, nullptr, 0, nullptr, nullptr, 2);                                                                  \
-    back_mfma_kernel<NTV, false, 2><<<(unsigned)nch, 256, 0, stream>>>(                                      \
-        pre2, tpre2, k2, 1, pl.tiles_per_group, s.co, s.s_out, W3b, dc->b3, norms, nullptr, sg_compact, nullptr,     \
-        nullptr, 0, 0, 1, nullptr, 0, nullptr, n_compact, 1);                                                       \
-    back_mfma_kernel<NTV, false, 1><<<(unsigned)side_tiles, 256, 0, stream>>>(                                      \
-        pre2, tpre2, k2, 1, pl.tiles_per_group, s.co, s.s_out, W3b, dc->b3, norms, nullptr, sg_compact, nullptr,     \
-        nullptr, 0, 0, 1, nullptr, 0, row_map, nullptr, 1);                                                        \
-    } while (0)
-        if (dedup) { if (back_nt == 1) GEO_BACK_D(1); else GEO_BACK_D(6); }
-#undef GEO_BACK_D
-        else if (per_node && back_nt == 1) { if (gs2) GEO_BACK_T(1, true); else GEO_BACK_T(1, false); }
-        else if (per_node) { if (gs2) GEO_BACK_T(6, true); else GEO_BACK_T(6, false); }
-#undef GEO_BACK_T
-        else if (back_mfma && back_nt == 1) { if (gs2) GEO_BACK(1, true); else GEO_BACK(1, false); }
-        else if (back_mfma) { if (gs2) GEO_BACK(6, true); else GEO_BACK(6, false); }
-#undef GEO_BACK
-        else
-            back_kernel<<<(unsigned)(p_slots / BACK_TS), 256, back_lds, stream>>>(
-                pre2, tpre2, k2, batch_stats ? 1 : 0, pl.slots_per_group, s.c2, s.co, s.s_out, s.pad3, W3p, dc->b3, norms);
-        GEO_LAUNCH_CHECK();
-        if (len_out) {
-            combine_kernel<<<geo::grid_for(e_count, 256), 256, 0, stream>>>(norms, e_base, e_count, batch,
-                                                                            pl.slots_per_group, len_out);
-            GEO_LAUNCH_CHECK();
-        }
-    }
-    return GEO_OK;
-}
-
-// Per-latent Jacobians (kernels above): which calls take that route, its workspace, and the run.
-struct JacobianPlan {
-    int64_t n_pseudo;
-    size_t np, extra_bytes, bytes;                            // extra: pseudo-edge lists + the columns; bytes: extra + inner run
+struct Route {
+    int status = GEO_OK;             // what the run answers for this decoder / workspace; `error` is geo_last_error's text
+    char error[192] = "";
+    Plan pl = {};                    // shape and tiling of the passes (node_jacobian: over the pseudo-edges)
+    int64_t run_edges = 0, passes = 0;                          // edges the passes cover (node_jacobian: pseudo-edges)
+    bool batch_stats = false, track = false, group_norm = false;
+    int front = GEO_JVP_FRONT_VALU, dmax = 16;                  // GEO_JVP_FRONT_*, compiled latent width of the front kernel
+    int mid = GEO_JVP_MID_CHUNK, back = GEO_JVP_BACK_VALU;      // GEO_JVP_MID_*, GEO_JVP_BACK_*
+    int back_nt = 0;                                            // 32-column output tiles of the matrix-core ConvT3 (1 or 6)
+    int parts2 = 16;                 // partial-sum rows per tile that the ConvT2 kernel leaves for finalize_batch_kernel
+    bool per_node = false, node_jacobian = false, dedup = false;
+    size_t back_lds = 0;             // dynamic LDS of back_kernel
+    size_t jac_np = 0, jac_extra_bytes = 0;                     // node_jacobian: padded outputs per column; pseudo-edge lists + columns
+    size_t bytes = 0;                // workspace as the matching *_workspace_bytes query sizes it (0: no answer)
 };
 
-bool node_jacobian_plan(const geo_decoder_desc *dc, int64_t n_nodes, int64_t n_edges, int batch, JacobianPlan *jp) {
-    const geo::Options &o = geo::options();
-    Shape s;
-    if (!dc || n_nodes <= 0 || n_edges <= 0 || !make_shape(dc, &s)) return false;
-    if (o.jvp_node_jacobian == 0 || o.jvp_per_node == 0 || o.jvp_back_valu || o.jvp_mid == 1 || o.jvp_mid == 2) return false;
-    if (dc->norm == 1 && dc->bn_train) return false;          // batch statistics: the Jacobian depends on the edge's batch
-    if (s.d > 16 || s.c1 % 16 != 0 || s.c1 < 32 || s.c2 != 64 || s.n_chunks != 8 || s.opix_per_chunk != 2) return false;
-    const int back_nt = (s.p_out + 31) / 32;
-    if (back_nt != 1 && back_nt != 6) return false;
-    // worth it from ~1.5 x fewer slots (the columns pass stores and the edge pass re-reads p_out x d floats per latent)
-    if (o.jvp_node_jacobian == 1 && 4 * n_edges < 3 * n_nodes * s.d) return false;
-    jp->n_pseudo = (n_nodes + 1) / 2 * s.d;
-    if (jp->n_pseudo >= (int64_t)1 << 31) return false;
-    jp->np = (size_t)back_nt * 32;
-    Plan pl;
-    if (!make_plan(dc, jp->n_pseudo, batch, &pl)) return false;
-    const size_t node_slots = ((size_t)n_nodes + TS - 1) / TS * TS;
-    if (node_slots > (size_t)pl.chunks_per_pass * 2 * pl.slots_per_group) return false;     // per-node primal would not fit a pass
-    jp->extra_bytes = 2 * geo::align_up((size_t)jp->n_pseudo * 4) + geo::align_up((size_t)n_nodes * s.d * jp->np * 4);
-    jp->bytes = jp->extra_bytes + pl.bytes + node_bytes(s, n_nodes);
+bool route_error(Route *r, int status, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(r->error, sizeof(r->error), fmt, ap);
+    va_end(ap);
+    r->status = status;
+    return false;
+}
+
+// ws_bytes = nullptr: the workspace is what the matching query returns.  The sizes are filled in whenever the shape parses, also for a
+// decoder the run refuses (status != GEO_OK): the queries answer for those as they always have.
+bool make_route(const geo_decoder_desc *dc, const geo::Options &o, bool graph_edges, int64_t n_nodes, int64_t n_edges, int batch,
+                const size_t *ws_bytes, Route *r) {
+    *r = Route{};
+    if (!dc) return route_error(r, GEO_E_ARG, "geo_decoder_jvp: null pointer");
+    if (batch <= 0) return route_error(r, GEO_E_ARG, "geo_decoder_jvp: batch_size must be positive");
+    Plan base;
+    if (n_edges < 0 || n_nodes < 0 || !make_plan(dc, n_edges, batch, &base))
+        return route_error(r, GEO_E_ARG, "geo_decoder_jvp: unsupported decoder (out_size %d, c2=%d must divide %d)", dc->out_size,
+                           dc->c2, NC);
+    const Shape &s = base.sh;
+
+    // ---- kernels by decoder shape and options
+    r->batch_stats = dc->norm == 1 && dc->bn_train;
+    // train-mode BatchNorm with tracked statistics: the batches are folded into running_mean / running_var in call order
+    r->track = r->batch_stats && dc->update_running && dc->rm1 && dc->rv1 && dc->rm2 && dc->rv2;
+    r->group_norm = dc->norm == 2;
+    r->dmax = s.d <= 16 ? 16 : (s.d <= 32 ? 32 : 64);
+    r->front = s.d > 16 && s.n1 % 32 == 0 && o.jvp_front_valu == 0 ? GEO_JVP_FRONT_MFMA : GEO_JVP_FRONT_VALU;
+    r->back_nt = (s.p_out + 31) / 32;
+    // the one-tile-per-workgroup / persistent ConvT2 kernels: 8 chunks of 2 output pixels (c2 = 64); jvp_mid = 2 keeps the per-chunk one
+    const bool mid_all = s.c1 % 16 == 0 && s.c1 >= 32 && s.n_chunks == 8 && s.opix_per_chunk == 2 && o.jvp_mid != 2;
+    // the shipped widths with BatchNorm / no norm: the persistent skewed kernel (jvp_mid = 3: mid_all_kernel)
+    const bool mid_pipe = mid_all && !r->group_norm && s.c1 == 128 && s.c2 == 64 && o.jvp_mid != 3;
+    const bool back_mfma = s.c1 % 16 == 0 && s.c2 == 64 && (r->back_nt == 1 || r->back_nt == 6) && !o.jvp_back_valu;
+    const bool per_node_kernels = graph_edges && !r->batch_stats && mid_all && back_mfma && o.jvp_per_node != 0;
+
+    // ---- workspace of the call, and what a given workspace leaves room for
+    const size_t node_slots = round_up_to_tile(n_nodes);
+    const size_t per_edge_end_bytes = base.bytes + (graph_edges ? node_bytes(s, n_nodes) : 0);
+    // per-latent Jacobians: worth it from ~1.5 x fewer slots (the columns pass stores and the edge pass re-reads p_out x d floats
+    // per latent); option 2 takes the route whenever it applies
+    Plan jpl;
+    const int64_t n_pseudo = (n_nodes + 1) / 2 * s.d;
+    size_t jac_bytes = 0;
+    if (per_node_kernels && n_nodes > 0 && n_edges > 0 && s.d <= 16 && o.jvp_node_jacobian != 0 &&
+        (o.jvp_node_jacobian != 1 || 4 * n_edges >= 3 * n_nodes * s.d) && n_pseudo < (int64_t)1 << 31 &&
+        make_plan(dc, n_pseudo, batch, &jpl) && node_slots <= jpl.pass_slots()) {
+        r->jac_np = (size_t)r->back_nt * 32;
+        r->jac_extra_bytes = 2 * geo::align_up((size_t)n_pseudo * 4) + geo::align_up((size_t)n_nodes * s.d * r->jac_np * 4);
+        jac_bytes = r->jac_extra_bytes + jpl.bytes + node_bytes(s, n_nodes);
+    }
+    r->bytes = jac_bytes > per_edge_end_bytes ? jac_bytes : per_edge_end_bytes;
+    const size_t ws = ws_bytes ? *ws_bytes : r->bytes;
+    r->node_jacobian = jac_bytes && ws >= jac_bytes;
+    r->pl = r->node_jacobian ? jpl : base;
+    r->run_edges = r->node_jacobian ? n_pseudo : n_edges;
+    const int64_t chunks = (r->run_edges + batch - 1) / batch;
+    r->passes = (chunks + r->pl.chunks_per_pass - 1) / r->pl.chunks_per_pass;
+    // a workspace of geo_jvp_workspace_bytes() only, or more latents than a pass has slots: the per-edge-end path
+    const size_t run_ws = ws - (r->node_jacobian ? r->jac_extra_bytes : 0);
+    r->per_node = per_node_kernels && node_slots && node_slots <= r->pl.pass_slots() &&
+                  run_ws >= r->pl.bytes + node_bytes(s, n_nodes);
+    const size_t slots = r->pl.pass_slots(), tiles = slots / TS, groups = (size_t)r->pl.chunks_per_pass * 2;
+    r->dedup = r->batch_stats && graph_edges && mid_pipe && back_mfma && o.jvp_start_dedup != 0 &&
+               (2 * slots + groups) * 4 <= tiles * s.n1 * 4 * 8 && (size_t)r->back_nt * 32 <= (size_t)s.n1;
+
+    r->mid = r->per_node ? GEO_JVP_MID_ALL_TANGENT
+           : mid_pipe    ? (r->dedup ? GEO_JVP_MID_PIPE_DEDUP : GEO_JVP_MID_PIPE)
+           : mid_all     ? GEO_JVP_MID_ALL
+                         : GEO_JVP_MID_CHUNK;
+    r->parts2 = mid_pipe && !r->per_node ? 4 : (mid_all ? 1 : 16);
+    r->back = r->dedup ? GEO_JVP_BACK_DEDUP : r->per_node ? GEO_JVP_BACK_PER_NODE : back_mfma ? GEO_JVP_BACK_MFMA : GEO_JVP_BACK_VALU;
+    r->back_lds = ((size_t)2 * BACK_TS * 16 * (s.c2 + 4) + (size_t)16 * s.co * (s.c2 + 4) + (size_t)BACK_TS * s.p_out) * 4;
+
+    // ---- what the run refuses
+    if (!(s.d >= 1 && s.d <= 64)) return route_error(r, GEO_E_ARG, "geo_decoder_jvp: latent_dim %d not in [1,64]", s.d);
+    if (!(s.c1 == 128 || s.c1 == 64 || s.c1 == 32))
+        return route_error(r, GEO_E_ARG, "geo_decoder_jvp: dec_channels[1]=%d not in {32,64,128}", s.c1);
+    if (!(dc->norm >= 0 && dc->norm <= 2)) return route_error(r, GEO_E_ARG, "geo_decoder_jvp: unknown norm code %d", dc->norm);
+    if (s.c2 % 16 != 0) return route_error(r, GEO_E_ARG, "geo_decoder_jvp: dec_channels[2]=%d must be a multiple of 16", s.c2);
+    if (r->back_lds > 160 * 1024)
+        return route_error(r, GEO_E_ARG, "geo_decoder_jvp: decoder too wide for the back kernel (%zu B LDS)", r->back_lds);
+    if (run_ws < r->pl.bytes) return route_error(r, GEO_E_WORKSPACE, "geo_decoder_jvp: workspace %zu < %zu", run_ws, r->pl.bytes);
+    // the GroupNorm path exists for the 32-group layouts of the matrix-core kernels (reference default decoder)
+    if (r->group_norm && !(dc->groups1 == 32 && dc->groups2 == 32 && s.c2 == 64 && back_mfma && mid_all))
+        return route_error(r, GEO_E_ARG,
+                           "geo_decoder_jvp: GroupNorm needs 32 groups per layer and dec_channels[2] == 64 (got %d/%d groups, c2=%d)",
+                           dc->groups1, dc->groups2, s.c2);
     return true;
 }
 
-int run_node_jacobian(const geo_decoder_desc *dc, const JacobianPlan &jp, const float *z, int64_t n_nodes, const int32_t *src,
-                      const int32_t *dst, int64_t n_edges, int32_t batch, float *len_out, void *ws, size_t ws_bytes,
-                      hipStream_t stream) {
-    Shape s;
-    make_shape(dc, &s);
-    geo::Arena ar(ws, ws_bytes);
-    int32_t *psrc = ar.take<int32_t>((size_t)jp.n_pseudo), *pdst = ar.take<int32_t>((size_t)jp.n_pseudo);
-    float *jac = ar.take<float>((size_t)n_nodes * s.d * jp.np);
-    GEO_REQUIRE(jac != nullptr, "geo_decoder_jvp_edges: workspace carve failed");
-    pair_edges_kernel<<<geo::grid_for(jp.n_pseudo, 256), 256, 0, stream>>>(n_nodes, s.d, jp.n_pseudo, psrc, pdst);
-    GEO_LAUNCH_CHECK();
-    const int rc = run_jvp(dc, z, n_nodes, psrc, pdst, nullptr, nullptr, jp.n_pseudo, batch, nullptr,
-                           static_cast<char *>(ws) + ar.off, ws_bytes - ar.off, stream, jac);
-    if (rc != GEO_OK) return rc;
-    const int64_t teams = (n_edges * 16 + 255) / 256;
-    GEO_REQUIRE(teams < ((int64_t)1 << 31), "geo_decoder_jvp_edges: too many edges for one launch (%lld)", (long long)n_edges);
-    jacobian_lengths_kernel<<<(unsigned)teams, 256, 0, stream>>>(z, src, dst, n_edges, s.d, s.p_out, (int)jp.np, jac, len_out);
+int encode_route(const Route &r) {
+    const int64_t passes = r.passes < 0x7fff ? r.passes : 0x7fff;
+    return r.front | (r.dmax == 16 ? 0 : (r.dmax == 32 ? 1 : 2)) << 2 | r.mid << 4 | r.back << 8 |
+           (r.per_node ? GEO_JVP_PER_NODE : 0) | (r.node_jacobian ? GEO_JVP_NODE_JACOBIAN : 0) | (r.dedup ? GEO_JVP_DEDUP : 0) |
+           (int)passes << 16;
+}
+
+// ---------------------------------------------------------------------------------- host side: launchers
+struct Buffers {
+    float *M01, *b01, *B2p, *W3p, *pre1, *tpre1, *pre2, *tpre2, *norms;
+    unsigned short *B3, *W3b;
+    double *part1, *part2; NormConst *k1, *k2;                // partial sums and norm constants of layers 1, 2
+    float2 *stats;                                              // batch statistics on their way into the running ones
+    int32_t *slot_valid;
+    float4 *gs1, *gs2;                                          // GroupNorm
+    float *pre2_node, *sg_node;                                 // per_node
+    int32_t *row_map, *rep, *n_compact;                         // dedup
+    float *sg_compact, *jac;                                    // dedup; node_jacobian
+    ChunkTable tab;
+};
+
+// One launch sequence front -> ConvT2 -> ConvT3: a pass of chunks over the edges, or the per-node primal pass over the latents
+// (one group: every latent on the "start" side).
+struct Pass {
+    int mid, back;                                              // GEO_JVP_MID_*, GEO_JVP_BACK_* | BACK_NODE_PRIMAL
+    int64_t tiles, e_base, n_edges;
+    int tiles_per_group, batch, unit_d, stat;                   // stat 1: batch statistics (constants per group, partial sums)
+    const float *z, *z_start, *z_end;                           // latents + edge list, or explicit end points
+    const int32_t *src, *dst;
+    float *mid_pre2;                                            // where ConvT2's primal rows go
+    const float *back_pre2;                                     // the primal rows ConvT3 (and GroupNorm 2) reads
+    int64_t slots() const { return tiles * TS; }
+    int64_t groups() const { return tiles / tiles_per_group; }
+};
+
+// template arguments from run-time values: f(std::integral_constant) of the matching one
+template <int... Vs, class F>
+void pick_int(int v, F &&f) { ((v == Vs ? (void)f(std::integral_constant<int, Vs>{}) : (void)0), ...); }
+template <class F>
+void pick_bool(bool v, F &&f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+
+int cu_count(int *n) {
+    static int n_cu = 0;
+    if (n_cu == 0) {
+        int devid = 0, cus = 0;
+        GEO_HIP_CHECK(hipGetDevice(&devid));
+        GEO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid));
+        n_cu = cus > 0 ? cus : 256;
+    }
+    *n = n_cu;
+    return GEO_OK;
+}
+
+int launch_front(const Route &r, const Pass &p, const Buffers &b, hipStream_t stream) {
+    const Shape &s = r.pl.sh;
+    if (r.front == GEO_JVP_FRONT_MFMA)
+        pick_int<32, 64>(r.dmax, [&](auto dm) {
+            front_mfma_kernel<decltype(dm)::value><<<(unsigned)p.tiles, 256, 0, stream>>>(
+                p.z, p.src, p.dst, p.z_start, p.z_end, p.e_base, p.n_edges, p.batch, p.tiles_per_group, s.d, s.n1, b.M01, b.b01,
+                b.pre1, b.tpre1, b.part1, p.stat);
+        });
+    else
+        pick_int<16, 32, 64>(r.dmax, [&](auto dm) {
+            front_kernel<decltype(dm)::value><<<(unsigned)p.tiles, 256, 0, stream>>>(
+                p.z, p.src, p.dst, p.z_start, p.z_end, p.e_base, p.n_edges, p.batch, p.tiles_per_group, s.d, s.n1, b.M01, b.b01,
+                b.pre1, b.tpre1, b.part1, p.stat, p.unit_d);
+        });
     GEO_LAUNCH_CHECK();
     return GEO_OK;
+}
+
+// Norm constants of layer 1 (after the front) or 2 (after ConvT2): batch statistics from the partial sums, folded into the
+// running statistics where tracked; GroupNorm's per-sample statistics.  Fixed statistics were set once per call.
+int launch_stats(const Route &r, const geo_decoder_desc *dc, int layer, const Pass &p, const Buffers &b, hipStream_t stream) {
+    const Shape &s = r.pl.sh;
+    const bool l1 = layer == 1;
+    const int C = l1 ? s.c1 : s.c2, npx = l1 ? 4 : 16;
+    if (p.stat) {
+        finalize_batch_kernel<<<geo::grid_for(p.groups() * C, 256), 256, 0, stream>>>(
+            l1 ? b.part1 : b.part2, p.tiles_per_group, l1 ? 1 : r.parts2, npx, C, p.e_base, p.n_edges, p.batch, l1 ? dc->g1 : dc->g2,
+            l1 ? dc->be1 : dc->be2, dc->eps, l1 ? b.k1 : b.k2, (int)p.groups(), r.track ? b.stats : nullptr);
+        if (r.track)
+            running_update_kernel<<<(unsigned)((C + 7) / 8), 256, 0, stream>>>(
+                b.stats, (int)p.groups(), C, dc->momentum, const_cast<float *>(l1 ? dc->rm1 : dc->rm2),
+                const_cast<float *>(l1 ? dc->rv1 : dc->rv2));
+        GEO_LAUNCH_CHECK();
+    }
+    if (r.group_norm) {
+        const int32_t *prim_row = nullptr;
+        if (!l1 && p.back == GEO_JVP_BACK_PER_NODE) {      // (slot_valid is not read on this path: it carries the slot -> latent map)
+            slot_node_kernel<<<geo::grid_for(p.slots(), 256), 256, 0, stream>>>(p.src, p.dst, p.e_base, p.n_edges, p.batch,
+                                                                                p.tiles_per_group, p.slots(), b.slot_valid);
+            prim_row = b.slot_valid;
+        }
+        group_stats_kernel<<<geo::grid_for(p.slots() * 32, 256), 256, 0, stream>>>(
+            l1 ? b.pre1 : p.back_pre2, l1 ? b.tpre1 : b.tpre2, p.slots(), npx, C, 32, dc->eps, l1 ? b.gs1 : b.gs2, prim_row);
+        GEO_LAUNCH_CHECK();
+    }
+    return GEO_OK;
+}
+
+int launch_mid(const Route &r, const geo_decoder_desc *dc, const Pass &p, const Buffers &b, hipStream_t stream) {
+    const Shape &s = r.pl.sh;
+    if (p.mid == GEO_JVP_MID_PIPE || p.mid == GEO_JVP_MID_PIPE_DEDUP) {
+        const bool dedup = p.mid == GEO_JVP_MID_PIPE_DEDUP;
+        const int64_t chunks = p.groups() / 2;
+        if (dedup) {
+            start_runs_kernel<<<(unsigned)chunks, 256, 0, stream>>>(p.src, p.e_base, p.n_edges, p.batch, p.tiles_per_group * TS,
+                                                                    b.row_map, b.rep, b.n_compact);
+            GEO_LAUNCH_CHECK();
+        }
+        int n_cu = 0;
+        if (const int rc = cu_count(&n_cu)) return rc;
+        const int64_t pipe_tiles = dedup ? p.tiles / 2 : p.tiles;                        // (dedup: the end side only)
+        const unsigned grid = (unsigned)std::min<int64_t>(pipe_tiles, n_cu);             // persistent workgroups, one resident per CU
+        pick_bool(dedup, [&](auto end_only) {
+            mid_pipe_kernel<decltype(end_only)::value><<<grid, 512, 0, stream>>>(
+                b.pre1, b.tpre1, b.k1, p.stat, p.tiles_per_group, (int)pipe_tiles, s.c2, b.B3, dc->b2, p.mid_pre2, b.tpre2, b.part2,
+                p.stat, p.e_base, p.n_edges, p.batch);
+        });
+        GEO_LAUNCH_CHECK();
+        if (dedup) {                                            // compact primal rows first: the tangent launch gathers them
+            mid_start_kernel<false><<<dim3(1, (unsigned)chunks), 512, 0, stream>>>(
+                b.pre1, b.tpre1, b.k1, p.tiles_per_group, b.B3, dc->b2, p.mid_pre2, b.tpre2, b.part2, b.row_map, b.rep, b.n_compact,
+                p.e_base, p.n_edges, p.batch);
+            GEO_LAUNCH_CHECK();
+            mid_start_kernel<true><<<dim3((unsigned)((p.tiles_per_group + 1) / 2), (unsigned)chunks), 512, 0, stream>>>(
+                b.pre1, b.tpre1, b.k1, p.tiles_per_group, b.B3, dc->b2, p.mid_pre2, b.tpre2, b.part2, b.row_map, b.rep, b.n_compact,
+                p.e_base, p.n_edges, p.batch);
+            GEO_LAUNCH_CHECK();
+        }
+    } else if (p.mid == GEO_JVP_MID_ALL || p.mid == GEO_JVP_MID_ALL_TANGENT) {
+        pick_int<128, 64, 32>(s.c1, [&](auto c1) {
+            pick_bool(r.group_norm, [&](auto gn) {
+                pick_bool(p.mid == GEO_JVP_MID_ALL_TANGENT, [&](auto tangent_only) {
+                    mid_all_kernel<decltype(c1)::value, decltype(gn)::value, decltype(tangent_only)::value>
+                        <<<(unsigned)p.tiles, 512, 0, stream>>>(b.pre1, b.tpre1, b.k1, p.stat, p.tiles_per_group, s.c2, b.B3, dc->b2,
+                                                                p.mid_pre2, b.tpre2, b.part2, p.stat, b.slot_valid, b.gs1, p.e_base,
+                                                                p.n_edges, p.batch);
+                });
+            });
+        });
+        GEO_LAUNCH_CHECK();
+    } else {                                                    // other widths: one workgroup per (tile, chunk of output pixels)
+        pick_int<128, 64, 32>(s.c1, [&](auto c1) {
+            mid_bf16_kernel<decltype(c1)::value><<<dim3((unsigned)p.tiles, (unsigned)s.n_chunks), 256, 0, stream>>>(
+                b.pre1, b.tpre1, b.k1, p.stat, p.tiles_per_group, b.tab, s.opix_per_chunk, s.c2, b.B3, dc->b2, p.mid_pre2, b.tpre2,
+                b.part2, p.stat, b.slot_valid);
+        });
+        GEO_LAUNCH_CHECK();
+    }
+    return GEO_OK;
+}
+
+int launch_back(const Route &r, const geo_decoder_desc *dc, const Pass &p, const Buffers &b, hipStream_t stream) {
+    const Shape &s = r.pl.sh;
+    if (p.back == GEO_JVP_BACK_VALU) {
+        back_kernel<<<(unsigned)(p.slots() / BACK_TS), 256, r.back_lds, stream>>>(
+            p.back_pre2, b.tpre2, b.k2, p.stat, p.tiles_per_group * TS, s.c2, s.co, s.s_out, s.pad3, b.W3p, dc->b3, b.norms);
+        GEO_LAUNCH_CHECK();
+        return GEO_OK;
+    }
+    const unsigned tiles = (unsigned)p.tiles, side_tiles = (unsigned)(p.tiles / 2), chunks = (unsigned)(p.groups() / 2);
+    pick_int<1, 6>(r.back_nt, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if (p.back == GEO_JVP_BACK_DEDUP) {       // end side per slot; start side: the compact primal rows, then the tangents
+            back_mfma_kernel<NT, false, 0><<<side_tiles, 256, 0, stream>>>(
+                p.back_pre2, b.tpre2, b.k2, 1, p.tiles_per_group, s.co, s.s_out, b.W3b, dc->b3, b.norms, nullptr, nullptr, nullptr,
+                nullptr, 0, 0, 1, nullptr, 0, nullptr, nullptr, 2);
+            back_mfma_kernel<NT, false, 2><<<chunks, 256, 0, stream>>>(
+                p.back_pre2, b.tpre2, b.k2, 1, p.tiles_per_group, s.co, s.s_out, b.W3b, dc->b3, b.norms, nullptr, b.sg_compact, nullptr,
+                nullptr, 0, 0, 1, nullptr, 0, nullptr, b.n_compact, 1);
+            back_mfma_kernel<NT, false, 1><<<side_tiles, 256, 0, stream>>>(
+                p.back_pre2, b.tpre2, b.k2, 1, p.tiles_per_group, s.co, s.s_out, b.W3b, dc->b3, b.norms, nullptr, b.sg_compact, nullptr,
+                nullptr, 0, 0, 1, nullptr, 0, b.row_map, nullptr, 1);
+            return;
+        }
+        pick_bool(r.group_norm, [&](auto gn) {
+            constexpr bool GN = decltype(gn)::value;
+            if (p.back == GEO_JVP_BACK_MFMA)
+                back_mfma_kernel<NT, GN, 0><<<tiles, 256, 0, stream>>>(p.back_pre2, b.tpre2, b.k2, p.stat, p.tiles_per_group, s.co,
+                                                                      s.s_out, b.W3b, dc->b3, b.norms, b.gs2);
+            else if (p.back == GEO_JVP_BACK_PER_NODE)           // tangent only, the primal from the slot's latent
+                back_mfma_kernel<NT, GN, 1><<<tiles, 256, 0, stream>>>(p.back_pre2, b.tpre2, b.k2, 0, p.tiles_per_group, s.co, s.s_out,
+                                                                      b.W3b, dc->b3, b.norms, b.gs2, b.sg_node, p.src, p.dst, p.e_base,
+                                                                      p.n_edges, p.batch, b.jac, p.unit_d);
+            else                                                // BACK_NODE_PRIMAL: primal only, keeps the output sigmoids
+                back_mfma_kernel<NT, GN, 2><<<tiles, 256, 0, stream>>>(p.back_pre2, b.tpre2, b.k2, 0, p.tiles_per_group, s.co, s.s_out,
+                                                                      b.W3b, dc->b3, b.norms, b.gs2, b.sg_node);
+        });
+    });
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+int launch_pass(const Route &r, const geo_decoder_desc *dc, const Pass &p, const Buffers &b, hipStream_t stream) {
+    if (const int rc = launch_front(r, p, b, stream)) return rc;
+    if (const int rc = launch_stats(r, dc, 1, p, b, stream)) return rc;
+    if (const int rc = launch_mid(r, dc, p, b, stream)) return rc;
+    if (const int rc = launch_stats(r, dc, 2, p, b, stream)) return rc;
+    return launch_back(r, dc, p, b, stream);
+}
+
+// ---------------------------------------------------------------------------------- host side: the run
+// graph edges (z, src, dst) or explicit end points (z_start, z_end); `r` is make_route's answer for exactly this call
+int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t n_nodes, const int32_t *src, const int32_t *dst,
+            const float *z_start, const float *z_end, int64_t n_edges, float *len_out, void *ws, size_t ws_bytes,
+            hipStream_t stream) {
+    const Plan &pl = r.pl;
+    const Shape &s = pl.sh;
+    const int batch = pl.batch;
+    const size_t slots = pl.pass_slots(), tiles = slots / TS, groups = (size_t)pl.chunks_per_pass * 2;
+
+    // ---- carve the workspace
+    geo::Arena ar(ws, ws_bytes);
+    Buffers b = {};
+    int32_t *psrc = nullptr, *pdst = nullptr;
+    if (r.node_jacobian) {
+        psrc = ar.take<int32_t>((size_t)r.run_edges);
+        pdst = ar.take<int32_t>((size_t)r.run_edges);
+        b.jac = ar.take<float>((size_t)n_nodes * s.d * r.jac_np);
+        GEO_REQUIRE(b.jac != nullptr, "geo_decoder_jvp_edges: workspace carve failed");
+    }
+    b.M01 = ar.take<float>((size_t)s.d * s.n1);
+    b.b01 = ar.take<float>((size_t)s.n1);
+    b.B2p = ar.take<float>((size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC);
+    b.B3 = ar.take<unsigned short>((size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC * 3);
+    b.W3p = ar.take<float>((size_t)16 * s.co * s.c2);
+    b.W3b = ar.take<unsigned short>((size_t)16 * s.c2 * 192 * 3);
+    b.pre1 = ar.take<float>(slots * s.n1); b.tpre1 = ar.take<float>(slots * s.n1);
+    b.pre2 = ar.take<float>(slots * s.n2); b.tpre2 = ar.take<float>(slots * s.n2);
+    b.part1 = ar.take<double>(tiles * s.n1 * 4); b.part2 = ar.take<double>(tiles * s.n2 * 4);
+    b.k1 = ar.take<NormConst>((groups + 1) * s.c1); b.k2 = ar.take<NormConst>((groups + 1) * s.c2);
+    b.norms = ar.take<float>(slots);
+    b.stats = ar.take<float2>((groups + 1) * (size_t)(s.c1 > s.c2 ? s.c1 : s.c2));
+    b.slot_valid = ar.take<int32_t>(slots);
+    if (r.group_norm) { b.gs1 = ar.take<float4>(slots * 32); b.gs2 = ar.take<float4>(slots * 32); }
+    const size_t node_slots = round_up_to_tile(n_nodes);
+    if (r.per_node) {
+        b.pre2_node = ar.take<float>(node_slots * s.n2);
+        b.sg_node = ar.take<float>(node_slots * (size_t)((s.p_out + 31) / 32) * 32);
+    }
+    GEO_REQUIRE(b.slot_valid && (!r.group_norm || b.gs2) && (!r.per_node || b.sg_node), "geo_decoder_jvp: workspace carve failed");
+    if (r.dedup) {
+        b.row_map = reinterpret_cast<int32_t *>(b.part1); b.rep = b.row_map + slots; b.n_compact = b.rep + slots;
+        b.sg_compact = b.pre1;
+    }
+
+    // ---- pack the weights, fixed norm constants
+    make_chunks(s, &b.tab);
+    int bad_chunk = 0;
+    GEO_REQUIRE(!(s.n_chunks == 8 && s.opix_per_chunk == 2) || chunks_match_mid_geom(b.tab, &bad_chunk),
+                "geo_decoder_jvp: chunk table / MidGeom mismatch (chunk %d)", bad_chunk);
+    compose_front_kernel<<<geo::grid_for((int64_t)(s.d + 1) * s.n1, 256), 256, 0, stream>>>(
+        dc->w_in, dc->b_in, dc->w1, dc->b1, s.d, s.c0, s.c1, b.M01, b.b01);
+    GEO_LAUNCH_CHECK();
+    pack_mid_kernel<<<geo::grid_for((int64_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC, 256), 256, 0, stream>>>(
+        dc->w2, s.c1, s.c2, b.tab, s.n_chunks, s.opix_per_chunk, b.B2p);
+    GEO_LAUNCH_CHECK();
+    pack_back_kernel<<<geo::grid_for(16 * s.co * s.c2, 256), 256, 0, stream>>>(dc->w3, s.c2, s.co, b.W3p);
+    GEO_LAUNCH_CHECK();
+    if (r.back != GEO_JVP_BACK_VALU) {
+        pack_back_bf16_kernel<<<geo::grid_for((int64_t)16 * s.c2 * r.back_nt * 32, 256), 256, 0, stream>>>(
+            dc->w3, s.c2, s.co, s.s_out, s.pad3, r.back_nt * 32, b.W3b);
+        GEO_LAUNCH_CHECK();
+    }
+    pack_mid_bf16_kernel<<<geo::grid_for((int64_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC, 256), 256, 0, stream>>>(
+        b.B2p, s.c1, s.n_chunks, b.B3);
+    GEO_LAUNCH_CHECK();
+    if (!r.batch_stats) {
+        finalize_fixed_kernel<<<1, 256, 0, stream>>>(s.c1, dc->norm, dc->g1, dc->be1, dc->rm1, dc->rv1, dc->eps, b.k1);
+        GEO_LAUNCH_CHECK();
+        finalize_fixed_kernel<<<1, 256, 0, stream>>>(s.c2, dc->norm, dc->g2, dc->be2, dc->rm2, dc->rv2, dc->eps, b.k2);
+        GEO_LAUNCH_CHECK();
+    }
+
+    // ---- per-node primal pass: every latent once, its ConvT2 rows and output sigmoids kept
+    if (r.per_node) {
+        Pass np = {};                                          // (no edge list: "end points" z, z)
+        np.mid = GEO_JVP_MID_ALL; np.back = BACK_NODE_PRIMAL;
+        np.tiles = (int64_t)(node_slots / TS); np.tiles_per_group = (int)np.tiles;
+        np.n_edges = n_nodes; np.batch = (int)node_slots;
+        np.z_start = np.z_end = z; np.mid_pre2 = b.pre2_node; np.back_pre2 = b.pre2_node;
+        if (const int rc = launch_pass(r, dc, np, b, stream)) return rc;
+    }
+
+    // ---- passes over the edges (node_jacobian: over the pseudo-edges, unit tangents, columns to b.jac instead of lengths)
+    if (r.node_jacobian) {
+        pair_edges_kernel<<<geo::grid_for(r.run_edges, 256), 256, 0, stream>>>(n_nodes, s.d, r.run_edges, psrc, pdst);
+        GEO_LAUNCH_CHECK();
+    }
+    const int64_t total_chunks = (r.run_edges + batch - 1) / batch;
+    for (int64_t c0 = 0; c0 < total_chunks; c0 += pl.chunks_per_pass) {
+        const int64_t nch = std::min<int64_t>(total_chunks - c0, pl.chunks_per_pass);
+        Pass ep = {};
+        ep.mid = r.mid; ep.back = r.back;
+        ep.tiles = nch * 2 * pl.tiles_per_group; ep.tiles_per_group = pl.tiles_per_group;
+        ep.e_base = c0 * batch; ep.n_edges = r.run_edges; ep.batch = batch; ep.stat = r.batch_stats ? 1 : 0;
+        ep.z = z; ep.src = r.node_jacobian ? psrc : src; ep.dst = r.node_jacobian ? pdst : dst;
+        ep.z_start = z_start; ep.z_end = z_end;
+        ep.unit_d = r.node_jacobian ? s.d : 0;
+        ep.mid_pre2 = b.pre2; ep.back_pre2 = r.per_node ? b.pre2_node : b.pre2;
+        slot_valid_kernel<<<geo::grid_for(ep.slots(), 256), 256, 0, stream>>>(ep.e_base, ep.n_edges, batch, pl.tiles_per_group,
+                                                                             ep.slots(), b.slot_valid);
+        GEO_LAUNCH_CHECK();
+        if (const int rc = launch_pass(r, dc, ep, b, stream)) return rc;
+        if (!r.node_jacobian) {
+            const int64_t e_count = std::min<int64_t>(n_edges - ep.e_base, nch * batch);
+            combine_kernel<<<geo::grid_for(e_count, 256), 256, 0, stream>>>(b.norms, ep.e_base, e_count, batch, pl.slots_per_group,
+                                                                            len_out);
+            GEO_LAUNCH_CHECK();
+        }
+    }
+    if (r.node_jacobian) {                                      // each edge end from its latent's columns
+        const int64_t teams = (n_edges * 16 + 255) / 256;
+        GEO_REQUIRE(teams < ((int64_t)1 << 31), "geo_decoder_jvp_edges: too many edges for one launch (%lld)", (long long)n_edges);
+        jacobian_lengths_kernel<<<(unsigned)teams, 256, 0, stream>>>(z, src, dst, n_edges, s.d, s.p_out, (int)r.jac_np, b.jac, len_out);
+        GEO_LAUNCH_CHECK();
+    }
+    return GEO_OK;
+}
+
+// validation shared by the two entry points, then the route and the run
+int decoder_jvp(const geo_decoder_desc *dc, const geo::Options &opt, bool graph_edges, const float *z, int64_t n_nodes,
+                const int32_t *src, const int32_t *dst, const float *z_start, const float *z_end, int64_t n_edges, int32_t batch,
+                float *len_out, void *ws, size_t ws_bytes, void *stream) {
+    GEO_REQUIRE(dc && len_out && ws, "geo_decoder_jvp: null pointer");
+    GEO_REQUIRE(batch > 0, "geo_decoder_jvp: batch_size must be positive");
+    if (n_edges == 0) return GEO_OK;
+    Route r;
+    if (!make_route(dc, opt, graph_edges, n_nodes, n_edges, batch, &ws_bytes, &r)) {
+        geo::set_error("%s", r.error);
+        return r.status;
+    }
+    return run_jvp(dc, r, z, n_nodes, src, dst, z_start, z_end, n_edges, len_out, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -2351,37 +2343,44 @@ extern "C" int geo_debug_mid_prof(unsigned long long *out, int reset) {
 #endif
 
 extern "C" size_t geo_jvp_workspace_bytes(const geo_decoder_desc *dec, int64_t n_edges, int32_t batch_size) {
-    Plan pl;
-    if (!dec || batch_size <= 0 || n_edges < 0 || !make_plan(dec, n_edges, batch_size, &pl)) return 0;
-    return pl.bytes;
+    const geo::Options opt = geo::options();
+    Route r;
+    make_route(dec, opt, false, 0, n_edges, batch_size, nullptr, &r);
+    return r.bytes;
 }
 
 extern "C" size_t geo_jvp_edges_workspace_bytes(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges,
                                                 int32_t batch_size) {
-    Plan pl;
-    if (!dec || batch_size <= 0 || n_edges < 0 || n_nodes < 0 || !make_plan(dec, n_edges, batch_size, &pl)) return 0;
-    const size_t per_edge_end = pl.bytes + node_bytes(pl.sh, n_nodes);
-    JacobianPlan jp;
-    if (node_jacobian_plan(dec, n_nodes, n_edges, batch_size, &jp) && jp.bytes > per_edge_end) return jp.bytes;
-    return per_edge_end;
+    const geo::Options opt = geo::options();
+    Route r;
+    make_route(dec, opt, true, n_nodes, n_edges, batch_size, nullptr, &r);
+    return r.bytes;
+}
+
+extern "C" int geo_jvp_plan(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size,
+                            int32_t graph_edges, size_t ws_bytes) {
+    const geo::Options opt = geo::options();
+    Route r;
+    if (!make_route(dec, opt, graph_edges != 0, graph_edges ? n_nodes : 0, n_edges, batch_size, ws_bytes ? &ws_bytes : nullptr, &r)) {
+        geo::set_error("%s", r.error);
+        return r.status;
+    }
+    return encode_route(r);
 }
 
 extern "C" int geo_decoder_jvp_edges(const geo_decoder_desc *dec, const float *z, int64_t n_nodes, const int32_t *src,
                                      const int32_t *dst, int64_t n_edges, int32_t batch_size, float *len_out, void *ws,
                                      size_t ws_bytes, void *stream) {
     GEO_REQUIRE(n_edges == 0 || (z && src && dst && n_nodes > 0), "geo_decoder_jvp_edges: null pointer");
-    JacobianPlan jp;
-    if (batch_size > 0 && len_out && ws && node_jacobian_plan(dec, n_nodes, n_edges, batch_size, &jp) && ws_bytes >= jp.bytes)
-        return run_node_jacobian(dec, jp, z, n_nodes, src, dst, n_edges, batch_size, len_out, ws, ws_bytes,
-                                 static_cast<hipStream_t>(stream));
-    return run_jvp(dec, z, n_nodes, src, dst, nullptr, nullptr, n_edges, batch_size, len_out, ws, ws_bytes,
-                   static_cast<hipStream_t>(stream));
+    const geo::Options opt = geo::options();
+    return decoder_jvp(dec, opt, true, z, n_nodes, src, dst, nullptr, nullptr, n_edges, batch_size, len_out, ws, ws_bytes, stream);
 }
 
 extern "C" int geo_decoder_jvp_pairs(const geo_decoder_desc *dec, const float *z_start, const float *z_end,
                                      int64_t n_edges, int32_t batch_size, float *len_out, void *ws, size_t ws_bytes,
                                      void *stream) {
     GEO_REQUIRE(n_edges == 0 || (z_start && z_end), "geo_decoder_jvp_pairs: null pointer");
-    return run_jvp(dec, nullptr, 0, nullptr, nullptr, z_start, z_end, n_edges, batch_size, len_out, ws, ws_bytes,
-                   static_cast<hipStream_t>(stream));
+    const geo::Options opt = geo::options();
+    return decoder_jvp(dec, opt, false, nullptr, 0, nullptr, nullptr, z_start, z_end, n_edges, batch_size, len_out, ws, ws_bytes,
+                       stream);
 }
