@@ -421,6 +421,40 @@ int geo_kmeans_lloyd(const float *X, int64_t n, int32_t d, int32_t K, int32_t n_
  * batch sizes and positions in the batch.  Asynchronous on `stream`. */
 int geo_image_pair_moments(const float *x, const float *y, int64_t n_images, int64_t n_pix, double *mom_out, void *stream);
 
+/* ---- Geodesic k-medoids analysis (the reference's demos/kmedoids_geodesic_analysis.py) ----
+ * geo_cluster_label_scores: assign i32 [n] (codes in [0, K); negative = not assigned, skipped), labels i32 [n] (classes in
+ * [0, C)), 1 <= K <= 4096, 1 <= C <= 1024, 0 <= n < 2^31 (GEO_E_ARG outside, before any launch: every pair count below is at
+ * most C(n, 2) < 2^61 and a workgroup's int32 cells cannot wrap).  grid_blocks = workgroups of the counting kernel, 0 =
+ * chosen from n.  table_out i64 [K][C] = the contingency table n_kc; row_counts_out i64 [K] = a_k (code usage);
+ * col_counts_out i64 [C] = b_c; isums_out i64 [6] = rows counted, sum_k max_c n_kc (purity numerator), sum C(n_kc, 2),
+ * sum C(a_k, 2), sum C(b_c, 2), rows skipped because a code >= K or a label lay outside [0, C) (the caller's error: they are
+ * in no count); fsums_out f64 [3] = sum n_kc log n_kc, sum a_k log a_k, sum b_c log b_c.  Integer counting (LDS per
+ * workgroup, 64-bit integer merge), fp64 sums in an association fixed by (K, C): every output is bit-identical across
+ * runs, streams and grid sizes.  Asynchronous. */
+int geo_cluster_label_scores(const int32_t *assign, const int32_t *labels, int64_t n, int32_t K, int32_t C, int32_t grid_blocks,
+                             int64_t *table_out, int64_t *row_counts_out, int64_t *col_counts_out, int64_t *isums_out,
+                             double *fsums_out, void *stream);
+
+/* PCA of the distance-to-medoid features X = D^T (plot_pca_with_clusters of the demo): D f32 [K][ld], row k = distances from
+ * medoid k to the n nodes (geo_sssp_multi's D_out), 1 <= K <= 4096, 1 <= n < 2^31, ld >= n.  A non-finite entry of row k
+ * counts as fill[k] = fl32(fl32(1.1) m_k), m_k = the row's largest finite value, 1 when that is 0 (or the row has no finite
+ * entry): numpy's float32 arithmetic on the reference's float32 X.  One workspace query serves colstats and gram.
+ * geo_feature_colstats: colmax_out f32 [K] = m_k (0 for a row without finite entries), fill_out f32 [K], mean_out f64 [K] =
+ *   fp64 mean of the row after replacement (16 384-column slices, fixed tree, slices in order).
+ * geo_feature_gram: gram_out f64 [K][K] = sum_v (x_iv - mean_i)(x_jv - mean_j), v_mfma_f64_16x16x4_f64 on 64 x 64 tiles of the
+ *   upper block triangle, the n columns cut into slices fixed by (n, K) whose partial matrices are added in slice order;
+ *   the lower triangle is the mirror image, so gram_out is exactly symmetric.
+ * geo_feature_project: Z_out f32 [n][n_components] = (x_v - mean) V, V f64 [K][n_components], 1 <= n_components <= min(K, 8),
+ *   fp64 fma chain over k ascending, rounded once.
+ * No atomics anywhere: bit-identical across runs and streams.  Asynchronous. */
+size_t geo_feature_workspace_bytes(int64_t n, int32_t K);
+int geo_feature_colstats(const float *D, int64_t ld, int32_t K, int64_t n, float *colmax_out, float *fill_out, double *mean_out,
+                         void *ws, size_t ws_bytes, void *stream);
+int geo_feature_gram(const float *D, int64_t ld, int32_t K, int64_t n, const float *fill, const double *mean, double *gram_out,
+                     void *ws, size_t ws_bytes, void *stream);
+int geo_feature_project(const float *D, int64_t ld, int32_t K, int64_t n, const float *fill, const double *mean, const double *V,
+                        int32_t n_components, float *Z_out, void *stream);
+
 /* ---- EMA vector quantizer (the reference's baseline VQ-VAE, VectorQuantizerEMA) ----
  * z_e [B][C][HW] (NCHW, contiguous) f32 (half = 0) or f16 (half = 1), 1 <= C <= 128, 1 <= K <= 4096, any n = B HW >= 1 (K > n
  * allowed).  Rows are z_e's positions (b, h, w) in that order, upcast to f32.  idx_out i64 [n] = geo_kmeans_assign's labels

@@ -123,7 +123,13 @@ def _draw_with_u(N: int, d_min: np.ndarray, centers: List[int], u: float):
     return j
 
 
-def _kpp_chain_host(G: DeviceCSR, K: int, seed: int, absorb_last: bool):
+def _snapshot(chain: _Chain, absorbed: int, snaps: Optional[dict]) -> None:
+    """fit_kmedoids_path: keep (d_min, argmin) as they are once exactly `absorbed` centres are folded in (device copies)."""
+    if snaps is not None and absorbed in snaps and snaps[absorbed] is None:
+        snaps[absorbed] = (chain.dmin.clone(), chain.arg.clone())
+
+
+def _kpp_chain_host(G: DeviceCSR, K: int, seed: int, absorb_last: bool, snaps: Optional[dict] = None):
     """Host-sampled chain: one device solve + one numpy draw per centre (reference structure)."""
     N = G.n
     rng = np.random.RandomState(seed)
@@ -132,6 +138,7 @@ def _kpp_chain_host(G: DeviceCSR, K: int, seed: int, absorb_last: bool):
     complete = True
     for _ in range(1, K):
         d_min = chain.absorb(centers[-1], len(centers) - 1)
+        _snapshot(chain, len(centers), snaps)
         nxt = _next_center(rng, N, d_min, centers)
         if nxt is None:
             print(f"Warning: Could not find {K} valid centers, stopping at {len(centers)}")
@@ -143,7 +150,7 @@ def _kpp_chain_host(G: DeviceCSR, K: int, seed: int, absorb_last: bool):
     return centers, chain
 
 
-def _kpp_chain_device(G: DeviceCSR, K: int, seed: int, absorb_last: bool):
+def _kpp_chain_device(G: DeviceCSR, K: int, seed: int, absorb_last: bool, snaps: Optional[dict] = None):
     """Device-resident chain (csrc/kpp.hip): the solves, the d_min update and numpy's draw all stay on the
     GPU; the host only supplies the uniform deviates of the same RandomState stream and steps in when the
     kernel declines a draw (u within rounding reach of a cdf boundary) or a solve needs more sweeps."""
@@ -184,7 +191,9 @@ def _kpp_chain_device(G: DeviceCSR, K: int, seed: int, absorb_last: bool):
     resident_ok = _KNOBS["resident"] and N <= lib.geo_kpp_resident_max_nodes()
     one_step_at = -1                                     # iteration the resident kernel handed back (reason 4)
     status = np.zeros(4, dtype=np.int32)
+    stops = sorted(snaps) if snaps else []              # fit_kmedoids_path: no segment runs across one of these
     while it < it1:
+        _snapshot(chain, it, snaps)                      # here exactly centres 0 .. it-1 are folded into d_min
         step_mode = finite and not fixed and K <= N
         r_from = _resident_from(N)
         resident = step_mode and resident_ok and it >= min(r_from, it1) and it != one_step_at
@@ -194,6 +203,7 @@ def _kpp_chain_device(G: DeviceCSR, K: int, seed: int, absorb_last: bool):
             seg_end = it + 1 if it == one_step_at else (min(it1, r_from) if resident_ok and it < r_from else it1)
         else:
             seg_end = min(it1, it + seg)
+        seg_end = min([seg_end] + [b for b in stops if b > it][:1])
         t_call = time.perf_counter()
         with torch.cuda.device(dev):
             _lib.check(lib.geo_kpp_chain(ptr(G.indptr), ptr(G.indices), ptr(G.data), N, ptr(centers_d),
@@ -250,12 +260,12 @@ def _kpp_chain_device(G: DeviceCSR, K: int, seed: int, absorb_last: bool):
     return centers, chain
 
 
-def _kpp_chain(G: DeviceCSR, K: int, seed: int, absorb_last: bool):
+def _kpp_chain(G: DeviceCSR, K: int, seed: int, absorb_last: bool, snaps: Optional[dict] = None):
     print(f"[kpp] Selecting {K} centers among {G.n} nodes")
     if os.environ.get("GEO_KPP_HOST_DRAW", "0") == "1":
-        centers, chain = _kpp_chain_host(G, K, seed, absorb_last)
+        centers, chain = _kpp_chain_host(G, K, seed, absorb_last, snaps)
     else:
-        centers, chain = _kpp_chain_device(G, K, seed, absorb_last)
+        centers, chain = _kpp_chain_device(G, K, seed, absorb_last, snaps)
     print(f"[kpp] Selected {len(centers)} centers")
     return centers, chain
 
@@ -340,6 +350,54 @@ def fit_kmedoids_optimized(W, K: int = 512, init: str = "kpp", seed: int = 42) -
     qe = _qe_from(d_assigned)
     print(f"[kmedoids] Done: clusters={len(medoids)}, qe={qe:.3f}")
     return medoids, assign, qe
+
+
+def fit_kmedoids_path(W, K_values, init: str = "kpp", seed: int = 42, info: Optional[dict] = None):
+    """fit_kmedoids_optimized for every K of K_values (any order, duplicates allowed) from ONE seeding chain.
+
+    Extension: the reference's K sweep (demos/kmedoids_geodesic_analysis.py) fits every K from scratch.  For one seed the
+    k-means++ centres of a smaller K are a prefix of those of a larger K (one randint, then one rng.choice per centre), and
+    the assignment is the chain's running (d_min, argmin): the sweep is the chain of max(K_values), copied on the device each
+    time exactly K_i centres are folded in -- max(K_values) solves instead of sum(K_values).  init="random" is nested the same
+    way (RandomState.choice(N, K, replace=False) is a prefix of one permutation) but has no chain: one label-carrying solve
+    per distinct K.  Entry i equals fit_kmedoids_optimized(W, K_values[i], init, seed) bit for bit.
+    `info`, if given, receives solves (single-source solves of the chain, or label-carrying solves for "random") and, per
+    entry, finite_fraction (share of nodes whose distance to their medoid is finite, from d_min)."""
+    if init not in ("kpp", "random"):
+        raise ValueError("init must be 'kpp' or 'random'")
+    Ks = [int(K) for K in K_values]
+    if not Ks or min(Ks) < 1:
+        raise ValueError("K_values must be a non-empty sequence of positive integers")
+    G = _to_device_graph(W)
+    N, Kmax = G.n, max(Ks)
+    print(f"[kmedoids] N={N}, K path={Ks}, edges={G.nnz}, avg_deg={G.nnz/max(1,N):.1f}")
+    states = {}
+    if init == "kpp":
+        snaps = {K: None for K in set(Ks) if K < Kmax}
+        centers, chain = _kpp_chain(G, Kmax, seed, absorb_last=True, snaps=snaps)
+        for K in set(Ks):
+            # a chain that ran out of nodes stopped with every centre folded in: that state answers every larger K
+            dmin, arg = snaps[K] if K < len(centers) else (chain.dmin, chain.arg)
+            states[K] = (np.array(centers[:K], dtype=int), dmin, arg)
+        solves = chain.solves
+    else:
+        rng = np.random.RandomState(seed)
+        full = rng.choice(N, size=min(Kmax, N), replace=False).astype(int)
+        for K in set(Ks):
+            dmin, arg = _assign_device(G, full[:K])
+            states[K] = (full[:K].copy(), dmin, arg)
+        solves = len(states)
+    out, fractions = [], []
+    for K in Ks:
+        medoids, dmin, arg = states[K]
+        assign = arg.cpu().numpy().astype(int)
+        qe = _qe_from(dmin.cpu().numpy())
+        fractions.append(int(torch.isfinite(dmin).sum()) / N)
+        print(f"[kmedoids] K={K}: clusters={len(medoids)}, qe={qe:.3f}")
+        out.append((medoids.copy(), assign, qe))
+    if info is not None:
+        info.update(solves=int(solves), finite_fraction=fractions)
+    return out
 
 
 def fit_kmedoids_with_connectivity_check(W, K: int = 512, init: str = "kpp", seed: int = 42):
