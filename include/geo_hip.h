@@ -475,6 +475,32 @@ int geo_vq_forward(const void *z_e, int32_t half, int32_t B, int32_t C, int32_t 
 int geo_vq_backward(const float *g_st, const float *g_loss, double beta, const void *z_e, int32_t half, const float *z_q_st,
                     int64_t numel, void *grad_out, void *stream);
 
+/* ---- ELBO of the vanilla VAE (reference src/models/vae.py VAE.loss) ----
+ * x_logits, x f32 [B][P]; mu, logvar f32 [B][d] (device, contiguous); 1 <= B, P, d < 2^31.
+ *   recon = (1 / B) sum of  BCE: max(l, 0) - l x + log1p(exp(-|l|))  |  MSE_SIGMOID: (sigmoid(l) - x)^2  |  MSE_LOGITS: (l - x)^2
+ *   kl    = (1 / B) sum of  max(k, free_bits) when has_free_bits, else k;   k = -0.5 (1 + logvar - mu^2 - exp(logvar))
+ *   reg   = kl (capacity OFF)  |  |kl - capacity_target| (ABS)  |  max(kl - capacity_target, 0) (CLIPPED)
+ * geo_vae_elbo_forward: out f64 [4] (device) = recon + beta reg, recon, kl, reg.  Terms in fp64 from the f32 inputs;
+ *   per-workgroup partials in ws, then one ordered pass; no atomics: bit-identical across runs and streams.
+ * geo_vae_elbo_backward: grad_total f64 [1] (device) = the gradient of out[0]; out = the forward's (kl is read on the device).
+ *   d_logits f32 [B][P], d_mu, d_logvar f32 [B][d], each an fp64 value rounded once.  Free bits: zero where k < free_bits,
+ *   passed at equality (torch.clamp's backward); ABS: sign(kl - target), 0 at 0; CLIPPED: passed where kl - target >= 0.
+ * geo_vae_elbo_workspace_bytes: 0 for shapes outside the limits.  Neither call synchronises. */
+#define GEO_VAE_RECON_BCE 0
+#define GEO_VAE_RECON_MSE_SIGMOID 1
+#define GEO_VAE_RECON_MSE_LOGITS 2
+#define GEO_VAE_CAPACITY_OFF 0
+#define GEO_VAE_CAPACITY_ABS 1
+#define GEO_VAE_CAPACITY_CLIPPED 2
+size_t geo_vae_elbo_workspace_bytes(int64_t B, int64_t P, int64_t d);
+int geo_vae_elbo_forward(const float *x_logits, const float *x, const float *mu, const float *logvar, int64_t B, int64_t P,
+                         int64_t d, int32_t recon_mode, int32_t has_free_bits, double free_bits, double beta,
+                         double capacity_target, int32_t capacity_mode, double *out, void *ws, size_t ws_bytes, void *stream);
+int geo_vae_elbo_backward(const double *grad_total, const double *out, const float *x_logits, const float *x, const float *mu,
+                          const float *logvar, int64_t B, int64_t P, int64_t d, int32_t recon_mode, int32_t has_free_bits,
+                          double free_bits, double beta, double capacity_target, int32_t capacity_mode, float *d_logits,
+                          float *d_mu, float *d_logvar, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,11 @@ _SIGNATURES = {
     "geo_vq_forward": (ctypes.c_int, [c_p, i32, i32, i32, i32, c_p, c_p, c_p, i32, i32, ctypes.c_double, ctypes.c_double,
                                       ctypes.c_double, c_p, c_p, c_p, c_p, c_p, c_p, c_p, sz, c_p]),
     "geo_vq_backward": (ctypes.c_int, [c_p, c_p, ctypes.c_double, c_p, i32, c_p, i64, c_p, c_p]),
+    "geo_vae_elbo_workspace_bytes": (sz, [i64, i64, i64]),
+    "geo_vae_elbo_forward": (ctypes.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i32, i32, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, i32, c_p, c_p, sz, c_p]),
+    "geo_vae_elbo_backward": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, i64, i32, i32, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_double, i32, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

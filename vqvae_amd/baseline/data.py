@@ -64,8 +64,8 @@ class DeviceImages:
         return (self.batch(slice(s, s + batch_size)) for s in range(0, len(self), batch_size))
 
 
-def shuffled_order(n: int, batch_size: int) -> List[List[int]]:
-    """The batches of indices a DataLoader(shuffle=True, drop_last=True) over n items yields, with the same CPU RNG draws."""
+def shuffled_order(n: int, batch_size: int, drop_last: bool = True) -> List[List[int]]:
+    """The batches of indices a DataLoader(shuffle=True, drop_last=drop_last) over n items yields, with the same CPU RNG draws."""
     _iterator_seed_draw()
     out, cur = [], []
     for i in RandomSampler(range(n)):
@@ -73,6 +73,8 @@ def shuffled_order(n: int, batch_size: int) -> List[List[int]]:
         if len(cur) == batch_size:
             out.append(cur)
             cur = []
+    if cur and not drop_last:
+        out.append(cur)
     return out
 
 

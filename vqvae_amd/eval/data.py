@@ -3,6 +3,7 @@ root, and the transforms the reference's evaluation scripts apply (Resize, ToTen
 a missing file is a FileNotFoundError that names the paths looked for.
 
     <root>/FashionMNIST/raw/t10k-images-idx3-ubyte[.gz], t10k-labels-idx1-ubyte[.gz]
+    <root>/FashionMNIST/raw/train-images-idx3-ubyte[.gz], train-labels-idx1-ubyte[.gz]      (MNIST/raw likewise)
     <root>/cifar-10-batches-py/test_batch, data_batch_1 .. data_batch_5
 """
 import gzip
@@ -45,6 +46,29 @@ def fashionmnist_test(root: str) -> Tuple[np.ndarray, np.ndarray]:
     images = read_idx(os.path.join(raw, "t10k-images-idx3-ubyte"))
     labels = read_idx(os.path.join(raw, "t10k-labels-idx1-ubyte")).astype(np.int64)
     return images, labels
+
+
+def idx_split(root: str, dataset: str, train: bool) -> Tuple[np.ndarray, np.ndarray]:
+    """(images uint8 [N, 28, 28], labels int64 [N]) of one split of an idx-format data set ("FashionMNIST" or "MNIST":
+    torchvision's folder names) under `root`: train-* for the training split, t10k-* for the test split."""
+    raw = os.path.join(root, dataset, "raw")
+    stem = "train" if train else "t10k"
+    images = read_idx(os.path.join(raw, f"{stem}-images-idx3-ubyte"))
+    labels = read_idx(os.path.join(raw, f"{stem}-labels-idx1-ubyte")).astype(np.int64)
+    return images, labels
+
+
+def fashionmnist_train(root: str) -> Tuple[np.ndarray, np.ndarray]:
+    """(images uint8 [N, 28, 28], labels int64 [N]) of the FashionMNIST training split under `root`."""
+    return idx_split(root, "FashionMNIST", train=True)
+
+
+def mnist_train(root: str) -> Tuple[np.ndarray, np.ndarray]:
+    return idx_split(root, "MNIST", train=True)
+
+
+def mnist_test(root: str) -> Tuple[np.ndarray, np.ndarray]:
+    return idx_split(root, "MNIST", train=False)
 
 
 def _cifar10_batches(root: str, names) -> Tuple[np.ndarray, np.ndarray]:

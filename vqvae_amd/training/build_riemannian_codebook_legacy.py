@@ -43,46 +43,60 @@ N_BANDS = 5                     # Euclidean-weight bands of the subset mode
 _RUN_DIRS = {"mnist": "experiments/vae_mnist", "fashion": "experiments/vae_fashion", "cifar10": "experiments/vae_cifar10"}
 
 
+def _run_dir(cfg: Dict, default: str) -> str:
+    data = cfg.get("data") if isinstance(cfg.get("data"), dict) else {}
+    name = str(data.get("dataset", default)).strip().lower()
+    return _RUN_DIRS.get(name, _RUN_DIRS[default])
+
+
 @dataclass
-class LegacyJob:
-    """The reference's configuration dictionary, resolved (same keys, same fall-backs)."""
+class GraphJob:
+    """What both legacy builders read from the reference's configuration dictionary (same keys, same fall-backs): the
+    latents, the output directory, the kNN graph and the k-medoids settings."""
     latents: Path
-    checkpoint: Path
     out_dir: Path
-    vae_config: Dict
     k: int
     metric: str
     sym: str
     graph_mode: str
-    reweight_mode: str
-    max_edges: int
-    batch_size: int
     K: int
     init: str
     seed: int
 
     @staticmethod
-    def from_config(cfg: Dict) -> "LegacyJob":
+    def fields(cfg: Dict) -> Dict:
         data = cfg.get("data") if isinstance(cfg.get("data"), dict) else {}
+        graph, quant = cfg["graph"], cfg["quantize"]
+        return dict(latents=Path(data.get("latents_path") or _run_dir(cfg, "mnist") + "/latents_train/z.pt"),
+                    out_dir=Path(cfg["out"]["dir"]),
+                    k=int(graph["k"]), metric=str(graph["metric"]), sym=str(graph["sym"]), graph_mode=str(graph["mode"]),
+                    K=int(quant["K"]), init=str(quant["init"]), seed=int(quant["seed"]))
 
-        def run_dir(default: str) -> str:
-            name = str(data.get("dataset", default)).strip().lower()
-            return _RUN_DIRS.get(name, _RUN_DIRS[default])
+    @classmethod
+    def from_config(cls, cfg: Dict) -> "GraphJob":
+        return cls(**GraphJob.fields(cfg))
 
+
+@dataclass
+class LegacyJob(GraphJob):
+    """The Riemannian builder's configuration, resolved: GraphJob plus the checkpoint, the VAE and the re-weighting."""
+    checkpoint: Path
+    vae_config: Dict
+    reweight_mode: str
+    max_edges: int
+    batch_size: int
+
+    @classmethod
+    def from_config(cls, cfg: Dict) -> "LegacyJob":
         model_cfg = cfg.get("model") if isinstance(cfg.get("model"), dict) else {}
         ckpt = cfg.get("checkpoint_path") or cfg.get("vae", {}).get("ckpt_path") or model_cfg.get("checkpoint_path")
         vae_config = cfg.get("vae_config") or cfg.get("model") or cfg.get("vae")
         if vae_config is None:
             raise ValueError("VAE configuration not found. Expected 'vae_config', 'model', or 'vae' key in config.")
-        graph, riem, quant = cfg["graph"], cfg.get("riemannian", {}), cfg["quantize"]
-        return LegacyJob(
-            latents=Path(data.get("latents_path") or run_dir("mnist") + "/latents_train/z.pt"),
-            checkpoint=Path(ckpt or run_dir("fashion") + "/checkpoints/best.pt"),
-            out_dir=Path(cfg["out"]["dir"]), vae_config=vae_config,
-            k=int(graph["k"]), metric=str(graph["metric"]), sym=str(graph["sym"]), graph_mode=str(graph["mode"]),
-            reweight_mode=riem.get("mode", "subset"), max_edges=int(riem.get("max_edges", 5000)),
-            batch_size=int(riem.get("batch_size", 512)),
-            K=int(quant["K"]), init=str(quant["init"]), seed=int(quant["seed"]))
+        riem = cfg.get("riemannian", {})
+        return cls(**GraphJob.fields(cfg), checkpoint=Path(ckpt or _run_dir(cfg, "fashion") + "/checkpoints/best.pt"),
+                   vae_config=vae_config, reweight_mode=riem.get("mode", "subset"), max_edges=int(riem.get("max_edges", 5000)),
+                   batch_size=int(riem.get("batch_size", 512)))
 
 
 def read_latents(path: Path) -> torch.Tensor:
