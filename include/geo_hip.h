@@ -501,6 +501,21 @@ int geo_vae_elbo_backward(const double *grad_total, const double *out, const flo
                           double free_bits, double beta, double capacity_target, int32_t capacity_mode, float *d_logits,
                           float *d_mu, float *d_logvar, void *stream);
 
+/* ---- Training batches from resident uint8 images (the reference's src/data/factory.py transforms) ----
+ * u8 [N][H][W][C] (device), rows i64 [B] in [0, N) (device; the caller checks them on the host -- an index outside the range
+ * reads as a black image), offset i32 [B][2] = (oy, ox) or NULL, flip u8 [B] (non-zero = mirror) or NULL, mean, std f32 [C]
+ * (device), out f32 [B][C][H][W].
+ *   out[b][c][y][x] = ((p * fl32(1 / 255)) - mean[c]) / std[c],  p = u8[rows[b]][y + oy - pad][sx0 + ox - pad][c],
+ *   sx0 = flip[b] ? W - 1 - x : x;  p = 0 where the source position lies outside the image.  offset == NULL means
+ *   (oy, ox) = (pad, pad): with flip == NULL too, the plain batch.  RandomCrop(H, padding = pad) draws (oy, ox) in [0, 2 pad]^2.
+ * Three float32 roundings, no contraction: bit for bit torch's x.to(float32).div(255).sub_(mean).div_(std) on the device
+ * (a division by a host scalar is torch's product with the scalar's float32 reciprocal).
+ * Limits: 1 <= C <= 4, 1 <= H, W <= 256, 0 <= pad <= 16, N, B >= 1, B C H ceil(W / 4) < 2^31; GEO_E_ARG outside, before any
+ * launch.  One kernel, 16-byte stores when W % 4 == 0 and out is 16-byte aligned, scalar stores otherwise.  Asynchronous. */
+int geo_batch_assemble(const uint8_t *u8, int64_t N, int32_t H, int32_t W, int32_t C, const int64_t *rows, int32_t B,
+                       const int32_t *offset, const uint8_t *flip, int32_t pad, const float *mean, const float *std, float *out,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

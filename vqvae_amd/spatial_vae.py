@@ -1,14 +1,20 @@
-"""SpatialVAE for latent production on the MI355X: the reference's encoder half
-(src/models/spatial_vae.py:22-44) next to the decoder of vqvae_amd/spatial_decoder.py, with the SAME parameter names,
-so a `best.pt` written by the reference's trainer ({'model_state_dict', 'epoch'}, spatial_engine.py:142) loads unchanged.
-Only inference is kept (encode -> mu, logvar, z): training the VAE is outside the geodesic-codebook path.  The layers
-are PyTorch-ROCm modules (device memory and convolutions are plumbing here; the path's own arithmetic is in csrc/)."""
+"""SpatialVAE on the MI355X: the reference's model (src/models/spatial_vae.py) -- its encoder half next to the
+decoder of vqvae_amd/spatial_decoder.py -- with the SAME parameter names, so a `best.pt` written by either trainer
+({'model_state_dict', 'epoch'}, spatial_engine.py:142) loads into the other's model unchanged.
+
+Inference (encode -> mu, logvar, z) feeds the geodesic-codebook path; `loss` is the reference's spatial ELBO and is what
+training/spatial_engine.py and scripts/train_vae.py train with.  On CUDA tensors it is the fused HIP
+ELBO the vanilla VAE uses (`elbo_hip` of vae.py, csrc/vae_loss.hip) on the latent grids viewed as [B][d h w], and returns
+float64 scalars that live on the device; on CPU tensors it is the reference's formula in torch ops.  The layers are
+PyTorch-ROCm modules (device memory and convolutions are plumbing here; the path's own arithmetic is in csrc/)."""
 from typing import Sequence, Tuple
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .spatial_decoder import SpatialDecoder, make_norm
+from .vae import CAPACITY_MODES, RECON_MODES, elbo_hip
 
 
 class SpatialEncoder(nn.Module):
@@ -41,6 +47,7 @@ class SpatialVAE(nn.Module):
         self.decoder = SpatialDecoder(in_channels, tuple(dec_channels), latent_dim, output_image_size, norm_type)
         self.recon_loss = recon_loss
         self.mse_use_sigmoid = kwargs.get("mse_use_sigmoid", True)
+        self._step = 0
 
     @staticmethod
     def reparameterize(mu: torch.Tensor, logvar: torch.Tensor) -> torch.Tensor:
@@ -51,3 +58,22 @@ class SpatialVAE(nn.Module):
         mu, logvar = self.encoder(x)
         z = self.reparameterize(mu, logvar)
         return self.decoder(z), mu, logvar, z
+
+    def loss(self, x, x_logits, mu, logvar, beta: float, **kwargs) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(total, recon, kl) of the reference (spatial_vae.py:110-125): recon = the summed BCE-with-logits, or squared error
+        of sigmoid(x_logits) or of x_logits, over the batch size; kl = the batch mean of the sum over (d, h, w) of
+        -0.5 (1 + logvar - mu^2 - exp(logvar)); total = recon + beta kl.  Other keywords (the engine's `step=`) are ignored."""
+        B = x.size(0)
+        if x_logits.is_cuda:
+            mode = RECON_MODES["bce" if self.recon_loss == "bce" else "mse_sigmoid" if self.mse_use_sigmoid else "mse_logits"]
+            # reshape copies a grid that is not contiguous (a channels-last convolution output) once; elbo_hip does the same
+            # for x_logits and x
+            out = elbo_hip(x_logits, x, mu.reshape(B, -1), logvar.reshape(B, -1), mode, None, beta, 0.0, CAPACITY_MODES["off"])
+            return out[0], out[1].detach(), out[2].detach()
+        if self.recon_loss == "bce":
+            recon = F.binary_cross_entropy_with_logits(x_logits, x, reduction="sum") / B
+        else:
+            x_pred = torch.sigmoid(x_logits) if self.mse_use_sigmoid else x_logits
+            recon = F.mse_loss(x_pred, x, reduction="sum") / B
+        kl = (-0.5 * (1 + logvar - mu.pow(2) - logvar.exp())).sum(dim=[1, 2, 3]).mean()
+        return recon + beta * kl, recon, kl

@@ -10,8 +10,14 @@ augment=True.  CIFAR-10: RandomCrop(32, padding=4) + RandomHorizontalFlip on the
 the loader's own that is seeded from the CPU generator when the loader is built: seeded and reproducible, but NOT torchvision's
 random stream (torchvision draws inside each worker process, per image).  The grey sets' RandomRotation(10) is not implemented.
 
+Batch assembly.  On a CUDA device a batch is ONE kernel (`assemble_batch`: geo_batch_assemble of csrc/batch.hip, DESIGN.md
+section 14) that writes the normalised float32 NCHW batch from the resident uint8 rows, after ONE host-to-device copy that
+carries the batch's rows, crop offsets and flips.  On the CPU, or with `fused=False`, a batch is the torch expression the
+kernel reproduces bit for bit (`DeviceImages.batch`, `ResidentLoader._augmented`).  Both paths make the same random draws.
+
 Nothing is downloaded: a missing file is eval/data.py's FileNotFoundError.
 """
+import ctypes
 from typing import Iterator, Optional, Sequence, Tuple
 
 import numpy as np
@@ -26,14 +32,55 @@ ROTATION_MESSAGE = ("augment=True on MNIST / FashionMNIST is torchvision's Rando
                     "implemented for resident data")
 
 
+CROP_PAD = 4                              # RandomCrop(32, padding=4)
+
+
+def assemble_batch(images: DeviceImages, rows: torch.Tensor, offset: Optional[torch.Tensor] = None,
+                   flip: Optional[torch.Tensor] = None, pad: int = 0) -> torch.Tensor:
+    """The float32 NCHW batch of `rows` (host int64 [B], checked against len(images) here) by geo_batch_assemble; `offset`
+    (host integers [B][2] = (oy, ox)) and `flip` (host booleans [B]) select the crop of the image padded by `pad` and the
+    mirror, None = none.  One host-to-device copy: rows | offsets | flips in one byte buffer.  Asynchronous."""
+    from .. import _lib
+    if not images.u8.is_cuda:
+        raise ValueError("assemble_batch needs images resident on a CUDA device")
+    rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+    B, (N, H, W, C) = rows.numel(), images.u8.shape
+    if B == 0 or int(rows.min()) < 0 or int(rows.max()) >= N:
+        raise IndexError(f"batch rows must be a non-empty set of indices in [0, {N})")
+    parts = [rows.view(torch.uint8)]
+    if offset is not None:
+        parts.append(offset.to(torch.int32).reshape(B, 2).contiguous().view(torch.uint8).reshape(-1))
+    if flip is not None:
+        parts.append(flip.to(torch.uint8).reshape(B))
+    dev = images.device
+    packed = (torch.cat(parts) if len(parts) > 1 else parts[0]).to(dev)
+    at = 8 * B
+    p_off = p_flip = None
+    if offset is not None:
+        p_off, at = packed.data_ptr() + at, at + 8 * B
+    if flip is not None:
+        p_flip = packed.data_ptr() + at
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().geo_batch_assemble(images.u8.data_ptr(), N, H, W, C, packed.data_ptr(), B, p_off, p_flip, int(pad),
+                                                  images.mean.data_ptr(), images.std.data_ptr(), out.data_ptr(), stream),
+                   "geo_batch_assemble")
+    return out
+
+
 class ResidentLoader:
-    """(x float32 NCHW on the device, y int64 on the host) batches over `images`; len() = number of batches."""
+    """(x float32 NCHW on the device, y int64 on the host) batches over `images`; len() = number of batches.
+    `fused`: None = the batch kernel when the images are on a CUDA device, False = the torch expression everywhere."""
 
     def __init__(self, images: DeviceImages, batch_size: int, shuffle: bool, normalize: Optional[Tuple[Sequence[float], Sequence[float]]] = None,
-                 crop_flip: bool = False):
+                 crop_flip: bool = False, fused: Optional[bool] = None):
         self.images, self.batch_size, self.shuffle = images, int(batch_size), bool(shuffle)
         self.normalize = normalize            # (mean, std) the batches carry, for un-normalising a display; None = plain [0, 1]
         self.crop_flip = bool(crop_flip)
+        self.fused = images.u8.is_cuda if fused is None else bool(fused)
+        if self.fused and not images.u8.is_cuda:
+            raise ValueError("fused=True needs images resident on a CUDA device")
         self.aug_rng = None
         if self.crop_flip:
             self.aug_rng = torch.Generator().manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
@@ -44,10 +91,12 @@ class ResidentLoader:
     def _augmented(self, rows: torch.Tensor) -> torch.Tensor:
         """Pad 4 with zeros, crop at a uniform offset in [0, 8]^2, mirror with probability 1/2: index arithmetic on uint8."""
         im = self.images
-        u8 = torch.nn.functional.pad(im.u8[rows.to(im.device)], (0, 0, 4, 4, 4, 4))        # [B, H + 8, W + 8, C]
-        B, H, W = u8.size(0), im.u8.size(1), im.u8.size(2)
-        off = torch.randint(0, 9, (B, 2), generator=self.aug_rng)
+        B, H, W = rows.numel(), im.u8.size(1), im.u8.size(2)
+        off = torch.randint(0, 2 * CROP_PAD + 1, (B, 2), generator=self.aug_rng)
         flip = torch.rand(B, generator=self.aug_rng) < 0.5
+        if self.fused:
+            return assemble_batch(im, rows, off, flip, CROP_PAD)
+        u8 = torch.nn.functional.pad(im.u8[rows.to(im.device)], (0, 0, 4, 4, 4, 4))        # [B, H + 8, W + 8, C]
         ys = off[:, :1] + torch.arange(H)                                                   # [B, H]
         xs = off[:, 1:] + torch.arange(W)
         xs = torch.where(flip[:, None], xs.flip(1), xs)
@@ -64,7 +113,10 @@ class ResidentLoader:
             _iterator_seed_draw()
             batches = [torch.arange(s, min(s + self.batch_size, n)) for s in range(0, n, self.batch_size)]
         for rows in batches:
-            x = self._augmented(rows) if self.crop_flip else self.images.batch(rows)
+            if self.crop_flip:
+                x = self._augmented(rows)
+            else:
+                x = assemble_batch(self.images, rows) if self.fused else self.images.batch(rows)
             # plain NCHW strides: a one-channel batch permuted from NHWC would otherwise pass for channels-last
             yield x.reshape(x.size(0), -1).view(x.shape), self.images.labels[rows]
 

@@ -37,6 +37,8 @@ def _batch_moments(x_rec: torch.Tensor, x: torch.Tensor):
 
 
 class TrainingEngine:
+    latent_writer = staticmethod(save_latents)          # (model, loader, device, out_dir); spatial_engine.py swaps it
+
     def __init__(self, model, optimizer: torch.optim.Optimizer, device: torch.device) -> None:
         self.model = model
         self.optimizer = optimizer
@@ -137,8 +139,8 @@ class TrainingEngine:
                 scheduler.step()
 
         if save_latents_flag and output_dir is not None:
-            save_latents(self.model, train_loader, self.device, output_dir / 'latents_train')
-            save_latents(self.model, val_loader, self.device, output_dir / 'latents_val')
+            self.latent_writer(self.model, train_loader, self.device, output_dir / 'latents_train')
+            self.latent_writer(self.model, val_loader, self.device, output_dir / 'latents_val')
         if output_dir is not None:
             self._save_recon_grid(val_loader, output_dir, logger)
         if checkpoint_dir is not None:
