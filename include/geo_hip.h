@@ -328,6 +328,49 @@ int geo_decoder_jvp_pairs(const geo_decoder_desc *dec, const float *z_start, con
                           int64_t n_edges, int32_t batch_size, float *len_out,
                           void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The same quantity for the vanilla (vector-latent) VAE decoder with FIXED statistics (src/models/vae.py:53-85 in eval mode:
+ * BatchNorm with running statistics, or no normalisation):
+ *   fc: Linear(d, c0 16) -> view c0x4x4 -> ConvT(c0,c1,k3,s2,p1[,output_padding]) -> norm -> ReLU
+ *       -> ConvT(c1,c2,k4,s2,p1) -> norm -> ReLU -> ConvT(c2,C,k4,s2,p1) -> sigmoid;   4 -> 7 -> 14 -> 28 px | 4 -> 8 -> 16 -> 32 px.
+ * Everything up to the first norm's scale and shift is affine in z and arrives composed (in fp64, rounded once):
+ *   pre1[n] = c[n] + sum_k z[k] At[k][n],  n = (y s1 + x) c1 + channel,  s1 = out_size / 4,  n1 = s1^2 c1.
+ * Covered: 1 <= latent_dim <= 128, (c1, c2) = (128, 64) or (64, 32), out_channels 1 or 3, out_size 28 or 32.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct geo_vanilla_decoder_desc {
+    int32_t latent_dim;        /* d */
+    int32_t c1, c2;            /* dec_channels[1], dec_channels[2] */
+    int32_t out_channels;      /* C */
+    int32_t out_size;          /* 28 or 32 */
+    /* device pointers, f32 */
+    const float *At;           /* [d rounded up to even][n1]; the padding row is zero */
+    const float *c;            /* [n1] */
+    const float *w2p;          /* ConvT2 weight w2 [c1][c2][4][4] as [parity 2 py + px][tap 2 a + b][c1 / 4][c2][4]:
+                                  element (.., q, co, r) = w2[4 q + r][co][2 a + 1 - py][2 b + 1 - px] */
+    const float *scale2;       /* [c2] second norm folded: pre2 = scale2 * ConvT2(h1) + shift2 (ConvT2's bias inside shift2) */
+    const float *shift2;       /* [c2] */
+    const float *w3p;          /* ConvT3 weight w3 [c2][C][4][4] as [parity][tap][C][c2], same parity / tap meaning */
+    const float *b3;           /* [C] */
+} geo_vanilla_decoder_desc;
+
+/* Workspace of geo_vanilla_jvp_pairs for n_edges edges; 0 for a descriptor outside the coverage above (host arithmetic).
+ * The calls cut the edges into passes that fit the workspace they are given: any size from
+ * geo_vanilla_jvp_workspace_bytes(dec, 1) (the minimum: one edge per pass) upwards is legal for BOTH calls, a smaller
+ * workspace only means more passes, and no length depends on the number of passes. */
+size_t geo_vanilla_jvp_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n_edges);
+/* Workspace with which geo_vanilla_jvp_edges runs the per-point work (ReLU masks, sigmoid') once per latent when
+ * n_nodes <= 2 n_edges (it holds every latent's masks); with less, or with fewer edges, once per edge end. */
+size_t geo_vanilla_jvp_edges_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n_nodes, int64_t n_edges);
+/* z_start / z_end f32 [E][d] -> len_out f32 [E].  batch_size is accepted and ignored: with fixed statistics the value does
+ * not depend on it.  Fixed-order f32 chains, no atomics: bit-identical across runs, streams, workspace sizes and between the
+ * two entry points; z_start[e] == z_end[e] gives exactly 0.  Asynchronous on `stream`. */
+int geo_vanilla_jvp_pairs(const geo_vanilla_decoder_desc *dec, const float *z_start, const float *z_end, int64_t n_edges,
+                          int32_t batch_size, float *len_out, void *ws, size_t ws_bytes, void *stream);
+/* z f32 [n_nodes][d] resident, src / dst i32 [E] in [0, n_nodes) (the caller checks them). */
+int geo_vanilla_jvp_edges(const geo_vanilla_decoder_desc *dec, const float *z, int64_t n_nodes, const int32_t *src,
+                          const int32_t *dst, int64_t n_edges, int32_t batch_size, float *len_out, void *ws, size_t ws_bytes,
+                          void *stream);
+
 /* Gather: data_out[e] = len[entry_edge[e]] for every stored entry (W_geo = U + U^T). */
 int geo_gather_edge_weights(const float *len, const int32_t *entry_edge, int64_t nnz, float *data_out, void *stream);
 

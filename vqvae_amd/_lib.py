@@ -23,6 +23,12 @@ class DecoderDesc(ctypes.Structure):
                 + [("update_running", i32), ("momentum", ctypes.c_float)])
 
 
+class VanillaDecoderDesc(ctypes.Structure):
+    """geo_vanilla_decoder_desc of include/geo_hip.h."""
+    _fields_ = ([(n, i32) for n in ("latent_dim", "c1", "c2", "out_channels", "out_size")]
+                + [(n, c_p) for n in ("At", "c", "w2p", "scale2", "shift2", "w3p", "b3")])
+
+
 class PriorDesc(ctypes.Structure):
     """geo_prior_desc of include/geo_hip.h."""
     _fields_ = ([(n, i32) for n in ("num_tokens", "embed_dim", "n_layers", "n_head", "max_seq_len", "num_classes")]
@@ -71,6 +77,10 @@ _SIGNATURES = {
     "geo_jvp_plan": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), i64, i64, i32, i32, sz]),
     "geo_decoder_jvp_edges": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, i64, c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
     "geo_decoder_jvp_pairs": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
+    "geo_vanilla_jvp_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64]),
+    "geo_vanilla_jvp_edges_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64, i64]),
+    "geo_vanilla_jvp_pairs": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
+    "geo_vanilla_jvp_edges": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, i64, c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
     "geo_gather_edge_weights": (ctypes.c_int, [c_p, c_p, i64, c_p, c_p]),
     "geo_prior_sample_workspace_bytes": (sz, [ctypes.POINTER(PriorDesc), i32, i32]),
     "geo_prior_sample": (ctypes.c_int, [ctypes.POINTER(PriorDesc), c_p, i32, i32, c_p, c_p, ctypes.c_float, i32, c_p, c_p, i32,

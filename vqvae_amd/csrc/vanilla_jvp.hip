@@ -1,0 +1,475 @@
+// vanilla_jvp.hip -- pull-back edge lengths of the vanilla (vector-latent) VAE decoder with FIXED statistics on gfx950.
+//
+//   fc: Linear(d, c0*16) -> view c0x4x4 -> ConvT(c0,c1,k3,s2,p1[,op]) -> norm -> ReLU -> ConvT(c1,c2,k4,s2,p1) -> norm -> ReLU
+//       -> ConvT(c2,C,k4,s2,p1) -> sigmoid,     4 -> 7 -> 14 -> 28 px  |  4 -> 8 -> 16 -> 32 px
+//   len[e] = 0.5 (|J(z_a) dz| + |J(z_b) dz|),  dz = z_b - z_a                              
+//
+// With eval-mode BatchNorm (or no norm) everything up to the first norm's scale and shift is affine in z; the export composes
+// it once in fp64: pre1 = z . At + c, At [d_even][n1], n1 = s1^2 c1, column = pixel * c1 + channel.  What the tangent needs
+// from a point are the two ReLU sign masks (bits) and sigmoid' of the output.  Two passes over one layout:
+//
+//   point pass (per latent slot)   vj_front_kernel<false>  pre1 on v_mfma_f32_32x32x2_f32 -> mask1 bits, relu(pre1)
+//                                  vj_mid_kernel<.., false> ConvT2 + folded norm2 -> mask2 bits, relu
+//                                  vj_back_kernel<.., false> ConvT3 + bias -> sigmoid'
+//   edge pass (per edge)           vj_front_kernel<true>   t1 = dz . At, once per edge (the same at both ends)
+//                                  vj_mid_kernel<.., true>  per end: mask1 -> ConvT2 tangent -> scale2 -> mask2
+//                                  vj_back_kernel<.., true> per end: ConvT3 tangent -> sigmoid' scale -> sum of squares; len[e]
+//
+// ConvT2 (k4, s2, p1) is four implicit GEMMs, one per output-pixel parity: out[(2y+py, 2x+px)][co] = sum over the taps
+// (a, b) in {0,1}^2 and ci of in[(y+py-a, x+px-b)][ci] w2[ci][co][2a+1-py][2b+1-px]; M = (item, pixel) rows, K = 4 c1, N = c2, on
+// the exact-f32 matrix instruction.  Every value is a fixed-order fmaf chain of its own row, no atomics: a length does not
+// depend on the pass size, the position in a pass, the entry point, the run or the stream.  dz = 0 gives exactly 0.
+#include "geo_common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int MAX_D = 128;
+constexpr int64_t EDGES_PER_PASS = 2048;        // at most this many edges (twice as many items) per pass
+constexpr int FRONT_ROWS = 64, FRONT_SPLIT = 4;
+constexpr int MID_ROWS = 256;                   // (item, pixel) rows of one mid workgroup: 4 items at 8x8, 5 at 7x7
+
+struct Shape {
+    int d, dp, c1, c2, co, s1, s2, S, n1, n2, nout, G;
+};
+
+bool make_shape(const geo_vanilla_decoder_desc *dc, Shape *s) {
+    if (!dc) return false;
+    if (dc->latent_dim < 1 || dc->latent_dim > MAX_D) return false;
+    if (!((dc->c1 == 128 && dc->c2 == 64) || (dc->c1 == 64 && dc->c2 == 32))) return false;
+    if (dc->out_channels != 1 && dc->out_channels != 3) return false;
+    if (dc->out_size != 28 && dc->out_size != 32) return false;
+    s->d = dc->latent_dim;
+    s->dp = (s->d + 1) & ~1;
+    s->c1 = dc->c1;
+    s->c2 = dc->c2;
+    s->co = dc->out_channels;
+    s->S = dc->out_size;
+    s->s2 = s->S / 2;
+    s->s1 = s->S / 4;
+    s->n1 = s->s1 * s->s1 * s->c1;
+    s->n2 = s->s2 * s->s2 * s->c2;
+    s->nout = s->co * s->S * s->S;
+    s->G = MID_ROWS / (s->s1 * s->s1);
+    return true;
+}
+
+// Workspace: per point slot the two masks and sigmoid'; per pass of EB edges the front's and the mid's outputs of 2 EB items.
+size_t layout_bytes(const Shape &s, int64_t slots, int64_t eb) {
+    using geo::align_up;
+    return align_up((size_t)slots * (s.n1 / 32) * 4) + align_up((size_t)slots * (s.n2 / 32) * 4) +
+           align_up((size_t)slots * s.nout * 4) + align_up((size_t)2 * eb * s.n1 * 4) + align_up((size_t)2 * eb * s.n2 * 4);
+}
+
+// Where the latents of a pass come from.  List A holds the start points, list B the end points: entry i of a list is row
+// (index ? index[base + i] : base + i) of its array.  The points of a point pass are A[0 .. nA) followed by B[0 ..).
+struct Ends {
+    const float *zA, *zB;
+    const int32_t *iA, *iB;
+    int64_t base;
+    int nA;
+};
+
+__device__ __forceinline__ const float *row_a(const Ends &s, int64_t i, int d) {
+    return s.zA + (size_t)(s.iA ? (int64_t)s.iA[s.base + i] : s.base + i) * d;
+}
+__device__ __forceinline__ const float *row_b(const Ends &s, int64_t i, int d) {
+    return s.zB + (size_t)(s.iB ? (int64_t)s.iB[s.base + i] : s.base + i) * d;
+}
+// The slot of item (edge l, side): the latent's own index when the point pass ran over the resident latents, else its
+// position in the pass's point list.
+__device__ __forceinline__ int64_t item_slot(const Ends &s, int resident, int64_t l, int side) {
+    if (resident) return side ? (int64_t)s.iB[s.base + l] : (int64_t)s.iA[s.base + l];
+    return side ? (int64_t)s.nA + l : l;
+}
+
+// ---- front: rows of z (points) or of dz (edges) times At on the f32 matrix cores; a workgroup = 64 rows x a quarter of
+// the column tiles, a wave = two 32 x 32 tiles sharing the B operand.  The chain starts at c (points) or 0 (edges).
+template <bool EDGE>
+__global__ __launch_bounds__(256) void vj_front_kernel(Ends s, int count, int d, int dp, int n1, const float *__restrict__ At,
+                                                       const float *__restrict__ c, float *__restrict__ out,
+                                                       uint32_t *__restrict__ mask1, int64_t slot0) {
+    __shared__ float zs[FRONT_ROWS][MAX_D + 1];
+    const int64_t tile0 = (int64_t)blockIdx.x * FRONT_ROWS;
+    for (int q = threadIdx.x; q < FRONT_ROWS * dp; q += 256) {
+        const int r = q / dp, k = q - r * dp;
+        const int64_t p = tile0 + r;
+        float v = 0.f;
+        if (p < count && k < d) {
+            if (EDGE) v = row_b(s, p, d)[k] - row_a(s, p, d)[k];
+            else v = p < s.nA ? row_a(s, p, d)[k] : row_b(s, p - s.nA, d)[k];
+        }
+        zs[r][k] = v;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int ntiles = n1 / 32;
+    for (int ct = blockIdx.y * 4 + wave; ct < ntiles; ct += 4 * gridDim.y) {
+        const int n = ct * 32 + r;
+        const float init = EDGE ? 0.f : c[n];
+        f32x16 acc0, acc1;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) { acc0[q] = init; acc1[q] = init; }
+        for (int i = 0; i < dp / 2; ++i) {
+            const int k = 2 * i + h;
+            const float bm = At[(size_t)k * n1 + n];
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(zs[r][k], bm, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(zs[32 + r][k], bm, acc1, 0, 0, 0);
+        }
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int row = m * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int64_t p = tile0 + row;
+                const float x = m ? acc1[q] : acc0[q];
+                if (EDGE) {
+                    if (p < count) out[(size_t)p * n1 + n] = x;
+                } else {
+                    const unsigned long long bits = __ballot(x > 0.f);     // low half: the h = 0 row, high half: the h = 1 row
+                    if (p < count) {
+                        out[(size_t)p * n1 + n] = x > 0.f ? x : 0.f;
+                        if (r == 0) mask1[(size_t)(slot0 + p) * ntiles + ct] = (uint32_t)(h ? bits >> 32 : bits);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---- mid: ConvT2 of G items.  The items' inputs ([pixel][c1], masked for the tangent) are staged in LDS with rows padded by
+// four floats (conflict-free 16-byte reads) plus one zero row for taps outside the image.  8 waves: wave = (N tile, M tiles);
+// K runs over (tap, 8-channel block): lane half h takes channels 4h .. 4h+3 of the block, one 16-byte read each of A and B
+// feeds four MFMAs.  w2p: [parity][tap][c1 / 4][c2][4] so that the B read is 16 bytes per lane, consecutive over co.
+template <int C1, int C2, bool TANGENT>
+__global__ __launch_bounds__(512) void vj_mid_kernel(const float *__restrict__ in, float *__restrict__ out,
+                                                     const uint32_t *__restrict__ mask1, uint32_t *__restrict__ mask2, Ends s,
+                                                     int resident, int64_t slot0, int64_t n_items, int s1, int G,
+                                                     const float *__restrict__ w2p, const float *__restrict__ sc2,
+                                                     const float *__restrict__ sh2) {
+    constexpr int LD = C1 + 4, TN = C2 / 32, WPN = 8 / TN, MT = TN;
+    __shared__ __attribute__((aligned(16))) float lds[(MID_ROWS + 1) * LD];
+    __shared__ int64_t slot_s[8];
+    const int P = s1 * s1, s2 = 2 * s1, n1 = P * C1, n2 = 4 * P * C2;
+    const int rows = G * P, ZR = rows;
+    const int64_t item0 = (int64_t)blockIdx.x * G;
+    const int tid = threadIdx.x;
+    if (tid < G) {
+        const int64_t it = item0 + tid;
+        int64_t slot = -1;
+        if (it < n_items) slot = TANGENT ? item_slot(s, resident, it >> 1, (int)(it & 1)) : slot0 + it;
+        slot_s[tid] = slot;
+    }
+    __syncthreads();
+    for (int g = 0; g < G; ++g) {
+        const int64_t slot = slot_s[g], it = item0 + g;
+        const float4 *src = reinterpret_cast<const float4 *>(in + (size_t)(TANGENT ? it >> 1 : it) * n1);
+        const uint32_t *mk = mask1 + (size_t)(slot < 0 ? 0 : slot) * (n1 / 32);
+        for (int q = tid; q < n1 / 4; q += 512) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (slot >= 0) {
+                v = src[q];
+                if (TANGENT) {
+                    const uint32_t nib = mk[q >> 3] >> ((q & 7) * 4);
+                    if (!(nib & 1)) v.x = 0.f;
+                    if (!(nib & 2)) v.y = 0.f;
+                    if (!(nib & 4)) v.z = 0.f;
+                    if (!(nib & 8)) v.w = 0.f;
+                }
+            }
+            const int pix = (q * 4) / C1, ci = (q * 4) % C1;
+            *reinterpret_cast<float4 *>(lds + (size_t)(g * P + pix) * LD + ci) = v;
+        }
+    }
+    for (int k = tid; k < LD; k += 512) lds[(size_t)ZR * LD + k] = 0.f;
+    __syncthreads();
+
+    const int lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int nt = wave % TN, m0 = wave / TN;
+    int rg[MT], ry[MT], rx[MT];
+    bool rv[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int r = (m0 + m * WPN) * 32 + j;
+        rv[m] = r < rows;
+        rg[m] = rv[m] ? r / P : 0;
+        const int pq = rv[m] ? r - rg[m] * P : 0;
+        ry[m] = pq / s1;
+        rx[m] = pq - ry[m] * s1;
+    }
+    const int co = nt * 32 + j;
+    const float scale = sc2[co], shift = sh2[co];
+    for (int par = 0; par < 4; ++par) {
+        const int py = par >> 1, px = par & 1;
+        f32x16 acc[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[m][q] = 0.f;
+        for (int tap = 0; tap < 4; ++tap) {
+            const int a = tap >> 1, b = tap & 1;
+            const float *ap[MT];
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const int iy = ry[m] + py - a, ix = rx[m] + px - b;
+                const bool ok = rv[m] && iy >= 0 && iy < s1 && ix >= 0 && ix < s1;
+                ap[m] = lds + (size_t)(ok ? rg[m] * P + iy * s1 + ix : ZR) * LD + 4 * h;
+            }
+            const float4 *wp = reinterpret_cast<const float4 *>(w2p) + ((size_t)(par * 4 + tap) * (C1 / 4) + h) * C2 + co;
+#pragma unroll 4
+            for (int cb = 0; cb < C1 / 8; ++cb) {
+                const float4 bv = wp[(size_t)cb * 2 * C2];
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    const float4 av = *reinterpret_cast<const float4 *>(ap[m] + cb * 8);
+                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[m], 0, 0, 0);
+                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc[m], 0, 0, 0);
+                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[m], 0, 0, 0);
+                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[m], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int r = (m0 + m * WPN) * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int g = r < rows ? r / P : 0;
+                const int64_t slot = r < rows ? slot_s[g] : -1;
+                const bool valid = slot >= 0;
+                const int pq = r - g * P, y = pq / s1, x = pq - y * s1;
+                const int opix = (2 * y + py) * s2 + 2 * x + px;
+                const size_t o = (size_t)(item0 + g) * n2 + (size_t)opix * C2 + co;
+                const size_t w = (size_t)(valid ? slot : 0) * (n2 / 32) + (size_t)opix * TN + nt;
+                if (TANGENT) {
+                    if (valid) out[o] = (mask2[w] >> j) & 1u ? scale * acc[m][q] : 0.f;
+                } else {
+                    const float x2 = fmaf(scale, acc[m][q], shift);
+                    const unsigned long long bits = __ballot(x2 > 0.f);
+                    if (valid) {
+                        out[o] = x2 > 0.f ? x2 : 0.f;
+                        if (j == 0) mask2[w] = (uint32_t)(h ? bits >> 32 : bits);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---- back: ConvT3 (same parity form, w3p [parity][tap][C][c2]: uniform reads) of one item per workgroup, the input
+// ([pixel][c2]) in LDS.  Point pass: sigmoid' = e / (1 + e)^2, e = exp(-|logit|), to the slot.  Edge pass: both ends of one
+// edge in turn; squares summed per thread in position order, then a fixed tree over the wave and the four waves in order.
+template <int C2, int CO, bool TANGENT>
+__global__ __launch_bounds__(256) void vj_back_kernel(const float *__restrict__ in, float *__restrict__ sigp, Ends s,
+                                                      int resident, int64_t slot0, int s2, const float *__restrict__ w3p,
+                                                      const float *__restrict__ b3, float *__restrict__ len_out) {
+    constexpr int LD = C2 + 4;
+    __shared__ __attribute__((aligned(16))) float lds[(MID_ROWS + 1) * LD];
+    __shared__ float wsum[4];
+    const int P2 = s2 * s2, S = 2 * s2, n2 = P2 * C2, nout = CO * S * S, ZR = P2;
+    const int tid = threadIdx.x;
+    float norm[2] = {0.f, 0.f};
+    for (int side = 0; side < (TANGENT ? 2 : 1); ++side) {
+        const int64_t it = TANGENT ? 2 * (int64_t)blockIdx.x + side : (int64_t)blockIdx.x;
+        const int64_t slot = TANGENT ? item_slot(s, resident, blockIdx.x, side) : slot0 + it;
+        float *sg = sigp + (size_t)slot * nout;
+        __syncthreads();
+        const float4 *src = reinterpret_cast<const float4 *>(in + (size_t)it * n2);
+        for (int q = tid; q < n2 / 4; q += 256) {
+            const int pix = (q * 4) / C2, ci = (q * 4) % C2;
+            *reinterpret_cast<float4 *>(lds + (size_t)pix * LD + ci) = src[q];
+        }
+        for (int k = tid; k < LD; k += 256) lds[(size_t)ZR * LD + k] = 0.f;
+        __syncthreads();
+        float ss = 0.f;
+        for (int par = 0; par < 4; ++par) {
+            const int py = par >> 1, px = par & 1;
+            for (int pos = tid; pos < P2; pos += 256) {
+                const int y = pos / s2, x = pos - y * s2;
+                float acc[CO];
+#pragma unroll
+                for (int c = 0; c < CO; ++c) acc[c] = TANGENT ? 0.f : b3[c];
+                for (int tap = 0; tap < 4; ++tap) {
+                    const int iy = y + py - (tap >> 1), ix = x + px - (tap & 1);
+                    const bool ok = iy >= 0 && iy < s2 && ix >= 0 && ix < s2;
+                    const float *ar = lds + (size_t)(ok ? iy * s2 + ix : ZR) * LD;
+                    const float *wr = w3p + (size_t)(par * 4 + tap) * CO * C2;
+#pragma unroll 4
+                    for (int cb = 0; cb < C2 / 4; ++cb) {
+                        const float4 av = *reinterpret_cast<const float4 *>(ar + cb * 4);
+#pragma unroll
+                        for (int c = 0; c < CO; ++c) {
+                            const float *w = wr + c * C2 + cb * 4;
+                            acc[c] = fmaf(av.x, w[0], acc[c]);
+                            acc[c] = fmaf(av.y, w[1], acc[c]);
+                            acc[c] = fmaf(av.z, w[2], acc[c]);
+                            acc[c] = fmaf(av.w, w[3], acc[c]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < CO; ++c) {
+                    const size_t o = ((size_t)c * S + (2 * y + py)) * S + 2 * x + px;
+                    if (TANGENT) {
+                        const float v = sg[o] * acc[c];
+                        ss = fmaf(v, v, ss);
+                    } else {
+                        const float e = expf(-fabsf(acc[c]));
+                        sg[o] = e / ((1.f + e) * (1.f + e));
+                    }
+                }
+            }
+        }
+        if (TANGENT) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off, 64);
+            if ((tid & 63) == 0) wsum[tid >> 6] = ss;
+            __syncthreads();
+            norm[side] = sqrtf(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+        }
+    }
+    if (TANGENT && tid == 0) len_out[blockIdx.x] = 0.5f * (norm[0] + norm[1]);
+}
+
+template <int C1, int C2, bool TANGENT>
+int launch_mid(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *in, float *out, const uint32_t *mask1,
+               uint32_t *mask2, const Ends &e, int resident, int64_t slot0, int64_t n_items, hipStream_t st) {
+    const unsigned grid = (unsigned)((n_items + sh.G - 1) / sh.G);
+    vj_mid_kernel<C1, C2, TANGENT><<<grid, 512, 0, st>>>(in, out, mask1, mask2, e, resident, slot0, n_items, sh.s1, sh.G, dc->w2p,
+                                                         dc->scale2, dc->shift2);
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+template <bool TANGENT>
+int run_mid(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *in, float *out, const uint32_t *mask1, uint32_t *mask2,
+            const Ends &e, int resident, int64_t slot0, int64_t n_items, hipStream_t st) {
+    if (sh.c1 == 128) return launch_mid<128, 64, TANGENT>(sh, dc, in, out, mask1, mask2, e, resident, slot0, n_items, st);
+    return launch_mid<64, 32, TANGENT>(sh, dc, in, out, mask1, mask2, e, resident, slot0, n_items, st);
+}
+
+template <bool TANGENT>
+int run_back(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *in, float *sigp, const Ends &e, int resident,
+             int64_t slot0, int64_t blocks, float *len_out, hipStream_t st) {
+    const unsigned grid = (unsigned)blocks;
+#define VJ_BACK(C2_, CO_)                                                                                                     \
+    vj_back_kernel<C2_, CO_, TANGENT><<<grid, 256, 0, st>>>(in, sigp, e, resident, slot0, sh.s2, dc->w3p, dc->b3, len_out)
+    if (sh.c2 == 64 && sh.co == 1) VJ_BACK(64, 1);
+    else if (sh.c2 == 64) VJ_BACK(64, 3);
+    else if (sh.co == 1) VJ_BACK(32, 1);
+    else VJ_BACK(32, 3);
+#undef VJ_BACK
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// n_resident > 0: the point pass runs once over the latents z[0 .. n_resident) and the edges index them (iA = src, iB = dst);
+// 0: every pass runs the point pass over its own 2 EB edge ends.  The same kernels and the same chains either way.
+int run(const geo_vanilla_decoder_desc *dc, const Shape &sh, const float *zA, const float *zB, const int32_t *iA, const int32_t *iB,
+        int64_t n_resident, int64_t n_edges, float *len_out, void *ws, size_t ws_bytes, hipStream_t st, const char *who) {
+    const int resident = n_resident > 0;
+    int64_t eb = n_edges < EDGES_PER_PASS ? n_edges : EDGES_PER_PASS;
+    while (eb >= 1 && layout_bytes(sh, resident ? n_resident : 2 * eb, eb) > ws_bytes) eb = eb > 64 ? eb - eb / 8 : eb - 1;
+    if (eb < 1) {
+        geo::set_error("%s: workspace of %zu bytes is below the minimum of %zu", who, ws_bytes,
+                       layout_bytes(sh, resident ? n_resident : 2, 1));
+        return GEO_E_WORKSPACE;
+    }
+    const int64_t slots = resident ? n_resident : 2 * eb;
+    geo::Arena ar(ws, ws_bytes);
+    uint32_t *mask1 = ar.take<uint32_t>((size_t)slots * (sh.n1 / 32));
+    uint32_t *mask2 = ar.take<uint32_t>((size_t)slots * (sh.n2 / 32));
+    float *sigp = ar.take<float>((size_t)slots * sh.nout);
+    float *buf1 = ar.take<float>((size_t)2 * eb * sh.n1);
+    float *buf2 = ar.take<float>((size_t)2 * eb * sh.n2);
+    if (!mask1 || !mask2 || !sigp || !buf1 || !buf2) {
+        geo::set_error("%s: workspace too small", who);
+        return GEO_E_WORKSPACE;
+    }
+    auto point_pass = [&](const Ends &e, int64_t count, int64_t slot0) -> int {
+        const dim3 grid((unsigned)((count + FRONT_ROWS - 1) / FRONT_ROWS), FRONT_SPLIT);
+        vj_front_kernel<false><<<grid, 256, 0, st>>>(e, (int)count, sh.d, sh.dp, sh.n1, dc->At, dc->c, buf1, mask1, slot0);
+        GEO_LAUNCH_CHECK();
+        int rc = run_mid<false>(sh, dc, buf1, buf2, mask1, mask2, e, 0, slot0, count, st);
+        if (rc != GEO_OK) return rc;
+        return run_back<false>(sh, dc, buf2, sigp, e, 0, slot0, count, nullptr, st);
+    };
+    if (resident)
+        for (int64_t p0 = 0; p0 < n_resident; p0 += 2 * eb) {
+            const int64_t cnt = n_resident - p0 < 2 * eb ? n_resident - p0 : 2 * eb;
+            const Ends e{zA, zA, nullptr, nullptr, p0, (int)cnt};
+            int rc = point_pass(e, cnt, p0);
+            if (rc != GEO_OK) return rc;
+        }
+    for (int64_t e0 = 0; e0 < n_edges; e0 += eb) {
+        const int64_t ne = n_edges - e0 < eb ? n_edges - e0 : eb;
+        const Ends e{zA, zB, iA, iB, e0, (int)ne};
+        if (!resident) {
+            int rc = point_pass(e, 2 * ne, 0);
+            if (rc != GEO_OK) return rc;
+        }
+        const dim3 grid((unsigned)((ne + FRONT_ROWS - 1) / FRONT_ROWS), FRONT_SPLIT);
+        vj_front_kernel<true><<<grid, 256, 0, st>>>(e, (int)ne, sh.d, sh.dp, sh.n1, dc->At, dc->c, buf1, nullptr, 0);
+        GEO_LAUNCH_CHECK();
+        int rc = run_mid<true>(sh, dc, buf1, buf2, mask1, mask2, e, resident, 0, 2 * ne, st);
+        if (rc != GEO_OK) return rc;
+        rc = run_back<true>(sh, dc, buf2, sigp, e, resident, 0, ne, len_out + e0, st);
+        if (rc != GEO_OK) return rc;
+    }
+    return GEO_OK;
+}
+
+int check_desc(const geo_vanilla_decoder_desc *dc, Shape *sh, const char *who) {
+    GEO_REQUIRE(make_shape(dc, sh), "%s: decoder configuration not covered (see geo_hip.h)", who);
+    GEO_REQUIRE(dc->At && dc->c && dc->w2p && dc->w3p && dc->scale2 && dc->shift2 && dc->b3, "%s: null pointer in the descriptor", who);
+    return GEO_OK;
+}
+
+}  // namespace
+
+extern "C" size_t geo_vanilla_jvp_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n_edges) {
+    Shape sh;
+    if (!make_shape(dec, &sh) || n_edges < 0) return 0;
+    const int64_t eb = n_edges < 1 ? 1 : (n_edges < EDGES_PER_PASS ? n_edges : EDGES_PER_PASS);
+    return layout_bytes(sh, 2 * eb, eb);
+}
+
+extern "C" size_t geo_vanilla_jvp_edges_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n_nodes, int64_t n_edges) {
+    Shape sh;
+    if (!make_shape(dec, &sh) || n_edges < 0 || n_nodes < 0) return 0;
+    const int64_t eb = n_edges < 1 ? 1 : (n_edges < EDGES_PER_PASS ? n_edges : EDGES_PER_PASS);
+    return layout_bytes(sh, n_nodes >= 1 && n_nodes <= 2 * n_edges ? n_nodes : 2 * eb, eb);
+}
+
+extern "C" int geo_vanilla_jvp_pairs(const geo_vanilla_decoder_desc *dec, const float *z_start, const float *z_end, int64_t n_edges,
+                                     int32_t batch_size, float *len_out, void *ws, size_t ws_bytes, void *stream) {
+    (void)batch_size;
+    Shape sh;
+    int rc = check_desc(dec, &sh, "geo_vanilla_jvp_pairs");
+    if (rc != GEO_OK) return rc;
+    GEO_REQUIRE(n_edges >= 0, "geo_vanilla_jvp_pairs: n_edges %lld", (long long)n_edges);
+    if (n_edges == 0) return GEO_OK;
+    GEO_REQUIRE(z_start && z_end && len_out && ws, "geo_vanilla_jvp_pairs: null pointer");
+    return run(dec, sh, z_start, z_end, nullptr, nullptr, 0, n_edges, len_out, ws, ws_bytes, static_cast<hipStream_t>(stream),
+               "geo_vanilla_jvp_pairs");
+}
+
+extern "C" int geo_vanilla_jvp_edges(const geo_vanilla_decoder_desc *dec, const float *z, int64_t n_nodes, const int32_t *src,
+                                     const int32_t *dst, int64_t n_edges, int32_t batch_size, float *len_out, void *ws,
+                                     size_t ws_bytes, void *stream) {
+    (void)batch_size;
+    Shape sh;
+    int rc = check_desc(dec, &sh, "geo_vanilla_jvp_edges");
+    if (rc != GEO_OK) return rc;
+    GEO_REQUIRE(n_edges >= 0 && n_nodes >= 0 && n_nodes < ((int64_t)1 << 31), "geo_vanilla_jvp_edges: n_nodes %lld, n_edges %lld",
+                (long long)n_nodes, (long long)n_edges);
+    if (n_edges == 0) return GEO_OK;
+    GEO_REQUIRE(z && src && dst && len_out && ws && n_nodes >= 1, "geo_vanilla_jvp_edges: null pointer or no latents");
+    // once per latent when that is less work than once per edge end and the workspace holds every latent's masks
+    const bool resident = n_nodes <= 2 * n_edges && layout_bytes(sh, n_nodes, 1) <= ws_bytes;
+    return run(dec, sh, z, z, src, dst, resident ? n_nodes : 0, n_edges, len_out, ws, ws_bytes, static_cast<hipStream_t>(stream),
+               "geo_vanilla_jvp_edges");
+}

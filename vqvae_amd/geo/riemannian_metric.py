@@ -4,16 +4,20 @@ src/geo/riemannian_metric.py (decoder_logits_to_img :7, edge_lengths_riemannian 
 For decoders with the SpatialDecoder layer layout the Jacobian-vector products run in the HIP
 kernels of csrc/jvp.hip (forward-mode tangent propagation, MFMA for the dominant ConvT layer),
 chunked by `batch_size` exactly like riemannian_metric.py:50-58 so that train-mode BatchNorm sees
-the same batches.  Any other nn.Module (e.g. the Linear test decoder of the reference's
-tests/test_riemannian_metric.py, the vanilla VAE decoder, or a SpatialDecoder variant outside the kernels'
-coverage, see spatial_decoder.hip_kernels_cover) has no kernel: it is differentiated by autograd on the
-decoder's own device.  BatchNorm (train and eval), GroupNorm and no normalisation are all in the kernels.
+the same batches; BatchNorm (train and eval), GroupNorm and no normalisation are all in those kernels.  The vanilla
+(vector-latent) VAE decoder with fixed statistics -- eval-mode BatchNorm with running statistics, or no norm: every call site
+of the reference -- runs in the kernels of csrc/vanilla_jvp.hip (composed affine front, ReLU masks as bits, ConvT2 on the
+float32 matrix cores; vanilla_decoder.vanilla_kernels_cover states the coverage); `batch_size` does not
+enter there.  Any other nn.Module (e.g. the Linear test decoder of the reference's tests/test_riemannian_metric.py, a
+vanilla decoder with GroupNorm or train-mode BatchNorm, or a SpatialDecoder variant outside spatial_decoder.hip_kernels_cover)
+has no kernel: it is differentiated by autograd on the decoder's own device.
 """
 import torch
 
 from .. import _lib
 from .._device import device, ptr, stream_ptr, workspace
 from ..spatial_decoder import DecoderExport, hip_kernels_cover, looks_like_spatial_decoder
+from ..vanilla_decoder import VanillaDecoderExport, vanilla_kernels_cover
 
 
 @torch.no_grad()
@@ -63,6 +67,56 @@ def edge_lengths_graph_device(export: DecoderExport, z: torch.Tensor, src: torch
     return out
 
 
+def _vanilla_workspace(query_bytes: int, max_workspace_bytes, what: str, dev: torch.device) -> torch.Tensor:
+    if query_bytes == 0:
+        raise _lib.GeoHipError(f"{what}: decoder configuration not supported by the HIP path")
+    nbytes = query_bytes if max_workspace_bytes is None else min(query_bytes, int(max_workspace_bytes))
+    return workspace(nbytes, dev)[:nbytes]
+
+
+def edge_lengths_vanilla_device(export: VanillaDecoderExport, z_start: torch.Tensor, z_end: torch.Tensor,
+                                max_workspace_bytes=None) -> torch.Tensor:
+    """Vanilla-decoder HIP path on explicit endpoint arrays (f32, contiguous, on the export's device).  The edges are cut
+    into passes that fit the workspace; `max_workspace_bytes` caps it (not below geo_vanilla_jvp_workspace_bytes(desc, 1))
+    and changes no length."""
+    lib = _lib.load()
+    dev = z_start.device
+    E = z_start.shape[0]
+    assert z_start.shape == z_end.shape and z_start.shape[1] == export.latent_dim, (z_start.shape, z_end.shape)
+    out = torch.empty(E, dtype=torch.float32, device=dev)
+    if E == 0:
+        return out
+    with torch.cuda.device(dev):
+        ws = _vanilla_workspace(lib.geo_vanilla_jvp_workspace_bytes(export.desc, E), max_workspace_bytes,
+                                "geo_vanilla_jvp_workspace_bytes", dev)
+        _lib.check(lib.geo_vanilla_jvp_pairs(export.desc, ptr(z_start), ptr(z_end), E, 0, ptr(out), ptr(ws), ws.numel(),
+                                             stream_ptr()), "geo_vanilla_jvp_pairs")
+    return out
+
+
+def edge_lengths_vanilla_graph_device(export: VanillaDecoderExport, z: torch.Tensor, src: torch.Tensor, dst: torch.Tensor,
+                                      max_workspace_bytes=None) -> torch.Tensor:
+    """Vanilla-decoder HIP path on an edge list (int32 src / dst) over resident latents, no gathered copies: with the
+    queried workspace and at least half as many edges as latents the per-point work runs once per latent.  Bit for bit the
+    lengths of edge_lengths_vanilla_device on z[src], z[dst]."""
+    lib = _lib.load()
+    dev = z.device
+    E, N = int(src.numel()), int(z.shape[0])
+    assert z.shape[1] == export.latent_dim and src.dtype == torch.int32 and dst.dtype == torch.int32 and dst.numel() == E
+    out = torch.empty(E, dtype=torch.float32, device=dev)
+    if E == 0:
+        return out
+    lo, hi = torch.aminmax(torch.stack((src, dst)))
+    if int(lo) < 0 or int(hi) >= N:
+        raise ValueError(f"edge endpoints outside [0, {N})")
+    with torch.cuda.device(dev):
+        ws = _vanilla_workspace(lib.geo_vanilla_jvp_edges_workspace_bytes(export.desc, N, E), max_workspace_bytes,
+                                "geo_vanilla_jvp_edges_workspace_bytes", dev)
+        _lib.check(lib.geo_vanilla_jvp_edges(export.desc, ptr(z), N, ptr(src), ptr(dst), E, 0, ptr(out), ptr(ws), ws.numel(),
+                                             stream_ptr()), "geo_vanilla_jvp_edges")
+    return out
+
+
 def _generic_jvp_norms(decoder, z: torch.Tensor, direction: torch.Tensor) -> torch.Tensor:
     """|J(z) v| for a decoder the kernels cannot represent, by autograd on the decoder's own device
     (works for any module, including train-mode BatchNorm with its running-statistic updates).
@@ -90,6 +144,12 @@ def edge_lengths_riemannian(decoder, z_start: torch.Tensor, z_end: torch.Tensor,
         zs = z_start.detach().to(dev, torch.float32).contiguous()
         ze = z_end.detach().to(dev, torch.float32).contiguous()
         return edge_lengths_device(export, zs, ze, batch_size).to(dec_dev)
+    if z_start.ndim == 2 and vanilla_kernels_cover(decoder):           # fixed statistics: batch_size does not enter
+        dev = dec_dev if dec_dev.type == "cuda" else device()
+        export = VanillaDecoderExport(decoder, dev)
+        zs = z_start.detach().to(dev, torch.float32).contiguous()
+        ze = z_end.detach().to(dev, torch.float32).contiguous()
+        return edge_lengths_vanilla_device(export, zs, ze).to(dec_dev)
     z_start, z_end = z_start.to(dec_dev), z_end.to(dec_dev)
     delta = z_end - z_start
     pieces = []

@@ -17,8 +17,12 @@ What the reference does, stated as the contract this file implements:
 
 How it runs here: the graph never leaves HBM between steps 1 and 4.  The kNN graph, its components and the compaction to
 the largest component are the `DeviceCSR` primitives of vqvae_amd.geo; an entry's row comes from one
-`repeat_interleave` of the row pointer; lengths are computed on the device (HIP kernels for SpatialDecoder-shaped
-decoders, autograd on the GPU for the Linear-first vanilla decoder) and scattered into the entry array; the maximum over
+`repeat_interleave` of the row pointer; lengths are computed on the device and scattered into the entry array -- for the
+vanilla decoder with fixed statistics (eval-mode BatchNorm or no norm: what `read_decoder` returns for those two) by the HIP
+kernels of csrc/vanilla_jvp.hip straight from the resident latents and the entries' (row, column) indices, in full mode once
+per undirected edge (J(z)(-dz) = -J(z) dz and IEEE arithmetic is sign-symmetric: both directions are the same float); for
+SpatialDecoder-shaped decoders by csrc/jvp.hip; for anything else (GroupNorm, a module of another shape) by autograd on the
+GPU; the maximum over
 the two directions of an edge is a scatter-max / gather through the entry -> undirected-edge map that `upper_edges_device`
 already provides.  The host sees only what the contract puts there: the band quantiles and the `np.random.choice` draws of
 the subset mode (numpy's generator is host state by definition), the printed statistics, and the artefacts on disk.
@@ -36,8 +40,9 @@ from scipy import sparse
 from .._device import DeviceCSR, device
 from ..geo.kmeans_optimized import fit_kmedoids_optimized
 from ..geo.knn_graph_optimized import (compact_device, connected_components_device, knn_graph_device, upper_edges_device)
-from ..geo.riemannian_metric import edge_lengths_riemannian
+from ..geo.riemannian_metric import edge_lengths_riemannian, edge_lengths_vanilla_graph_device
 from ..vae import decoder_from_vae_checkpoint
+from ..vanilla_decoder import VanillaDecoderExport, vanilla_kernels_cover
 
 N_BANDS = 5                     # Euclidean-weight bands of the subset mode
 _RUN_DIRS = {"mnist": "experiments/vae_mnist", "fashion": "experiments/vae_fashion", "cifar10": "experiments/vae_cifar10"}
@@ -144,14 +149,24 @@ def reweight_graph_device(G: DeviceCSR, z: torch.Tensor, decoder: torch.nn.Modul
     rows, cols = entry_rows(G), G.indices.long()
     nnz = G.nnz
     print(f"Graph has {nnz} edges")
-    if mode == "subset" and nnz > max_edges:
+    every_entry = not (mode == "subset" and nnz > max_edges)
+    if not every_entry:
         chosen = torch.from_numpy(banded_entry_sample(G.data.cpu().numpy(), max_edges)).to(dev)
         print(f"Reweighting {chosen.numel()} edges (subset mode)")
     else:
         chosen = torch.arange(nnz, device=dev)
         print(f"Reweighting all {chosen.numel()} edges (full mode)")
     print(f"Computing Riemannian distances for {chosen.numel()} edges...")
-    lengths = edge_lengths_riemannian(decoder, z[rows[chosen]], z[cols[chosen]], batch_size=batch_size).to(dev)
+    src_u, dst_u, entry_edge = upper_edges_device(G)
+    if z.ndim == 2 and vanilla_kernels_cover(decoder):
+        export = VanillaDecoderExport(decoder, dev)
+        zf = z.detach().to(dev, torch.float32).contiguous()
+        if every_entry:                      # each undirected edge once, both of its entries take that float
+            lengths = edge_lengths_vanilla_graph_device(export, zf, src_u, dst_u)[entry_edge.long()]
+        else:
+            lengths = edge_lengths_vanilla_graph_device(export, zf, rows[chosen].int(), cols[chosen].int())
+    else:
+        lengths = edge_lengths_riemannian(decoder, z[rows[chosen]], z[cols[chosen]], batch_size=batch_size).to(dev)
     data = G.data.clone()
     # an entry sitting exactly on a band boundary can be drawn twice: the later draw wins, as in a numpy fancy assignment
     order = torch.argsort(chosen, stable=True)
@@ -160,7 +175,6 @@ def reweight_graph_device(G: DeviceCSR, z: torch.Tensor, decoder: torch.nn.Modul
     winners = order[last_of_run]
     data[chosen[winners]] = lengths[winners]
     # the two directions of an edge -> their maximum (structure is symmetric: both entries exist)
-    _, _, entry_edge = upper_edges_device(G)
     edge = entry_edge.long()
     n_edges = int(edge.max()) + 1 if nnz else 0
     top = torch.full((n_edges,), float("-inf"), device=dev).scatter_reduce(0, edge, data, "amax", include_self=True)

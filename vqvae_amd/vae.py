@@ -1,7 +1,8 @@
 """The decoder of the vanilla (vector-latent) VAE of the legacy builders (reference src/models/vae.py:53-85): Linear -> ConvT
 stack with the reference's parameter names, so the `decoder.*` entries of a reference checkpoint load unchanged.  The legacy
-Riemannian builder differentiates this module -- Linear-first, so edge_lengths_riemannian takes its autograd path on the GPU
-(riemannian_metric.py:18-22).
+Riemannian builder differentiates this module: in eval mode (BatchNorm with running statistics, or no norm) in the HIP kernels
+of csrc/vanilla_jvp.hip (vqvae_amd.vanilla_decoder), otherwise -- GroupNorm, train-mode BatchNorm -- by
+autograd on the GPU (riemannian_metric.py:18-22).
 
 `Encoder` and `VAE` complete the reference's model (src/models/vae.py:22-50, :88-198) with its constructor arguments, attribute
 and parameter names: a reference `model_state_dict` loads with strict=True and `VAE(**cfg['model'])` takes the reference's YAML.

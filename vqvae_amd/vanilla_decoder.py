@@ -1,0 +1,161 @@
+"""Host-side description of the vanilla (vector-latent) VAE decoder the kernels of csrc/vanilla_jvp.hip differentiate
+(vqvae_amd.vae.Decoder, reference src/models/vae.py:53-85, with FIXED statistics: eval-mode BatchNorm or no normalisation).
+
+    fc: Linear(d, c0 16) -> view c0x4x4 -> deconv1: ConvT(c0,c1,k3,s2,p1[,output_padding 1]) -> norm -> ReLU
+        -> deconv2: ConvT(c1,c2,k4,s2,p1) -> norm -> ReLU -> output_layer: ConvT(c2,C,k4,s2,p1)        (-> sigmoid in the metric)
+
+With fixed statistics everything up to the first norm's scale and shift is affine in z.  `VanillaDecoderExport` composes it
+once in fp64 (pre1 = A z + c, rounded to f32), folds the second norm into a scale and a shift, re-lays the two k4 transposed
+convolutions out by output-pixel parity and tap, and holds the `geo_vanilla_decoder_desc` of include/geo_hip.h over those
+tensors.  DESIGN.md section 15."""
+import ctypes
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+
+MAX_LATENT_DIM = 128
+COVERED_WIDTHS = ((128, 64), (64, 32))          # (dec_channels[1], dec_channels[2]) the kernels are compiled for
+
+
+def _stage(seq):
+    """(ConvTranspose2d, norm, ReLU) of a decoder stage, or None."""
+    if not isinstance(seq, nn.Sequential) or len(seq) != 3:
+        return None
+    conv, norm, act = seq[0], seq[1], seq[2]
+    if not isinstance(conv, nn.ConvTranspose2d) or not isinstance(act, nn.ReLU):
+        return None
+    return conv, norm
+
+
+def _is_convt(c, kernel, output_paddings) -> bool:
+    return (isinstance(c, nn.ConvTranspose2d) and c.kernel_size == (kernel, kernel) and c.stride == (2, 2) and c.padding == (1, 1)
+            and c.output_padding in output_paddings and c.dilation == (1, 1) and c.groups == 1)
+
+
+def looks_like_vanilla_decoder(m: nn.Module) -> bool:
+    """True for vqvae_amd.vae.Decoder and for any module with the reference Decoder's layer layout (duck typing on `fc`,
+    `deconv1`, `deconv2`, `output_layer`): Linear to a 4x4 grid, ConvT k3 s2 p1 (output_padding 0 or 1), ConvT k4 s2 p1 twice,
+    each of the first two followed by one norm layer (BatchNorm2d, GroupNorm or Identity, the same kind twice) and a ReLU."""
+    fc, out = getattr(m, "fc", None), getattr(m, "output_layer", None)
+    st1, st2 = _stage(getattr(m, "deconv1", None)), _stage(getattr(m, "deconv2", None))
+    if not isinstance(fc, nn.Linear) or st1 is None or st2 is None:
+        return False
+    (conv1, norm1), (conv2, norm2) = st1, st2
+    if not (_is_convt(conv1, 3, ((0, 0), (1, 1))) and _is_convt(conv2, 4, ((0, 0),)) and _is_convt(out, 4, ((0, 0),))):
+        return False
+    if fc.out_features != conv1.in_channels * 16 or conv1.out_channels != conv2.in_channels or conv2.out_channels != out.in_channels:
+        return False
+    kinds = {type(norm1), type(norm2)}
+    return len(kinds) == 1 and kinds <= {nn.BatchNorm2d, nn.GroupNorm, nn.Identity}
+
+
+def _fixed_statistics(norm: nn.Module) -> bool:
+    if isinstance(norm, nn.Identity):
+        return True
+    # torch normalises with the running statistics exactly when the LAYER is in eval mode and tracks them
+    return (isinstance(norm, nn.BatchNorm2d) and not norm.training and norm.running_mean is not None
+            and norm.running_var is not None)
+
+
+def vanilla_kernels_cover(m: nn.Module) -> bool:
+    """Whether csrc/vanilla_jvp.hip implements this module (else the caller differentiates it with autograd).  Exactly:
+    looks_like_vanilla_decoder(m), and
+      - both norm layers are nn.Identity, or both are nn.BatchNorm2d in eval mode with running statistics (affine or not);
+      - fc and the three transposed convolutions have a bias;
+      - 1 <= latent_dim <= 128; (dec_channels[1], dec_channels[2]) is (128, 64) or (64, 32), any dec_channels[0];
+      - 1 or 3 output channels; output 28 px (output_padding 0) or 32 px (output_padding 1).
+    Anything else -- GroupNorm, train-mode BatchNorm, BatchNorm without running statistics, a layer without bias, other
+    widths -- is not covered."""
+    if not looks_like_vanilla_decoder(m):
+        return False
+    conv1, norm1 = _stage(m.deconv1)
+    conv2, norm2 = _stage(m.deconv2)
+    if not (_fixed_statistics(norm1) and _fixed_statistics(norm2)):
+        return False
+    if any(layer.bias is None for layer in (m.fc, conv1, conv2, m.output_layer)):
+        return False
+    return (1 <= m.fc.in_features <= MAX_LATENT_DIM and (conv1.out_channels, conv2.out_channels) in COVERED_WIDTHS
+            and m.output_layer.out_channels in (1, 3))
+
+
+def _fold(norm: nn.Module, channels: int):
+    """(scale, shift) in fp64 on the CPU of a fixed-statistics norm layer: y = scale x + shift."""
+    if isinstance(norm, nn.Identity):
+        return torch.ones(channels, dtype=torch.float64), torch.zeros(channels, dtype=torch.float64)
+    rm, rv = norm.running_mean.detach().double().cpu(), norm.running_var.detach().double().cpu()
+    scale = 1.0 / torch.sqrt(rv + norm.eps)
+    if norm.weight is not None:
+        scale = scale * norm.weight.detach().double().cpu()
+    shift = -rm * scale
+    if norm.bias is not None:
+        shift = shift + norm.bias.detach().double().cpu()
+    return scale, shift
+
+
+def _parity_taps(w: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d(k4, s2, p1) weight [cin][cout][4][4] -> [parity 2 py + px][tap 2 a + b][cin][cout]: output pixel
+    (2 y + py, 2 x + px) reads input pixel (y + py - a, x + px - b) through kernel element (2 a + 1 - py, 2 b + 1 - px)."""
+    rows = []
+    for py in (0, 1):
+        for px in (0, 1):
+            rows.append(torch.stack([w[:, :, 2 * a + 1 - py, 2 * b + 1 - px] for a in (0, 1) for b in (0, 1)]))
+    return torch.stack(rows)
+
+
+class VanillaDecoderExport:
+    """The composed front, the folded second norm and the re-laid-out convolutions of a covered decoder as f32 tensors on
+    `dev`, plus the ctypes descriptor over them.  `A` [n1, d] and `c` [n1] are the composed front (n = pixel * c1 + channel).
+    A snapshot: later changes of the module (weights, statistics, mode) are not seen."""
+
+    def __init__(self, dec: nn.Module, dev: torch.device):
+        if not vanilla_kernels_cover(dec):
+            raise ValueError("decoder not covered by the vanilla JVP kernels (see vanilla_kernels_cover)")
+        conv1, norm1 = _stage(dec.deconv1)
+        conv2, norm2 = _stage(dec.deconv2)
+        out = dec.output_layer
+        d, c1, c2, C = dec.fc.in_features, conv1.out_channels, conv2.out_channels, out.out_channels
+        s1 = 7 + conv1.output_padding[0]
+
+        def f64(t):
+            return t.detach().double().cpu()
+
+        with torch.no_grad():
+            # the affine front on the zero latent and the d unit latents, in fp64
+            basis = torch.cat([torch.zeros(1, d, dtype=torch.float64), torch.eye(d, dtype=torch.float64)])
+            h = F.linear(basis, f64(dec.fc.weight), f64(dec.fc.bias)).view(d + 1, -1, 4, 4)
+            h = F.conv_transpose2d(h, f64(conv1.weight), f64(conv1.bias), stride=2, padding=1, output_padding=conv1.output_padding)
+            scale1, shift1 = _fold(norm1, c1)
+            h = h * scale1[None, :, None, None] + shift1[None, :, None, None]
+            assert h.shape == (d + 1, c1, s1, s1), h.shape
+            h = h.permute(0, 2, 3, 1).reshape(d + 1, s1 * s1 * c1)                   # column = pixel * c1 + channel
+            c = h[0]
+            At = torch.zeros(d + (d & 1), h.shape[1], dtype=torch.float64)           # rows padded to an even count
+            At[:d] = h[1:] - c
+            scale2, shift2 = _fold(norm2, c2)
+            shift2 = shift2 + scale2 * f64(conv2.bias)
+            w2p = _parity_taps(f64(conv2.weight))                                    # [4][4][c1][c2]
+            w2p = w2p.reshape(4, 4, c1 // 4, 4, c2).permute(0, 1, 2, 4, 3)           # [4][4][c1 / 4][c2][4]
+            w3p = _parity_taps(f64(out.weight)).permute(0, 1, 3, 2)                  # [4][4][C][c2]
+
+        def f32(t):
+            return t.to(torch.float32).contiguous().to(dev)
+
+        self.tensors = {"At": f32(At), "c": f32(c), "w2p": f32(w2p), "scale2": f32(scale2), "shift2": f32(shift2),
+                        "w3p": f32(w3p), "b3": f32(f64(out.bias))}
+        self.latent_dim, self.out_size, self.n1 = d, 4 * s1, s1 * s1 * c1
+        desc = _lib.VanillaDecoderDesc()
+        desc.latent_dim, desc.c1, desc.c2, desc.out_channels, desc.out_size = d, c1, c2, C, 4 * s1
+        for name, t in self.tensors.items():
+            setattr(desc, name, ctypes.c_void_p(t.data_ptr()))
+        self.desc = desc
+
+    @property
+    def A(self) -> torch.Tensor:
+        return self.tensors["At"][:self.latent_dim].t()
+
+    @property
+    def c(self) -> torch.Tensor:
+        return self.tensors["c"]
