@@ -318,6 +318,7 @@ int geo_decoder_jvp_edges(const geo_decoder_desc *dec, const float *z, int64_t n
 #define GEO_JVP_PER_NODE 0x1000      /* flag: primal pass once per latent */
 #define GEO_JVP_NODE_JACOBIAN 0x2000 /* flag: decoder Jacobian once per latent, edge ends from its columns */
 #define GEO_JVP_DEDUP 0x4000         /* flag: start-side primal rows once per run of equal src */
+#define GEO_JVP_FRONT_ONCE 0x8000    /* flag: front_edge_kernel, the first layer once per edge (tangent) and per run of equal src (start primal) */
 #define GEO_JVP_PLAN_PASSES(p) ((p) >> 16)              /* passes over the (pseudo-)edges, capped at 32767 */
 int geo_jvp_plan(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size, int32_t graph_edges,
                  size_t ws_bytes);

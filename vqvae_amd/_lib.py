@@ -117,11 +117,18 @@ JVP_BACK = ("mfma", "per_node", "dedup", "valu")
 
 
 def decode_jvp_plan(code: int) -> dict:
-    """A non-negative geo_jvp_plan answer as names: front / mid / back kernels, the front's compiled width, flags, passes."""
+    """A non-negative geo_jvp_plan answer as names: front / mid / back kernels, the front's compiled width, flags, passes.
+    `front_once` (GEO_JVP_FRONT_ONCE, library 1.0.5) is a key of the answer only where the flag is set: a code without it decodes
+    to exactly the dictionary it always did -- read it with .get("front_once", False)."""
     assert code >= 0, code
-    return {"front": JVP_FRONT[code & 3], "dmax": 16 << ((code >> 2) & 3), "mid": JVP_MID[(code >> 4) & 15],
-            "back": JVP_BACK[(code >> 8) & 15], "per_node": bool(code & 0x1000), "node_jacobian": bool(code & 0x2000),
-            "dedup": bool(code & 0x4000), "passes": code >> 16}
+    r = {"front": JVP_FRONT[code & 3], "dmax": 16 << ((code >> 2) & 3), "mid": JVP_MID[(code >> 4) & 15],
+         "back": JVP_BACK[(code >> 8) & 15], "per_node": bool(code & 0x1000), "node_jacobian": bool(code & 0x2000),
+         "dedup": bool(code & 0x4000), "passes": code >> 16}
+    if code & 0x8000:
+        r["front_once"] = True
+    return r
+
+
 _lib = None
 
 

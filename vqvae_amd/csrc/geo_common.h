@@ -39,7 +39,8 @@ struct Options {
         sssp_delta = 8 /* near-far bucket width in mean edge weights */, sssp_order = 0 /* sources ordered along 0: two exact landmark distances, 1: graph cells, 2: two landmark hop counts (1, 2: cheaper to compute, worse batches on the bench's swiss graph) */, sssp_push_blocks = 64, knn_filter = 1, kpp_grid = 256, kpp_profile = 0, jvp_mid = 0 /* ConvT2: 2 = per-chunk kernel, 3 = one tile per workgroup instead of the persistent kernel */,
         jvp_back_valu = 0, jvp_front_valu = 0, jvp_per_node = 1 /* fixed-statistics decoders: primal ConvT2 / ConvT3 once per latent */,
         jvp_node_jacobian = 1 /* fixed statistics, d <= 16: decoder Jacobian once per latent, edge ends from its columns (1: when the graph has enough edges per latent, 2: always, 0: never) */,
-        jvp_start_dedup = 1 /* train-mode BatchNorm, graph edges: each chunk's start-side primal ConvT2 / ConvT3 rows once per run of equal src (0: once per slot) */;
+        jvp_start_dedup = 1 /* train-mode BatchNorm, graph edges: each chunk's start-side primal ConvT2 / ConvT3 rows once per run of equal src (0: once per slot) */,
+        jvp_front_once = 1 /* on that route with the vector first layer: the tangent row once per edge, the start-side primal row once per run (0: every row of both sides) */;
 };
 Options &options();
 

@@ -16,6 +16,8 @@
 // per call; geo_jvp_plan reports it):
 //   front  pre1 = z . M01 + b01, M01 = conv_in o ConvT1 composed once in fp64; per-tile partial BN sums in fp64.
 //            front_kernel (VALU)   d <= 16, or jvp_front_valu
+//            front_edge_kernel     the VALU front on the dedup route (jvp_front_once): one workgroup per tile of edges, the
+//                                  tangent row once per edge, the start-side primal row once per run of equal src
 //            front_mfma_kernel     d > 16: v_mfma_f32_32x32x2_f32, the same k-ordered fmaf chain
 //   mid    ConvT2 as a block-sparse product over (input pixel -> output pixel) blocks on the bf16 matrix cores (f32 operands split
 //          exactly into three bf16 parts); prologue = norm1 + ReLU while staging A into LDS; epilogue = bias, store, BN sums.
@@ -207,6 +209,135 @@ __global__ __launch_bounds__(256) void front_kernel(const float *__restrict__ z,
             double *p = partial + ((size_t)tile * c1 + c) * 4;
             p[0] = a0; p[1] = a1; p[2] = a2; p[3] = a3;
         }
+    }
+}
+
+// A start slot opens a run of equal src (jvp_start_dedup): the one rule behind start_runs_kernel's rep[] and the start-side primal
+// rows front_edge_kernel keeps.  `within` = the slot's position in its chunk, e = its (valid) edge.
+__device__ __forceinline__ bool start_run_head(const int32_t *__restrict__ src, int64_t e, int within) {
+    return within == 0 || src[e] != src[e - 1];
+}
+
+// The first layer once per EDGE (jvp_front_once: train-mode BatchNorm over graph edges with the start-side dedup, c1 = 128).
+// One workgroup = one tile of TS edges = start tile (chunk, 0, tg) and end tile (chunk, 1, tg) of front_kernel.  The tangent
+// dz . M01 is the same row on both sides of an edge, and the start-side primal is the same row for every slot of a run of equal
+// src, so of the four rows per edge only these reach memory (pre / tpre keep their slot-indexed layout):
+//     pre, tpre of the END slot;  pre of a START slot that heads a run (start_run_head: the rows rep[] points at).
+// Nothing on this route reads any other start-side row of pre1 / tpre1: mid_start_kernel<false> gathers pre1 through rep[],
+// mid_start_kernel<true, true> takes the primal from rep[row_map[slot]] and the tangent from the partner end slot,
+// mid_pipe_kernel<true> walks the end tiles only, and ConvT3 (back_mfma_kernel) reads pre2 / tpre2 (it reuses pre1 as sg_compact,
+// written before read).  The unwritten rows hold whatever the last pass left.
+// Same fmaf chains as front_kernel (bias first, k ascending; v_pk_fma_f32 over two samples), now three per sample pair -- end
+// primal, start primal, tangent -- and over the thread's TWO columns at once: one LDS broadcast read feeds two packed FMAs
+// (front_kernel is bound by those reads, one per FMA).  BN1 partial sums of both tiles in front_kernel's association (per column
+// the samples ascending under `valid`, then the four pixels in order) into the same partial[tile][c1][4] entries: bit-identical.
+constexpr int FRONT_EDGE_N1 = 512;   // 4 pixels x c1 = 128: the only width of the dedup route (mid_pipe_kernel)
+template <int DMAX>
+__global__ __launch_bounds__(256) void front_edge_kernel(const float *__restrict__ z, const int32_t *__restrict__ src,
+                                                        const int32_t *__restrict__ dst, int64_t e_base, int64_t n_edges,
+                                                        int batch, int tiles_per_group, int d, const float *__restrict__ M01,
+                                                        const float *__restrict__ b01, float *__restrict__ pre,
+                                                        float *__restrict__ tpre, double *__restrict__ partial) {
+    constexpr int N1 = FRONT_EDGE_N1, C1 = N1 / 4;
+    constexpr int NCOL = DMAX == 16 ? 2 : 1;                // columns a thread runs together (wider latents: registers)
+    __shared__ __attribute__((aligned(8))) float za[DMAX][TS];   // [latent dimension][sample], as front_kernel
+    __shared__ __attribute__((aligned(8))) float zb[DMAX][TS];
+    __shared__ __attribute__((aligned(8))) float dz[DMAX][TS];
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    __shared__ int valid_s[TS], head_s[TS];
+    __shared__ double ps[2][N1][4];                         // [side][column]: statistics before the pixel reduction
+    const int chunk = blockIdx.x / tiles_per_group, tg = blockIdx.x % tiles_per_group;
+    const size_t tile_s = (size_t)(2 * chunk) * tiles_per_group + tg, tile_e = tile_s + tiles_per_group;
+    for (int i = threadIdx.x; i < TS * d; i += 256) {
+        const int s = i / d, k = i % d;
+        const int within = tg * TS + s;
+        const int64_t e = e_base + (int64_t)chunk * batch + within;
+        float a = 0.f, b = 0.f;
+        const bool ok = within < batch && e < n_edges;
+        if (ok) {
+            a = z[(int64_t)src[e] * d + k];
+            b = z[(int64_t)dst[e] * d + k];
+        }
+        za[k][s] = a;
+        zb[k][s] = b;
+        dz[k][s] = b - a;
+        if (k == 0) {
+            valid_s[s] = ok ? 1 : 0;
+            head_s[s] = ok && start_run_head(src, e, within) ? 1 : 0;
+        }
+    }
+    for (int i = threadIdx.x; i < TS * (DMAX - d); i += 256) {      // padded latent columns: zeros, not stale LDS
+        const int s = i / (DMAX - d), k = d + i % (DMAX - d);
+        za[k][s] = 0.f;
+        zb[k][s] = 0.f;
+        dz[k][s] = 0.f;
+    }
+    __syncthreads();
+    float *__restrict__ pre_s = pre + tile_s * TS * N1;
+    float *__restrict__ pre_e = pre + tile_e * TS * N1;
+    float *__restrict__ tpre_e = tpre + tile_e * TS * N1;
+    for (int n0 = threadIdx.x; n0 < N1; n0 += 256 * NCOL) {
+        float m[NCOL][DMAX], bias[NCOL];
+#pragma unroll
+        for (int c = 0; c < NCOL; ++c) {
+#pragma unroll
+            for (int k = 0; k < DMAX; ++k) m[c][k] = k < d ? M01[(size_t)k * N1 + n0 + 256 * c] : 0.f;
+            bias[c] = b01[n0 + 256 * c];
+        }
+        double se[NCOL][4], ss[NCOL][4];                    // sx, sxx, st, sxt of the end / start tile
+#pragma unroll
+        for (int c = 0; c < NCOL; ++c)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { se[c][j] = 0; ss[c][j] = 0; }
+        for (int s = 0; s < TS; s += 2) {
+            f32x2 xe[NCOL], xs[NCOL], t2[NCOL];
+#pragma unroll
+            for (int c = 0; c < NCOL; ++c) { xe[c] = {bias[c], bias[c]}; xs[c] = {bias[c], bias[c]}; t2[c] = {0.f, 0.f}; }
+#pragma unroll
+            for (int k = 0; k < DMAX; ++k) {
+                const f32x2 a2 = *reinterpret_cast<const f32x2 *>(&za[k][s]);
+                const f32x2 b2 = *reinterpret_cast<const f32x2 *>(&zb[k][s]);
+                const f32x2 d2 = *reinterpret_cast<const f32x2 *>(&dz[k][s]);
+#pragma unroll
+                for (int c = 0; c < NCOL; ++c) {
+                    const f32x2 mk = {m[c][k], m[c][k]};
+                    xe[c] = __builtin_elementwise_fma(b2, mk, xe[c]);
+                    xs[c] = __builtin_elementwise_fma(a2, mk, xs[c]);
+                    t2[c] = __builtin_elementwise_fma(d2, mk, t2[c]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const bool valid = valid_s[s + u] != 0, head = head_s[s + u] != 0;     // (workgroup-uniform)
+#pragma unroll
+                for (int c = 0; c < NCOL; ++c) {
+                    const size_t o = (size_t)(s + u) * N1 + n0 + 256 * c;
+                    const float x = u ? xe[c].y : xe[c].x, y = u ? xs[c].y : xs[c].x, t = u ? t2[c].y : t2[c].x;
+                    pre_e[o] = x;
+                    tpre_e[o] = t;
+                    if (head) pre_s[o] = y;
+                    if (valid) {
+                        se[c][0] += x; se[c][1] += (double)x * x; se[c][2] += t; se[c][3] += (double)x * t;
+                        ss[c][0] += y; ss[c][1] += (double)y * y; ss[c][2] += t; ss[c][3] += (double)y * t;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NCOL; ++c)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { ps[0][n0 + 256 * c][j] = ss[c][j]; ps[1][n0 + 256 * c][j] = se[c][j]; }
+    }
+    __syncthreads();                                        // the four pixels of a channel, in pixel order: [tile][c1][4]
+    {
+        const int side = threadIdx.x / C1, c = threadIdx.x % C1;        // 256 threads = 2 sides x C1 channels
+        double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+#pragma unroll
+        for (int px = 0; px < 4; ++px) {
+            a0 += ps[side][px * C1 + c][0]; a1 += ps[side][px * C1 + c][1]; a2 += ps[side][px * C1 + c][2]; a3 += ps[side][px * C1 + c][3];
+        }
+        double *p = partial + ((side ? tile_e : tile_s) * C1 + c) * 4;
+        p[0] = a0; p[1] = a1; p[2] = a2; p[3] = a3;
     }
 }
 
@@ -1233,7 +1364,7 @@ __global__ __launch_bounds__(256) void start_runs_kernel(const int32_t *__restri
         const int within = w0 + (int)threadIdx.x;
         const int64_t e = e_base + (int64_t)chunk * batch + within;
         const bool valid = within < slots_per_group && within < batch && e < n_edges;
-        const bool head = valid && (within == 0 || src[e] != src[e - 1]);
+        const bool head = valid && start_run_head(src, e, within);
         const unsigned long long m = __ballot(head);
         const int below = __popcll(m & ((1ull << lane) - 1ull));
         if (lane == 0) wsum[wave] = __popcll(m);
@@ -1257,11 +1388,13 @@ __global__ __launch_bounds__(256) void start_runs_kernel(const int32_t *__restri
 // ConvT2 of the start side in full 64-row tiles of two independent 32-row halves, both of one start group (one set of constants):
 //   TT = true   halves = the tangents of start tiles 2j and 2j + 1 of the group (their own pre1 rows give the BN1 / ReLU terms);
 //               tangent rows -> tpre2, and the tiles' BN2 partial sums with the primal gathered from the compact rows (bn2_partial),
-//               so this launch follows the TT = false one
+//               so this launch follows the TT = false one.  ONCE (jvp_front_once, front_edge_kernel): a start slot has no rows
+//               of its own; its primal is the row of its run's head, rep[row_map[slot]] (~33 L2-resident rows per chunk, padding
+//               slots: the group's first head), its tangent the row of the partner end slot, one group further on
 //   TT = false  halves = compact primal tiles 2j and 2j + 1 (rows gathered through rep) -> the compact rows of pre2
 // Same staging arithmetic, products (mid_products) and order as mid_all_kernel / mid_pipe_kernel: every row is bit-identical to the
 // row those kernels compute for the same inputs.  grid = (ceil(tiles_per_group / 2), chunks of the pass), 512 threads.
-template <bool TT>
+template <bool TT, bool ONCE = false>
 __global__ __launch_bounds__(512, 2) void mid_start_kernel(const float *__restrict__ pre1, const float *__restrict__ tpre1,
                                                           const NormConst *__restrict__ consts1, int tiles_per_group,
                                                           const unsigned short *__restrict__ B3, const float *__restrict__ b2,
@@ -1293,19 +1426,43 @@ __global__ __launch_bounds__(512, 2) void mid_start_kernel(const float *__restri
     const int k0p = 2 * lane, s0p = 4 * wave;
     const NormConst *kp = consts1 + (size_t)group * C1 + k0p;
     const NormConst kA = kp[0], kB = kp[1];
+    static_assert(TT || !ONCE, "ONCE selects where the tangent launch reads");
     size_t xrow[2][4];                                          // pre1 rows feeding the wave's staging rows (wave-uniform)
+    // ONCE: both row sets as scalar byte offsets into two buffer descriptors, the start group's pre1 (the heads) and the end
+    // group's tpre1 (the partner slots); the lane adds one loop-invariant offset (mid_pipe_kernel's fetch)
+    const size_t g0 = (size_t)group * tiles_per_group * TS, group_slots = (size_t)tiles_per_group * TS;
+    unsigned xoff[2][4], toff[2];
+    __amdgpu_buffer_rsrc_t x_src, t_src;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const size_t s0 = (size_t)tile0 * TS + s0p + i, s1 = (size_t)tile1 * TS + s0p + i;
-        xrow[0][i] = TT ? s0 : (size_t)__builtin_amdgcn_readfirstlane(rep[s0]);
-        xrow[1][i] = TT ? s1 : (size_t)__builtin_amdgcn_readfirstlane(rep[s1]);
+        if (ONCE) {
+            xoff[0][i] = (unsigned)(__builtin_amdgcn_readfirstlane(rep[__builtin_amdgcn_readfirstlane(row_map[s0])]) - (int)g0) * (n1 * 4u);
+            xoff[1][i] = (unsigned)(__builtin_amdgcn_readfirstlane(rep[__builtin_amdgcn_readfirstlane(row_map[s1])]) - (int)g0) * (n1 * 4u);
+        } else {
+            xrow[0][i] = TT ? s0 : (size_t)__builtin_amdgcn_readfirstlane(rep[s0]);
+            xrow[1][i] = TT ? s1 : (size_t)__builtin_amdgcn_readfirstlane(rep[s1]);
+        }
     }
+    if (ONCE) {
+        x_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pre1 + g0 * n1), 0, (int)(group_slots * n1 * 4), 0x00020000);
+        t_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tpre1 + (g0 + group_slots) * n1), 0, (int)(group_slots * n1 * 4), 0x00020000);
+        toff[0] = (unsigned)(lt0 * TS + s0p) * (n1 * 4u);
+        toff[1] = (unsigned)((live1 ? lt0 + 1 : lt0) * TS + s0p) * (n1 * 4u);
+    }
+    const unsigned v_pair = (unsigned)k0p * 4u;
     f32x2 rx[2][4], rt[2][4];
     auto fetch = [&](int nx) {
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
+                if (ONCE) {
+                    const int px_off = MidGeom::pix(nx) * C1 * 4;
+                    rx[hh][i] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(x_src, v_pair, xoff[hh][i] + px_off, 0));
+                    rt[hh][i] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(t_src, v_pair, toff[hh] + i * n1 * 4 + px_off, 0));
+                    continue;
+                }
                 const size_t off = xrow[hh][i] * n1 + (size_t)MidGeom::pix(nx) * C1 + k0p;
                 rx[hh][i] = *reinterpret_cast<const f32x2 *>(pre1 + off);
                 if (TT) rt[hh][i] = *reinterpret_cast<const f32x2 *>(tpre1 + off);
@@ -1886,6 +2043,8 @@ bool make_plan(const geo_decoder_desc *dc, int64_t n_edges, int batch, Plan *p) 
 //                  leave the Jacobian's columns per latent; each edge end is then |J(z_node) dz| from those columns.
 //   dedup          Train-mode BatchNorm over graph edges: the start side's primal rows once per run of equal src.  The maps live
 //                  in part1 (dead after finalize_batch_kernel), the compact rows' output sigmoids in pre1 (dead after ConvT2).
+//   front_once     dedup with the VALU front (jvp_front_once): front_edge_kernel, the first layer once per edge.  start_runs_kernel
+//                  then runs before the front, so the maps sit behind the quarter of part1 the front's partial sums take.
 enum { BACK_NODE_PRIMAL = 15 };      // launch_back only: ConvT3 of the per-node primal pass (never a route's `back`)
 
 struct Route {
@@ -1898,7 +2057,7 @@ struct Route {
     int mid = GEO_JVP_MID_CHUNK, back = GEO_JVP_BACK_VALU;      // GEO_JVP_MID_*, GEO_JVP_BACK_*
     int back_nt = 0;                                            // 32-column output tiles of the matrix-core ConvT3 (1 or 6)
     int parts2 = 16;                 // partial-sum rows per tile that the ConvT2 kernel leaves for finalize_batch_kernel
-    bool per_node = false, node_jacobian = false, dedup = false;
+    bool per_node = false, node_jacobian = false, dedup = false, front_once = false;
     size_t back_lds = 0;             // dynamic LDS of back_kernel
     size_t jac_np = 0, jac_extra_bytes = 0;                     // node_jacobian: padded outputs per column; pseudo-edge lists + columns
     size_t bytes = 0;                // workspace as the matching *_workspace_bytes query sizes it (0: no answer)
@@ -1970,6 +2129,12 @@ bool make_route(const geo_decoder_desc *dc, const geo::Options &o, bool graph_ed
     const size_t slots = r->pl.pass_slots(), tiles = slots / TS, groups = (size_t)r->pl.chunks_per_pass * 2;
     r->dedup = r->batch_stats && graph_edges && mid_pipe && back_mfma && o.jvp_start_dedup != 0 &&
                (2 * slots + groups) * 4 <= tiles * s.n1 * 4 * 8 && (size_t)r->back_nt * 32 <= (size_t)s.n1;
+    // (dedup implies c1 = 128, the width front_edge_kernel is compiled for, and the maps fit behind the front's partial sums:
+    // 4 KB of the 16 KB a tile has in part1, the maps take 260 B; mid_start_kernel addresses a group's rows through one buffer
+    // descriptor with 32-bit offsets: all spelled out)
+    r->front_once = r->dedup && r->front == GEO_JVP_FRONT_VALU && o.jvp_front_once != 0 && s.n1 == FRONT_EDGE_N1 &&
+                    tiles * s.c1 * 4 * 8 + (2 * slots + groups) * 4 <= tiles * s.n1 * 4 * 8 &&
+                    (size_t)base.slots_per_group * s.n1 * 4 < ((size_t)1 << 31);
 
     r->mid = r->per_node ? GEO_JVP_MID_ALL_TANGENT
            : mid_pipe    ? (r->dedup ? GEO_JVP_MID_PIPE_DEDUP : GEO_JVP_MID_PIPE)
@@ -2000,7 +2165,7 @@ int encode_route(const Route &r) {
     const int64_t passes = r.passes < 0x7fff ? r.passes : 0x7fff;
     return r.front | (r.dmax == 16 ? 0 : (r.dmax == 32 ? 1 : 2)) << 2 | r.mid << 4 | r.back << 8 |
            (r.per_node ? GEO_JVP_PER_NODE : 0) | (r.node_jacobian ? GEO_JVP_NODE_JACOBIAN : 0) | (r.dedup ? GEO_JVP_DEDUP : 0) |
-           (int)passes << 16;
+           (r.front_once ? GEO_JVP_FRONT_ONCE : 0) | (int)passes << 16;
 }
 
 // ---------------------------------------------------------------------------------- host side: launchers
@@ -2049,9 +2214,22 @@ int cu_count(int *n) {
     return GEO_OK;
 }
 
+// the start side's run maps of a dedup pass (row_map, rep, n_compact)
+int launch_start_runs(const Pass &p, const Buffers &b, hipStream_t stream) {
+    start_runs_kernel<<<(unsigned)(p.groups() / 2), 256, 0, stream>>>(p.src, p.e_base, p.n_edges, p.batch, p.tiles_per_group * TS,
+                                                                     b.row_map, b.rep, b.n_compact);
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
 int launch_front(const Route &r, const Pass &p, const Buffers &b, hipStream_t stream) {
     const Shape &s = r.pl.sh;
-    if (r.front == GEO_JVP_FRONT_MFMA)
+    if (r.front_once)                                           // one workgroup per tile of edges: both sides of the pass
+        pick_int<16, 32, 64>(r.dmax, [&](auto dm) {
+            front_edge_kernel<decltype(dm)::value><<<(unsigned)(p.tiles / 2), 256, 0, stream>>>(
+                p.z, p.src, p.dst, p.e_base, p.n_edges, p.batch, p.tiles_per_group, s.d, b.M01, b.b01, b.pre1, b.tpre1, b.part1);
+        });
+    else if (r.front == GEO_JVP_FRONT_MFMA)
         pick_int<32, 64>(r.dmax, [&](auto dm) {
             front_mfma_kernel<decltype(dm)::value><<<(unsigned)p.tiles, 256, 0, stream>>>(
                 p.z, p.src, p.dst, p.z_start, p.z_end, p.e_base, p.n_edges, p.batch, p.tiles_per_group, s.d, s.n1, b.M01, b.b01,
@@ -2102,11 +2280,8 @@ int launch_mid(const Route &r, const geo_decoder_desc *dc, const Pass &p, const 
     if (p.mid == GEO_JVP_MID_PIPE || p.mid == GEO_JVP_MID_PIPE_DEDUP) {
         const bool dedup = p.mid == GEO_JVP_MID_PIPE_DEDUP;
         const int64_t chunks = p.groups() / 2;
-        if (dedup) {
-            start_runs_kernel<<<(unsigned)chunks, 256, 0, stream>>>(p.src, p.e_base, p.n_edges, p.batch, p.tiles_per_group * TS,
-                                                                    b.row_map, b.rep, b.n_compact);
-            GEO_LAUNCH_CHECK();
-        }
+        if (dedup && !r.front_once)                             // (front_once: before the front, launch_pass)
+            if (const int rc = launch_start_runs(p, b, stream)) return rc;
         int n_cu = 0;
         if (const int rc = cu_count(&n_cu)) return rc;
         const int64_t pipe_tiles = dedup ? p.tiles / 2 : p.tiles;                        // (dedup: the end side only)
@@ -2122,9 +2297,12 @@ int launch_mid(const Route &r, const geo_decoder_desc *dc, const Pass &p, const 
                 b.pre1, b.tpre1, b.k1, p.tiles_per_group, b.B3, dc->b2, p.mid_pre2, b.tpre2, b.part2, b.row_map, b.rep, b.n_compact,
                 p.e_base, p.n_edges, p.batch);
             GEO_LAUNCH_CHECK();
-            mid_start_kernel<true><<<dim3((unsigned)((p.tiles_per_group + 1) / 2), (unsigned)chunks), 512, 0, stream>>>(
-                b.pre1, b.tpre1, b.k1, p.tiles_per_group, b.B3, dc->b2, p.mid_pre2, b.tpre2, b.part2, b.row_map, b.rep, b.n_compact,
-                p.e_base, p.n_edges, p.batch);
+            pick_bool(r.front_once, [&](auto once) {
+                mid_start_kernel<true, decltype(once)::value>
+                    <<<dim3((unsigned)((p.tiles_per_group + 1) / 2), (unsigned)chunks), 512, 0, stream>>>(
+                        b.pre1, b.tpre1, b.k1, p.tiles_per_group, b.B3, dc->b2, p.mid_pre2, b.tpre2, b.part2, b.row_map, b.rep,
+                        b.n_compact, p.e_base, p.n_edges, p.batch);
+            });
             GEO_LAUNCH_CHECK();
         }
     } else if (p.mid == GEO_JVP_MID_ALL || p.mid == GEO_JVP_MID_ALL_TANGENT) {
@@ -2192,6 +2370,8 @@ int launch_back(const Route &r, const geo_decoder_desc *dc, const Pass &p, const
 }
 
 int launch_pass(const Route &r, const geo_decoder_desc *dc, const Pass &p, const Buffers &b, hipStream_t stream) {
+    if (r.front_once)
+        if (const int rc = launch_start_runs(p, b, stream)) return rc;
     if (const int rc = launch_front(r, p, b, stream)) return rc;
     if (const int rc = launch_stats(r, dc, 1, p, b, stream)) return rc;
     if (const int rc = launch_mid(r, dc, p, b, stream)) return rc;
@@ -2240,7 +2420,8 @@ int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t 
     }
     GEO_REQUIRE(b.slot_valid && (!r.group_norm || b.gs2) && (!r.per_node || b.sg_node), "geo_decoder_jvp: workspace carve failed");
     if (r.dedup) {
-        b.row_map = reinterpret_cast<int32_t *>(b.part1); b.rep = b.row_map + slots; b.n_compact = b.rep + slots;
+        // (front_once: the maps exist before the front writes its partial sums, [tile][c1][4], to the head of part1)
+        b.row_map = reinterpret_cast<int32_t *>(b.part1 + (r.front_once ? tiles * s.c1 * 4 : 0)); b.rep = b.row_map + slots; b.n_compact = b.rep + slots;
         b.sg_compact = b.pre1;
     }
 
