@@ -499,6 +499,23 @@ int geo_feature_gram(const float *D, int64_t ld, int32_t K, int64_t n, const flo
 int geo_feature_project(const float *D, int64_t ld, int32_t K, int64_t n, const float *fill, const double *mean, const double *V,
                         int32_t n_components, float *Z_out, void *stream);
 
+/* ---- Riemannian graph experiments (the reference's experiments/geo/run_riemann_experiments.py) ----
+ * geo_path_stats: D f32 [n_rows][ld] (geo_sssp_multi's D_out, or any rows of it), n_rows >= 1, n >= 1 columns read per row,
+ * ld >= n; a row may start at any 4-byte aligned address.  Per row r: sum_out f64 [r] = the fp64 sum of the entries that are
+ * finite and > 0, n_pos_out i64 [r] = how many those are, n_unreached_out i64 [r] = the number of +inf entries, max_out f32 [r]
+ * = the largest finite entry (0 when the row has none).  One workgroup per row; the association of the fp64 sum depends on
+ * n alone, there are no atomics: a row's outputs are bit-identical across runs, streams and whatever other rows share the
+ * call.  Asynchronous. */
+int geo_path_stats(const float *D, int64_t ld, int32_t n_rows, int64_t n, double *sum_out, int64_t *n_pos_out,
+                   int64_t *n_unreached_out, float *max_out, void *stream);
+
+/* geo_csr_set_symmetric: data[(src[t], dst[t])] = data[(dst[t], src[t])] = val[t] for t < m on a CSR of n rows whose rows are
+ * sorted by column (binary search).  The m pairs must be unique as unordered pairs (the caller's contract: two threads
+ * would otherwise store to one entry).  A pair with either entry absent, or an endpoint outside [0, n), stores nothing and
+ * adds one to n_missing_out i32 [1] (device; set to 0 first).  0 <= m < 2^31; m = 0 only clears the counter.  Asynchronous. */
+int geo_csr_set_symmetric(const int32_t *indptr, const int32_t *indices, float *data, int32_t n, const int32_t *src,
+                          const int32_t *dst, const float *val, int64_t m, int32_t *n_missing_out, void *stream);
+
 /* ---- EMA vector quantizer (the reference's baseline VQ-VAE, VectorQuantizerEMA) ----
  * z_e [B][C][HW] (NCHW, contiguous) f32 (half = 0) or f16 (half = 1), 1 <= C <= 128, 1 <= K <= 4096, any n = B HW >= 1 (K > n
  * allowed).  Rows are z_e's positions (b, h, w) in that order, upcast to f32.  idx_out i64 [n] = geo_kmeans_assign's labels
