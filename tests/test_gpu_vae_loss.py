@@ -2,7 +2,10 @@
 the same float32 inputs.
 
 Tolerances.  Forward: relative 1e-10 -- both sides form every term in fp64, only the order of the sum differs (n terms of
-one sign, or a KL sum dominated by its largest terms: the reordering error is a few n eps_64 at most, n <= 8e5).  Gradients:
+one sign, or a KL sum dominated by its largest terms), n <= 4.2e6.  Neither side adds the terms one after the other: the kernel
+sums at most 8 terms per lane, then folds lanes, waves and workgroup partials as a tree, and torch's reduction is tree-shaped
+too.  The error of such a sum of same-sign terms grows with the depth of the tree times eps_64 (about 40 levels here: 1e-14),
+not with n; even the worst case n eps_64 = 5e-10 of one long chain is not approached.  Gradients:
 |got - ref| <= 1e-6 |ref| + 1e-9 -- the kernel rounds an fp64 value to float32 once (relative 6e-8); the bound is one order
 over that, the absolute term covers float32 underflow next to saturated logits.
 
@@ -18,6 +21,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(B, P, d) for B in (1, 3, 257) for P in (784, 3072) for d in (2, 128)]
+# B P % 4 = 1, 3, 2: the scalar loops by size.  8200 x 512: B P > 4 x 256 x 4096 and B d > 256 x 4096, so the grids are capped
+# and both grid-stride loops (float4 reconstruction, KL) go round a second time.
+SHAPES += [(1, 1, 1), (3, 785, 2), (5, 786, 3), (8200, 512, 128)]
 RECON = {0: ("bce", True), 1: ("mse", True), 2: ("mse", False)}
 
 
@@ -91,6 +97,46 @@ def test_kernel_matches_float64_formula(models, B, P, d):
                     assert_close(got, want, (recon_mode, free_bits, mode, step))
                     if mode == "clipped" and step == 100:
                         assert got[0][0].item() == got[0][1].item() and not got[1][1].any() and not got[1][2].any()
+
+
+def misaligned(t):
+    """The values of t as a contiguous view that starts 4 bytes past a 16-byte boundary."""
+    base = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    base[1:] = t.flatten()
+    view = base[1:].view(t.shape)
+    assert base.data_ptr() % 16 == 0 and view.data_ptr() % 16 != 0 and view.is_contiguous()
+    return view
+
+
+@pytest.mark.parametrize("which", ["x", "logits", "both"])
+def test_misaligned_views_take_the_scalar_route_and_change_no_gradient_bit(models, which):
+    """B P % 4 == 0, but a base pointer off the 16-byte boundary: the launch picks the scalar kernels.  The views go to elbo_hip
+    as leaves (run() would clone them onto an aligned allocation).  Forward: the 1e-10 of this file against the float64 formula.
+    Gradients are elementwise, so they equal those of the aligned (float4) call on the same values bit for bit."""
+    from vqvae_amd.vae import CAPACITY_MODES, elbo_hip
+    _, ref = models
+    B, P, d = 3, 784, 2
+    assert (B * P) % 4 == 0
+    logits, x, mu, logvar = make_inputs(B, P, d)
+    for recon_mode in RECON:
+        configure(ref, recon_mode, 0.125)
+        kw = dict(beta=0.7, capacity_max=5.0, capacity_anneal_steps=10, step=3, capacity_mode="abs")
+        want = run(ref, (logits, x, mu, logvar), torch.float64, **kw)[0]
+        results = []
+        for off in (False, True):
+            lg = misaligned(logits) if off and which in ("logits", "both") else logits.clone()
+            xs = misaligned(x) if off and which in ("x", "both") else x.clone()
+            assert (lg.data_ptr() % 16 != 0 or xs.data_ptr() % 16 != 0) == off
+            leaves = [t.detach().requires_grad_() for t in (lg, mu, logvar)]
+            assert leaves[0].data_ptr() == lg.data_ptr()
+            out = elbo_hip(leaves[0], xs, leaves[1], leaves[2], recon_mode, 0.125, 0.7, ref._compute_capacity_target(5.0, 10, 3),
+                           CAPACITY_MODES["abs"])
+            out[0].backward()
+            rel = ((out[:3].detach() - want).abs() / want.abs()).max().item()
+            assert rel <= 1e-10, (recon_mode, which, off, rel)
+            results.append([t.grad for t in leaves])
+        for name, a, b in zip(("d_logits", "d_mu", "d_logvar"), *results):
+            assert a.dtype == torch.float32 and a.any() and torch.equal(a, b), (recon_mode, which, name)
 
 
 def test_free_bits_gradient_at_below_and_above_the_clamp(models):

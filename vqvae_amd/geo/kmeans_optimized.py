@@ -488,27 +488,32 @@ def fit_kmedoids_voronoi(W, K: int = 512, init: str = "kpp", seed: int = 42, max
 
 
 # ---- extension: PAM swap over the resident all-pairs matrix ---------------------------------------------------------------
-def pam_swap_pass_device(D: torch.Tensor, medoids: torch.Tensor, power: int = 2):
+def pam_swap_deltas_device(D: torch.Tensor, medoids: torch.Tensor, power: int = 2):
     """PAM's SWAP evaluation for ALL (medoid, candidate) pairs in one pass over the resident matrix (csrc/medoid.hip:
-    pam_swap_kernel, FastPAM1 form).  Returns (delta, i, x, total): the swap medoids[i] -> x with the most negative change of
-    the total cost sum_j D[nearest(j)][j]^power (ties: lowest x, then first medoid), and the current total cost."""
+    pam_swap_kernel, FastPAM1 form), per candidate: returns (best_delta f64 [n], best_medoid i32 [n], total).  best_delta[x]
+    is the most negative change of the total cost sum_j D[nearest(j)][j]^power over the swaps medoids[i] -> x, best_medoid[x]
+    the first i attaining it; the row of a medoid holds (+inf, 0).  total is the current total cost.
+    D f32 [n, n] may be a row-strided view (D.stride(0) >= n, D.stride(1) == 1); K = len(medoids) >= 2.
+    Every node needs a finite second-nearest medoid: the kernel's decomposition subtracts that cost, so where it is infinite (a
+    connected component of the graph that holds exactly one medoid) the change would come out as inf - inf.  Such an input
+    raises ValueError, naming the number of those nodes, before anything is launched."""
     lib = _lib.load()
     dev = D.device
     n, K = int(D.shape[0]), int(medoids.numel())
+    if K < 2:
+        raise ValueError(f"pam_swap_deltas_device needs at least 2 medoids, got {K}")
     med = medoids.to(torch.int64)
     dmin, near = assign_from_rows_device(D, medoids)                 # nearest medoid, first on ties
     near = near.to(torch.int64)
     c1 = dmin.double() ** power
-    if K == 1:                                                       # nothing to fall back on: the swap replaces the only medoid
-        tot = torch.cat([(D[r0:r0 + 4096].double() ** power).sum(dim=1) for r0 in range(0, n, 4096)])
-        tot[med] = float("inf")
-        delta = tot.min() - c1.sum()
-        x = int(torch.nonzero(tot == tot.min())[0])
-        return float(delta), 0, x, float(c1.sum())
     rows = D[med]                                                    # K x n float32 (a copy)
     rows.scatter_(0, near[None, :], float("inf"))
     d2 = rows.min(dim=0).values
     del rows
+    no_second = int((d2 == float("inf")).sum())
+    if no_second:
+        raise ValueError(f"PAM swap: {no_second} of {n} nodes have no finite second-nearest medoid (a connected component "
+                         f"with a single medoid); the swap evaluation is undefined there")
     # base[i] = sum over the nodes of medoid i of (c2 - c1), members in ascending node order, sequential fp64 sums
     # (segment sums through the sorted order: deterministic)
     gain = d2.double() ** power - c1
@@ -523,9 +528,28 @@ def pam_swap_pass_device(D: torch.Tensor, medoids: torch.Tensor, power: int = 2)
     with torch.cuda.device(dev):
         _lib.check(lib.geo_pam_swap_deltas(ptr(D), D.stride(0), ptr(near32), ptr(d1), ptr(d2), ptr(base.contiguous()), ptr(is_med), n, K,
                                            int(power), ptr(best), ptr(which), stream_ptr()), "geo_pam_swap_deltas")
+    return best, which, float(c1.sum())
+
+
+def pam_swap_pass_device(D: torch.Tensor, medoids: torch.Tensor, power: int = 2):
+    """The best single PAM swap over the resident matrix (pam_swap_deltas_device; K = 1 is handled here).  Returns
+    (delta, i, x, total): the swap medoids[i] -> x with the most negative change of the total cost
+    sum_j D[nearest(j)][j]^power (ties: lowest x, then first medoid), and the current total cost.
+    With K >= 2 every node needs a finite second-nearest medoid: ValueError otherwise (see pam_swap_deltas_device)."""
+    n, K = int(D.shape[0]), int(medoids.numel())
+    if K == 1:                                                       # nothing to fall back on: the swap replaces the only medoid
+        med = medoids.to(torch.int64)
+        dmin, _ = assign_from_rows_device(D, medoids)
+        c1 = dmin.double() ** power
+        tot = torch.cat([(D[r0:r0 + 4096].double() ** power).sum(dim=1) for r0 in range(0, n, 4096)])
+        tot[med] = float("inf")
+        delta = tot.min() - c1.sum()
+        x = int(torch.nonzero(tot == tot.min())[0])
+        return float(delta), 0, x, float(c1.sum())
+    best, which, total = pam_swap_deltas_device(D, medoids, power)
     delta = best.min()
     x = int(torch.nonzero(best == delta)[0])                         # lowest candidate among equal changes
-    return float(delta), int(which[x]), x, float(c1.sum())
+    return float(delta), int(which[x]), x, total
 
 
 def fit_kmedoids_pam(W, K: int = 512, init: str = "kpp", seed: int = 42, max_swaps: int = 50, power: int = 2,
@@ -533,7 +557,9 @@ def fit_kmedoids_pam(W, K: int = 512, init: str = "kpp", seed: int = 42, max_swa
     """fit_kmedoids_optimized followed by PAM swaps: the best (medoid -> non-medoid) exchange is applied while it lowers the
     total cost (power=2: the reference's quantisation error).  Extension (the reference's k-medoids
     is seeding + one assignment, kmeans_optimized.py:141-183).  Every swap evaluation reads the resident N x N matrix once.
-    Returns (medoids, assign, qe, history of total costs)."""
+    Returns (medoids, assign, qe, history of total costs).
+    With K >= 2 every node must reach at least two medoids at every step (in a disconnected graph: no component with exactly
+    one medoid); pam_swap_pass_device raises ValueError otherwise."""
     from .geo_shortest_paths import all_pairs_geodesic_device
     G = _to_device_graph(W)
     dev = G.indptr.device
