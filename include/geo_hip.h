@@ -372,6 +372,57 @@ int geo_vanilla_jvp_edges(const geo_vanilla_decoder_desc *dec, const float *z, i
                           const int32_t *dst, int64_t n_edges, int32_t batch_size, float *len_out, void *ws, size_t ws_bytes,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Image decode: latents or codes -> the decoder's raw output (before any sigmoid), f32 NCHW
+ * [n][C][S][S].  Only the primal chain of the kernels above: no masks, no sigmoid'; the workspace is the two activation
+ * buffers of a pass.  Rules of both entries: every output value is a fixed-order fmaf chain of its own row, no atomics; a
+ * row's logits do not depend on n, its position in the batch, the pass size, the workspace size, the stream or the run, nor
+ * on whether its latent arrived directly or through index / (table, codes).  Any workspace from *_workspace_bytes(dec, 1)
+ * upwards is legal (a smaller one: GEO_E_WORKSPACE); *_workspace_bytes answers 0 for a descriptor outside the coverage and
+ * the call rejects it (GEO_E_ARG, as a null pointer, before any launch).  n == 0 returns GEO_OK without a launch;
+ * n < 2^31.  Index and code ranges are the caller's duty.  Asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------ */
+size_t geo_vanilla_decode_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n);
+/* The vanilla decoder (geo_vanilla_decoder_desc, same coverage): row i decodes z[index ? index[i] : i]; z f32 [.][d],
+ * index NULL or i32 [n].  A quantized batch is z = z_medoid, index = codes: no gathered copy. */
+int geo_vanilla_decode(const geo_vanilla_decoder_desc *dec, const float *z, const int32_t *index, int64_t n, float *logits_out,
+                       void *ws, size_t ws_bytes, void *stream);
+
+/* The spatial decoder with FIXED statistics (src/models/spatial_vae.py:47-81 in eval mode: BatchNorm with running
+ * statistics, or no normalisation), decoding whole 4 x 4 latent grids:
+ *   conv_in: Conv(d,c0,1) -> ConvT(c0,c1,k4,s2,p1) -> norm -> ReLU -> ConvT(c1,c2,k4,s2,p1) -> norm -> ReLU
+ *       -> ConvT(c2,C,k4,s2,p 1 | 3);   4 -> 8 -> 16 -> 32 px, or 28 px = rows and columns 2 .. 29 of the 32-px output.
+ * conv_in arrives composed into ConvT1 (in fp64, rounded once), per output-pixel parity and tap as for w2p.  conv_in's bias
+ * reaches an 8 x 8 pixel only through the taps that lie inside the 4 x 4 grid, so it is no per-channel constant: it rides
+ * as input channel d, held at 1 inside the grid (and, like every channel, 0 outside it).  With dp = d + 1 rounded up to a
+ * multiple of 8 (the padding channels are zero):
+ *   pre1[(2 y + py, 2 x + px)][co] = shift1[co] + scale1[co] * sum over taps (a, b), k < dp of
+ *                                    in[(y + py - a, x + px - b)][k] * W[2 py + px][2 a + b][k][co].
+ * Covered: 1 <= latent_dim <= 64, (c1, c2) = (128, 64) or (64, 32) (any c0), out_channels 1 or 3, out_size 28 or 32. */
+typedef struct geo_spatial_image_decoder_desc {
+    int32_t latent_dim;        /* d */
+    int32_t c1, c2;            /* dec_channels[1], dec_channels[2] */
+    int32_t out_channels;      /* C */
+    int32_t out_size;          /* 28 or 32 */
+    /* device pointers, f32 */
+    const float *w1p;          /* W as [parity][tap][dp / 4][c1][4]: element (.., q, co, r) = W[..][4 q + r][co];
+                                  W[..][k][co] = sum_c0 w_in[c0][k] w1[c0][co][2 a + 1 - py][2 b + 1 - px] for k < d,
+                                  sum_c0 b_in[c0] w1[c0][co][..][..] for k = d, 0 above */
+    const float *scale1;       /* [c1] first norm folded (ConvT1's bias inside shift1) */
+    const float *shift1;       /* [c1] */
+    const float *w2p;          /* as in geo_vanilla_decoder_desc */
+    const float *scale2;       /* [c2] */
+    const float *shift2;       /* [c2] */
+    const float *w3p;          /* [parity][tap][C][c2] */
+    const float *b3;           /* [C] */
+} geo_spatial_image_decoder_desc;
+
+size_t geo_spatial_decode_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int64_t n);
+/* Exactly one of z (f32 [n][d][4][4], NCHW) and (table f32 [K][d], codes i32 [n][16] in (y, x) order) is given; with the
+ * latter, position p of image i is table[codes[i][p]] -- how build_codebook's codes quantize a grid. */
+int geo_spatial_decode(const geo_spatial_image_decoder_desc *dec, const float *z, const float *table, const int32_t *codes,
+                       int64_t n, float *logits_out, void *ws, size_t ws_bytes, void *stream);
+
 /* Gather: data_out[e] = len[entry_edge[e]] for every stored entry (W_geo = U + U^T). */
 int geo_gather_edge_weights(const float *len, const int32_t *entry_edge, int64_t nnz, float *data_out, void *stream);
 

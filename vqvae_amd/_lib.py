@@ -29,6 +29,12 @@ class VanillaDecoderDesc(ctypes.Structure):
                 + [(n, c_p) for n in ("At", "c", "w2p", "scale2", "shift2", "w3p", "b3")])
 
 
+class SpatialImageDecoderDesc(ctypes.Structure):
+    """geo_spatial_image_decoder_desc of include/geo_hip.h."""
+    _fields_ = ([(n, i32) for n in ("latent_dim", "c1", "c2", "out_channels", "out_size")]
+                + [(n, c_p) for n in ("w1p", "scale1", "shift1", "w2p", "scale2", "shift2", "w3p", "b3")])
+
+
 class PriorDesc(ctypes.Structure):
     """geo_prior_desc of include/geo_hip.h."""
     _fields_ = ([(n, i32) for n in ("num_tokens", "embed_dim", "n_layers", "n_head", "max_seq_len", "num_classes")]
@@ -81,6 +87,10 @@ _SIGNATURES = {
     "geo_vanilla_jvp_edges_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64, i64]),
     "geo_vanilla_jvp_pairs": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
     "geo_vanilla_jvp_edges": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, i64, c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
+    "geo_vanilla_decode_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64]),
+    "geo_vanilla_decode": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, c_p, c_p, sz, c_p]),
+    "geo_spatial_decode_workspace_bytes": (sz, [ctypes.POINTER(SpatialImageDecoderDesc), i64]),
+    "geo_spatial_decode": (ctypes.c_int, [ctypes.POINTER(SpatialImageDecoderDesc), c_p, c_p, c_p, i64, c_p, c_p, sz, c_p]),
     "geo_gather_edge_weights": (ctypes.c_int, [c_p, c_p, i64, c_p, c_p]),
     "geo_prior_sample_workspace_bytes": (sz, [ctypes.POINTER(PriorDesc), i32, i32]),
     "geo_prior_sample": (ctypes.c_int, [ctypes.POINTER(PriorDesc), c_p, i32, i32, c_p, c_p, ctypes.c_float, i32, c_p, c_p, i32,

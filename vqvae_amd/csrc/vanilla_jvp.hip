@@ -15,6 +15,9 @@
 //                                  vj_mid_kernel<.., true>  per end: mask1 -> ConvT2 tangent -> scale2 -> mask2
 //                                  vj_back_kernel<.., true> per end: ConvT3 tangent -> sigmoid' scale -> sum of squares; len[e]
 //
+// The image decode at the end of this file (geo_vanilla_decode, geo_spatial_decode) runs the point pass's
+// front and mid without the masks and writes the logits instead of sigmoid'.
+//
 // ConvT2 (k4, s2, p1) is four implicit GEMMs, one per output-pixel parity: out[(2y+py, 2x+px)][co] = sum over the taps
 // (a, b) in {0,1}^2 and ci of in[(y+py-a, x+px-b)][ci] w2[ci][co][2a+1-py][2b+1-px]; M = (item, pixel) rows, K = 4 c1, N = c2, on
 // the exact-f32 matrix instruction.  Every value is a fixed-order fmaf chain of its own row, no atomics: a length does not
@@ -86,7 +89,8 @@ __device__ __forceinline__ int64_t item_slot(const Ends &s, int resident, int64_
 
 // ---- front: rows of z (points) or of dz (edges) times At on the f32 matrix cores; a workgroup = 64 rows x a quarter of
 // the column tiles, a wave = two 32 x 32 tiles sharing the B operand.  The chain starts at c (points) or 0 (edges).
-template <bool EDGE>
+// MASKS = false (the image decode): relu(pre1) only, no sign bits.
+template <bool EDGE, bool MASKS = true>
 __global__ __launch_bounds__(256) void vj_front_kernel(Ends s, int count, int d, int dp, int n1, const float *__restrict__ At,
                                                        const float *__restrict__ c, float *__restrict__ out,
                                                        uint32_t *__restrict__ mask1, int64_t slot0) {
@@ -127,12 +131,14 @@ __global__ __launch_bounds__(256) void vj_front_kernel(Ends s, int count, int d,
                 const float x = m ? acc1[q] : acc0[q];
                 if (EDGE) {
                     if (p < count) out[(size_t)p * n1 + n] = x;
-                } else {
+                } else if (MASKS) {
                     const unsigned long long bits = __ballot(x > 0.f);     // low half: the h = 0 row, high half: the h = 1 row
                     if (p < count) {
                         out[(size_t)p * n1 + n] = x > 0.f ? x : 0.f;
                         if (r == 0) mask1[(size_t)(slot0 + p) * ntiles + ct] = (uint32_t)(h ? bits >> 32 : bits);
                     }
+                } else if (p < count) {
+                    out[(size_t)p * n1 + n] = x > 0.f ? x : 0.f;
                 }
             }
         }
@@ -143,7 +149,8 @@ __global__ __launch_bounds__(256) void vj_front_kernel(Ends s, int count, int d,
 // four floats (conflict-free 16-byte reads) plus one zero row for taps outside the image.  8 waves: wave = (N tile, M tiles);
 // K runs over (tap, 8-channel block): lane half h takes channels 4h .. 4h+3 of the block, one 16-byte read each of A and B
 // feeds four MFMAs.  w2p: [parity][tap][c1 / 4][c2][4] so that the B read is 16 bytes per lane, consecutive over co.
-template <int C1, int C2, bool TANGENT>
+// MASKS = false (the image decode, primal only): no sign bits, mask1 / mask2 may be null.
+template <int C1, int C2, bool TANGENT, bool MASKS = true>
 __global__ __launch_bounds__(512) void vj_mid_kernel(const float *__restrict__ in, float *__restrict__ out,
                                                      const uint32_t *__restrict__ mask1, uint32_t *__restrict__ mask2, Ends s,
                                                      int resident, int64_t slot0, int64_t n_items, int s1, int G,
@@ -246,13 +253,16 @@ __global__ __launch_bounds__(512) void vj_mid_kernel(const float *__restrict__ i
                 const size_t w = (size_t)(valid ? slot : 0) * (n2 / 32) + (size_t)opix * TN + nt;
                 if (TANGENT) {
                     if (valid) out[o] = (mask2[w] >> j) & 1u ? scale * acc[m][q] : 0.f;
-                } else {
+                } else if (MASKS) {
                     const float x2 = fmaf(scale, acc[m][q], shift);
                     const unsigned long long bits = __ballot(x2 > 0.f);
                     if (valid) {
                         out[o] = x2 > 0.f ? x2 : 0.f;
                         if (j == 0) mask2[w] = (uint32_t)(h ? bits >> 32 : bits);
                     }
+                } else if (valid) {
+                    const float x2 = fmaf(scale, acc[m][q], shift);
+                    out[o] = x2 > 0.f ? x2 : 0.f;
                 }
             }
         }
@@ -428,6 +438,209 @@ int check_desc(const geo_vanilla_decoder_desc *dc, Shape *sh, const char *who) {
     return GEO_OK;
 }
 
+// ================================ image decode ================================
+// The primal chain alone, kept whole: front -> mid -> an image-writing ConvT3.  The vanilla decoder reuses the point
+// pass's front and mid with MASKS = false; the spatial decoder (conv_in 1x1 -> ConvT1 k4 s2 p1 -> norm -> ReLU, then the same
+// two layers at 8x8 -> 16x16 -> 32x32) has a first stage of its own and shares the other two.  Workspace: the two
+// activation buffers of a pass, nothing else.
+
+constexpr int64_t ITEMS_PER_PASS = 4096;
+constexpr int SD_MAX_D = 64;
+constexpr int SD_MAX_DP = (SD_MAX_D + 1 + 7) & ~7;      // latent channels + the constant-one channel, in 8-channel K blocks
+constexpr int SD_ITEMS = MID_ROWS / 16;                 // 16 grids of 4 x 4 per first-stage workgroup
+
+size_t decode_bytes(size_t n1, size_t n2, int64_t items) {
+    return geo::align_up((size_t)items * n1 * 4) + geo::align_up((size_t)items * n2 * 4);
+}
+
+// ---- ConvT3 of one item per workgroup, as vj_back_kernel's point pass computes the logit (the same chain: b3, then taps
+// 0..3, channels in order), written to logits [C][So][So], So = 2 s2 - 2 crop: output rows and columns crop .. 2 s2 - crop - 1
+// (crop = 2 is the spatial decoder's padding 3 at 28 px: exactly the 32-px output without a border of two).
+template <int C2, int CO>
+__global__ __launch_bounds__(256) void vj_image_kernel(const float *__restrict__ in, float *__restrict__ logits, int s2, int crop,
+                                                       const float *__restrict__ w3p, const float *__restrict__ b3) {
+    constexpr int LD = C2 + 4;
+    __shared__ __attribute__((aligned(16))) float lds[(MID_ROWS + 1) * LD];
+    const int P2 = s2 * s2, S = 2 * s2, So = S - 2 * crop, n2 = P2 * C2, ZR = P2;
+    const int tid = threadIdx.x;
+    float *img = logits + (size_t)blockIdx.x * CO * So * So;
+    const float4 *src = reinterpret_cast<const float4 *>(in + (size_t)blockIdx.x * n2);
+    for (int q = tid; q < n2 / 4; q += 256) {
+        const int pix = (q * 4) / C2, ci = (q * 4) % C2;
+        *reinterpret_cast<float4 *>(lds + (size_t)pix * LD + ci) = src[q];
+    }
+    for (int k = tid; k < LD; k += 256) lds[(size_t)ZR * LD + k] = 0.f;
+    __syncthreads();
+    for (int par = 0; par < 4; ++par) {
+        const int py = par >> 1, px = par & 1;
+        for (int pos = tid; pos < P2; pos += 256) {
+            const int y = pos / s2, x = pos - y * s2;
+            const int oy = 2 * y + py - crop, ox = 2 * x + px - crop;
+            if (oy < 0 || oy >= So || ox < 0 || ox >= So) continue;
+            float acc[CO];
+#pragma unroll
+            for (int c = 0; c < CO; ++c) acc[c] = b3[c];
+            for (int tap = 0; tap < 4; ++tap) {
+                const int iy = y + py - (tap >> 1), ix = x + px - (tap & 1);
+                const bool ok = iy >= 0 && iy < s2 && ix >= 0 && ix < s2;
+                const float *ar = lds + (size_t)(ok ? iy * s2 + ix : ZR) * LD;
+                const float *wr = w3p + (size_t)(par * 4 + tap) * CO * C2;
+#pragma unroll 4
+                for (int cb = 0; cb < C2 / 4; ++cb) {
+                    const float4 av = *reinterpret_cast<const float4 *>(ar + cb * 4);
+#pragma unroll
+                    for (int c = 0; c < CO; ++c) {
+                        const float *w = wr + c * C2 + cb * 4;
+                        acc[c] = fmaf(av.x, w[0], acc[c]);
+                        acc[c] = fmaf(av.y, w[1], acc[c]);
+                        acc[c] = fmaf(av.z, w[2], acc[c]);
+                        acc[c] = fmaf(av.w, w[3], acc[c]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CO; ++c) img[((size_t)c * So + oy) * So + ox] = acc[c];
+        }
+    }
+}
+
+// ---- the spatial decoder's first stage: conv_in composed into ConvT1 (w1p), four parity GEMMs in vj_mid_kernel's form.
+// M = (item, pixel of the 4 x 4 grid) rows, K = (tap, channel) with the channels in 8-blocks, N = c1.  Channel d of every
+// staged row is the constant 1 that carries conv_in's bias through ConvT1: a tap outside the grid reads the zero row, whose
+// constant channel is 0 too, so the border sees the bias through exactly the taps it has.  Channels d+1 .. dp-1 are zero.
+// A row is a latent grid's position (z, NCHW) or a table row (table[codes[item][pixel]]): the same staged values, hence
+// the same logits.  w1p: [parity][tap][dp / 4][c1][4]; out [item][8 x 8 pixel][c1] = relu(scale1 * acc + shift1).
+template <int C1>
+__global__ __launch_bounds__(512) void sd_front_kernel(const float *__restrict__ z, const float *__restrict__ table,
+                                                       const int32_t *__restrict__ codes, int64_t base, int64_t n_items, int d,
+                                                       int dp, const float *__restrict__ w1p, const float *__restrict__ sc1,
+                                                       const float *__restrict__ sh1, float *__restrict__ out) {
+    constexpr int TN = C1 / 32, WPN = 8 / TN, MT = TN, P = 16, ZR = MID_ROWS;
+    __shared__ __attribute__((aligned(16))) float lds[(MID_ROWS + 1) * (SD_MAX_DP + 4)];
+    const int LD = dp + 4;
+    const int64_t item0 = (int64_t)blockIdx.x * SD_ITEMS;
+    const int tid = threadIdx.x;
+    const int live = (int)(n_items - item0 < SD_ITEMS ? n_items - item0 : SD_ITEMS);
+    for (int q = tid; q < (MID_ROWS + 1) * LD; q += 512) {              // the constant channel, the padding, the zero row
+        const int r = q / LD, k = q - r * LD;
+        if (k >= d || r >= live * P) lds[q] = (k == d && r < live * P) ? 1.f : 0.f;
+    }
+    if (z) {
+        const float *src = z + (size_t)(base + item0) * d * P;          // [item][d][pixel], contiguous over the workgroup
+        for (int q = tid; q < live * d * P; q += 512) {
+            const int g = q / (d * P), k = (q - g * d * P) / P, pix = q % P;
+            lds[(size_t)(g * P + pix) * LD + k] = src[q];
+        }
+    } else {
+        for (int q = tid; q < live * P * d; q += 512) {
+            const int r = q / d, k = q - r * d;
+            lds[(size_t)r * LD + k] = table[(size_t)codes[(size_t)(base + item0) * P + r] * d + k];
+        }
+    }
+    __syncthreads();
+
+    const int lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int nt = wave % TN, m0 = wave / TN;
+    const int co = nt * 32 + j;
+    const float scale = sc1[co], shift = sh1[co];
+    for (int par = 0; par < 4; ++par) {
+        const int py = par >> 1, px = par & 1;
+        f32x16 acc[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[m][q] = 0.f;
+        for (int tap = 0; tap < 4; ++tap) {
+            const int a = tap >> 1, b = tap & 1;
+            const float *ap[MT];
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const int r = (m0 + m * WPN) * 32 + j;                  // < MID_ROWS: 8 M tiles of 32 rows
+                const int iy = ((r >> 2) & 3) + py - a, ix = (r & 3) + px - b;
+                const bool ok = iy >= 0 && iy < 4 && ix >= 0 && ix < 4;
+                ap[m] = lds + (size_t)(ok ? (r & ~15) + iy * 4 + ix : ZR) * LD + 4 * h;
+            }
+            const float4 *wp = reinterpret_cast<const float4 *>(w1p) + ((size_t)(par * 4 + tap) * (dp / 4) + h) * C1 + co;
+            for (int cb = 0; cb < dp / 8; ++cb) {
+                const float4 bv = wp[(size_t)cb * 2 * C1];
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    const float4 av = *reinterpret_cast<const float4 *>(ap[m] + cb * 8);
+                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[m], 0, 0, 0);
+                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc[m], 0, 0, 0);
+                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[m], 0, 0, 0);
+                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[m], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int r = (m0 + m * WPN) * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int g = r >> 4, y = (r >> 2) & 3, x = r & 3;
+                if (g < live) {
+                    const int opix = (2 * y + py) * 8 + 2 * x + px;
+                    const float x1 = fmaf(scale, acc[m][q], shift);
+                    out[(size_t)(item0 + g) * (64 * C1) + (size_t)opix * C1 + co] = x1 > 0.f ? x1 : 0.f;
+                }
+            }
+        }
+    }
+}
+
+// The primal ConvT2 of `count` items (no masks) and the image-writing ConvT3, shared by the two decoders.
+int decode_tail(int c1, int c2, int co, int s1, int crop, const float *w2p, const float *sc2, const float *sh2, const float *w3p,
+                const float *b3, const float *buf1, float *buf2, int64_t count, float *logits, hipStream_t st) {
+    const int G = MID_ROWS / (s1 * s1);
+    const unsigned grid = (unsigned)((count + G - 1) / G);
+    const Ends none{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    if (c1 == 128)
+        vj_mid_kernel<128, 64, false, false><<<grid, 512, 0, st>>>(buf1, buf2, nullptr, nullptr, none, 0, 0, count, s1, G, w2p, sc2, sh2);
+    else
+        vj_mid_kernel<64, 32, false, false><<<grid, 512, 0, st>>>(buf1, buf2, nullptr, nullptr, none, 0, 0, count, s1, G, w2p, sc2, sh2);
+    GEO_LAUNCH_CHECK();
+#define VJ_IMAGE(C2_, CO_) vj_image_kernel<C2_, CO_><<<(unsigned)count, 256, 0, st>>>(buf2, logits, 2 * s1, crop, w3p, b3)
+    if (c2 == 64 && co == 1) VJ_IMAGE(64, 1);
+    else if (c2 == 64) VJ_IMAGE(64, 3);
+    else if (co == 1) VJ_IMAGE(32, 1);
+    else VJ_IMAGE(32, 3);
+#undef VJ_IMAGE
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// Items per pass that fit the workspace (0: not even one).
+int64_t decode_pass_items(size_t n1, size_t n2, int64_t n, size_t ws_bytes) {
+    int64_t pb = n < ITEMS_PER_PASS ? n : ITEMS_PER_PASS;
+    while (pb >= 1 && decode_bytes(n1, n2, pb) > ws_bytes) pb = pb > 64 ? pb - pb / 8 : pb - 1;
+    return pb;
+}
+
+struct SpatialShape {
+    int d, dp, c1, c2, co, So, crop;
+    size_t n1, n2;
+};
+
+bool make_spatial_shape(const geo_spatial_image_decoder_desc *dc, SpatialShape *s) {
+    if (!dc) return false;
+    if (dc->latent_dim < 1 || dc->latent_dim > SD_MAX_D) return false;
+    if (!((dc->c1 == 128 && dc->c2 == 64) || (dc->c1 == 64 && dc->c2 == 32))) return false;
+    if (dc->out_channels != 1 && dc->out_channels != 3) return false;
+    if (dc->out_size != 28 && dc->out_size != 32) return false;
+    s->d = dc->latent_dim;
+    s->dp = (s->d + 1 + 7) & ~7;
+    s->c1 = dc->c1;
+    s->c2 = dc->c2;
+    s->co = dc->out_channels;
+    s->So = dc->out_size;
+    s->crop = (32 - s->So) / 2;
+    s->n1 = (size_t)64 * s->c1;
+    s->n2 = (size_t)256 * s->c2;
+    return true;
+}
+
 }  // namespace
 
 extern "C" size_t geo_vanilla_jvp_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n_edges) {
@@ -472,4 +685,90 @@ extern "C" int geo_vanilla_jvp_edges(const geo_vanilla_decoder_desc *dec, const 
     const bool resident = n_nodes <= 2 * n_edges && layout_bytes(sh, n_nodes, 1) <= ws_bytes;
     return run(dec, sh, z, z, src, dst, resident ? n_nodes : 0, n_edges, len_out, ws, ws_bytes, static_cast<hipStream_t>(stream),
                "geo_vanilla_jvp_edges");
+}
+
+extern "C" size_t geo_vanilla_decode_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n) {
+    Shape sh;
+    if (!make_shape(dec, &sh) || n < 0) return 0;
+    return decode_bytes(sh.n1, sh.n2, n < 1 ? 1 : (n < ITEMS_PER_PASS ? n : ITEMS_PER_PASS));
+}
+
+extern "C" int geo_vanilla_decode(const geo_vanilla_decoder_desc *dec, const float *z, const int32_t *index, int64_t n,
+                                  float *logits_out, void *ws, size_t ws_bytes, void *stream) {
+    Shape sh;
+    int rc = check_desc(dec, &sh, "geo_vanilla_decode");
+    if (rc != GEO_OK) return rc;
+    GEO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "geo_vanilla_decode: n %lld", (long long)n);
+    if (n == 0) return GEO_OK;
+    GEO_REQUIRE(z && logits_out && ws, "geo_vanilla_decode: null pointer");
+    const int64_t pb = decode_pass_items(sh.n1, sh.n2, n, ws_bytes);
+    if (pb < 1) {
+        geo::set_error("geo_vanilla_decode: workspace of %zu bytes is below the minimum of %zu", ws_bytes, decode_bytes(sh.n1, sh.n2, 1));
+        return GEO_E_WORKSPACE;
+    }
+    geo::Arena ar(ws, ws_bytes);
+    float *buf1 = ar.take<float>((size_t)pb * sh.n1);
+    float *buf2 = ar.take<float>((size_t)pb * sh.n2);
+    if (!buf1 || !buf2) {
+        geo::set_error("geo_vanilla_decode: workspace too small");
+        return GEO_E_WORKSPACE;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (int64_t p0 = 0; p0 < n; p0 += pb) {
+        const int64_t cnt = n - p0 < pb ? n - p0 : pb;
+        const Ends e{z, z, index, nullptr, p0, (int)cnt};
+        const dim3 grid((unsigned)((cnt + FRONT_ROWS - 1) / FRONT_ROWS), FRONT_SPLIT);
+        vj_front_kernel<false, false><<<grid, 256, 0, st>>>(e, (int)cnt, sh.d, sh.dp, sh.n1, dec->At, dec->c, buf1, nullptr, 0);
+        GEO_LAUNCH_CHECK();
+        rc = decode_tail(sh.c1, sh.c2, sh.co, sh.s1, 0, dec->w2p, dec->scale2, dec->shift2, dec->w3p, dec->b3, buf1, buf2, cnt,
+                         logits_out + (size_t)p0 * sh.nout, st);
+        if (rc != GEO_OK) return rc;
+    }
+    return GEO_OK;
+}
+
+extern "C" size_t geo_spatial_decode_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int64_t n) {
+    SpatialShape sh;
+    if (!make_spatial_shape(dec, &sh) || n < 0) return 0;
+    return decode_bytes(sh.n1, sh.n2, n < 1 ? 1 : (n < ITEMS_PER_PASS ? n : ITEMS_PER_PASS));
+}
+
+extern "C" int geo_spatial_decode(const geo_spatial_image_decoder_desc *dec, const float *z, const float *table, const int32_t *codes,
+                                  int64_t n, float *logits_out, void *ws, size_t ws_bytes, void *stream) {
+    SpatialShape sh;
+    GEO_REQUIRE(make_spatial_shape(dec, &sh), "geo_spatial_decode: decoder configuration not covered (see geo_hip.h)");
+    GEO_REQUIRE(dec->w1p && dec->scale1 && dec->shift1 && dec->w2p && dec->scale2 && dec->shift2 && dec->w3p && dec->b3,
+                "geo_spatial_decode: null pointer in the descriptor");
+    GEO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "geo_spatial_decode: n %lld", (long long)n);
+    if (n == 0) return GEO_OK;
+    GEO_REQUIRE((z != nullptr) != (table != nullptr || codes != nullptr) && (table != nullptr) == (codes != nullptr),
+                "geo_spatial_decode: give either z or (table, codes), not both and not neither");
+    GEO_REQUIRE(logits_out && ws, "geo_spatial_decode: null pointer");
+    const int64_t pb = decode_pass_items(sh.n1, sh.n2, n, ws_bytes);
+    if (pb < 1) {
+        geo::set_error("geo_spatial_decode: workspace of %zu bytes is below the minimum of %zu", ws_bytes, decode_bytes(sh.n1, sh.n2, 1));
+        return GEO_E_WORKSPACE;
+    }
+    geo::Arena ar(ws, ws_bytes);
+    float *buf1 = ar.take<float>((size_t)pb * sh.n1);
+    float *buf2 = ar.take<float>((size_t)pb * sh.n2);
+    if (!buf1 || !buf2) {
+        geo::set_error("geo_spatial_decode: workspace too small");
+        return GEO_E_WORKSPACE;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t nout = (size_t)sh.co * sh.So * sh.So;
+    for (int64_t p0 = 0; p0 < n; p0 += pb) {
+        const int64_t cnt = n - p0 < pb ? n - p0 : pb;
+        const unsigned grid = (unsigned)((cnt + SD_ITEMS - 1) / SD_ITEMS);
+        if (sh.c1 == 128)
+            sd_front_kernel<128><<<grid, 512, 0, st>>>(z, table, codes, p0, cnt, sh.d, sh.dp, dec->w1p, dec->scale1, dec->shift1, buf1);
+        else
+            sd_front_kernel<64><<<grid, 512, 0, st>>>(z, table, codes, p0, cnt, sh.d, sh.dp, dec->w1p, dec->scale1, dec->shift1, buf1);
+        GEO_LAUNCH_CHECK();
+        int rc = decode_tail(sh.c1, sh.c2, sh.co, 8, sh.crop, dec->w2p, dec->scale2, dec->shift2, dec->w3p, dec->b3, buf1, buf2, cnt,
+                             logits_out + (size_t)p0 * nout, st);
+        if (rc != GEO_OK) return rc;
+    }
+    return GEO_OK;
 }

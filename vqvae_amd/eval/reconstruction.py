@@ -11,6 +11,8 @@
     unnormalize_images (float32 torch ops, so the images are the reference's for the same decoder output), then the moments
     kernel into one device f64 [N][6] per image pair.  Images stay on the device unless the caller asks for them.
 The decoder itself stays torch: the JVP kernels of csrc/jvp.hip decode a 1x1 latent patch, not a whole image.
+A native decode of whole images now exists (vqvae_amd.decode); the evaluation CLIs built on this module
+do not use it yet.
 """
 from typing import Dict, Optional
 

@@ -1,4 +1,5 @@
-"""Host-side description of the decoder the JVP kernels differentiate.
+"""Host-side description of the decoder the JVP kernels differentiate, and of the same decoder as the image decode of
+csrc/vanilla_jvp.hip runs it (`spatial_image_kernels_cover`, `SpatialImageDecoderExport`).
 
 The function being differentiated is the reference's SpatialDecoder
 (src/models/spatial_vae.py:47-81; norm factory :8-19).  Only what the geodesic-codebook path needs
@@ -14,6 +15,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .vanilla_decoder import COVERED_WIDTHS, _fixed_statistics, _fold, _parity_taps
+
+MAX_IMAGE_LATENT_DIM = 64
 
 _NORM_CODE = {"none": 0, "batch": 1, "group": 2}
 
@@ -170,3 +174,73 @@ class DecoderExport:
                         buf.copy_(mine.to(buf.device, buf.dtype))
                 if layer.num_batches_tracked is not None:
                     layer.num_batches_tracked += n_calls
+
+
+def spatial_image_kernels_cover(m: nn.Module) -> bool:
+    """Whether geo_spatial_decode (csrc/vanilla_jvp.hip) decodes whole 4x4 latent grids of this module to images (else
+    vqvae_amd.decode runs the module itself).  Exactly: looks_like_spatial_decoder(m), and
+      - both norm layers are nn.Identity, or both are nn.BatchNorm2d in eval mode with running statistics (affine or not);
+      - conv_in and the three transposed convolutions have a bias;
+      - 1 <= latent_dim <= 64; (dec_channels[1], dec_channels[2]) is (128, 64) or (64, 32), any dec_channels[0];
+      - 1 or 3 output channels; output 32 px (last padding 1) or 28 px (last padding 3).
+    Anything else -- GroupNorm, train-mode BatchNorm, BatchNorm without running statistics, a layer without bias, other
+    widths -- is not covered."""
+    if not looks_like_spatial_decoder(m):
+        return False
+    seq = m.deconv_layers
+    if not (_fixed_statistics(seq[1]) and _fixed_statistics(seq[4])):
+        return False
+    if any(layer.bias is None for layer in (m.conv_in, seq[0], seq[3], seq[6])):
+        return False
+    return (1 <= m.conv_in.in_channels <= MAX_IMAGE_LATENT_DIM and m.conv_in.out_channels == seq[0].in_channels
+            and seq[0].out_channels == seq[3].in_channels and seq[3].out_channels == seq[6].in_channels
+            and (seq[0].out_channels, seq[3].out_channels) in COVERED_WIDTHS and seq[6].out_channels in (1, 3))
+
+
+class SpatialImageDecoderExport:
+    """A covered decoder as geo_spatial_decode reads it: conv_in composed into ConvT1 in fp64 and rounded to f32 once, both
+    norms folded into a scale and a shift, the three transposed convolutions laid out by output-pixel parity and tap
+    (`_parity_taps`), as f32 tensors on `dev` plus the ctypes descriptor over them.
+
+    conv_in's bias reaches an 8x8 pixel only through the taps that lie inside the 4x4 grid, so it is not a per-channel
+    constant.  It is carried as input channel d, which the kernel holds at 1 inside the grid; outside the grid every channel,
+    that one included, is 0.  `host` keeps the fp64 originals: "W" [parity][tap][d + 1][c1] (row d is the bias row),
+    "scale1", "shift1" [c1] with pre1 = scale1 * sum(taps, channels) + shift1 (ConvT1's bias inside shift1).
+    A snapshot: later changes of the module (weights, statistics, mode) are not seen."""
+
+    def __init__(self, dec: nn.Module, dev: torch.device):
+        if not spatial_image_kernels_cover(dec):
+            raise ValueError("decoder not covered by the spatial image decode (see spatial_image_kernels_cover)")
+        seq = dec.deconv_layers
+        conv1, norm1, conv2, norm2, out = seq[0], seq[1], seq[3], seq[4], seq[6]
+        d, c0, c1, c2, C = dec.conv_in.in_channels, dec.conv_in.out_channels, conv1.out_channels, conv2.out_channels, out.out_channels
+
+        def f64(t):
+            return t.detach().double().cpu()
+
+        with torch.no_grad():
+            aug = torch.cat([f64(dec.conv_in.weight).view(c0, d), f64(dec.conv_in.bias)[:, None]], 1)      # [c0][d + 1]
+            W = torch.einsum("ck,ptco->ptko", aug, _parity_taps(f64(conv1.weight)))                        # [4][4][d + 1][c1]
+            scale1, shift1 = _fold(norm1, c1)
+            shift1 = shift1 + scale1 * f64(conv1.bias)
+            dp = (d + 1 + 7) // 8 * 8
+            w1p = torch.zeros(4, 4, dp, c1, dtype=torch.float64)
+            w1p[:, :, :d + 1] = W
+            w1p = w1p.reshape(4, 4, dp // 4, 4, c1).permute(0, 1, 2, 4, 3)                                 # [4][4][dp / 4][c1][4]
+            scale2, shift2 = _fold(norm2, c2)
+            shift2 = shift2 + scale2 * f64(conv2.bias)
+            w2p = _parity_taps(f64(conv2.weight)).reshape(4, 4, c1 // 4, 4, c2).permute(0, 1, 2, 4, 3)     # [4][4][c1 / 4][c2][4]
+            w3p = _parity_taps(f64(out.weight)).permute(0, 1, 3, 2)                                        # [4][4][C][c2]
+
+        def f32(t):
+            return t.to(torch.float32).contiguous().to(dev)
+
+        self.host = {"W": W, "scale1": scale1, "shift1": shift1}
+        self.tensors = {"w1p": f32(w1p), "scale1": f32(scale1), "shift1": f32(shift1), "w2p": f32(w2p), "scale2": f32(scale2),
+                        "shift2": f32(shift2), "w3p": f32(w3p), "b3": f32(f64(out.bias))}
+        self.latent_dim, self.out_channels, self.out_size = d, C, {1: 32, 3: 28}[out.padding[0]]
+        desc = _lib.SpatialImageDecoderDesc()
+        desc.latent_dim, desc.c1, desc.c2, desc.out_channels, desc.out_size = d, c1, c2, C, self.out_size
+        for name, t in self.tensors.items():
+            setattr(desc, name, ctypes.c_void_p(t.data_ptr()))
+        self.desc = desc
