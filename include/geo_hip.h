@@ -205,6 +205,17 @@ int geo_knn_last_path(void);
  * no stored zeros).  Two calls: geo_symmetrize_count fills indptr_out [n+1] and returns nnz through
  * nnz_out [host] (synchronises); the caller allocates indices/data and calls geo_symmetrize_fill
  * with the same workspace (its contents carry over).
+ * An id outside [0, n) in nbr_idx (a padded list: -1, n, ...) is no entry: it is skipped, with its weight, as an out entry of
+ * its row and never counted as an in entry of anything -- the result is that of the lists without it; a row may consist of
+ * such ids only.  A row listing itself gives no entry (zero diagonal).  Inside one row the valid ids must be distinct (kNN
+ * lists are; scipy would sum a repeated column).  Limits: n, k >= 1, n k < 2^30, mode 0 or 1 (GEO_E_ARG outside) and a
+ * workspace of at least geo_symmetrize_workspace_bytes(n, k) (GEO_E_WORKSPACE below it), all checked before any launch.
+ * The other calls of this group that take a workspace refuse one below their size query in the same way:
+ * geo_connected_components and geo_upper_edges_count (which has no query of its own) are sized by geo_cc_workspace_bytes(n),
+ * geo_csr_compact_count by geo_csr_compact_workspace_bytes(n).
+ * Every array argument of these calls must be a non-NULL pointer even when it has no element (a graph without an entry:
+ * indices / data of length 0, src / dst of no edge) -- NULL is GEO_E_ARG; such an array is never read or written, any valid
+ * device address will do.  NULL is accepted only where a parameter says so (nbr_w, data, keep_node, entry_edge_out, data_out of geo_csr_compact_fill).
  * ------------------------------------------------------------------------------------------ */
 size_t geo_symmetrize_workspace_bytes(int32_t n, int32_t k);
 int geo_symmetrize_count(const int32_t *nbr_idx, const float *nbr_w, int32_t n, int32_t k, int32_t mode,
@@ -218,7 +229,9 @@ int geo_symmetrize_fill(const int32_t *nbr_idx, const float *nbr_w, int32_t n, i
  * src/scripts/build_codebook.py:43-45.  upper_ptr_out i32 [n+1] = exclusive count of entries with
  * col > row; n_edges through [host] pointer (synchronises).  geo_upper_edges_fill writes
  * src/dst i32 [E] and entry_edge i32 [nnz]: for every stored entry the index of its undirected
- * edge (so that W_geo = U + U^T of build_codebook.py:53-54 is a gather).
+ * edge (so that W_geo = U + U^T of build_codebook.py:53-54 is a gather).  entry_edge is -1 for a stored diagonal entry and
+ * for an entry below the diagonal whose mirror (col, row) is not stored; geo_gather_edge_weights writes 0.0 there.  Rows
+ * must have ascending columns.
  * ------------------------------------------------------------------------------------------ */
 int geo_upper_edges_count(const int32_t *indptr, const int32_t *indices, int32_t n,
                           int32_t *upper_ptr_out, int64_t *n_edges_out, void *ws, size_t ws_bytes, void *stream);

@@ -25,6 +25,22 @@ def ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+_stand_ins = {}
+
+
+def ptr_or_stand_in(t: torch.Tensor):
+    """ptr() for an array that may have no element (a graph without edges, a kept set without an entry): the ABI refuses
+    NULL and an empty tensor has no address, so such an array is passed as a resident 1-element stand-in of its dtype --
+    no kernel indexes into an array of length 0, so it is never read or written."""
+    if t.numel():
+        return ptr(t)
+    key = (t.dtype, t.device.type, t.device.index)
+    with _ws_lock:
+        if key not in _stand_ins:
+            _stand_ins[key] = torch.zeros(1, dtype=t.dtype, device=t.device)
+        return ptr(_stand_ins[key])
+
+
 def stream_ptr():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 

@@ -167,7 +167,7 @@ struct SymWs {
     size_t scan_bytes;
 };
 
-bool carve_sym(void *ws, size_t ws_bytes, int32_t n, int32_t k, SymWs *o) {
+void carve_sym(void *ws, size_t ws_bytes, int32_t n, int32_t k, SymWs *o) {
     geo::Arena ar(ws, ws_bytes);
     const size_t nk = (size_t)n * k;
     o->cnt_in = ar.take<int32_t>((size_t)n + 1);
@@ -180,7 +180,6 @@ bool carve_sym(void *ws, size_t ws_bytes, int32_t n, int32_t k, SymWs *o) {
     o->tmp_val = ar.take<float>(2 * nk + 1);
     o->scan_bytes = geo::scan_tmp_bytes((int64_t)n + 1);
     o->scan_tmp = ar.take<char>(o->scan_bytes);
-    return o->scan_tmp != nullptr;
 }
 
 // ------------------------------------------------------------------------------------ upper edges
@@ -353,6 +352,16 @@ __global__ __launch_bounds__(256) void compact_fill_kernel(const int32_t *__rest
 
 unsigned rows_grid(int32_t n) { return (unsigned)((n + WPB - 1) / WPB); }
 
+// The ABI's rule (geo_hip.h): a workspace smaller than the size query that belongs to the call is refused before any launch.
+// The queries cover the carves below with slack, so a carve cannot fail once this has passed.
+#define GEO_REQUIRE_WORKSPACE(name, ws_bytes, need)                                                  \
+    do {                                                                                             \
+        if ((ws_bytes) < (need)) {                                                                   \
+            geo::set_error(name ": workspace %zu too small (%zu needed)", (size_t)(ws_bytes), (size_t)(need)); \
+            return GEO_E_WORKSPACE;                                                                  \
+        }                                                                                            \
+    } while (0)
+
 }  // namespace
 
 // ============================================================================================ ABI
@@ -369,11 +378,9 @@ extern "C" int geo_symmetrize_count(const int32_t *nbr_idx, const float *nbr_w, 
     GEO_REQUIRE(nbr_idx && indptr_out && nnz_out && ws, "geo_symmetrize_count: null pointer");
     GEO_REQUIRE(n > 0 && k > 0 && (int64_t)n * k < ((int64_t)1 << 30), "geo_symmetrize_count: bad n=%d k=%d", n, k);
     GEO_REQUIRE(mode == 0 || mode == 1, "geo_symmetrize_count: mode must be 0 (union) or 1 (mutual)");
+    GEO_REQUIRE_WORKSPACE("geo_symmetrize_count", ws_bytes, geo_symmetrize_workspace_bytes(n, k));
     SymWs w;
-    if (!carve_sym(ws, ws_bytes, n, k, &w)) {
-        geo::set_error("geo_symmetrize_count: workspace %zu too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
+    carve_sym(ws, ws_bytes, n, k, &w);
     const int64_t total = (int64_t)n * k;
     GEO_HIP_CHECK(hipMemsetAsync(w.cnt_in, 0, ((size_t)n + 1) * 4, s));
     GEO_HIP_CHECK(hipMemsetAsync(w.cursor, 0, ((size_t)n + 1) * 4, s));
@@ -393,11 +400,11 @@ extern "C" int geo_symmetrize_fill(const int32_t *nbr_idx, const float *nbr_w, i
                                    size_t ws_bytes, void *stream_) {
     hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(nbr_idx && indptr && indices_out && data_out && ws, "geo_symmetrize_fill: null pointer");
+    GEO_REQUIRE(n > 0 && k > 0 && (int64_t)n * k < ((int64_t)1 << 30), "geo_symmetrize_fill: bad n=%d k=%d", n, k);
+    GEO_REQUIRE(mode == 0 || mode == 1, "geo_symmetrize_fill: mode must be 0 (union) or 1 (mutual)");
+    GEO_REQUIRE_WORKSPACE("geo_symmetrize_fill", ws_bytes, geo_symmetrize_workspace_bytes(n, k));
     SymWs w;
-    if (!carve_sym(ws, ws_bytes, n, k, &w)) {
-        geo::set_error("geo_symmetrize_fill: workspace %zu too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
+    carve_sym(ws, ws_bytes, n, k, &w);
     sym_scatter_kernel<<<rows_grid(n), 256, 0, s>>>(nbr_idx, nbr_w, n, k, mode, w.off_in, w.in_src, w.in_w, indptr,
                                                     w.tmp_col, w.tmp_val);
     GEO_LAUNCH_CHECK();
@@ -416,14 +423,11 @@ extern "C" int geo_upper_edges_count(const int32_t *indptr, const int32_t *indic
                                      int64_t *n_edges_out, void *ws, size_t ws_bytes, void *stream_) {
     hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(indptr && indices && upper_ptr_out && n_edges_out && ws && n > 0, "geo_upper_edges_count: bad argument");
+    GEO_REQUIRE_WORKSPACE("geo_upper_edges_count", ws_bytes, geo_cc_workspace_bytes(n));
     geo::Arena ar(ws, ws_bytes);
     int32_t *cnt = ar.take<int32_t>((size_t)n + 1);
     const size_t sb = geo::scan_tmp_bytes((int64_t)n + 1);
     void *st = ar.take<char>(sb);
-    if (!cnt || !st) {
-        geo::set_error("geo_upper_edges_count: workspace %zu too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
     upper_count_kernel<<<geo::grid_for(n, 256), 256, 0, s>>>(indptr, indices, n, cnt);
     GEO_LAUNCH_CHECK();
     return geo::exclusive_scan_i32(cnt, upper_ptr_out, n, st, sb, n_edges_out, s);
@@ -458,6 +462,7 @@ extern "C" int geo_connected_components(const int32_t *indptr, const int32_t *in
     hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(indptr && indices && labels_out && n_components_out && ws && n > 0,
                 "geo_connected_components: bad argument");
+    GEO_REQUIRE_WORKSPACE("geo_connected_components", ws_bytes, geo_cc_workspace_bytes(n));
     geo::Arena ar(ws, ws_bytes);
     int32_t *label = ar.take<int32_t>((size_t)n + 1);
     int32_t *is_root = ar.take<int32_t>((size_t)n + 1);
@@ -465,10 +470,6 @@ extern "C" int geo_connected_components(const int32_t *indptr, const int32_t *in
     int32_t *changed = ar.take<int32_t>(64);
     const size_t sb = geo::scan_tmp_bytes((int64_t)n + 1);
     void *st = ar.take<char>(sb);
-    if (!label || !is_root || !rank || !changed || !st) {
-        geo::set_error("geo_connected_components: workspace %zu too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
     const int g = geo::grid_for(n, 256, 2048);
     const int gh = geo::grid_for(n, 16, 2048);
     cc_init_kernel<<<g, 256, 0, s>>>(label, n);
@@ -512,16 +513,13 @@ extern "C" int geo_csr_compact_count(const int32_t *indptr, const int32_t *indic
     hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(indptr && indices && new_index_out && indptr_out && n_out && nnz_out && ws && n > 0,
                 "geo_csr_compact_count: bad argument");
+    GEO_REQUIRE_WORKSPACE("geo_csr_compact_count", ws_bytes, geo_csr_compact_workspace_bytes(n));
     geo::Arena ar(ws, ws_bytes);
     int32_t *flag = ar.take<int32_t>((size_t)n + 1);
     int32_t *pos = ar.take<int32_t>((size_t)n + 1);
     int32_t *row_cnt = ar.take<int32_t>((size_t)n + 1);
     const size_t sb = geo::scan_tmp_bytes((int64_t)n + 1);
     void *st = ar.take<char>(sb);
-    if (!flag || !pos || !row_cnt || !st) {
-        geo::set_error("geo_csr_compact_count: workspace %zu too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
     const int g = geo::grid_for(n, 256, 2048);
     keep_flags_kernel<<<g, 256, 0, s>>>(keep_node, n, flag);
     GEO_LAUNCH_CHECK();

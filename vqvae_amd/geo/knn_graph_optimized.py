@@ -15,7 +15,7 @@ import torch
 from scipy import sparse
 
 from .. import _lib
-from .._device import DeviceCSR, device, ptr, stream_ptr, workspace
+from .._device import DeviceCSR, device, ptr, ptr_or_stand_in, stream_ptr, workspace
 
 _SYM_MODE = {"union": 0, "mutual": 1}
 MAX_NEIGHBORS = 256         # n_neighbors (k + 1) supported by the wave-resident top-k lists (geo_hip.h)
@@ -56,8 +56,8 @@ def symmetrize_device(nbr_idx: torch.Tensor, nbr_w: Optional[torch.Tensor], sym:
                                             ptr(ws), ws.numel(), stream_ptr()), "geo_symmetrize_count")
         indices = torch.empty(int(nnz[0]), dtype=torch.int32, device=dev)
         data = torch.empty(int(nnz[0]), dtype=torch.float32, device=dev)
-        _lib.check(lib.geo_symmetrize_fill(ptr(nbr_idx), ptr(nbr_w), n, k, mode, ptr(indptr), ptr(indices), ptr(data),
-                                           ptr(ws), ws.numel(), stream_ptr()), "geo_symmetrize_fill")
+        _lib.check(lib.geo_symmetrize_fill(ptr(nbr_idx), ptr(nbr_w), n, k, mode, ptr(indptr), ptr_or_stand_in(indices),
+                                           ptr_or_stand_in(data), ptr(ws), ws.numel(), stream_ptr()), "geo_symmetrize_fill")
     return DeviceCSR(n, indptr, indices, data)
 
 
@@ -166,8 +166,9 @@ def connected_components_device(G: DeviceCSR):
     ncomp = np.zeros(1, dtype=np.int32)
     ws = workspace(lib.geo_cc_workspace_bytes(G.n), dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.geo_connected_components(ptr(G.indptr), ptr(G.indices), G.n, ptr(labels), ncomp.ctypes.data,
-                                                ptr(ws), ws.numel(), stream_ptr()), "geo_connected_components")
+        _lib.check(lib.geo_connected_components(ptr(G.indptr), ptr_or_stand_in(G.indices), G.n, ptr(labels),
+                                                ncomp.ctypes.data, ptr(ws), ws.numel(), stream_ptr()),
+                   "geo_connected_components")
     return int(ncomp[0]), labels
 
 
@@ -190,16 +191,17 @@ def compact_device(G: DeviceCSR, keep: Optional[torch.Tensor], drop_zero: bool) 
     indptr_new = torch.empty(G.n + 1, dtype=torch.int32, device=dev)
     n_new, nnz_new = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int64)
     with torch.cuda.device(dev):
-        _lib.check(lib.geo_csr_compact_count(ptr(G.indptr), ptr(G.indices), ptr(G.data), G.n, ptr(keep_u8),
+        _lib.check(lib.geo_csr_compact_count(ptr(G.indptr), ptr_or_stand_in(G.indices), ptr(G.data), G.n, ptr(keep_u8),
                                              1 if drop_zero else 0, ptr(new_index), ptr(indptr_new),
                                              n_new.ctypes.data, nnz_new.ctypes.data, ptr(ws), ws.numel(),
                                              stream_ptr()), "geo_csr_compact_count")
         indices = torch.empty(int(nnz_new[0]), dtype=torch.int32, device=dev)
         data = torch.empty(int(nnz_new[0]), dtype=torch.float32, device=dev)
         if int(n_new[0]) > 0:
-            _lib.check(lib.geo_csr_compact_fill(ptr(G.indptr), ptr(G.indices), ptr(G.data), G.n, ptr(keep_u8),
-                                                1 if drop_zero else 0, ptr(new_index), ptr(indptr_new), ptr(indices),
-                                                ptr(data), stream_ptr()), "geo_csr_compact_fill")
+            _lib.check(lib.geo_csr_compact_fill(ptr(G.indptr), ptr_or_stand_in(G.indices), ptr(G.data), G.n, ptr(keep_u8),
+                                                1 if drop_zero else 0, ptr(new_index), ptr(indptr_new),
+                                                ptr_or_stand_in(indices), ptr_or_stand_in(data), stream_ptr()),
+                       "geo_csr_compact_fill")
     n = int(n_new[0])
     return DeviceCSR(n, indptr_new[: n + 1].contiguous(), indices, data), new_index
 
@@ -213,14 +215,15 @@ def upper_edges_device(G: DeviceCSR):
     upper_ptr = torch.empty(G.n + 1, dtype=torch.int32, device=dev)
     n_edges = np.zeros(1, dtype=np.int64)
     with torch.cuda.device(dev):
-        _lib.check(lib.geo_upper_edges_count(ptr(G.indptr), ptr(G.indices), G.n, ptr(upper_ptr), n_edges.ctypes.data,
-                                             ptr(ws), ws.numel(), stream_ptr()), "geo_upper_edges_count")
+        _lib.check(lib.geo_upper_edges_count(ptr(G.indptr), ptr_or_stand_in(G.indices), G.n, ptr(upper_ptr),
+                                             n_edges.ctypes.data, ptr(ws), ws.numel(), stream_ptr()), "geo_upper_edges_count")
         E = int(n_edges[0])
         src = torch.empty(E, dtype=torch.int32, device=dev)
         dst = torch.empty(E, dtype=torch.int32, device=dev)
         entry_edge = torch.empty(G.nnz, dtype=torch.int32, device=dev)
-        _lib.check(lib.geo_upper_edges_fill(ptr(G.indptr), ptr(G.indices), G.n, ptr(upper_ptr), ptr(src), ptr(dst),
-                                            ptr(entry_edge), stream_ptr()), "geo_upper_edges_fill")
+        _lib.check(lib.geo_upper_edges_fill(ptr(G.indptr), ptr_or_stand_in(G.indices), G.n, ptr(upper_ptr),
+                                            ptr_or_stand_in(src), ptr_or_stand_in(dst), ptr(entry_edge), stream_ptr()),
+                   "geo_upper_edges_fill")
     return src, dst, entry_edge
 
 
@@ -229,8 +232,8 @@ def reweight_device(G: DeviceCSR, entry_edge: torch.Tensor, lengths: torch.Tenso
     lib = _lib.load()
     data = torch.empty(G.nnz, dtype=torch.float32, device=G.indptr.device)
     with torch.cuda.device(G.indptr.device):
-        _lib.check(lib.geo_gather_edge_weights(ptr(lengths), ptr(entry_edge), G.nnz, ptr(data), stream_ptr()),
-                   "geo_gather_edge_weights")
+        _lib.check(lib.geo_gather_edge_weights(ptr_or_stand_in(lengths), ptr_or_stand_in(entry_edge), G.nnz,
+                                               ptr_or_stand_in(data), stream_ptr()), "geo_gather_edge_weights")
     return DeviceCSR(G.n, G.indptr, G.indices, data)
 
 
