@@ -436,6 +436,51 @@ size_t geo_spatial_decode_workspace_bytes(const geo_spatial_image_decoder_desc *
 int geo_spatial_decode(const geo_spatial_image_decoder_desc *dec, const float *z, const float *table, const int32_t *codes,
                        int64_t n, float *logits_out, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Image encode: images -> (mu, logvar) of the encoder of either VAE with FIXED statistics
+ * (src/models/vae.py:22-50, src/models/spatial_vae.py:22-44 in eval mode: BatchNorm with running statistics, or none):
+ *   Conv(C,e1,k3,s2,p1) -> norm -> ReLU -> Conv(e1,e2,k3,s2,p1) -> norm -> ReLU -> Conv(e2,e3,k3,s2,p1) -> norm -> ReLU,
+ *   28 -> 14 -> 7 -> 4 px or 32 -> 16 -> 8 -> 4 px, then the head: fc_mu, fc_logvar = Linear(16 e3, d) on the NCHW flatten
+ *   (spatial_head 0; mu, logvar f32 [n][d]) or Conv(e3, d, 1) (spatial_head 1; mu, logvar f32 NCHW [n][d][4][4]).
+ * Activations are f32 [item][pixel][channel]; layer i computes relu(scale_i[co] * sum + shift_i[co]) with the sum a chain
+ * from 0 (layer 1: over (c, ky, kx); layers 2, 3: over tap 3 ky + kx, then the input channels in blocks of 8, within a
+ * block in the order 0 4 1 5 2 6 3 7), output pixel (oy, ox) reading input pixel (2 oy - 1 + ky, 2 ox - 1 + kx), nothing
+ * outside the image.  A head value is bh[col] added to the sum, in segment order, of one such chain per segment: 16
+ * segments (the 4 x 4 pixels) of e3 channels for the vanilla head, one for the spatial head.
+ * Covered: (C, in_size) = (1, 28) or (3, 32); (e1, e2, e3) = (64, 128, 256) or (32, 64, 128); 1 <= latent_dim <= 128
+ * (spatial_head 0) or <= 64 (spatial_head 1).  The rules are those of the image decode above: passes of at most 4096
+ * items shrunk to fit any workspace from geo_image_encode_workspace_bytes(enc, 1) upwards (the three activation buffers of
+ * a pass; below it GEO_E_WORKSPACE); the query answers 0 and the call GEO_E_ARG for a descriptor outside the coverage, as
+ * for a null pointer or n >= 2^31, before any launch; n == 0 returns GEO_OK without a launch.  No atomics: a row's
+ * (mu, logvar) does not depend on n, its position, the pass or workspace size, the stream or the run.  Asynchronous on
+ * `stream`.  x is the tensor the module would be given (normalisation is the caller's).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct geo_image_encoder_desc {
+    int32_t in_channels;       /* C */
+    int32_t in_size;           /* 28 or 32 */
+    int32_t e1, e2, e3;        /* enc_channels */
+    int32_t latent_dim;        /* d */
+    int32_t spatial_head;      /* 0: Linear heads on the flatten, 1: 1 x 1 convolution heads */
+    /* device pointers, f32 */
+    const float *w1p;          /* [9 C][e1]: row (c 3 + ky) 3 + kx, element = conv1.weight[co][c][ky][kx] */
+    const float *scale1;       /* [e1] norm i folded, convolution i's bias inside shift_i */
+    const float *shift1;       /* [e1] */
+    const float *w2p;          /* [9][e1 / 4][e2][4]: element (tap, q, co, r) = conv2.weight[co][4 q + r][ky][kx], tap = 3 ky + kx */
+    const float *scale2;       /* [e2] */
+    const float *shift2;       /* [e2] */
+    const float *w3p;          /* [9][e2 / 4][e3][4], as w2p */
+    const float *scale3;       /* [e3] */
+    const float *shift3;       /* [e3] */
+    const float *whp;          /* [segments][e3 / 4][npad][4], npad = 2 d rounded up to a multiple of 32, columns 0 .. d-1 mu,
+                                  d .. 2d-1 logvar, 0 above: element (p, q, col, r) = fc.weight[col][(4 q + r) 16 + p] (vanilla, 16
+                                  segments: the module's flatten index is channel * 16 + pixel) or fc.weight[col][4 q + r] (spatial) */
+    const float *bh;           /* [npad] the two biases, 0 above 2 d */
+} geo_image_encoder_desc;
+
+size_t geo_image_encode_workspace_bytes(const geo_image_encoder_desc *enc, int64_t n);   /* 0: not covered */
+int geo_image_encode(const geo_image_encoder_desc *enc, const float *x /* [n][C][S][S] */, int64_t n, float *mu_out,
+                     float *logvar_out, void *ws, size_t ws_bytes, void *stream);
+
 /* Gather: data_out[e] = len[entry_edge[e]] for every stored entry (W_geo = U + U^T). */
 int geo_gather_edge_weights(const float *len, const int32_t *entry_edge, int64_t nnz, float *data_out, void *stream);
 

@@ -35,6 +35,12 @@ class SpatialImageDecoderDesc(ctypes.Structure):
                 + [(n, c_p) for n in ("w1p", "scale1", "shift1", "w2p", "scale2", "shift2", "w3p", "b3")])
 
 
+class ImageEncoderDesc(ctypes.Structure):
+    """geo_image_encoder_desc of include/geo_hip.h."""
+    _fields_ = ([(n, i32) for n in ("in_channels", "in_size", "e1", "e2", "e3", "latent_dim", "spatial_head")]
+                + [(n, c_p) for n in ("w1p", "scale1", "shift1", "w2p", "scale2", "shift2", "w3p", "scale3", "shift3", "whp", "bh")])
+
+
 class PriorDesc(ctypes.Structure):
     """geo_prior_desc of include/geo_hip.h."""
     _fields_ = ([(n, i32) for n in ("num_tokens", "embed_dim", "n_layers", "n_head", "max_seq_len", "num_classes")]
@@ -91,7 +97,9 @@ _SIGNATURES = {
     "geo_vanilla_decode": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, c_p, c_p, sz, c_p]),
     "geo_spatial_decode_workspace_bytes": (sz, [ctypes.POINTER(SpatialImageDecoderDesc), i64]),
     "geo_spatial_decode": (ctypes.c_int, [ctypes.POINTER(SpatialImageDecoderDesc), c_p, c_p, c_p, i64, c_p, c_p, sz, c_p]),
-    "geo_gather_edge_weights": (ctypes.c_int, [c_p, c_p, i64, c_p, c_p]),
+    "geo_image_encode_workspace_bytes": (sz, [ctypes.POINTER(ImageEncoderDesc), i64]),
+    "geo_image_encode": (ctypes.c_int, [ctypes.POINTER(ImageEncoderDesc), c_p, i64, c_p, c_p, c_p, sz, c_p]),
+    "geo_gather_edge_weights":(ctypes.c_int, [c_p, c_p, i64, c_p, c_p]),
     "geo_prior_sample_workspace_bytes": (sz, [ctypes.POINTER(PriorDesc), i32, i32]),
     "geo_prior_sample": (ctypes.c_int, [ctypes.POINTER(PriorDesc), c_p, i32, i32, c_p, c_p, ctypes.c_float, i32, c_p, c_p, i32,
                                         c_p, sz, c_p]),

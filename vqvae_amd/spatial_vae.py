@@ -6,7 +6,9 @@ Inference (encode -> mu, logvar, z) feeds the geodesic-codebook path; `loss` is 
 training/spatial_engine.py and scripts/train_vae.py train with.  On CUDA tensors it is the fused HIP
 ELBO the vanilla VAE uses (`elbo_hip` of vae.py, csrc/vae_loss.hip) on the latent grids viewed as [B][d h w], and returns
 float64 scalars that live on the device; on CPU tensors it is the reference's formula in torch ops.  The layers are
-PyTorch-ROCm modules (device memory and convolutions are plumbing here; the path's own arithmetic is in csrc/)."""
+PyTorch-ROCm modules, and training, `forward` and the latent writers run them as such.  Inference of the encoder alone also
+exists in HIP: vqvae_amd.encode.encode_latents (csrc/encode.hip) runs a SpatialEncoder with fixed
+statistics natively, and scripts/encode_latents.py is the command that uses it; the callers of `model(x)` are not switched."""
 from typing import Sequence, Tuple
 
 import torch

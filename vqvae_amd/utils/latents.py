@@ -1,5 +1,10 @@
 """Latent files of the vanilla VAE: the reference's save_latents (src/utils/latents.py) and a resident variant that keeps the
-latents on the device, like utils/spatial_latents.py."""
+latents on the device, like utils/spatial_latents.py.
+
+These writers call `model(x)`: the torch encoder, the draw of z, and the decoder, whose output is dropped.  Their files are
+pinned by fixtures, so they stay as they are; the encoder alone runs natively in vqvae_amd.encode.encode_latents
+(DESIGN.md section 18), which scripts/encode_latents.py uses to write the same four files from a checkpoint.  Switching the
+writers is a later change, to be argued from the measurements of that section."""
 from pathlib import Path
 from typing import Iterable
 

@@ -1,6 +1,11 @@
 """Latent production on the MI355X: the reference's save_spatial_latents
 (src/utils/spatial_latents.py:10-36) plus a resident variant that hands the latents to the codebook builder without
-leaving HBM (the reference writes z.pt and build_codebook.py reads it back: a host round trip of N*C*H*W*4 bytes)."""
+leaving HBM (the reference writes z.pt and build_codebook.py reads it back: a host round trip of N*C*H*W*4 bytes).
+
+Everything here calls `model(x)`: the torch encoder, the draw of z, and the decoder, whose output is dropped.  The outputs are
+pinned by fixtures, so that stays; the encoder alone runs natively in vqvae_amd.encode.encode_latents,
+which scripts/encode_latents.py uses to write the same four files from a checkpoint.  Switching these functions is a later
+change, to be argued from the measurements of that section."""
 from pathlib import Path
 from typing import Iterable, Tuple
 
