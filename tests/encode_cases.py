@@ -7,6 +7,8 @@ import functools
 import torch
 import torch.nn as nn
 
+from vanilla_jvp_cases import plain_batchnorm
+
 # (kind, name) -> (enc_channels, latent_dim, in_channels, image size, norm_type)
 CASES = {
     ("vanilla", "wide-bn-28"): ((64, 128, 256), 128, 1, 28, "batch"),
@@ -18,6 +20,23 @@ CASES = {
     ("spatial", "narrow-none-28-d5"): ((32, 64, 128), 5, 1, 28, "none"),
 }
 ALL_CASES = list(CASES)
+# Points of the admitted envelope (encoder_kernels_cover) chosen for the branches of enc_head_kernel they reach: ntiles =
+# ceil(2 d / 32) column tiles, of which wave w takes w and w + 4.  "batch-plain" is BatchNorm2d(affine=False).
+ENVELOPE_CASES = {
+    ("vanilla", "narrow-bn-28-d1"): ((32, 64, 128), 1, 1, 28, "batch"),               # d = 1: two live columns
+    ("vanilla", "wide-none-32x3-d33"): ((64, 128, 256), 33, 3, 32, "none"),           # 3 tiles: one idle wave
+    ("vanilla", "narrow-bn-32x3-d65"): ((32, 64, 128), 65, 3, 32, "batch"),           # 5 tiles: only wave 0 takes a second one
+    ("vanilla", "wide-none-28-d96"): ((64, 128, 256), 96, 1, 28, "none"),             # 6 tiles, mu / logvar boundary on a tile edge
+    ("vanilla", "narrow-none-28-d100"): ((32, 64, 128), 100, 1, 28, "none"),          # 7 tiles
+    ("vanilla", "wide-bn-28-d127"): ((64, 128, 256), 127, 1, 28, "batch"),            # 8 tiles, two dead columns in the last
+    ("spatial", "narrow-bn-32x3-d1"): ((32, 64, 128), 1, 3, 32, "batch"),
+    ("spatial", "wide-none-28-d33"): ((64, 128, 256), 33, 1, 28, "none"),             # 3 tiles
+    ("spatial", "narrow-none-32x3-d64"): ((32, 64, 128), 64, 3, 32, "none"),          # 4 tiles, the maximum
+    ("spatial", "wide-bn-28-d63"): ((64, 128, 256), 63, 1, 28, "batch"),              # odd d just under the maximum
+    ("vanilla", "wide-plainbn-32x3-d40"): ((64, 128, 256), 40, 3, 32, "batch-plain"),
+    ("spatial", "narrow-plainbn-28-d20"): ((32, 64, 128), 20, 1, 28, "batch-plain"),
+}
+ALL_ENVELOPE_CASES = list(ENVELOPE_CASES)
 N_VANILLA, N_SPATIAL = 77, 37           # no multiple of the 1, 2 or 4 items of a convolution workgroup, nor of the 32 head rows
 
 
@@ -43,6 +62,13 @@ def make_encoder(kind, channels, latent_dim, in_channels, norm_type, seed=0, eva
     return enc.eval() if eval_mode else enc.train()
 
 
+def build(kind, channels, latent_dim, in_channels, norm_type, seed=0) -> nn.Module:
+    """make_encoder in eval mode, with "batch-plain" meaning plain_batchnorm of the "batch" encoder."""
+    if norm_type == "batch-plain":
+        return plain_batchnorm(make_encoder(kind, channels, latent_dim, in_channels, "batch", seed=seed), seed)
+    return make_encoder(kind, channels, latent_dim, in_channels, norm_type, seed=seed)
+
+
 def images(n, in_channels, size, seed=1) -> torch.Tensor:
     """Uniform [0, 1) images for one channel, normal ones for three; image 0 is all zeros and image 1 all ones (the border
     outputs of a constant image differ from the interior only through the padding taps)."""
@@ -59,8 +85,18 @@ def images(n, in_channels, size, seed=1) -> torch.Tensor:
 @functools.lru_cache(maxsize=None)
 def case(kind, name):
     """(encoder on the CPU in eval mode, x, fp64 mu, fp64 logvar, float32-torch maximum error of mu, of logvar)."""
-    channels, d, C, size, norm = CASES[(kind, name)]
-    enc = make_encoder(kind, channels, d, C, norm, seed=len(name))
+    return _case(CASES, kind, name)
+
+
+@functools.lru_cache(maxsize=None)
+def envelope_case(kind, name):
+    """`case` for ENVELOPE_CASES."""
+    return _case(ENVELOPE_CASES, kind, name)
+
+
+def _case(table, kind, name):
+    channels, d, C, size, norm = table[(kind, name)]
+    enc = build(kind, channels, d, C, norm, seed=len(name))
     x = images(N_VANILLA if kind == "vanilla" else N_SPATIAL, C, size)
     with torch.no_grad():
         mu64, lv64 = copy.deepcopy(enc).double()(x.double())

@@ -8,6 +8,7 @@ import torch.nn as nn
 from PIL import Image
 
 import decode_cases as D
+import vanilla_jvp_cases as V
 
 
 def composed_front(export, z: np.ndarray) -> np.ndarray:
@@ -32,9 +33,20 @@ def composed_front(export, z: np.ndarray) -> np.ndarray:
 
 @pytest.mark.parametrize("name", list(D.SPATIAL_CASES))
 def test_composed_front_matches_the_module_in_fp64(name):
+    _check_composed_front(name, D.SPATIAL_CASES[name])
+
+
+@pytest.mark.parametrize("name", list(D.SPATIAL_ENVELOPE_CASES))
+def test_composed_front_matches_the_envelope_modules_in_fp64(name):
+    """The same check over decode_cases.SPATIAL_ENVELOPE_CASES: the constant-one channel on either side of a K block's edge,
+    d = 1 and 64, BatchNorm2d(affine=False), a dec_channels[0] other than 256 / 128."""
+    _check_composed_front(name, D.SPATIAL_ENVELOPE_CASES[name])
+
+
+def _check_composed_front(name, config):
     from vqvae_amd.spatial_decoder import SpatialImageDecoderExport, spatial_image_kernels_cover
-    channels, d, C, size, norm = D.SPATIAL_CASES[name]
-    dec = D.make_spatial_decoder(channels, d, C, size, norm, seed=len(name))
+    channels, d, C, size, norm = config
+    dec = D.build_spatial(channels, d, C, size, norm, seed=len(name))
     assert spatial_image_kernels_cover(dec)
     export = SpatialImageDecoderExport(dec, torch.device("cpu"))
     z = D.grids(9, d, seed=5).double()
@@ -77,6 +89,40 @@ def test_coverage_predicate_rejects_what_the_kernels_do_not_run():
     assert native_decode_covers(V.make_decoder((256, 128, 64), 128, 1, 28, "batch"))
     assert not native_decode_covers(V.make_decoder((256, 128, 64), 128, 1, 28, "group"))
     assert not native_decode_covers(nn.Linear(4, 4))
+
+
+@pytest.mark.parametrize("kind,name", [("spatial", n) for n in D.SPATIAL_ENVELOPE_CASES] + [("vanilla", n) for n in V.ENVELOPE_CASES])
+def test_envelope_cases_are_covered_and_one_step_outside_is_not(kind, name):
+    """Predicate and make_shape / make_spatial_shape agree on every envelope case: covered, with a workspace of the two
+    activation buffers; the same module one latent dimension above the maximum (65 | 129) is not covered, and the descriptor
+    with that dimension, with 0, or with a size or channel count next to the admitted ones answers 0."""
+    from vqvae_amd import _lib
+    from vqvae_amd.decode import native_decode_covers
+    from vqvae_amd.spatial_decoder import SpatialImageDecoderExport
+    from vqvae_amd.vanilla_decoder import VanillaDecoderExport
+    lib = _lib.load()
+    if kind == "spatial":
+        channels, d, C, size, norm = D.SPATIAL_ENVELOPE_CASES[name]
+        build, d_max, Export, query = D.build_spatial, 64, SpatialImageDecoderExport, lib.geo_spatial_decode_workspace_bytes
+        per_item = 4 * (64 * channels[1] + 256 * channels[2])
+    else:
+        channels, d, C, size, norm = V.ENVELOPE_CASES[name]
+        build, d_max, Export, query = V.build, 128, VanillaDecoderExport, lib.geo_vanilla_decode_workspace_bytes
+        per_item = 4 * ((size // 4) ** 2 * channels[1] + (size // 2) ** 2 * channels[2])
+    dec = build(channels, d, C, size, norm, seed=len(name))
+    assert native_decode_covers(dec)
+    if norm == "batch-plain":
+        norms = [m for m in dec.modules() if isinstance(m, nn.BatchNorm2d)]
+        assert len(norms) == 2 and all(m.weight is None and m.bias is None and not m.training for m in norms)
+    assert not native_decode_covers(build(channels, d_max + 1, C, size, norm))
+    desc = Export(dec, torch.device("cpu")).desc
+    assert per_item % 256 == 0 and query(desc, 1) == per_item and query(desc, D.N_SPATIAL) == D.N_SPATIAL * per_item
+    for change in (dict(latent_dim=d_max + 1), dict(latent_dim=0), dict(out_size=24 if size == 28 else 36), dict(out_channels=2),
+                   dict(out_channels=4)):
+        bad = type(desc).from_buffer_copy(desc)
+        for k, v in change.items():
+            setattr(bad, k, v)
+        assert query(bad, 8) == 0, change
 
 
 def test_workspace_query_answers_zero_outside_the_coverage():

@@ -76,9 +76,19 @@ def packed_head(a3: np.ndarray, whp: np.ndarray, bh: np.ndarray, d: int, spatial
 
 @pytest.mark.parametrize("kind,name", E.ALL_CASES)
 def test_packed_arrays_reproduce_the_module_in_fp64(kind, name):
+    _check_packed_arrays(kind, name, E.CASES[(kind, name)], E.case(kind, name))
+
+
+@pytest.mark.parametrize("kind,name", E.ALL_ENVELOPE_CASES)
+def test_packed_arrays_reproduce_the_envelope_modules_in_fp64(kind, name):
+    """The same check over encode_cases.ENVELOPE_CASES: every head tile count, d = 1, BatchNorm2d(affine=False)."""
+    _check_packed_arrays(kind, name, E.ENVELOPE_CASES[(kind, name)], E.envelope_case(kind, name))
+
+
+def _check_packed_arrays(kind, name, config, case):
     from vqvae_amd.image_encoder import ImageEncoderExport, encoder_kernels_cover
-    channels, d, C, size, _ = E.CASES[(kind, name)]
-    enc, x, mu64, lv64, _, _ = E.case(kind, name)
+    channels, d, C, size, _ = config
+    enc, x, mu64, lv64, _, _ = case
     assert encoder_kernels_cover(enc) and encoder_kernels_cover(enc, size)
     export = ImageEncoderExport(enc, torch.device("cpu"))
     h = {k: v.numpy() for k, v in export.host.items()}
@@ -142,6 +152,35 @@ def test_coverage_predicate_rejects_what_the_kernels_do_not_run():
         with pytest.raises(ValueError):
             ImageEncoderExport(E.make_encoder(kind, wide, 16, 1, "group"), torch.device("cpu"))
     assert not encoder_kernels_cover(nn.Linear(4, 4)) and not native_encode_covers(nn.Linear(4, 4))
+
+
+@pytest.mark.parametrize("kind,name", E.ALL_ENVELOPE_CASES)
+def test_envelope_cases_are_covered_and_one_step_outside_is_not(kind, name):
+    """Predicate and make_shape agree on every envelope case: covered, with a workspace of the three activation buffers; the
+    same module one latent dimension above the maximum (129 | 65) is not covered, and the descriptor with that dimension, with
+    0, or with the other image size answers 0."""
+    from vqvae_amd import _lib
+    from vqvae_amd.encode import native_encode_covers
+    from vqvae_amd.image_encoder import ImageEncoderExport, encoder_kernels_cover
+    lib = _lib.load()
+    channels, d, C, size, norm = E.ENVELOPE_CASES[(kind, name)]
+    enc = E.envelope_case(kind, name)[0]
+    assert encoder_kernels_cover(enc) and encoder_kernels_cover(enc, size) and native_encode_covers(enc, size)
+    assert not encoder_kernels_cover(enc, 60 - size)
+    if norm == "batch-plain":
+        norms = [m for m in enc.modules() if isinstance(m, nn.BatchNorm2d)]
+        assert len(norms) == 3 and all(m.weight is None and m.bias is None and not m.training for m in norms)
+    d_max = 128 if kind == "vanilla" else 64
+    assert not encoder_kernels_cover(E.build(kind, channels, d_max + 1, C, norm))
+    desc = ImageEncoderExport(enc, torch.device("cpu")).desc
+    per_item = 4 * ((size // 2) ** 2 * channels[0] + (size // 4) ** 2 * channels[1] + 16 * channels[2])
+    assert per_item % 256 == 0 and lib.geo_image_encode_workspace_bytes(desc, 1) == per_item
+    assert lib.geo_image_encode_workspace_bytes(desc, E.N_VANILLA) == E.N_VANILLA * per_item
+    for change in (dict(latent_dim=d_max + 1), dict(latent_dim=0), dict(in_size=60 - size), dict(in_channels=4 - C)):
+        bad = type(desc).from_buffer_copy(desc)
+        for k, v in change.items():
+            setattr(bad, k, v)
+        assert lib.geo_image_encode_workspace_bytes(bad, 8) == 0, change
 
 
 def test_workspace_query_answers_zero_outside_the_coverage():

@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import vanilla_jvp_cases as V
 from vanilla_jvp_cases import autograd_lengths, make_decoder, make_edges
 
 CPU = torch.device("cpu")
@@ -74,7 +75,7 @@ def test_predicate_truth_table():
 
 
 @pytest.mark.parametrize("channels", [(256, 128, 64), (128, 64, 32)])
-@pytest.mark.parametrize("size,C", [(28, 1), (32, 3)])
+@pytest.mark.parametrize("size,C", [(28, 1), (32, 3), (28, 3), (32, 1)])
 @pytest.mark.parametrize("norm", ["batch", "none"])
 def test_composed_front_equals_the_module_in_fp64(channels, size, C, norm):
     from vqvae_amd.vanilla_decoder import VanillaDecoderExport
@@ -139,6 +140,42 @@ def test_export_layouts_reproduce_the_jacobian(channels, d, C, size, norm):
     want = autograd_lengths(dec, zs, ze, torch.float64)
     got = _emulate(VanillaDecoderExport(dec, CPU), zs, ze)
     assert np.all(want > 0) and float(np.max(np.abs(got - want) / want)) < 1e-5
+
+
+@pytest.mark.parametrize("name", list(V.ENVELOPE_CASES))
+def test_envelope_cases_export_and_coverage(name):
+    """vanilla_jvp_cases.ENVELOPE_CASES on the host: the predicate covers each and not the same module at d = 129; the composed
+    front against the module in fp64 (d = 1, 2, odd d with the zero row that makes dp even, a dec_channels[0] other than
+    256 / 128, BatchNorm2d(affine=False)); the export's layouts against fp64 autograd as in
+    test_export_layouts_reproduce_the_jacobian; both workspace queries non-zero, and zero one step outside make_shape."""
+    from vqvae_amd import _lib
+    from vqvae_amd.vanilla_decoder import VanillaDecoderExport, vanilla_kernels_cover
+    channels, d, C, size, norm = V.ENVELOPE_CASES[name]
+    dec = V.build(channels, d, C, size, norm, seed=len(name))
+    assert vanilla_kernels_cover(dec) and not vanilla_kernels_cover(V.build(channels, 129, C, size, norm))
+    if norm == "batch-plain":
+        norms = [m for m in dec.modules() if isinstance(m, nn.BatchNorm2d)]
+        assert len(norms) == 2 and all(m.weight is None and m.bias is None and not m.training for m in norms)
+    ex = VanillaDecoderExport(dec, CPU)
+    s1, c1 = size // 4, channels[1]
+    assert (ex.desc.latent_dim, ex.desc.c1, ex.desc.c2, ex.desc.out_channels, ex.desc.out_size) == (d, c1, channels[2], C, size)
+    assert ex.A.shape == (s1 * s1 * c1, d) and ex.tensors["At"].shape[0] == d + (d & 1) and not ex.tensors["At"][d:].any()
+    z = torch.randn(9, d, generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+    dd = copy.deepcopy(dec).double()
+    with torch.no_grad():
+        want = dd.deconv1[1](dd.deconv1[0](dd.fc(z).view(9, -1, 4, 4))).permute(0, 2, 3, 1).reshape(9, -1)
+    got = z @ ex.A.double().t() + ex.c.double()
+    assert float((got - want).abs().max() / want.abs().max()) <= 1e-6
+    zs, ze = make_edges(d, n_edges=12, seed=4)
+    want_len = autograd_lengths(dec, zs, ze, torch.float64)
+    assert np.all(want_len > 0) and float(np.max(np.abs(_emulate(ex, zs, ze) - want_len) / want_len)) < 1e-5
+    lib = _lib.load()
+    pairs, edges = lib.geo_vanilla_jvp_workspace_bytes, lib.geo_vanilla_jvp_edges_workspace_bytes
+    assert 0 < pairs(ex.desc, 1) < pairs(ex.desc, V.N_EDGES) and 0 < edges(ex.desc, 300, 1500) < pairs(ex.desc, 1500)
+    for field, value in (("latent_dim", 129), ("latent_dim", 0), ("out_size", 24 if size == 28 else 36), ("out_channels", 2), ("out_channels", 4)):
+        bad = _lib.VanillaDecoderDesc.from_buffer_copy(ex.desc)
+        setattr(bad, field, value)
+        assert pairs(bad, 100) == 0 and edges(bad, 50, 100) == 0, (field, value)
 
 
 def test_workspace_queries():
