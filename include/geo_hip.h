@@ -119,11 +119,13 @@ int geo_sssp_single_update(const int32_t *indptr, const int32_t *indices, const 
  * small cells; a centre whose cell outgrows the table is run by the step kernel inside the call.
  * assume_finite != 0 promises that d_min has no inf entry left (status_out[2] of an earlier call): the
  * per-iteration maximum pass is skipped.
- * status_out [host, 4 ints]: {abort_iter or -1, reason, inf entries of d_min at the last maximum pass,
- * most sweeps any solve of this call needed (step kernel: launches that did work)}:
+ * status_out [host, 4 ints]: {abort_iter or -1, reason, inf entries of d_min at the last maximum pass (0 in resident
+ * mode), a count that depends on the mode}:
  * reason 1 = solve not converged (nothing of that iteration is applied), 2 = u too close to a cdf boundary,
  * 3 = degenerate weights (for 2 and 3 the solve of that iteration IS applied, the draw is not).  The caller
- * repeats that step another way and resumes.  Resident mode: status_out[3] = centres handed to the step kernel.
+ * repeats that step another way and resumes.  Reason 4 (cell too large for the resident table) never leaves the call.
+ * status_out[3] is, with sweeps_per_solve >= 2 (budgeted): the most sweeps any solve of this call needed;
+ * 0 (step kernel): launches that did work; -1 (resident): centres handed to the step kernel.
  * One synchronisation at the end.
  * ------------------------------------------------------------------------------------------ */
 size_t geo_kpp_workspace_bytes(int32_t n);

@@ -367,6 +367,40 @@ def test_resident_chain_equals_step_kernel_and_oracle():
         km._KNOBS.update(saved)
 
 
+def test_chain_stays_budgeted_while_a_component_is_unreached(capfd):
+    """Two components (700 + 900 Gaussian latents in 8 dimensions, k = 6, union): until a centre sits in each, d_min keeps
+    inf entries and the chain keeps its budgeted mode -- sweeps enqueued per solve, the maximum pass and the
+    inf -> 2 * max_finite rule before every draw.  1 600 nodes are one ragged numpy buffer whose tree has several levels.
+    Seeds chosen with the oracle: seed 1 puts its first three centres into the second component (centre 3 is the first in
+    the other one), so two draws are made with inf entries present; seed 2 reaches both with centres 0 and 1."""
+    import re
+    from oracle import kmedoids as ok
+    from oracle import knn as okn
+    from vqvae_amd.geo import kmeans_optimized as km
+    parts = [okn.build_knn_graph(latents(n, 8, s), k=6, mode="distance", sym="union")[0] for n, s in ((700, 21), (900, 22))]
+    W = sparse.block_diag(parts, format="csr", dtype=np.float32)
+    for seed, first_other in ((1, 3), (2, 1)):
+        mo, ao, qo = ok.fit_kmedoids_optimized(W, K=24, init="kpp", seed=seed)
+        side = np.asarray(ok.kpp_initialization_graph(W, 24, seed=seed)) >= 700
+        assert first_other == int(np.argmax(side != side[0]))              # the seed does what the docstring says
+        capfd.readouterr()
+        km._KNOBS["log"] = True
+        try:
+            med, assign, qe = km.fit_kmedoids_optimized(W, K=24, init="kpp", seed=seed)
+        finally:
+            km._KNOBS["log"] = False
+        log = capfd.readouterr().err
+        np.testing.assert_array_equal(med, mo)
+        np.testing.assert_array_equal(assign, ao)
+        assert qe == qo
+        calls = [(int(m.group(1)), m.group(2)) for m in re.finditer(r"\[kpp-log\] it (\d+)\.\.\d+ mode (\S+) ", log)]
+        assert calls and calls[0][0] == 0, log
+        # iteration first_other folds the first centre of the other component in: every call that starts at or before it
+        # still sees inf entries
+        early = [mode for it0, mode in calls if it0 <= first_other]
+        assert early and all(mode.isdigit() for mode in early), log
+
+
 def _with_option(name, value, fn):
     from vqvae_amd import _lib
     lib = _lib.load()

@@ -1303,19 +1303,34 @@ int32_t pw_build(PwPlan &p, int32_t start, int32_t n, int *level) {
     return -(int32_t)p.node_l.size();                         // node ids: encoded -(k+1), fixed up below
 }
 
-struct DevPlan {
-    int n_leaves, n_nodes, n_levels, n_chunks;
-    int32_t *leaf_start, *leaf_len, *node_l, *node_r, *level_off, *chunk_root;
-    float *val;
-};
+// The inner nodes of a tree ordered by level (children always sit on a lower level; levels start at 1): pos[j] is node j's
+// rank in that order, level_off[lv] the rank at which level lv + 1 starts, level_off[max_level] the node count.
+void order_by_level(const PwPlan &p, int max_level, std::vector<int32_t> &pos, std::vector<int32_t> &level_off) {
+    const int M = (int)p.node_l.size();
+    pos.assign(M, 0);
+    level_off.assign(max_level + 2, 0);
+    for (int j = 0; j < M; ++j) level_off[p.node_level[j]]++;          // counts at [level]
+    int run = 0;
+    for (int lv = 1; lv <= max_level; ++lv) { const int c = level_off[lv]; level_off[lv - 1] = run; run += c; }
+    level_off[max_level] = run;
+    std::vector<int32_t> cursor(level_off);
+    for (int j = 0; j < M; ++j) pos[j] = cursor[p.node_level[j] - 1]++;
+}
+
+// What SumPlan and ResidentPlan share: the whole tree as laid out in the uploaded blob (build_plan).
+template <class Plan>
+void fill_tree(Plan &p, const int32_t *blob, int n_leaves, int n_nodes, int n_levels, int n_chunks) {
+    p.leaf_start = blob; p.leaf_len = p.leaf_start + n_leaves; p.node_l = p.leaf_len + n_leaves;
+    p.node_r = p.node_l + n_nodes; p.level_off = p.node_r + n_nodes; p.chunk_root = p.level_off + n_levels + 1;
+    p.n_leaves = n_leaves; p.n_nodes = n_nodes; p.n_levels = n_levels; p.n_chunks = n_chunks;
+}
 
 struct KppWs {
     KppCtl *ctl;
     double *d, *cdf, *tile_sum, *tile_off, *u_dev;
     KppState *state;
     int32_t *mark, *front[2], *part_inf;
-    float *probs, *part_max;
-    DevPlan plan;
+    float *probs, *part_max, *plan_val;
     int32_t *plan_blob;
     size_t plan_ints;
     uint16_t *tail_leaf;                   // resident chain: leaf of the nodes of the last (partial) numpy chunk
@@ -1345,10 +1360,238 @@ bool carve(void *ws, size_t ws_bytes, int32_t n, KppWs *o) {
     o->part_inf = ar.take<int32_t>(FINISH_GRID);
     o->plan_ints = plan_ints_bound(n);
     o->plan_blob = ar.take<int32_t>(o->plan_ints);
-    o->plan.val = ar.take<float>(o->plan_ints);
+    o->plan_val = ar.take<float>(o->plan_ints);
     o->tail_leaf = ar.take<uint16_t>(NP_BUFSIZE);
     o->progress = ar.take<int32_t>(4);
     return o->progress != nullptr;
+}
+
+enum class ChainMode { Budgeted, Step, Resident };
+
+// What one geo_kpp_chain call shares between its plan and its mode: the caller's arrays, the carved workspace, the
+// device-side plans and the launch constants.
+struct ChainCtx {
+    hipStream_t s;
+    const int32_t *indptr, *indices;       // the graph
+    const float *weights;
+    int32_t n, n_centers_total, *centers, *argmin;
+    uint8_t *is_center;
+    float *dmin;
+    const double *u_host;
+    KppWs w;
+    SumPlan spl;
+    ResidentPlan rp;                       // filled in resident mode only
+    double tol;
+    int n_tiles, g_push_big, g_push_small;
+    int32_t stamp_next;                    // solve counter of the step kernel, carried across run_steps calls
+    std::vector<int32_t> blob;             // host side of the plan uploads: lives until the call's last synchronisation
+    std::vector<uint16_t> tail;
+};
+
+// kernel<true> on a weighted graph, kernel<false> otherwise, on the context's stream
+#define KPP_LAUNCH_WEIGHTED(c, kernel, grid, block, smem, ...)                         \
+    do {                                                                               \
+        if ((c).weights) kernel<true><<<grid, block, smem, (c).s>>>(__VA_ARGS__);      \
+        else kernel<false><<<grid, block, smem, (c).s>>>(__VA_ARGS__);                 \
+    } while (0)
+
+// numpy's reduction tree for an array of n float32 (chunks of NP_BUFSIZE, pairwise inside), uploaded, and the kernels'
+// views of it: c.spl always, c.rp and the tail's leaf table in resident mode.
+int build_plan(ChainCtx &c, ChainMode mode) {
+    const int32_t n = c.n;
+    KppWs &w = c.w;
+    PwPlan pp;
+    std::vector<int32_t> roots_raw;
+    for (int32_t c0 = 0; c0 < n; c0 += NP_BUFSIZE) {
+        int lv;
+        roots_raw.push_back(pw_build(pp, c0, (n - c0 < NP_BUFSIZE) ? n - c0 : NP_BUFSIZE, &lv));
+    }
+    const int L = (int)pp.leaf_start.size(), M = (int)pp.node_l.size(), C = (int)roots_raw.size();
+    int max_level = 0;
+    for (int lv : pp.node_level) max_level = lv > max_level ? lv : max_level;
+    std::vector<int32_t> pos, level_off;
+    order_by_level(pp, max_level, pos, level_off);
+    auto fix = [&](int32_t id) { return id >= 0 ? id : L + pos[-id - 1]; };     // raw ids -> val[] positions
+    std::vector<int32_t> &blob = c.blob;
+    blob = pp.leaf_start;
+    blob.insert(blob.end(), pp.leaf_len.begin(), pp.leaf_len.end());
+    blob.resize(2 * (size_t)(L + M));
+    for (int j = 0; j < M; ++j) { blob[2 * L + pos[j]] = fix(pp.node_l[j]); blob[2 * L + M + pos[j]] = fix(pp.node_r[j]); }
+    blob.insert(blob.end(), level_off.begin(), level_off.begin() + max_level + 1);
+    for (int32_t r : roots_raw) blob.push_back(fix(r));
+    // the tree of one buffer in local ids (kpp_sum_body, large n): a full buffer and the last one; then one ticket per buffer
+    const size_t cplan_at = blob.size();
+    for (int kind = 0; kind < 2; ++kind) {
+        const int32_t len = kind == 0 ? (n < NP_BUFSIZE ? n : NP_BUFSIZE) : n - (C - 1) * NP_BUFSIZE;
+        PwPlan lp;
+        int lv_root;
+        const int32_t root = pw_build(lp, 0, len, &lv_root);
+        const int cl = (int)lp.leaf_start.size(), cn = (int)lp.node_l.size();
+        GEO_REQUIRE(cl <= CPLAN_MAX_LEAVES && cn < CPLAN_MAX_LEAVES && lv_root <= 11, "geo_kpp_chain: buffer tree too large (%d leaves)", cl);
+        std::vector<int32_t> lpos, loff;
+        order_by_level(lp, lv_root, lpos, loff);
+        auto lfix = [&](int32_t id) { return id >= 0 ? id : cl + lpos[-id - 1]; };
+        std::vector<int32_t> cpv(CPLAN_INTS, 0);
+        cpv[0] = cl; cpv[1] = cn; cpv[2] = lv_root; cpv[3] = lfix(root);
+        for (int lv = 0; lv <= lv_root; ++lv) cpv[4 + lv] = loff[lv];
+        for (int j = 0; j < cn; ++j) { cpv[16 + lpos[j]] = lfix(lp.node_l[j]); cpv[16 + CPLAN_MAX_LEAVES + lpos[j]] = lfix(lp.node_r[j]); }
+        blob.insert(blob.end(), cpv.begin(), cpv.end());
+    }
+    const size_t ticket_at = blob.size();
+    blob.insert(blob.end(), (size_t)C, 0);
+    GEO_REQUIRE(blob.size() <= w.plan_ints && (size_t)(L + M + C) <= w.plan_ints, "geo_kpp_chain: reduction plan overflow");
+    GEO_HIP_CHECK(hipMemcpyAsync(w.plan_blob, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice, c.s));
+    fill_tree(c.spl, w.plan_blob, L, M, max_level, C);
+    c.spl.val = w.plan_val;
+    c.spl.cplan = w.plan_blob + cplan_at; c.spl.chunk_ticket = w.plan_blob + ticket_at; c.spl.chunk_val = w.plan_val + L + M;
+    if (mode != ChainMode::Resident) return GEO_OK;
+    GEO_REQUIRE(L <= PG_MAX_LEAVES && M <= PG_MAX_LEAVES && C <= 64 && max_level < 31,
+                "geo_kpp_chain: reduction tree of n=%d too large for the resident chain", n);
+    ResidentPlan &rp = c.rp;
+    fill_tree(rp, w.plan_blob, L, M, max_level, C);
+    rp.tail_leaf = w.tail_leaf;
+    rp.tail_start = (n / NP_BUFSIZE) * NP_BUFSIZE;
+    rp.tail_first_leaf = (n / NP_BUFSIZE) * (NP_BUFSIZE / PW_BLOCK);
+    c.tail.assign(NP_BUFSIZE, 0);
+    for (int l = rp.tail_first_leaf; l < L; ++l)
+        for (int32_t v = pp.leaf_start[l]; v < pp.leaf_start[l] + pp.leaf_len[l]; ++v) c.tail[v - rp.tail_start] = (uint16_t)l;
+    GEO_HIP_CHECK(hipMemcpyAsync(w.tail_leaf, c.tail.data(), NP_BUFSIZE * sizeof(uint16_t), hipMemcpyHostToDevice, c.s));
+    return GEO_OK;
+}
+
+// ---- budgeted mode: per iteration `sweeps` relaxation launches, the d_min update, the sum and the draw as kernels of their own ----
+int run_budgeted(ChainCtx &c, int32_t it0, int32_t it1, int32_t sweeps, int32_t assume_finite, int32_t *status_out) {
+    const KppWs &w = c.w;
+    hipStream_t s = c.s;
+    const int32_t n = c.n;
+    const int exact_max = assume_finite ? 0 : 1;     // with every d_min finite no maximum is needed for the draw
+    if (it0 < it1) kpp_begin_kernel<<<1, 64, 0, s>>>(w.ctl, c.centers, it0, w.d, w.front[0]);
+    GEO_LAUNCH_CHECK();
+    for (int32_t t = it0; t < it1; ++t) {
+        const int32_t stamp_solve = (t - it0) + 1;
+        int last_next = 0;
+        // frontier sweeps: the first solves cross the whole graph, later ones only the new centre's (pruned)
+        // cell, where a small grid keeps the launch itself cheap
+        const int g_push = t < 16 ? c.g_push_big : c.g_push_small;
+        for (int sw = 0; sw < sweeps; ++sw) {
+            const int cur = sw % 3, next = (sw + 1) % 3, clear = (sw + 2) % 3;
+            KPP_LAUNCH_WEIGHTED(c, kpp_push_kernel, g_push, 256, 0, w.ctl, c.indptr, c.indices, c.weights, w.d, c.dmin, w.mark,
+                                w.front[sw & 1], w.front[(sw + 1) & 1], cur, next, clear, stamp_solve, sw);
+            last_next = next;
+        }
+        const bool draw = t + 1 < c.n_centers_total;
+        const int fuse = (!exact_max && draw) ? 1 : 0;
+        if (!fuse)
+            kpp_finish_kernel<<<geo::grid_for(n, 256, 256), 256, 0, s>>>(w.ctl, w.d, c.dmin, c.argmin, n, last_next, t);
+        if (draw) {
+            if (exact_max) kpp_max_kernel<<<FINISH_GRID, 256, 0, s>>>(w.ctl, c.dmin, n, w.part_max, w.part_inf);
+            kpp_sum_kernel<<<(c.spl.n_leaves + SUM_LEAVES - 1) / SUM_LEAVES, 256, 0, s>>>(
+                w.ctl, c.dmin, c.argmin, w.d, fuse, last_next, t, c.is_center, w.part_max, w.part_inf, FINISH_GRID, exact_max,
+                w.probs, c.spl);
+            kpp_draw_kernel<<<c.n_tiles, SCAN_T, (size_t)(c.n_tiles + 1) * sizeof(double), s>>>(
+                w.ctl, w.probs, n, w.cdf, w.tile_sum, c.n_tiles, c.u_host[t], c.tol, c.centers, c.is_center, t + 1, t,
+                t + 1 < it1 ? 1 : 0, w.d, w.front[0]);
+        }
+        GEO_LAUNCH_CHECK();
+    }
+    KppCtl h1;
+    GEO_HIP_CHECK(hipMemcpyAsync(&h1, w.ctl, sizeof(KppCtl), hipMemcpyDeviceToHost, s));
+    GEO_HIP_CHECK(hipStreamSynchronize(s));
+    status_out[0] = h1.abort_iter;
+    status_out[1] = h1.abort_reason;
+    status_out[2] = h1.n_inf;                 // unreachable entries of d_min at the last maximum pass
+    status_out[3] = h1.max_sw;                // budgeted mode: sweeps the longest solve of this call used
+    return GEO_OK;
+}
+
+// ---- step-kernel mode for iterations [ia, ib): one kernel, launched until the chain reports DONE ----
+int run_steps(ChainCtx &c, int32_t ia, int32_t ib, KppState *hs_out, KppCtl *hc_out) {
+    const KppWs &w = c.w;
+    hipStream_t s = c.s;
+    kpp_begin_kernel<<<1, 64, 0, s>>>(w.ctl, c.centers, ia, w.d, w.front[0]);
+    KppState st0;
+    st0.mode = 0; st0.t = ia; st0.sw = 0; st0.stamp = c.stamp_next; st0.launches = 0; st0.pad = 0;
+    GEO_HIP_CHECK(hipMemcpyAsync(w.state, &st0, sizeof(KppState), hipMemcpyHostToDevice, s));
+    const int nsum = (c.spl.n_leaves + SUM_LEAVES - 1) / SUM_LEAVES;
+    int g_small = 256;
+    if (nsum > g_small) g_small = nsum;
+    if (c.n_tiles > g_small) g_small = c.n_tiles;
+    const size_t smem = (size_t)(c.n_tiles + 1) * sizeof(double);
+    int64_t launched = 0;
+    int32_t batch = ib - ia == 1 ? 12 : 64, t_now = ia;
+    KppState hs = st0;
+    KppCtl hc;
+    for (;;) {
+        const int grid = t_now < 16 && c.g_push_big > g_small ? c.g_push_big : g_small;
+        for (int32_t i = 0; i < batch; ++i, ++launched) {
+            const int parity = (int)(launched % 6);
+            KPP_LAUNCH_WEIGHTED(c, kpp_step_kernel, grid, 256, smem, w.ctl, w.state, parity, c.indptr, c.indices, c.weights, c.n,
+                                w.d, c.dmin, c.argmin, w.mark, w.front[0], w.front[1], c.centers, c.is_center, w.probs, w.cdf,
+                                w.tile_sum, c.n_tiles, w.u_dev, c.tol, c.spl, ib, c.n_centers_total);
+        }
+        GEO_LAUNCH_CHECK();
+        GEO_HIP_CHECK(hipMemcpyAsync(&hs, w.state + (launched & 1), sizeof(KppState), hipMemcpyDeviceToHost, s));
+        GEO_HIP_CHECK(hipMemcpyAsync(&hc, w.ctl, sizeof(KppCtl), hipMemcpyDeviceToHost, s));
+        GEO_HIP_CHECK(hipStreamSynchronize(s));
+        if (hs.mode == 2 || hc.abort_iter >= 0) break;
+        // launches still needed ~ centres left x launches per centre so far (+10 %), at most 512 per round trip
+        const int32_t done_centres = hs.t - ia > 0 ? hs.t - ia : 1;
+        const double per_centre = (double)hs.launches / done_centres;
+        const double est = (double)(ib - hs.t) * per_centre * 1.1 + 8.0;
+        batch = est > 512.0 ? 512 : (int32_t)est;      // (launches enqueued behind a declined draw run empty: ~13 us each)
+        t_now = hs.t;
+        GEO_REQUIRE(launched < ((int64_t)1 << 31), "geo_kpp_chain: step kernel did not finish");
+    }
+    c.stamp_next = hs.stamp + 1;
+    *hs_out = hs;
+    *hc_out = hc;
+    return GEO_OK;
+}
+
+// ---- resident mode: ONE workgroup runs the iterations in a single launch; a centre whose cell outgrows the
+//      workgroup's table (abort reason 4, nothing applied) is run by the step kernel right here, then the
+//      resident kernel takes over again ----
+int run_resident(ChainCtx &c, int32_t it0, int32_t it1, int32_t *status_out) {
+    const KppWs &w = c.w;
+    hipStream_t s = c.s;
+    const bool profile = geo::options().kpp_profile != 0;                 // diagnostic runs only
+    unsigned long long *prof = profile ? reinterpret_cast<unsigned long long *>(w.cdf) : nullptr;   // cdf[] is free meanwhile
+    int32_t cur_it = it0, handed_back = 0;
+    KppCtl hc;
+    for (;;) {
+        int32_t prog0 = cur_it;
+        GEO_HIP_CHECK(hipMemcpyAsync(w.progress, &prog0, sizeof(int32_t), hipMemcpyHostToDevice, s));
+        KPP_LAUNCH_WEIGHTED(c, kpp_resident_kernel, 1, PG_THREADS, 0, w.ctl, c.indptr, c.indices, c.weights, c.n, c.dmin, c.argmin,
+                            c.centers, c.is_center, w.u_dev, c.tol, c.rp, cur_it, it1, c.n_centers_total, w.progress, prof);
+        GEO_LAUNCH_CHECK();
+        if (profile) {
+            unsigned long long hp[14];
+            GEO_HIP_CHECK(hipMemcpyAsync(hp, prof, sizeof(hp), hipMemcpyDeviceToHost, s));
+            GEO_HIP_CHECK(hipStreamSynchronize(s));
+            fprintf(stderr, "[kpp-resident] it %d..%d cycles: solve-rest %llu (init %llu marks %llu fill %llu pass-rest %llu loads %llu relax %llu) apply %llu leaf %llu locate %llu exact-draws %llu (%llu taken) | sweeps %llu frontier nodes %llu\n",
+                    cur_it, it1, hp[0], hp[8], hp[9], hp[10], hp[11], hp[12], hp[13], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7]);
+        }
+        GEO_HIP_CHECK(hipMemcpyAsync(&hc, w.ctl, sizeof(KppCtl), hipMemcpyDeviceToHost, s));
+        GEO_HIP_CHECK(hipStreamSynchronize(s));
+        if (hc.abort_iter < 0 || hc.abort_reason != 4) break;
+        const int32_t t = hc.abort_iter;
+        ++handed_back;
+        KppCtl hr = hc;                                  // the margin (maxf) of the call stays
+        hr.abort_iter = -1; hr.abort_reason = 0;
+        memset(hr.fcount, 0, sizeof(hr.fcount));
+        memset(hr.ticket, 0, sizeof(hr.ticket));
+        GEO_HIP_CHECK(hipMemcpyAsync(w.ctl, &hr, sizeof(KppCtl), hipMemcpyHostToDevice, s));
+        KppState hs;
+        if (int rc = run_steps(c, t, t + 1, &hs, &hc)) return rc;
+        if (hc.abort_iter >= 0) break;                 // the step kernel declined too (reasons 1-3): the caller's turn
+        cur_it = t + 1;
+        if (cur_it >= it1) break;
+    }
+    status_out[0] = hc.abort_iter;
+    status_out[1] = hc.abort_reason;             // never 4: that one is handled above
+    status_out[2] = 0;                           // resident mode is only entered with d_min finite everywhere
+    status_out[3] = handed_back;                 // resident mode: centres run by the step kernel
+    return GEO_OK;
 }
 
 }  // namespace
@@ -1368,271 +1611,56 @@ extern "C" int geo_kpp_chain(const int32_t *indptr, const int32_t *indices, cons
                              int32_t it0, int32_t it1, int32_t n_centers_total, int32_t sweeps_per_solve,
                              int32_t assume_finite, void *ws, size_t ws_bytes, int32_t *status_out,
                              void *stream_) {
-    hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(indptr && indices && centers && is_center && dmin && argmin && ws && status_out,
                 "geo_kpp_chain: null pointer");
     GEO_REQUIRE((size_t)((n + SCAN_TILE - 1) / SCAN_TILE + 1) * 8 <= 64 * 1024, "geo_kpp_chain: n too large for the pick kernel");
     GEO_REQUIRE(n > 0 && 0 <= it0 && it0 <= it1 && it1 <= n_centers_total, "geo_kpp_chain: bad iteration range");
-    GEO_REQUIRE(((sweeps_per_solve >= 2 && sweeps_per_solve < 4096) ||
-                 ((sweeps_per_solve == 0 || sweeps_per_solve == -1) && assume_finite && n_centers_total <= n)) &&
-                    it1 - it0 < 250000,
-                "geo_kpp_chain: sweeps_per_solve out of range (0 = step kernel, -1 = resident workgroup: both need "
-                "assume_finite and K <= n)");
-    GEO_REQUIRE(sweeps_per_solve != -1 || n <= PG_MAX_NODES, "geo_kpp_chain: n=%d exceeds the resident chain's %d nodes", n,
-                PG_MAX_NODES);
+    GEO_REQUIRE(it1 - it0 < 250000, "geo_kpp_chain: more than 249999 iterations in one call");
+    GEO_REQUIRE(sweeps_per_solve == -1 || sweeps_per_solve == 0 || (sweeps_per_solve >= 2 && sweeps_per_solve < 4096),
+                "geo_kpp_chain: sweeps_per_solve out of range (2..4095 = sweeps per solve, 0 = step kernel, -1 = resident workgroup)");
+    ChainMode mode = sweeps_per_solve == -1 ? ChainMode::Resident : sweeps_per_solve == 0 ? ChainMode::Step : ChainMode::Budgeted;
+    if (mode != ChainMode::Budgeted)
+        GEO_REQUIRE(assume_finite && n_centers_total <= n, "geo_kpp_chain: the step kernel and the resident workgroup need assume_finite and K <= n");
+    if (mode == ChainMode::Resident)
+        GEO_REQUIRE(n <= PG_MAX_NODES, "geo_kpp_chain: n=%d exceeds the resident chain's %d nodes", n, PG_MAX_NODES);
     GEO_REQUIRE(it1 - it0 <= 1 || u_host, "geo_kpp_chain: uniform deviates missing");
-    KppWs w;
-    if (!carve(ws, ws_bytes, n, &w)) {
+    if (it0 == it1) mode = ChainMode::Budgeted;      // nothing to run: only the state of d_min is reported, as that mode does
+    ChainCtx c{};
+    c.s = static_cast<hipStream_t>(stream_);
+    c.indptr = indptr; c.indices = indices; c.weights = weights; c.n = n; c.n_centers_total = n_centers_total;
+    c.centers = centers; c.argmin = argmin; c.is_center = is_center; c.dmin = dmin; c.u_host = u_host;
+    if (!carve(ws, ws_bytes, n, &c.w)) {
         geo::set_error("geo_kpp_chain: workspace %zu too small", ws_bytes);
         return GEO_E_WORKSPACE;
     }
-    // numpy's reduction tree for an array of n float32: chunks of NP_BUFSIZE, pairwise inside
-    PwPlan pp;
-    std::vector<int32_t> roots_raw;
-    for (int32_t c0 = 0; c0 < n; c0 += NP_BUFSIZE) {
-        int lv;
-        roots_raw.push_back(pw_build(pp, c0, (n - c0 < NP_BUFSIZE) ? n - c0 : NP_BUFSIZE, &lv));
-    }
-    const int L = (int)pp.leaf_start.size(), M = (int)pp.node_l.size();
-    int max_level = 0;
-    for (int lv : pp.node_level) max_level = lv > max_level ? lv : max_level;
-    // order nodes by level (children always sit on a lower level); remap ids to val[] positions
-    std::vector<int32_t> order(M), newpos(M), level_off(max_level + 2, 0);
-    for (int j = 0; j < M; ++j) level_off[pp.node_level[j]]++;          // counts at [level], levels start at 1
-    {
-        int run = 0;
-        for (int lv = 1; lv <= max_level; ++lv) { const int c = level_off[lv]; level_off[lv - 1] = run; run += c; }
-        level_off[max_level] = run;
-    }
-    {
-        std::vector<int32_t> cursor(level_off.begin(), level_off.end());
-        for (int j = 0; j < M; ++j) { const int lv = pp.node_level[j] - 1; newpos[j] = cursor[lv]++; order[newpos[j]] = j; }
-    }
-    auto fix = [&](int32_t id) { return id >= 0 ? id : L + newpos[-id - 1]; };
-    std::vector<int32_t> blob;
-    blob.reserve(2 * L + 2 * M + max_level + 2 + roots_raw.size());
-    blob.insert(blob.end(), pp.leaf_start.begin(), pp.leaf_start.end());
-    blob.insert(blob.end(), pp.leaf_len.begin(), pp.leaf_len.end());
-    for (int k = 0; k < M; ++k) blob.push_back(fix(pp.node_l[order[k]]));
-    for (int k = 0; k < M; ++k) blob.push_back(fix(pp.node_r[order[k]]));
-    for (int lv = 0; lv <= max_level; ++lv) blob.push_back(level_off[lv]);
-    for (int32_t r : roots_raw) blob.push_back(fix(r));
-    // the tree of one buffer in local ids (kpp_sum_body, large n): a full buffer and the last one; then one ticket per buffer
-    const size_t cplan_at = blob.size();
-    for (int kind = 0; kind < 2; ++kind) {
-        const int32_t len = kind == 0 ? (n < NP_BUFSIZE ? n : NP_BUFSIZE) : n - ((int32_t)roots_raw.size() - 1) * NP_BUFSIZE;
-        PwPlan lp;
-        int lv_root;
-        const int32_t root = pw_build(lp, 0, len, &lv_root);
-        const int cl = (int)lp.leaf_start.size(), cn = (int)lp.node_l.size();
-        GEO_REQUIRE(cl <= CPLAN_MAX_LEAVES && cn < CPLAN_MAX_LEAVES && lv_root <= 11, "geo_kpp_chain: buffer tree too large (%d leaves)", cl);
-        std::vector<int32_t> loff(lv_root + 2, 0), lpos(cn);
-        for (int j = 0; j < cn; ++j) loff[lp.node_level[j]]++;
-        {
-            int run = 0;
-            for (int lv = 1; lv <= lv_root; ++lv) { const int c = loff[lv]; loff[lv - 1] = run; run += c; }
-            loff[lv_root] = run;
-            std::vector<int32_t> cursor(loff.begin(), loff.end());
-            for (int j = 0; j < cn; ++j) lpos[j] = cursor[lp.node_level[j] - 1]++;
-        }
-        auto lfix = [&](int32_t id) { return id >= 0 ? id : cl + lpos[-id - 1]; };
-        std::vector<int32_t> cpv(CPLAN_INTS, 0);
-        cpv[0] = cl; cpv[1] = cn; cpv[2] = lv_root; cpv[3] = lfix(root);
-        for (int lv = 0; lv <= lv_root; ++lv) cpv[4 + lv] = loff[lv];
-        for (int j = 0; j < cn; ++j) { cpv[16 + lpos[j]] = lfix(lp.node_l[j]); cpv[16 + CPLAN_MAX_LEAVES + lpos[j]] = lfix(lp.node_r[j]); }
-        blob.insert(blob.end(), cpv.begin(), cpv.end());
-    }
-    const size_t ticket_at = blob.size();
-    blob.insert(blob.end(), roots_raw.size(), 0);
-    GEO_REQUIRE(blob.size() <= w.plan_ints && (size_t)(L + M) + roots_raw.size() <= w.plan_ints, "geo_kpp_chain: reduction plan overflow");
-    GEO_HIP_CHECK(hipMemcpyAsync(w.plan_blob, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    DevPlan &dp = w.plan;
-    dp.n_leaves = L; dp.n_nodes = M; dp.n_levels = max_level; dp.n_chunks = (int)roots_raw.size();
-    dp.leaf_start = w.plan_blob; dp.leaf_len = dp.leaf_start + L; dp.node_l = dp.leaf_len + L;
-    dp.node_r = dp.node_l + M; dp.level_off = dp.node_r + M; dp.chunk_root = dp.level_off + max_level + 1;
+    const KppWs &w = c.w;
+    hipStream_t s = c.s;
+    if (int rc = build_plan(c, mode)) return rc;
 
     KppCtl h0;
     memset(&h0, 0, sizeof(h0));
     h0.abort_iter = -1; h0.maxf = -1.f;
     GEO_HIP_CHECK(hipMemcpyAsync(w.ctl, &h0, sizeof(KppCtl), hipMemcpyHostToDevice, s));
     GEO_HIP_CHECK(hipMemsetAsync(w.mark, 0, (size_t)n * 4, s));
-
-    const int g_lin = geo::grid_for(n, 256, 2048);
-    // frontier sweeps: the first solves cross the whole graph, later ones only the new centre's (pruned)
-    // cell, where a small grid keeps the launch itself cheap
-    const int g_push_big = geo::grid_for(n, 32, 2048), g_push_small = geo::grid_for(n, 32, geo::options().kpp_grid);
-    const int n_tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    const double tol = ((double)n + 16.0) * 4.440892098500626e-16;            // (n+16) * 2^-51
-    const int exact_max = assume_finite ? 0 : 1;     // with every d_min finite no maximum is needed for the draw
-    kpp_fill_inf_kernel<<<g_lin, 256, 0, s>>>(w.d, n);
+    c.g_push_big = geo::grid_for(n, 32, 2048);
+    c.g_push_small = geo::grid_for(n, 32, geo::options().kpp_grid);
+    c.n_tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+    c.tol = ((double)n + 16.0) * 4.440892098500626e-16;            // (n+16) * 2^-51
+    c.stamp_next = 1;
+    kpp_fill_inf_kernel<<<geo::grid_for(n, 256, 2048), 256, 0, s>>>(w.d, n);
     kpp_max_kernel<<<FINISH_GRID, 256, 0, s>>>(w.ctl, dmin, n, w.part_max, w.part_inf);
     kpp_maxfin_kernel<<<1, 64, 0, s>>>(w.ctl, w.part_max, w.part_inf, FINISH_GRID);
-    if (it0 < it1 && sweeps_per_solve > 0) kpp_begin_kernel<<<1, 64, 0, s>>>(w.ctl, centers, it0, w.d, w.front[0]);
     GEO_LAUNCH_CHECK();
-    SumPlan spl;
-    spl.leaf_start = dp.leaf_start; spl.leaf_len = dp.leaf_len; spl.node_l = dp.node_l; spl.node_r = dp.node_r;
-    spl.level_off = dp.level_off; spl.chunk_root = dp.chunk_root;
-    spl.n_leaves = dp.n_leaves; spl.n_levels = dp.n_levels; spl.n_chunks = dp.n_chunks; spl.val = dp.val;
-    spl.n_nodes = M;
-    spl.cplan = w.plan_blob + cplan_at; spl.chunk_ticket = w.plan_blob + ticket_at; spl.chunk_val = dp.val + L + M;
-    const bool have_u = n_centers_total > 1 && u_host;
-    if (sweeps_per_solve <= 0 && have_u)
+    if (mode == ChainMode::Budgeted) return run_budgeted(c, it0, it1, sweeps_per_solve, assume_finite, status_out);
+    if (n_centers_total > 1 && u_host)               // the step and resident kernels read the deviates from the device
         GEO_HIP_CHECK(hipMemcpyAsync(w.u_dev, u_host, (size_t)(n_centers_total - 1) * sizeof(double), hipMemcpyHostToDevice, s));
-    // ---- step-kernel mode for iterations [ia, ib): one kernel, launched until the chain reports DONE ----
-    int32_t stamp_next = 1;
-    auto run_steps = [&](int32_t ia, int32_t ib, KppState *hs_out, KppCtl *hc_out) -> int {
-        kpp_begin_kernel<<<1, 64, 0, s>>>(w.ctl, centers, ia, w.d, w.front[0]);
-        KppState st0;
-        st0.mode = 0; st0.t = ia; st0.sw = 0; st0.stamp = stamp_next; st0.launches = 0; st0.pad = 0;
-        GEO_HIP_CHECK(hipMemcpyAsync(w.state, &st0, sizeof(KppState), hipMemcpyHostToDevice, s));
-        const int nsum = (dp.n_leaves + SUM_LEAVES - 1) / SUM_LEAVES;
-        int g_small = 256;
-        if (nsum > g_small) g_small = nsum;
-        if (n_tiles > g_small) g_small = n_tiles;
-        const size_t smem = (size_t)(n_tiles + 1) * sizeof(double);
-        int64_t launched = 0;
-        int32_t batch = ib - ia == 1 ? 12 : 64, t_now = ia;
-        KppState hs = st0;
-        KppCtl hc;
-        for (;;) {
-            const int grid = t_now < 16 && g_push_big > g_small ? g_push_big : g_small;
-            for (int32_t i = 0; i < batch; ++i, ++launched) {
-                const int parity = (int)(launched % 6);
-                if (weights)
-                    kpp_step_kernel<true><<<grid, 256, smem, s>>>(w.ctl, w.state, parity, indptr, indices, weights, n, w.d, dmin,
-                                                                  argmin, w.mark, w.front[0], w.front[1], centers, is_center,
-                                                                  w.probs, w.cdf, w.tile_sum, n_tiles, w.u_dev, tol, spl, ib,
-                                                                  n_centers_total);
-                else
-                    kpp_step_kernel<false><<<grid, 256, smem, s>>>(w.ctl, w.state, parity, indptr, indices, weights, n, w.d, dmin,
-                                                                   argmin, w.mark, w.front[0], w.front[1], centers, is_center,
-                                                                   w.probs, w.cdf, w.tile_sum, n_tiles, w.u_dev, tol, spl, ib,
-                                                                   n_centers_total);
-            }
-            GEO_LAUNCH_CHECK();
-            GEO_HIP_CHECK(hipMemcpyAsync(&hs, w.state + (launched & 1), sizeof(KppState), hipMemcpyDeviceToHost, s));
-            GEO_HIP_CHECK(hipMemcpyAsync(&hc, w.ctl, sizeof(KppCtl), hipMemcpyDeviceToHost, s));
-            GEO_HIP_CHECK(hipStreamSynchronize(s));
-            if (hs.mode == 2 || hc.abort_iter >= 0) break;
-            // launches still needed ~ centres left x launches per centre so far (+10 %), at most 512 per round trip
-            const int32_t done_centres = hs.t - ia > 0 ? hs.t - ia : 1;
-            const double per_centre = (double)hs.launches / done_centres;
-            const double est = (double)(ib - hs.t) * per_centre * 1.1 + 8.0;
-            batch = est > 512.0 ? 512 : (int32_t)est;      // (launches enqueued behind a declined draw run empty: ~13 us each)
-            t_now = hs.t;
-            GEO_REQUIRE(launched < ((int64_t)1 << 31), "geo_kpp_chain: step kernel did not finish");
-        }
-        stamp_next = hs.stamp + 1;
-        *hs_out = hs;
-        *hc_out = hc;
-        return GEO_OK;
-    };
-    if (sweeps_per_solve == -1 && it0 < it1) {
-        // ---- resident mode: ONE workgroup runs the iterations in a single launch; a centre whose cell outgrows the
-        //      workgroup's table (abort reason 4, nothing applied) is run by the step kernel right here, then the
-        //      resident kernel takes over again ----
-        GEO_REQUIRE(dp.n_leaves <= PG_MAX_LEAVES && M <= PG_MAX_LEAVES && dp.n_chunks <= 64 && dp.n_levels < 31,
-                    "geo_kpp_chain: reduction tree of n=%d too large for the resident chain", n);
-        ResidentPlan rp;
-        rp.leaf_start = dp.leaf_start; rp.leaf_len = dp.leaf_len; rp.node_l = dp.node_l; rp.node_r = dp.node_r;
-        rp.level_off = dp.level_off; rp.chunk_root = dp.chunk_root; rp.tail_leaf = w.tail_leaf;
-        rp.n_leaves = dp.n_leaves; rp.n_nodes = M; rp.n_levels = dp.n_levels; rp.n_chunks = dp.n_chunks;
-        rp.tail_start = (n / NP_BUFSIZE) * NP_BUFSIZE;
-        rp.tail_first_leaf = (n / NP_BUFSIZE) * (NP_BUFSIZE / PW_BLOCK);
-        std::vector<uint16_t> tail(NP_BUFSIZE, 0);
-        for (int l = rp.tail_first_leaf; l < L; ++l)
-            for (int32_t v = pp.leaf_start[l]; v < pp.leaf_start[l] + pp.leaf_len[l]; ++v) tail[v - rp.tail_start] = (uint16_t)l;
-        GEO_HIP_CHECK(hipMemcpyAsync(w.tail_leaf, tail.data(), NP_BUFSIZE * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        const bool profile = geo::options().kpp_profile != 0;                 // diagnostic runs only
-        unsigned long long *prof = profile ? reinterpret_cast<unsigned long long *>(w.cdf) : nullptr;   // cdf[] is free meanwhile
-        int32_t cur_it = it0, handed_back = 0;
-        KppCtl hc;
-        for (;;) {
-            int32_t prog0 = cur_it;
-            GEO_HIP_CHECK(hipMemcpyAsync(w.progress, &prog0, sizeof(int32_t), hipMemcpyHostToDevice, s));
-            if (weights)
-                kpp_resident_kernel<true><<<1, PG_THREADS, 0, s>>>(w.ctl, indptr, indices, weights, n, dmin, argmin, centers,
-                                                                 is_center, w.u_dev, tol, rp, cur_it, it1, n_centers_total, w.progress, prof);
-            else
-                kpp_resident_kernel<false><<<1, PG_THREADS, 0, s>>>(w.ctl, indptr, indices, weights, n, dmin, argmin, centers,
-                                                                  is_center, w.u_dev, tol, rp, cur_it, it1, n_centers_total, w.progress, prof);
-            GEO_LAUNCH_CHECK();
-            if (profile) {
-                unsigned long long hp[14];
-                GEO_HIP_CHECK(hipMemcpyAsync(hp, prof, sizeof(hp), hipMemcpyDeviceToHost, s));
-                GEO_HIP_CHECK(hipStreamSynchronize(s));
-                fprintf(stderr, "[kpp-resident] it %d..%d cycles: solve-rest %llu (init %llu marks %llu fill %llu pass-rest %llu loads %llu relax %llu) apply %llu leaf %llu locate %llu exact-draws %llu (%llu taken) | sweeps %llu frontier nodes %llu\n",
-                        cur_it, it1, hp[0], hp[8], hp[9], hp[10], hp[11], hp[12], hp[13], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7]);
-            }
-            GEO_HIP_CHECK(hipMemcpyAsync(&hc, w.ctl, sizeof(KppCtl), hipMemcpyDeviceToHost, s));
-            GEO_HIP_CHECK(hipStreamSynchronize(s));
-            if (hc.abort_iter < 0 || hc.abort_reason != 4) break;
-            const int32_t t = hc.abort_iter;
-            ++handed_back;
-            KppCtl hr = hc;                                  // the margin (maxf) of the call stays
-            hr.abort_iter = -1; hr.abort_reason = 0;
-            memset(hr.fcount, 0, sizeof(hr.fcount));
-            memset(hr.ticket, 0, sizeof(hr.ticket));
-            GEO_HIP_CHECK(hipMemcpyAsync(w.ctl, &hr, sizeof(KppCtl), hipMemcpyHostToDevice, s));
-            KppState hs;
-            if (int rc = run_steps(t, t + 1, &hs, &hc)) return rc;
-            if (hc.abort_iter >= 0) break;                 // the step kernel declined too (reasons 1-3): the caller's turn
-            cur_it = t + 1;
-            if (cur_it >= it1) break;
-        }
-        status_out[0] = hc.abort_iter;
-        status_out[1] = hc.abort_reason;
-        status_out[2] = 0;                           // resident mode is only entered with d_min finite everywhere
-        status_out[3] = handed_back;                 // centres run by the step kernel
-        return GEO_OK;
-    }
-    if (sweeps_per_solve == 0 && it0 < it1) {
-        KppState hs;
-        KppCtl hc;
-        if (int rc = run_steps(it0, it1, &hs, &hc)) return rc;
-        status_out[0] = hc.abort_iter;
-        status_out[1] = hc.abort_reason;
-        status_out[2] = hc.n_inf;
-        status_out[3] = (int32_t)(hs.launches);
-        return GEO_OK;
-    }
-    for (int32_t t = it0; t < it1; ++t) {
-        const int32_t stamp_solve = (t - it0) + 1;
-        int last_next = 0;
-        const int g_push = t < 16 ? g_push_big : g_push_small;
-        for (int sw = 0; sw < sweeps_per_solve; ++sw) {
-            const int cur = sw % 3, next = (sw + 1) % 3, clear = (sw + 2) % 3;
-            if (weights)
-                kpp_push_kernel<true><<<g_push, 256, 0, s>>>(w.ctl, indptr, indices, weights, w.d, dmin, w.mark,
-                                                             w.front[sw & 1], w.front[(sw + 1) & 1], cur, next, clear,
-                                                             stamp_solve, sw);
-            else
-                kpp_push_kernel<false><<<g_push, 256, 0, s>>>(w.ctl, indptr, indices, weights, w.d, dmin, w.mark,
-                                                              w.front[sw & 1], w.front[(sw + 1) & 1], cur, next, clear,
-                                                              stamp_solve, sw);
-            last_next = next;
-        }
-        const bool draw = t + 1 < n_centers_total;
-        const int fuse = (!exact_max && draw) ? 1 : 0;
-        if (!fuse)
-            kpp_finish_kernel<<<geo::grid_for(n, 256, 256), 256, 0, s>>>(w.ctl, w.d, dmin, argmin, n, last_next, t);
-        if (draw) {
-            if (exact_max) kpp_max_kernel<<<FINISH_GRID, 256, 0, s>>>(w.ctl, dmin, n, w.part_max, w.part_inf);
-            kpp_sum_kernel<<<(dp.n_leaves + SUM_LEAVES - 1) / SUM_LEAVES, 256, 0, s>>>(
-                w.ctl, dmin, argmin, w.d, fuse, last_next, t, is_center, w.part_max, w.part_inf, FINISH_GRID, exact_max,
-                w.probs, spl);
-            kpp_draw_kernel<<<n_tiles, SCAN_T, (size_t)(n_tiles + 1) * sizeof(double), s>>>(
-                w.ctl, w.probs, n, w.cdf, w.tile_sum, n_tiles, u_host[t], tol, centers, is_center, t + 1, t,
-                t + 1 < it1 ? 1 : 0, w.d, w.front[0]);
-        }
-        GEO_LAUNCH_CHECK();
-    }
-    KppCtl h1;
-    GEO_HIP_CHECK(hipMemcpyAsync(&h1, w.ctl, sizeof(KppCtl), hipMemcpyDeviceToHost, s));
-    GEO_HIP_CHECK(hipStreamSynchronize(s));
-    status_out[0] = h1.abort_iter;
-    status_out[1] = h1.abort_reason;
-    status_out[2] = h1.n_inf;                 // unreachable entries of d_min at the last maximum pass
-    status_out[3] = h1.max_sw;                // sweeps the longest solve of this call used
+    if (mode == ChainMode::Resident) return run_resident(c, it0, it1, status_out);
+    KppState hs;
+    KppCtl hc;
+    if (int rc = run_steps(c, it0, it1, &hs, &hc)) return rc;
+    status_out[0] = hc.abort_iter;
+    status_out[1] = hc.abort_reason;
+    status_out[2] = hc.n_inf;
+    status_out[3] = (int32_t)(hs.launches);      // step mode: launches that did work
     return GEO_OK;
 }

@@ -150,87 +150,126 @@ def _kpp_chain_host(G: DeviceCSR, K: int, seed: int, absorb_last: bool, snaps: O
     return centers, chain
 
 
+class _SegmentPlan:
+    """Which mode runs the chain's next segment, and up to which iteration (no torch, no library handle).
+    While d_min still has unreachable (inf) entries the chain runs "budgeted": separate kernels per phase with a sweep
+    budget per solve.  A solve exits early once converged, but every enqueued launch costs ~2 us, and a solve that needs
+    more than were enqueued aborts and is redone.  The need is the hop radius of the new centre's (pruned) cell: the whole
+    graph for the first centre, then shrinking -- segments of doubling length, each taking its budget from what the
+    previous one needed.  Once d_min is finite everywhere (after the first centre on a connected graph) the rest of the
+    chain is "step": ONE kernel launched over and over that always does "the next step" (csrc/kpp.hip, kpp_step_kernel),
+    no budget, no launch spent on an empty frontier.  Later centres have small cells (~N/t nodes): from `resident_from` on
+    the chain is "resident", ONE workgroup (kpp_resident_kernel) and a single launch for all remaining centres; a cell that
+    outgrows its LDS table is run by the step kernel inside that same library call.
+    `stops` (fit_kmedoids_path): no segment runs across one of these iterations."""
+    CAP = 4094                                           # most sweeps per solve the device counts
+
+    def __init__(self, K: int, N: int, it1: int, resident_ok: bool, resident_from: int, stops=()):
+        self.K, self.N, self.it1, self.resident_ok, self.resident_from = K, N, it1, resident_ok, resident_from
+        self.stops, self.budget, self.seg = sorted(stops), 16, 1
+
+    def next(self, it: int, finite: bool) -> Tuple[str, int]:
+        """(mode, seg_end) of the segment that starts at iteration it < it1; `finite`: d_min has no inf entry left."""
+        if not (finite and self.K <= self.N):
+            mode, seg_end = "budgeted", min(self.it1, it + self.seg)
+        elif self.resident_ok and it >= min(self.resident_from, self.it1):
+            mode, seg_end = "resident", self.it1
+        else:
+            mode, seg_end = "step", (min(self.it1, self.resident_from) if self.resident_ok else self.it1)
+        return mode, min([seg_end] + [b for b in self.stops if b > it][:1])
+
+    def library_args(self, mode: str, finite: bool) -> Tuple[int, int]:
+        """(sweeps_per_solve, assume_finite) of geo_kpp_chain for `mode`."""
+        return {"budgeted": self.budget, "step": 0, "resident": -1}[mode], 1 if finite else 0
+
+    def clean_segment(self, used: int) -> None:
+        """A budgeted segment ran through, its longest solve took `used` sweeps.  Cells shrink: the next needs no more."""
+        self.seg, self.budget = min(2 * self.seg, 256), min(self.CAP, max(4, used + used // 8 + 1))
+
+    def more_sweeps(self) -> bool:
+        """A budgeted solve did not converge (reason 1): quadruple the budget.  False at the cap (the host solves)."""
+        below = self.budget < self.CAP
+        if below:
+            self.budget, self.seg = min(self.CAP, 4 * self.budget), 1
+        return below
+
+
+class _Deviates:
+    """One RandomState, advanced in lock-step with the committed draws: `first` is the first centre, u[t] the deviate the
+    reference's rng.choice(N, p=probs) consumes for centre t+1.  The deviates are pre-drawn from `base_state` (the stream
+    position before draw `base_t`); a uniform fallback (degenerate weights) consumes the stream differently, so it is
+    replayed from base_state and the remaining deviates are drawn afresh from the position it leaves behind."""
+
+    def __init__(self, seed: int, N: int, K: int):
+        self.rng, self.K = np.random.RandomState(seed), K
+        self.first = int(self.rng.randint(0, N))
+        self.base_state, self.base_t = self.rng.get_state(), 0
+        u = self.rng.random_sample(max(K - 1, 0)) if K > 1 else np.zeros(0)
+        self.u = np.ascontiguousarray(u, dtype=np.float64)   # redrawn in place: the library reads it by address
+
+    def __getitem__(self, t: int) -> float:
+        return float(self.u[t])
+
+    def uniform_fallback(self, t: int, rest: List[int]) -> int:
+        """The reference's draw for degenerate weights at t, rng.choice(rest) (kmeans_optimized.py:66)."""
+        self.rng.set_state(self.base_state)
+        if t > self.base_t:
+            self.rng.random_sample(t - self.base_t)      # the p-weighted draws committed since base_t
+        nxt = int(self.rng.choice(rest))
+        self.base_state, self.base_t = self.rng.get_state(), t + 1
+        if self.K - 2 - t > 0:
+            self.u[t + 1:] = self.rng.random_sample(self.K - 2 - t)
+        return nxt
+
+
 def _kpp_chain_device(G: DeviceCSR, K: int, seed: int, absorb_last: bool, snaps: Optional[dict] = None):
     """Device-resident chain (csrc/kpp.hip): the solves, the d_min update and numpy's draw all stay on the
     GPU; the host only supplies the uniform deviates of the same RandomState stream and steps in when the
     kernel declines a draw (u within rounding reach of a cdf boundary) or a solve needs more sweeps."""
     lib = _lib.load()
     N, dev = G.n, G.indptr.device
-    rng = np.random.RandomState(seed)
-    first = int(rng.randint(0, N))
-    # One RandomState, advanced in lock-step with the committed draws: u[t] is the deviate the reference's
-    # rng.choice(N, p=probs) consumes for centre t+1.  The deviates are pre-drawn from `base_state` (the stream position
-    # before draw `base_t`); a uniform fallback (degenerate weights) consumes the stream differently, so it is replayed
-    # from base_state and the remaining deviates are drawn afresh from the position it leaves behind.
-    base_state, base_t = rng.get_state(), 0
-    u = rng.random_sample(max(K - 1, 0)) if K > 1 else np.zeros(0)
-    u = np.ascontiguousarray(u, dtype=np.float64)
+    draws = _Deviates(seed, N, K)
     chain = _Chain(G)           # chain.ws and `ws` below alias the same cached workspace buffer: geo_kpp_chain
     #                             re-initialises all of its workspace state on every call, and chain.absorb (which
     #                             overwrites it) only runs between two geo_kpp_chain calls, never during one
     centers_d = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
-    centers_d[0] = first
+    centers_d[0] = draws.first
     is_center = torch.zeros(N, dtype=torch.uint8, device=dev)
-    is_center[first] = 1
+    is_center[draws.first] = 1
     ws = workspace(lib.geo_kpp_workspace_bytes(N), dev)
-    it, it1 = 0, (K if absorb_last else K - 1)
-    n_valid = K
-    # While d_min still has unreachable (inf) entries the chain runs as separate kernels per phase with a sweep
-    # budget per solve: a solve exits early once converged, but every enqueued launch costs ~2 us, and a solve that
-    # needs more than were enqueued aborts and is redone.  The need is the hop radius of the new centre's (pruned)
-    # cell: the whole graph for the first centre, then shrinking -- segments of doubling length, each taking its
-    # budget from what the previous one needed.  Once d_min is finite everywhere (after the first centre on a
-    # connected graph) the rest of the chain is ONE kernel launched over and over that always does "the next
-    # step" (csrc/kpp.hip, kpp_step_kernel): no budget, no launch spent on an empty frontier.
-    # Later centres have small cells (~N/t nodes): from RESIDENT_FROM on, the chain runs inside ONE resident
-    # workgroup (kpp_resident_kernel), a single launch for all remaining centres; a cell that outgrows its LDS table
-    # comes back with reason 4 and that one centre is run by the step kernel.
-    fixed = os.environ.get("GEO_KPP_SWEEPS")
-    budget, seg, cap = (int(fixed) if fixed else 16), 1, 4094
-    finite = False
+    it, it1, n_valid = 0, (K if absorb_last else K - 1), K
     resident_ok = _KNOBS["resident"] and N <= lib.geo_kpp_resident_max_nodes()
-    one_step_at = -1                                     # iteration the resident kernel handed back (reason 4)
-    status = np.zeros(4, dtype=np.int32)
-    stops = sorted(snaps) if snaps else []              # fit_kmedoids_path: no segment runs across one of these
+    plan = _SegmentPlan(K, N, it1, resident_ok, _resident_from(N), snaps or ())
+    finite, status = False, np.zeros(4, dtype=np.int32)
     while it < it1:
         _snapshot(chain, it, snaps)                      # here exactly centres 0 .. it-1 are folded into d_min
-        step_mode = finite and not fixed and K <= N
-        r_from = _resident_from(N)
-        resident = step_mode and resident_ok and it >= min(r_from, it1) and it != one_step_at
-        if resident:
-            seg_end = it1
-        elif step_mode:
-            seg_end = it + 1 if it == one_step_at else (min(it1, r_from) if resident_ok and it < r_from else it1)
-        else:
-            seg_end = min(it1, it + seg)
-        seg_end = min([seg_end] + [b for b in stops if b > it][:1])
+        mode, seg_end = plan.next(it, finite)
+        sweeps_per_solve, assume_finite = plan.library_args(mode, finite)
         t_call = time.perf_counter()
         with torch.cuda.device(dev):
             _lib.check(lib.geo_kpp_chain(ptr(G.indptr), ptr(G.indices), ptr(G.data), N, ptr(centers_d),
-                                         ptr(is_center), ptr(chain.dmin), ptr(chain.arg), u.ctypes.data, it, seg_end,
-                                         K, (-1 if resident else 0) if step_mode else budget, 1 if finite else 0, ptr(ws),
-                                         ws.numel(), status.ctypes.data, stream_ptr()),
+                                         ptr(is_center), ptr(chain.dmin), ptr(chain.arg), draws.u.ctypes.data, it, seg_end,
+                                         K, sweeps_per_solve, assume_finite, ptr(ws), ws.numel(), status.ctypes.data,
+                                         stream_ptr()),
                        "geo_kpp_chain")
+        # status[3]: budgeted = most sweeps of a solve, step = launches that did work, resident = centres handed back
         t, reason, used = int(status[0]), int(status[1]), int(status[3])
         if _KNOBS["log"]:
             import sys
-            print(f"[kpp-log] it {it}..{seg_end} mode {'resident' if resident else 'step' if step_mode else budget} -> "
+            print(f"[kpp-log] it {it}..{seg_end} mode {plan.budget if mode == 'budgeted' else mode} -> "
                   f"abort {t} reason {reason} used {used} {1e3 * (time.perf_counter() - t_call):.2f} ms", file=sys.stderr)
         finite = finite or int(status[2]) == 0          # inf entries only ever disappear from d_min
-        if reason == 4:                                  # cell too large for the resident table: that centre by step kernel
-            chain.solves += t - it
-            it, one_step_at = t, t
-            continue
-        if t < 0:
+        if reason == 4:
+            raise _lib.GeoHipError(f"geo_kpp_chain: abort reason 4 at iteration {t}, which the library handles itself")
+        if t < 0:                                        # clean segment
             chain.solves += seg_end - it
             it = seg_end
-            seg = min(2 * seg, 256)
-            if not fixed and not step_mode:
-                budget = min(cap, max(4, used + used // 8 + 1))     # cells shrink: the next segment needs no more
+            if mode == "budgeted":
+                plan.clean_segment(used)
             continue
-        if reason == 1 and not step_mode and budget < cap:   # nothing of solve t was applied: redo it with more sweeps
-            chain.solves += t - it
-            budget, seg, it = min(cap, 4 * budget), 1, t
+        if reason == 1 and mode == "budgeted" and plan.more_sweeps():
+            chain.solves += t - it                       # nothing of solve t was applied: redo it with more sweeps
+            it = t
             continue
         chain.solves += t - it + 1
         centers_h = centers_d[: t + 1].cpu().numpy().astype(int).tolist()
@@ -238,21 +277,15 @@ def _kpp_chain_device(G: DeviceCSR, K: int, seed: int, absorb_last: bool, snaps:
             chain.absorb(centers_h[t], t)
         if t + 1 >= K:
             break
-        nxt = _draw_with_u(N, chain.dmin.cpu().numpy(), centers_h, float(u[t]))
+        nxt = _draw_with_u(N, chain.dmin.cpu().numpy(), centers_h, draws[t])   # host draw: the device declined this one
         if nxt is None:                                  # degenerate weights: the reference's uniform fallback
-            rng.set_state(base_state)
-            if t > base_t:
-                rng.random_sample(t - base_t)            # the p-weighted draws committed since base_t
             taken = set(centers_h)
             rest = [i for i in range(N) if i not in taken]
             if not rest:
                 print(f"Warning: Could not find {K} valid centers, stopping at {len(centers_h)}")
                 n_valid = t + 1
                 break
-            nxt = int(rng.choice(rest))                  # kmeans_optimized.py:66
-            base_state, base_t = rng.get_state(), t + 1
-            if K - 2 - t > 0:
-                u[t + 1:] = rng.random_sample(K - 2 - t)
+            nxt = draws.uniform_fallback(t, rest)
         centers_d[t + 1] = nxt
         is_center[nxt] = 1
         it = t + 1
