@@ -483,6 +483,43 @@ size_t geo_image_encode_workspace_bytes(const geo_image_encoder_desc *enc, int64
 int geo_image_encode(const geo_image_encoder_desc *enc, const float *x /* [n][C][S][S] */, int64_t n, float *mu_out,
                      float *logvar_out, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LPIPS: LPIPS v0.1, AlexNet backbone, normalize = False, spatial = False, of n pairs of f32
+ * 3 x 64 x 64 images in [-1, 1] (what lpips.LPIPS(net='alex') returns for them; src/eval/evaluate_model.py:110-142):
+ *   scaled = (x - shift) / scale per channel, shift = (-.030, -.088, -.188), scale = (.458, .448, .450), zero-padded AFTER scaling;
+ *   Conv(3,64,k11,s4,p2) ReLU -> f1 (15 x 15); MaxPool(3,s2) Conv(64,192,k5,p2) ReLU -> f2 (7 x 7); MaxPool(3,s2)
+ *   Conv(192,384,k3,p1) ReLU -> f3 (3 x 3); Conv(384,256,k3,p1) ReLU -> f4; Conv(256,256,k3,p1) ReLU -> f5;
+ *   d_l = mean over pixels of sum_c lin_l[c] (u0 - u1)^2 with u = f / (sqrt(sum_c f^2) + 1e-10); value = d_1 + ... + d_5.
+ * The features are f32 [image][pixel][channel], each value one chain from 0 (layer 1: over c, ky, then the kx pairs (0, 1) ..
+ * (10, -); layers 2 .. 5: over tap KS ky + kx, then the input channels in blocks of 8, within a block in the order
+ * 0 4 1 5 2 6 3 7), the bias added last; the distance is fp64 from those features: channel sums folded by an xor butterfly
+ * of 64 partials, the pixel mean in pixel order, the layer sum in layer order.  total_out f64 [n]; layer_out f64 [n][5] or
+ * NULL.  The rules are those of the image encode above: passes of at most 4096 pairs shrunk to fit any workspace from
+ * geo_lpips_alex_workspace_bytes(1) upwards (the five feature buffers of both images of a pass, 254 976 bytes per pair; below
+ * it GEO_E_WORKSPACE); a null pointer or n >= 2^31 returns GEO_E_ARG before any launch; n == 0 returns GEO_OK without a
+ * launch.  No atomics: a pair's result does not depend on n, its position, which image is x0, the pass or workspace size,
+ * the stream or the run.  Asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct geo_lpips_alex_desc {
+    /* device pointers, f32 */
+    const float *w1p;          /* [33 = c 11 + ky][2 = h][64 = co][8]: element s < 6 = conv1.weight[co][c][ky][2 s + h], 0 where
+                                  2 s + h = 11 and for s = 6, 7 */
+    const float *b1;           /* [64] */
+    const float *w2p;          /* [25][64 / 4][192][4]: element (tap, q, co, r) = conv2.weight[co][4 q + r][ky][kx], tap = 5 ky + kx */
+    const float *b2;           /* [192] */
+    const float *w3p;          /* [9][192 / 4][384][4], as w2p with tap = 3 ky + kx */
+    const float *b3;           /* [384] */
+    const float *w4p;          /* [9][384 / 4][256][4] */
+    const float *b4;           /* [256] */
+    const float *w5p;          /* [9][256 / 4][256][4] */
+    const float *b5;           /* [256] */
+    const float *lin1, *lin2, *lin3, *lin4, *lin5;   /* [64] [192] [384] [256] [256] */
+} geo_lpips_alex_desc;
+
+size_t geo_lpips_alex_workspace_bytes(int64_t n);
+int geo_lpips_alex(const geo_lpips_alex_desc *net, const float *x0, const float *x1 /* [n][3][64][64] */, int64_t n,
+                   double *total_out /* [n] */, double *layer_out /* [n][5] or NULL */, void *ws, size_t ws_bytes, void *stream);
+
 /* Gather: data_out[e] = len[entry_edge[e]] for every stored entry (W_geo = U + U^T). */
 int geo_gather_edge_weights(const float *len, const int32_t *entry_edge, int64_t nnz, float *data_out, void *stream);
 

@@ -41,6 +41,12 @@ class ImageEncoderDesc(ctypes.Structure):
                 + [(n, c_p) for n in ("w1p", "scale1", "shift1", "w2p", "scale2", "shift2", "w3p", "scale3", "shift3", "whp", "bh")])
 
 
+class LPIPSAlexDesc(ctypes.Structure):
+    """geo_lpips_alex_desc of include/geo_hip.h."""
+    _fields_ = [(n, c_p) for n in ("w1p", "b1", "w2p", "b2", "w3p", "b3", "w4p", "b4", "w5p", "b5",
+                                   "lin1", "lin2", "lin3", "lin4", "lin5")]
+
+
 class PriorDesc(ctypes.Structure):
     """geo_prior_desc of include/geo_hip.h."""
     _fields_ = ([(n, i32) for n in ("num_tokens", "embed_dim", "n_layers", "n_head", "max_seq_len", "num_classes")]
@@ -99,6 +105,8 @@ _SIGNATURES = {
     "geo_spatial_decode": (ctypes.c_int, [ctypes.POINTER(SpatialImageDecoderDesc), c_p, c_p, c_p, i64, c_p, c_p, sz, c_p]),
     "geo_image_encode_workspace_bytes": (sz, [ctypes.POINTER(ImageEncoderDesc), i64]),
     "geo_image_encode": (ctypes.c_int, [ctypes.POINTER(ImageEncoderDesc), c_p, i64, c_p, c_p, c_p, sz, c_p]),
+    "geo_lpips_alex_workspace_bytes": (sz, [i64]),
+    "geo_lpips_alex": (ctypes.c_int, [ctypes.POINTER(LPIPSAlexDesc), c_p, c_p, i64, c_p, c_p, c_p, sz, c_p]),
     "geo_gather_edge_weights":(ctypes.c_int, [c_p, c_p, i64, c_p, c_p]),
     "geo_prior_sample_workspace_bytes": (sz, [ctypes.POINTER(PriorDesc), i32, i32]),
     "geo_prior_sample": (ctypes.c_int, [ctypes.POINTER(PriorDesc), c_p, i32, i32, c_p, c_p, ctypes.c_float, i32, c_p, c_p, i32,

@@ -9,8 +9,12 @@ it already has that size.  Real images are the first samples_per_class test imag
 the files torchvision leaves under --data_root (vqvae_amd.eval.data; nothing is downloaded).  PSNR and SSIM run on the GPU
 (vqvae_amd.eval.metrics).
 
-LPIPS is not computed: it needs AlexNet weights, which cannot be fetched here and are not shipped.  metrics.yaml has no LPIPS
-key.
+LPIPS (AlexNet, v0.1) is computed when its weights are given, by --lpips_weights PATH or the config key `lpips_weights` (the
+flag wins): the file `torch.save(lpips.LPIPS(net='alex').state_dict(), PATH)` writes on a machine that has the package
+(vqvae_amd.eval.lpips).  Both image sets go through the reference's preprocess_for_lpips (three channels,
+bilinear resize to 64, [-1, 1]) and the pairs through the HIP kernels; metrics.yaml gains the reference's "LPIPS" string and
+the printed line is the reference's.  Without weights nothing can be fetched here, so metrics.yaml has no LPIPS key and the
+output is what it was before.
 """
 import argparse
 from pathlib import Path
@@ -24,6 +28,7 @@ from PIL import Image
 
 from .._device import device
 from ..eval.data import load_test_split, to_tensor
+from ..eval.lpips import load_lpips_weights, lpips_mean, preprocess_for_lpips
 from ..eval.metrics import psnr, ssim_simple
 from .generate_samples import save_image
 
@@ -73,7 +78,7 @@ def normalize_each(images: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def main(config_path: str, data_root: str = "data") -> int:
+def main(config_path: str, data_root: str = "data", lpips_weights: Optional[str] = None) -> int:
     with open(config_path, "r") as f:
         config = yaml.safe_load(f)
     dev = device()
@@ -88,8 +93,14 @@ def main(config_path: str, data_root: str = "data") -> int:
     psnr_val = psnr(generated, real)
     ssim_val = ssim_simple(generated, real)
     results = {"PSNR": f"{psnr_val:.4f}", "SSIM": f"{ssim_val:.4f}"}
-    print(f"PSNR: {psnr_val:.4f}, SSIM: {ssim_val:.4f}")
-    print("LPIPS not computed: it needs AlexNet weights, which are not available here")
+    weights = lpips_weights if lpips_weights is not None else config.get("lpips_weights")
+    if weights is not None:
+        lpips_val = lpips_mean(load_lpips_weights(weights), preprocess_for_lpips(generated), preprocess_for_lpips(real))
+        results["LPIPS"] = f"{lpips_val:.4f}"
+        print(f"PSNR: {psnr_val:.4f}, SSIM: {ssim_val:.4f}, LPIPS: {lpips_val:.4f}")
+    else:
+        print(f"PSNR: {psnr_val:.4f}, SSIM: {ssim_val:.4f}")
+        print("LPIPS not computed: it needs AlexNet weights, which are not available here")
 
     out_dir = Path(config["out_dir"])
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -112,12 +123,14 @@ def main(config_path: str, data_root: str = "data") -> int:
 
 
 def make_parser() -> argparse.ArgumentParser:
-    parser = argparse.ArgumentParser(description="Compare generated samples with real ones (PSNR, SSIM)")
+    parser = argparse.ArgumentParser(description="Compare generated samples with real ones (PSNR, SSIM, LPIPS)")
     parser.add_argument("--config", type=str, required=True, help="Path to the evaluation config file.")
     parser.add_argument("--data_root", type=str, default="data", help="Where torchvision left the test split")
+    parser.add_argument("--lpips_weights", type=str, default=None,
+                        help="State dict of lpips.LPIPS(net='alex'); overrides the config key lpips_weights.  Without it no LPIPS")
     return parser
 
 
 if __name__ == "__main__":
     a = make_parser().parse_args()
-    raise SystemExit(main(a.config, a.data_root))
+    raise SystemExit(main(a.config, a.data_root, a.lpips_weights))
