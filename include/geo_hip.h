@@ -185,7 +185,7 @@ int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neighbors, int3
  * empty row range or an argument error):
  *   GEO_KNN_PATH_EXACT        the exact fp64 scan of every pair (n_neighbors <= 64);
  *   GEO_KNN_PATH_EXACT_WIDE   the exact scan with lists of two or four entries per lane (n_neighbors > 64);
- *   GEO_KNN_PATH_FILTER_BF16  thresholds from a strided corpus subset (exact), bf16 hi/lo matrix-core scan, fp64 refinement;
+ *   GEO_KNN_PATH_FILTER_BF16  thresholds from a strided corpus subset (a bound), bf16 hi/lo matrix-core scan, fp64 refinement;
  *   GEO_KNN_PATH_FILTER_F32   the same with the float32 matrix-core scan (option knn_filter = 2);
  *   GEO_KNN_PATH_TWO_LEVEL    the bf16 filter whose thresholds come from a filtered pass over that subset themselves
  *                             (n >= 200 000);
@@ -198,6 +198,15 @@ int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neighbors, int3
 #define GEO_KNN_PATH_TWO_LEVEL 5
 #define GEO_KNN_PATH_OVERFLOW 16
 int geo_knn_last_path(void);
+
+/* The filter's thresholds on their own, for tests: tau_out f64 [row1 - row0] = the bound the filter paths take from every
+ * stride-th corpus row (rows 0, stride, 2 stride, ...) for the query rows [row0,row1), before the eps margin.  Each lane of a
+ * query's wave keeps the two (n_neighbors <= 24) or three smallest keys among the subset rows p with p % 64 = lane; tau is
+ * the n_neighbors-th smallest of those 128 or 192 values: the key of a subset row, at least the n_neighbors-th smallest key
+ * over the subset, hence over the corpus.  Runs at any n; n_neighbors <= min(64, subset rows); a workspace of 2 geo_knn_workspace_bytes(n, d) suffices. */
+int geo_knn_thresholds(const float *z, int64_t n, int32_t d, int32_t n_neighbors, int32_t form,
+                       int64_t row0, int64_t row1, int32_t stride, double *tau_out,
+                       void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Symmetrisation.  Replaces csr_matrix(...) + W.maximum/minimum(W.T) + setdiag(0) +

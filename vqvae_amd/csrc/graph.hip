@@ -78,39 +78,21 @@ __device__ __forceinline__ bool sym_element(const int32_t *__restrict__ nbr, con
     return *val != 0.0f;
 }
 
+// pass A: the kept primaries of row r, counted and left unsorted at a provisional position that needs no scan -- row r has at
+// most k + in-degree(r) of them, so it starts at r k + off_in[r] (<= 2 n k in all).  Every element is evaluated once: the row
+// offsets are known only after this pass, and sym_sort_kernel reads from the provisional position.
 __global__ __launch_bounds__(256) void sym_count_kernel(const int32_t *__restrict__ nbr, const float *__restrict__ w,
                                                        int32_t n, int32_t k, int mode,
                                                        const int32_t *__restrict__ off_in,
                                                        const int32_t *__restrict__ in_src,
-                                                       const float *__restrict__ in_w, int32_t *__restrict__ row_cnt) {
+                                                       const float *__restrict__ in_w, int32_t *__restrict__ row_cnt,
+                                                       int32_t *__restrict__ tmp_col, float *__restrict__ tmp_val) {
     const int lane = threadIdx.x & 63;
     const int32_t r = blockIdx.x * WPB + (threadIdx.x >> 6);
     if (r >= n) return;
     const int32_t len = k + (off_in[r + 1] - off_in[r]);
+    const int64_t base = (int64_t)r * k + off_in[r];
     int32_t cnt = 0;
-    for (int32_t t = lane; t < len; t += 64) {
-        int32_t c;
-        float v;
-        cnt += sym_element(nbr, w, n, k, mode, off_in, in_src, in_w, r, t, &c, &v) ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if (lane == 0) row_cnt[r] = cnt;
-}
-
-// pass A: kept primaries of row r, unsorted, into tmp at the row's final offsets
-__global__ __launch_bounds__(256) void sym_scatter_kernel(const int32_t *__restrict__ nbr, const float *__restrict__ w,
-                                                         int32_t n, int32_t k, int mode,
-                                                         const int32_t *__restrict__ off_in,
-                                                         const int32_t *__restrict__ in_src,
-                                                         const float *__restrict__ in_w,
-                                                         const int32_t *__restrict__ indptr,
-                                                         int32_t *__restrict__ tmp_col, float *__restrict__ tmp_val) {
-    const int lane = threadIdx.x & 63;
-    const int32_t r = blockIdx.x * WPB + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const int32_t len = k + (off_in[r + 1] - off_in[r]);
-    int32_t base = indptr[r];
     for (int32_t t0 = 0; t0 < len; t0 += 64) {
         const int32_t t = t0 + lane;
         int32_t c = 0;
@@ -118,12 +100,13 @@ __global__ __launch_bounds__(256) void sym_scatter_kernel(const int32_t *__restr
         const bool keep = t < len && sym_element(nbr, w, n, k, mode, off_in, in_src, in_w, r, t, &c, &v);
         const unsigned long long m = __ballot(keep);
         if (keep) {
-            const int32_t p = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+            const int64_t p = base + cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull));
             tmp_col[p] = c;
             tmp_val[p] = v;
         }
-        base += __builtin_popcountll(m);
+        cnt += __builtin_popcountll(m);
     }
+    if (lane == 0) row_cnt[r] = cnt;
 }
 
 // pass B: rank sort of every row segment by column (columns inside a row are distinct)
@@ -135,8 +118,9 @@ __global__ __launch_bounds__(256) void seg_count_kernel(const int32_t *__restric
         seg_cnt[r] = (indptr[r + 1] - indptr[r] + 63) >> 6;
 }
 
-__global__ __launch_bounds__(256) void sym_sort_kernel(int32_t n, const int32_t *__restrict__ indptr,
+__global__ __launch_bounds__(256) void sym_sort_kernel(int32_t n, int32_t k, const int32_t *__restrict__ indptr,
                                                       const int32_t *__restrict__ seg_off,
+                                                      const int32_t *__restrict__ off_in,
                                                       const int32_t *__restrict__ tmp_col,
                                                       const float *__restrict__ tmp_val, int32_t *__restrict__ indices,
                                                       float *__restrict__ data) {
@@ -149,14 +133,16 @@ __global__ __launch_bounds__(256) void sym_sort_kernel(int32_t n, const int32_t 
         if (seg_off[mid] <= w) lo = mid; else hi = mid;
     }
     const int32_t r = lo;
-    const int32_t b = indptr[r], e = indptr[r + 1];
-    const int32_t i = b + ((w - seg_off[r]) << 6) + lane;
-    if (i < e) {
-        const int32_t c = tmp_col[i];
+    const int32_t b = indptr[r], len = indptr[r + 1] - b;
+    const int32_t *__restrict__ col = tmp_col + (int64_t)r * k + off_in[r];    // where sym_count_kernel left the row
+    const float *__restrict__ val = tmp_val + (int64_t)r * k + off_in[r];
+    const int32_t i = ((w - seg_off[r]) << 6) + lane;
+    if (i < len) {
+        const int32_t c = col[i];
         int32_t rank = 0;
-        for (int32_t j = b; j < e; ++j) rank += tmp_col[j] < c ? 1 : 0;
+        for (int32_t j = 0; j < len; ++j) rank += col[j] < c ? 1 : 0;
         indices[b + rank] = c;
-        data[b + rank] = tmp_val[i];
+        data[b + rank] = val[i];
     }
 }
 
@@ -390,7 +376,8 @@ extern "C" int geo_symmetrize_count(const int32_t *nbr_idx, const float *nbr_w, 
     if (rc) return rc;
     fill_in_kernel<<<geo::grid_for(total, 256), 256, 0, s>>>(nbr_idx, nbr_w, total, n, k, w.off_in, w.cursor, w.in_src, w.in_w);
     GEO_LAUNCH_CHECK();
-    sym_count_kernel<<<rows_grid(n), 256, 0, s>>>(nbr_idx, nbr_w, n, k, mode, w.off_in, w.in_src, w.in_w, w.row_cnt);
+    sym_count_kernel<<<rows_grid(n), 256, 0, s>>>(nbr_idx, nbr_w, n, k, mode, w.off_in, w.in_src, w.in_w, w.row_cnt,
+                                                  w.tmp_col, w.tmp_val);
     GEO_LAUNCH_CHECK();
     return geo::exclusive_scan_i32(w.row_cnt, indptr_out, n, w.scan_tmp, w.scan_bytes, nnz_out, s);
 }
@@ -405,16 +392,14 @@ extern "C" int geo_symmetrize_fill(const int32_t *nbr_idx, const float *nbr_w, i
     GEO_REQUIRE_WORKSPACE("geo_symmetrize_fill", ws_bytes, geo_symmetrize_workspace_bytes(n, k));
     SymWs w;
     carve_sym(ws, ws_bytes, n, k, &w);
-    sym_scatter_kernel<<<rows_grid(n), 256, 0, s>>>(nbr_idx, nbr_w, n, k, mode, w.off_in, w.in_src, w.in_w, indptr,
-                                                    w.tmp_col, w.tmp_val);
-    GEO_LAUNCH_CHECK();
-    // (cnt_in / off_in are free again after the scatter: segment counts and their offsets)
+    // The workspace still holds what geo_symmetrize_count left: off_in and the rows' kept primaries at r k + off_in[r]
+    // (tmp_col / tmp_val).  cnt_in and cursor are free: segment counts and their offsets.
     seg_count_kernel<<<geo::grid_for(n, 256, 1024), 256, 0, s>>>(indptr, n, w.cnt_in);
     GEO_LAUNCH_CHECK();
-    if (int rc = geo::exclusive_scan_i32(w.cnt_in, w.off_in, n, w.scan_tmp, w.scan_bytes, nullptr, s)) return rc;
+    if (int rc = geo::exclusive_scan_i32(w.cnt_in, w.cursor, n, w.scan_tmp, w.scan_bytes, nullptr, s)) return rc;
     const int64_t max_segs = (int64_t)n + (2 * (int64_t)n * k) / 64 + 1;          // nnz <= 2 n k (union)
-    sym_sort_kernel<<<(unsigned)((max_segs + WPB - 1) / WPB), 256, 0, s>>>(n, indptr, w.off_in, w.tmp_col, w.tmp_val,
-                                                                          indices_out, data_out);
+    sym_sort_kernel<<<(unsigned)((max_segs + WPB - 1) / WPB), 256, 0, s>>>(n, k, indptr, w.cursor, w.off_in, w.tmp_col,
+                                                                          w.tmp_val, indices_out, data_out);
     GEO_LAUNCH_CHECK();
     return GEO_OK;
 }

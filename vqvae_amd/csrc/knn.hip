@@ -157,19 +157,24 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ zp32
 }
 
 // ---- exact search behind a float32 matrix-core filter (large corpora) -----------------------------------------------
-// 1. tau[i] = the kq-th smallest exact distance from query i to every S-th corpus row: an upper bound of the kq-th
-//    smallest over the whole corpus (knn_kernel on the subset).  S = filter_stride(kq) (FILTER_STRIDE for short lists).
+// 1. tau[i] = an upper bound of the kq-th smallest exact distance from query i to every S-th corpus row, itself an upper
+//    bound of the kq-th smallest over the whole corpus (knn_bound_kernel on the subset; the two-level path tightens it to the
+//    subset's exact kq-th distance).  S = filter_stride(kq) (FILTER_STRIDE for short lists).
 // 2. knn_scan_kernel: approximate squared distances of ALL pairs on the matrix cores (v_mfma_f32_32x32x2_f32, expansion
 //    form with the fp64 norms); pair (i, j) is kept when  approx <= tau[i] + eps * (|x_i|^2 + |x_j|^2),  eps far above
 //    the rounding of a d-term float32 dot product -- every true neighbour is kept, plus ~S * kq others.
 // 3. knn_refine_kernel: the kept candidates are re-evaluated with the same fp64 fma chains as knn_kernel and ranked
 //    by (distance, index): the result is the one knn_kernel gives.  A query whose list overflows FILTER_CAP (heavily
 //    duplicated points) is reported and the caller falls back to knn_kernel.
-constexpr int FILTER_STRIDE = 16, FILTER_STRIDE_MIN = 4, FILTER_CAP = 1024;
+constexpr int FILTER_STRIDE = 8, FILTER_STRIDE_MIN = 4, FILTER_CAP = 1024;
 // A query keeps ~S * kq candidates on average (about S kq corpus rows lie at or below the kq-th distance to every S-th row),
 // with a tail of a few hundred more: at S = 16 and kq = 64 the mean was the cap itself, half the queries overflowed and the
 // whole call fell back to the exact scan.  Denser subsets for longer lists keep S * kq <= 384 (kq <= 64 here).
-constexpr int filter_stride(int kq) { return kq <= 24 ? FILTER_STRIDE : kq <= 40 ? 8 : FILTER_STRIDE_MIN; }
+// Short lists took S = 16 while the thresholds were an exact ranking of the subset (1.0 ms at 60 000 x 16, kq = 21).  With
+// knn_bound_kernel they cost 0.32 ms at S = 16, 0.57 at 8 and 1.08 at 4, and the candidates -- the scan's slow path and the
+// refinement -- shrink with S: thresholds + scan + refinement per build 1.88 / 1.62 / 1.91 ms at S = 16 / 8 / 4 (five builds
+// each, spread 0.06), and 136.3 / 134.6 / 179.7 ms at one million rows (two levels: every 64th row at S = 8).  Hence 8.
+constexpr int filter_stride(int kq) { return kq <= 40 ? FILTER_STRIDE : FILTER_STRIDE_MIN; }
 constexpr int64_t TWO_LEVEL_MIN = 200000;      // from here on the thresholds themselves come from a filtered pass (below)
 typedef float f32x16v __attribute__((ext_vector_type(16)));
 
@@ -185,6 +190,7 @@ __global__ __launch_bounds__(256) void knn_subset_kernel(const float *__restrict
 }
 
 // u[i] = tau[i] - |x_i|^2 (1 - eps): the scan keeps (i, j) when  |x_j|^2 (1 - eps) - 2 x_i.x_j <= u[i]
+// (two-level path only: tau from the kq-th entry of the refined subset lists; knn_bound_kernel writes u itself)
 __global__ __launch_bounds__(256) void knn_tau_kernel(const double *__restrict__ d2_sub, const double *__restrict__ nrm,
                                                      int64_t row0, int64_t rows, int kq, double eps,
                                                      double *__restrict__ u, int32_t *__restrict__ cnt) {
@@ -192,6 +198,172 @@ __global__ __launch_bounds__(256) void knn_tau_kernel(const double *__restrict__
         const double nq = nrm[row0 + i];
         u[i] = d2_sub[i * kq + (kq - 1)] + eps * nq - nq;
         cnt[i] = 0;
+    }
+}
+
+// ---- thresholds of the filter: a bound from per-lane minima, not a ranking -----------------------------------------------
+// The filter needs tau[i] >= the kq-th smallest key of query i over the corpus and nothing more: the refinement re-evaluates
+// every kept pair and ranks it, so the lists are exact under any valid bound.  Ranking the subset exactly (knn_kernel: a sorted
+// list, one ballot + popcount + whole-wave shift per hit, ~120 serial insertions per query on a 3 750-row subset) cost as much
+// as the scan of all pairs.  Here subset row p belongs to lane p % 64, and a lane keeps the TWO smallest keys it has seen per
+// query: two fmin and one fmax per key, no ballots, no indices.  The 128 per-lane values of a query are keys of 128 distinct
+// subset rows (of all m rows when m <= 128, +inf in the empty slots), so their kq-th smallest (kq <= 64, kq <= m) has at least kq
+// corpus rows at or below it.  It is the exact subset threshold unless three of the kq best share a lane: 1.5 % more
+// candidates than the exact one at (kq, S) = (21, 16), 5 % at (40, 8), 14 % at (64, 4) (20 000 normal rows, d = 16); one
+// minimum per lane loses 20 % - 5x.  Lists longer than 24 keep THREE per lane (192 values, 0.6 % and 2 % more candidates).
+//
+// One workgroup owns Q queries; its four waves take the subset's 64-row steps round robin (same key chains as knn_kernel and
+// knn_refine_kernel: query coordinates wave-uniform through the scalar cache, the next step's row in flight under the fmas),
+// leave their minima in LDS, and each wave then merges and selects for Q / 4 of the queries.  30 000 waves of 15 steps at
+// 60 000 queries x 3 750 rows where knn_kernel<.., 16> had 3 750 of 59, and a rank's share of the rows still fills the chip.
+constexpr int BOUND_Q = 8;
+constexpr int bound_minima(int kq) { return kq <= 24 ? 2 : 3; }
+
+// v[0] <= v[1] <= .. stay the NM smallest of themselves and x
+template <int NM>
+__device__ __forceinline__ void keep_smallest(double (&v)[NM], double x) {
+#pragma unroll
+    for (int r = NM - 1; r > 0; --r) v[r] = fmin(v[r], fmax(v[r - 1], x));
+    v[0] = fmin(v[0], x);
+}
+
+// the kq-th smallest (1 <= kq <= 64 NM) of the wave's 64 NM values (keys >= 0 or +inf): quickselect in registers -- a pivot
+// from inside the window (lo, hi) (fewer than kq values <= lo, at least kq <= hi), NM ballots to count, ~10 rounds
+template <int NM>
+__device__ __forceinline__ double kth_of_wave(const double (&v)[NM], int kq) {
+    double lo = -1.0, hi = inf64();
+    int rot = 0;
+    for (int guard = 0; guard < 64 * NM + 2; ++guard) {       // every round takes its pivot out of the window
+        double cand = inf64();                                 // this lane's first value strictly inside the window
+#pragma unroll
+        for (int r = NM - 1; r >= 0; --r)
+            if (v[r] > lo && v[r] < hi) cand = v[r];
+        unsigned long long has = __ballot(cand < inf64());
+        if (!has) break;                                       // nothing strictly inside: the answer is hi
+        has = (has >> rot) | (rot ? has << (64 - rot) : 0ull);
+        const int src = (__builtin_ctzll(has) + rot) & 63;
+        rot = (rot + 23) & 63;
+        const double pivot = readlane_f64(cand, src);
+        int c = 0;
+#pragma unroll
+        for (int r = 0; r < NM; ++r) c += __builtin_popcountll(__ballot(v[r] <= pivot));
+        if (c >= kq) hi = pivot; else lo = pivot;
+    }
+    return hi;
+}
+
+// u[i] = tau[i] - |x_i|^2 (1 - eps) and cnt[i] = 0 for the scan (when u is given), tau[i] itself when tau_out is given
+template <int DCH, int Q, int NM, bool EXPANSION>
+__global__ __launch_bounds__(256) void knn_bound_kernel(const float *__restrict__ zs32, const double *__restrict__ zq64,
+                                                       const double *__restrict__ nrm_s, const double *__restrict__ nrm_q,
+                                                       int64_t m, int nch, int kq, int64_t row0, int64_t row1, double eps,
+                                                       double *__restrict__ u, int32_t *__restrict__ cnt,
+                                                       double *__restrict__ tau_out) {
+    static_assert(Q % KNN_WAVES == 0, "every wave selects for Q / KNN_WAVES queries");
+    __shared__ double mins[KNN_WAVES][Q][NM][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t q0 = row0 + (int64_t)blockIdx.x * Q;
+    const int dp = nch * DCH;
+    const int64_t steps = (m + 63) / 64;
+    double mn[Q][NM];                                          // this lane's NM smallest keys per query, ascending
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int r = 0; r < NM; ++r) mn[q][r] = inf64();
+
+    double nq[Q];                                              // wave-uniform
+#pragma unroll
+    for (int q = 0; q < Q; ++q) nq[q] = EXPANSION ? nrm_q[q0 + q < row1 ? q0 + q : row1 - 1] : 0.0;
+
+    float4 f[DCH / 4];                                         // the row chunk in flight
+    // A lane past the subset's end must not enter the minima: its key is made +inf by the arithmetic itself, with no select
+    // per query -- the expansion form adds a norm of +inf last (the clamp keeps +inf), the direct form starts its sum at +inf.
+    double nj_next = 0.0;
+    auto fetch = [&](int64_t s, int ch) {
+        const int64_t j = s * 64 + lane;
+        const int64_t jc = j < m ? j : m - 1;
+        const float4 *src = reinterpret_cast<const float4 *>(zs32 + jc * dp + ch * DCH);
+#pragma unroll
+        for (int v = 0; v < DCH / 4; ++v) f[v] = src[v];
+        if (ch == 0) nj_next = j < m ? (EXPANSION ? nrm_s[jc] : 0.0) : inf64();
+    };
+    double acc[Q];
+    double nj = 0.0;
+    int64_t s = wave;
+    int ch = 0;
+    if (s < steps) fetch(s, 0);
+    while (s < steps) {
+        double cj[DCH];
+#pragma unroll
+        for (int v = 0; v < DCH / 4; ++v) {
+            cj[4 * v] = (double)f[v].x; cj[4 * v + 1] = (double)f[v].y;
+            cj[4 * v + 2] = (double)f[v].z; cj[4 * v + 3] = (double)f[v].w;
+        }
+        if (ch == 0) {
+            nj = nj_next;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) acc[q] = EXPANSION ? 0.0 : nj;
+        }
+        int64_t s_n = s;
+        int ch_n = ch + 1;
+        if (ch_n == nch) { ch_n = 0; s_n = s + KNN_WAVES; }
+        if (s_n < steps) fetch(s_n, ch_n);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            int64_t qr = q0 + q;
+            if (qr >= row1) qr = row1 - 1;
+            const double *__restrict__ qv = zq64 + qr * dp + ch * DCH;         // wave-uniform address
+#pragma unroll
+            for (int k = 0; k < DCH; ++k) {
+                if (EXPANSION) {
+                    acc[q] = fma(qv[k], cj[k], acc[q]);
+                } else {
+                    const double t = qv[k] - cj[k];
+                    acc[q] = fma(t, t, acc[q]);
+                }
+            }
+        }
+        if (ch == nch - 1) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                double d2 = acc[q];
+                if (EXPANSION) {
+                    d2 = (nq[q] + (-2.0 * d2)) + nj;
+                    if (!(d2 > 0.0)) d2 = 0.0;
+                }
+                keep_smallest<NM>(mn[q], d2);
+            }
+        }
+        s = s_n;
+        ch = ch_n;
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int r = 0; r < NM; ++r) mins[wave][q][r][lane] = mn[q][r];
+    __syncthreads();
+    // the waves' sets merge elementwise (a lane's rows are its own in every wave): the NM smallest of the four sets
+    for (int t = 0; t < Q / KNN_WAVES; ++t) {
+        const int q = wave * (Q / KNN_WAVES) + t;
+        const int64_t qr = q0 + q;
+        if (qr >= row1) break;
+        double a[NM];
+#pragma unroll
+        for (int r = 0; r < NM; ++r) a[r] = mins[0][q][r][lane];
+#pragma unroll
+        for (int w = 1; w < KNN_WAVES; ++w)
+#pragma unroll
+            for (int r = 0; r < NM; ++r) keep_smallest<NM>(a, mins[w][q][r][lane]);
+        const double tau = kth_of_wave<NM>(a, kq);
+        if (lane == 0) {
+            if (u) {
+                const double nq = nrm_q[qr];
+                u[qr - row0] = tau + eps * nq - nq;
+                cnt[qr - row0] = 0;
+            }
+            if (tau_out) tau_out[qr - row0] = tau;
+        }
     }
 }
 
@@ -783,6 +955,22 @@ int launch_knn_wide(bool expansion, const float *zp32, const double *zq64, const
     return launch_knn<DCH, 4, 4>(expansion, zp32, zq64, nrm, nrm, n, nch, kq, row0, row1, idx_out, d2_out, s);
 }
 
+int launch_knn_bound(const KnnPlan &p, bool expansion, const float *zs32, const double *zq64, const double *nrm_s,
+                     const double *nrm_q, int64_t m, int kq, int64_t row0, int64_t row1, double eps, double *u, int32_t *cnt,
+                     double *tau_out, hipStream_t s) {
+    const unsigned grid = (unsigned)((row1 - row0 + BOUND_Q - 1) / BOUND_Q);
+#define GEO_BOUND(DCHV, NMV, EXV) \
+    knn_bound_kernel<DCHV, BOUND_Q, NMV, EXV><<<grid, 256, 0, s>>>(zs32, zq64, nrm_s, nrm_q, m, p.nch, kq, row0, row1, eps, u, cnt, tau_out)
+#define GEO_BOUND_NM(DCHV, EXV) do { if (bound_minima(kq) == 2) GEO_BOUND(DCHV, 2, EXV); else GEO_BOUND(DCHV, 3, EXV); } while (0)
+    if (p.dch == 8) { if (expansion) GEO_BOUND_NM(8, true); else GEO_BOUND_NM(8, false); }
+    else if (p.dch == 16) { if (expansion) GEO_BOUND_NM(16, true); else GEO_BOUND_NM(16, false); }
+    else { if (expansion) GEO_BOUND_NM(32, true); else GEO_BOUND_NM(32, false); }
+#undef GEO_BOUND_NM
+#undef GEO_BOUND
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
 // the path the calling thread's last geo_knn_topk took (GEO_KNN_PATH_* of include/geo_hip.h), for tests and profiles
 thread_local int32_t g_last_path = 0;
 
@@ -888,10 +1076,6 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
             if (sp > (corpus + 255) / 256) sp = (corpus + 255) / 256;
             return (int)(sp > 1 ? sp : 1);
         };
-#define GEO_EXACT_SUBSET(ZS, NRMS, MS)                                                                              \
-    (p.dch == 8 ? launch_knn<8, 16>(ex, ZS, zq64, NRMS, nrm, MS, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream)    \
-     : p.dch == 16 ? launch_knn<16, 16>(ex, ZS, zq64, NRMS, nrm, MS, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream) \
-                   : launch_knn<32, 16>(ex, ZS, zq64, NRMS, nrm, MS, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream))
 #define GEO_REFINE(DCHV, EXV, ZC, NRMC) \
     knn_refine_kernel<DCHV, EXV><<<rgrid, 256, 0, stream>>>(ZC, zq64, NRMC, nrm, p.nch, n_neighbors, row0, rows, cnt, list, \
                                                           idx_out, d2_out, overflow)
@@ -903,18 +1087,16 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
     } while (0)
         int rc = 0;
         bool tau_done = false;
-        // Large inputs: the exact pass over every 16th row is itself N^2 / 16 fp64 work (100 ms of 255 at a million latents).
-        // Two levels instead: thresholds from every 256th row (exact), with them the SAME filter + refinement over the
-        // every-16th-row subset gives the exact kq-th distance to that subset -- the threshold the one-level scheme uses.
-        // (Every S-th row of every S-th row for longer lists: the same candidate counts at both levels.)
+        // Large inputs: the pass over every S-th row is itself N^2 / S fp64 work (S = 16: 100 ms of 255 at a million latents).
+        // Two levels instead: thresholds from every S-th row of every S-th row (knn_bound_kernel), with them the SAME filter +
+        // refinement over the every-S-th-row subset gives the exact kq-th distance to that subset -- at least as tight as the
+        // threshold of the one-level scheme; the same candidate counts at both levels.
         const int64_t m0 = (m + S - 1) / S;
         if (bf16_scan && zs0 && n >= TWO_LEVEL_MIN && m0 >= n_neighbors) {
             knn_subset_kernel<<<geo::grid_for(m0 * p.dp, 256, 4096), 256, 0, stream>>>(zs32, nrm_s, m, p.dp, S, m0, zs0, nrm_s0);
             GEO_LAUNCH_CHECK();
-            rc = GEO_EXACT_SUBSET(zs0, nrm_s0, m0);
+            rc = launch_knn_bound(p, ex, zs0, zq64, nrm_s0, nrm, m0, n_neighbors, row0, row1, eps, u, cnt, nullptr, stream);
             if (rc) return rc;
-            knn_tau_kernel<<<geo::grid_for(rows, 256, 4096), 256, 0, stream>>>(d2_out, nrm, row0, rows, n_neighbors, eps, u, cnt);
-            GEO_LAUNCH_CHECK();
             knn_split_kernel<<<geo::grid_for(m_pad * dpb, 256, 4096), 256, 0, stream>>>(zs32, nrm_s, m, m_pad, p.dp, dpb, eps, zb_s, negn_s);
             GEO_LAUNCH_CHECK();
             const int sp1 = splits_for(m);
@@ -932,13 +1114,14 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
             if (tau_done) g_last_path = GEO_KNN_PATH_TWO_LEVEL;
             if (!tau_done) GEO_HIP_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
         }
-        if (!tau_done) {
+        if (tau_done) {                                        // the subset's exact kq-th distances, left in d2_out by the refinement
+            knn_tau_kernel<<<geo::grid_for(rows, 256, 4096), 256, 0, stream>>>(d2_out, nrm, row0, rows, n_neighbors, eps, u, cnt);
+            GEO_LAUNCH_CHECK();
+        } else {
             g_last_path = bf16_scan ? GEO_KNN_PATH_FILTER_BF16 : GEO_KNN_PATH_FILTER_F32;
-            rc = GEO_EXACT_SUBSET(zs32, nrm_s, m);
+            rc = launch_knn_bound(p, ex, zs32, zq64, nrm_s, nrm, m, n_neighbors, row0, row1, eps, u, cnt, nullptr, stream);
             if (rc) return rc;
         }
-        knn_tau_kernel<<<geo::grid_for(rows, 256, 4096), 256, 0, stream>>>(d2_out, nrm, row0, rows, n_neighbors, eps, u, cnt);
-        GEO_LAUNCH_CHECK();
         const int splits = splits_for(n);
         const unsigned sgrid = (unsigned)((rows + 127) / 128) * (unsigned)splits;
         if (bf16_scan) {
@@ -954,7 +1137,6 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
         GEO_REFINE_ANY(zp32, nrm);
 #undef GEO_REFINE_ANY
 #undef GEO_REFINE
-#undef GEO_EXACT_SUBSET
         GEO_LAUNCH_CHECK();
         int32_t h_over = 0;
         GEO_HIP_CHECK(hipMemcpyAsync(&h_over, overflow, 4, hipMemcpyDeviceToHost, stream));
@@ -980,3 +1162,33 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
 }
 
 extern "C" int geo_knn_last_path(void) { return g_last_path; }
+
+extern "C" int geo_knn_thresholds(const float *z, int64_t n, int32_t d, int32_t n_neighbors, int32_t form, int64_t row0,
+                                  int64_t row1, int32_t stride, double *tau_out, void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    GEO_REQUIRE(z && tau_out && ws, "geo_knn_thresholds: null pointer");
+    GEO_REQUIRE(n > 0 && n < (int64_t)1 << 31, "geo_knn_thresholds: n=%lld out of range", (long long)n);
+    GEO_REQUIRE(d > 0 && d <= 128, "geo_knn_thresholds: d=%d not in [1,128]", d);
+    GEO_REQUIRE(stride >= 1, "geo_knn_thresholds: stride=%d", stride);
+    const int64_t m = (n + stride - 1) / stride;
+    GEO_REQUIRE(n_neighbors > 0 && n_neighbors <= 64 && n_neighbors <= m,
+                "geo_knn_thresholds: n_neighbors=%d not in [1, min(64, subset rows)]", n_neighbors);
+    GEO_REQUIRE(0 <= row0 && row0 <= row1 && row1 <= n, "geo_knn_thresholds: bad row range");
+    if (row0 == row1) return GEO_OK;
+    const KnnPlan p = plan_for(d);
+    geo::Arena ar(ws, ws_bytes);
+    float *zp32 = ar.take<float>((size_t)n * p.dp);
+    double *zq64 = ar.take<double>((size_t)n * p.dp);
+    double *nrm = ar.take<double>((size_t)n);
+    float *zs32 = ar.take<float>((size_t)m * p.dp);
+    double *nrm_s = ar.take<double>((size_t)m);
+    if (!zp32 || !zq64 || !nrm || !zs32 || !nrm_s) {
+        geo::set_error("geo_knn_thresholds: workspace %zu too small", ws_bytes);
+        return GEO_E_WORKSPACE;
+    }
+    knn_prep_kernel<<<geo::grid_for(n, 256, 4096), 256, 0, stream>>>(z, n, d, p.dp, zp32, zq64, nrm);
+    GEO_LAUNCH_CHECK();
+    knn_subset_kernel<<<geo::grid_for(m * p.dp, 256, 4096), 256, 0, stream>>>(zp32, nrm, n, p.dp, stride, m, zs32, nrm_s);
+    GEO_LAUNCH_CHECK();
+    return launch_knn_bound(p, form != 0, zs32, zq64, nrm_s, nrm, m, n_neighbors, row0, row1, 0.0, nullptr, nullptr, tau_out, stream);
+}
