@@ -354,6 +354,14 @@ int geo_decoder_jvp_pairs(const geo_decoder_desc *dec, const float *z_start, con
                           void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K-quad weights and the chain order, shared by the native pull-back, decode, encode and LPIPS below.
+ * A convolution weight read as a matrix [K][N] (K = input channels of one tap, N = output channels) is packed
+ * [K / 4][N][4]: element (q, n, r) = weight (k = 4 q + r, column n); the descriptors give each tensor's own element formula.
+ * An output value is one chain from 0 over the taps, then over the input channels in blocks of 8, within a block in the
+ * order 0 4 1 5 2 6 3 7 ("the K-quad chain order" below); bias, folded norm and ReLU come after the chain.
+ * ------------------------------------------------------------------------------------------ */
+
+/* ------------------------------------------------------------------------------------------
  * The same quantity for the vanilla (vector-latent) VAE decoder with FIXED statistics (src/models/vae.py:53-85 in eval mode:
  * BatchNorm with running statistics, or no normalisation):
  *   fc: Linear(d, c0 16) -> view c0x4x4 -> ConvT(c0,c1,k3,s2,p1[,output_padding]) -> norm -> ReLU
@@ -454,9 +462,8 @@ int geo_spatial_decode(const geo_spatial_image_decoder_desc *dec, const float *z
  *   28 -> 14 -> 7 -> 4 px or 32 -> 16 -> 8 -> 4 px, then the head: fc_mu, fc_logvar = Linear(16 e3, d) on the NCHW flatten
  *   (spatial_head 0; mu, logvar f32 [n][d]) or Conv(e3, d, 1) (spatial_head 1; mu, logvar f32 NCHW [n][d][4][4]).
  * Activations are f32 [item][pixel][channel]; layer i computes relu(scale_i[co] * sum + shift_i[co]) with the sum a chain
- * from 0 (layer 1: over (c, ky, kx); layers 2, 3: over tap 3 ky + kx, then the input channels in blocks of 8, within a
- * block in the order 0 4 1 5 2 6 3 7), output pixel (oy, ox) reading input pixel (2 oy - 1 + ky, 2 ox - 1 + kx), nothing
- * outside the image.  A head value is bh[col] added to the sum, in segment order, of one such chain per segment: 16
+ * from 0 (layer 1: over (c, ky, kx); layers 2, 3: over tap 3 ky + kx in the K-quad chain order), output pixel (oy, ox)
+ * reading input pixel (2 oy - 1 + ky, 2 ox - 1 + kx), nothing outside the image.  A head value is bh[col] added to the sum, in segment order, of one such chain per segment: 16
  * segments (the 4 x 4 pixels) of e3 channels for the vanilla head, one for the spatial head.
  * Covered: (C, in_size) = (1, 28) or (3, 32); (e1, e2, e3) = (64, 128, 256) or (32, 64, 128); 1 <= latent_dim <= 128
  * (spatial_head 0) or <= 64 (spatial_head 1).  The rules are those of the image decode above: passes of at most 4096
@@ -500,9 +507,8 @@ int geo_image_encode(const geo_image_encoder_desc *enc, const float *x /* [n][C]
  *   Conv(192,384,k3,p1) ReLU -> f3 (3 x 3); Conv(384,256,k3,p1) ReLU -> f4; Conv(256,256,k3,p1) ReLU -> f5;
  *   d_l = mean over pixels of sum_c lin_l[c] (u0 - u1)^2 with u = f / (sqrt(sum_c f^2) + 1e-10); value = d_1 + ... + d_5.
  * The features are f32 [image][pixel][channel], each value one chain from 0 (layer 1: over c, ky, then the kx pairs (0, 1) ..
- * (10, -); layers 2 .. 5: over tap KS ky + kx, then the input channels in blocks of 8, within a block in the order
- * 0 4 1 5 2 6 3 7), the bias added last; the distance is fp64 from those features: channel sums folded by an xor butterfly
- * of 64 partials, the pixel mean in pixel order, the layer sum in layer order.  total_out f64 [n]; layer_out f64 [n][5] or
+ * (10, -); layers 2 .. 5: over tap KS ky + kx in the K-quad chain order), the bias added last; the distance is fp64 from
+ * those features: channel sums folded by an xor butterfly of 64 partials, the pixel mean in pixel order, the layer sum in layer order.  total_out f64 [n]; layer_out f64 [n][5] or
  * NULL.  The rules are those of the image encode above: passes of at most 4096 pairs shrunk to fit any workspace from
  * geo_lpips_alex_workspace_bytes(1) upwards (the five feature buffers of both images of a pass, 254 976 bytes per pair; below
  * it GEO_E_WORKSPACE); a null pointer or n >= 2^31 returns GEO_E_ARG before any launch; n == 0 returns GEO_OK without a

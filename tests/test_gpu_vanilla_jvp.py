@@ -91,12 +91,7 @@ def test_graph_entry_equals_pairs_entry(name):
     dev = torch.device("cuda", 0)
     dec = V.case(name)[0]
     ex = VanillaDecoderExport(dec, dev)
-    g = torch.Generator().manual_seed(9)
-    z = torch.randn(300, ex.latent_dim, generator=g).to(dev)
-    src = torch.randint(0, 300, (1500,), generator=g, dtype=torch.int32)
-    dst = torch.randint(0, 300, (1500,), generator=g, dtype=torch.int32)
-    dst[::50] = src[::50]
-    src, dst = src.to(dev), dst.to(dev)
+    z, src, dst = (t.to(dev) for t in V.small_graph(ex.latent_dim))
     pairs = edge_lengths_vanilla_device(ex, z[src.long()].contiguous(), z[dst.long()].contiguous()).cpu().numpy()
     graph = edge_lengths_vanilla_graph_device(ex, z, src, dst).cpu().numpy()
     assert np.array_equal(graph, pairs)

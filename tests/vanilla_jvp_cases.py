@@ -78,6 +78,16 @@ def make_edges(latent_dim, n_edges=N_EDGES, seed=1):
     return zs, zs + 0.3 * torch.randn(n_edges, latent_dim, generator=g)
 
 
+def small_graph(latent_dim, n_nodes=300, n_edges=1500, seed=9):
+    """(z [n_nodes, d], src, dst int32 [n_edges]) on the CPU: random endpoints, every 50th edge a self loop."""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(n_nodes, latent_dim, generator=g)
+    src = torch.randint(0, n_nodes, (n_edges,), generator=g, dtype=torch.int32)
+    dst = torch.randint(0, n_nodes, (n_edges,), generator=g, dtype=torch.int32)
+    dst[::50] = src[::50]
+    return z, src, dst
+
+
 def autograd_lengths(decoder, zs, ze, dtype) -> np.ndarray:
     """The package's autograd route (riemannian_metric._generic_jvp_norms as imported here, before any monkeypatching) on a
     CPU copy of the decoder in `dtype`."""

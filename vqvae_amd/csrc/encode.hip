@@ -17,10 +17,11 @@
 // Every output value is a fixed-order chain of its own item, no atomics, no split across workgroups: a row's (mu, logvar) does
 // not depend on the batch, its position in it, the pass size, the workspace, the stream or the run.
 #include "geo_common.h"
+#include "mfma_conv.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mfma_conv::f32x16;
 
 constexpr int64_t ITEMS_PER_PASS = 4096;
 constexpr int MAX_D_VANILLA = 128, MAX_D_SPATIAL = 64;
@@ -28,7 +29,7 @@ constexpr int HEAD_ROWS = 32;
 
 struct Shape {
     int C, S, e1, e2, e3, d, spatial, npad;
-    size_t n1, n2, n3;         // floats per item of the three activation buffers
+    size_t per_item[3];        // floats per item of the three activation buffers
 };
 
 bool make_shape(const geo_image_encoder_desc *e, Shape *s) {
@@ -45,22 +46,10 @@ bool make_shape(const geo_image_encoder_desc *e, Shape *s) {
     s->d = e->latent_dim;
     s->spatial = e->spatial_head;
     s->npad = (2 * s->d + 31) & ~31;
-    s->n1 = (size_t)(s->S / 2) * (s->S / 2) * s->e1;
-    s->n2 = (size_t)(s->S / 4) * (s->S / 4) * s->e2;
-    s->n3 = (size_t)16 * s->e3;
+    s->per_item[0] = (size_t)(s->S / 2) * (s->S / 2) * s->e1;
+    s->per_item[1] = (size_t)(s->S / 4) * (s->S / 4) * s->e2;
+    s->per_item[2] = (size_t)16 * s->e3;
     return true;
-}
-
-size_t encode_bytes(const Shape &s, int64_t items) {
-    using geo::align_up;
-    return align_up((size_t)items * s.n1 * 4) + align_up((size_t)items * s.n2 * 4) + align_up((size_t)items * s.n3 * 4);
-}
-
-// Items per pass that fit the workspace (0: not even one).
-int64_t pass_items(const Shape &s, int64_t n, size_t ws_bytes) {
-    int64_t pb = n < ITEMS_PER_PASS ? n : ITEMS_PER_PASS;
-    while (pb >= 1 && encode_bytes(s, pb) > ws_bytes) pb = pb > 64 ? pb - pb / 8 : pb - 1;
-    return pb;
 }
 
 // ---- layer 1: one image per workgroup.  The image is staged with one row and one column of zeros in front (the only padding
@@ -101,10 +90,9 @@ __global__ __launch_bounds__(256) void enc_first_kernel(const float *__restrict_
 }
 
 // ---- layers 2 and 3: Conv(CIN, COUT, k3, s2, p1) of G items per workgroup, sin x sin -> so x so pixels (so = ceil(sin / 2)).
-// The items' inputs ([pixel][CIN]) are staged in LDS with rows padded by four floats, plus one zero row for taps in the
-// padding and for rows past the last item.  8 waves, one 32 x 32 tile each: wave = (N tile, M tile), G and the sizes are chosen
-// so that the workgroup has exactly 8 tiles.  K runs over (tap 0..8, 8-channel block); lane half h takes channels 4h .. 4h+3
-// of the block, one 16-byte read each of A (LDS) and B (global) feeds four MFMAs.  wp: [tap][CIN / 4][COUT][4].
+// The items' inputs ([pixel][CIN]) are staged in LDS in mfma_conv.h's layout.  8 waves, one 32 x 32 tile each: wave = (N tile,
+// M tile), G and the sizes are chosen so that the workgroup has exactly 8 tiles.  K runs over (tap 0..8, 8-channel block).
+// wp: [tap][CIN / 4][COUT][4].
 template <int CIN, int COUT, int G, int PIN_MAX>
 __global__ __launch_bounds__(512) void enc_conv_kernel(const float *__restrict__ in, float *__restrict__ out, int64_t n_items, int sin,
                                                        const float *__restrict__ wp, const float *__restrict__ sc,
@@ -117,14 +105,8 @@ __global__ __launch_bounds__(512) void enc_conv_kernel(const float *__restrict__
     const int64_t item0 = (int64_t)blockIdx.x * G;
     const int live = (int)(n_items - item0 < G ? n_items - item0 : G);
     const int tid = threadIdx.x;
-    {
-        const float4 *src = reinterpret_cast<const float4 *>(in + (size_t)item0 * pin * CIN);   // contiguous over the live items
-        for (int q = tid; q < live * pin * (CIN / 4); q += 512) {
-            const int row = q / (CIN / 4), ci = (q - row * (CIN / 4)) * 4;
-            *reinterpret_cast<float4 *>(lds + (size_t)row * LD + ci) = src[q];
-        }
-        for (int k = tid; k < LD; k += 512) lds[(size_t)ZR * LD + k] = 0.f;
-    }
+    mfma_conv::stage_rows<CIN, 512>(lds, in + (size_t)item0 * pin * CIN, live * pin, tid);       // contiguous over the live items
+    mfma_conv::fill_zero_row<512>(lds, ZR, LD, tid);
     __syncthreads();
 
     const int lane = tid & 63, wave = tid >> 6;
@@ -137,33 +119,22 @@ __global__ __launch_bounds__(512) void enc_conv_kernel(const float *__restrict__
     const int g = rv ? r / pout : 0, pq = rv ? r - g * pout : 0;
     const int oy = pq / so, ox = pq - oy * so;
     const int co = nt * 32 + j;
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    f32x16 acc[1];
+    mfma_conv::clear(acc);
     for (int tap = 0; tap < 9; ++tap) {
         const int ky = tap / 3, kx = tap - ky * 3;
-        const int iy = 2 * oy - 1 + ky, ix = 2 * ox - 1 + kx;
-        const bool ok = rv && iy >= 0 && iy < sin && ix >= 0 && ix < sin;
-        const float *ap = lds + (size_t)(ok ? g * pin + iy * sin + ix : ZR) * LD + 4 * h;
+        const float *ap[1] = {mfma_conv::tap_row(lds, LD, ZR, rv, g, 2 * oy - 1 + ky, 2 * ox - 1 + kx, sin, pin, h)};
         const float4 *bp = reinterpret_cast<const float4 *>(wp) + ((size_t)tap * (CIN / 4) + h) * COUT + co;
-#pragma unroll 4
-        for (int cb = 0; cb < CIN / 8; ++cb) {
-            const float4 bv = bp[(size_t)cb * 2 * COUT];
-            const float4 av = *reinterpret_cast<const float4 *>(ap + cb * 8);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-        }
+        mfma_conv::k_chain<1, 4>(acc, ap, bp, CIN / 8, COUT);
     }
     const float scale = sc[co], shift = sh[co];
     float *dst = out + (size_t)item0 * pout * COUT;                 // row r of the workgroup = (item, pixel), contiguous too
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const int ro = mt * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+        const int ro = mfma_conv::acc_row(q, h, mt * 32);
         if (ro < rows) {
-            const float v = fmaf(scale, acc[q], shift);
-            dst[(size_t)ro * COUT + co] = v > 0.f ? v : 0.f;
+            const float v = fmaf(scale, acc[0][q], shift);
+            dst[(unsigned)(ro * COUT + co)] = v > 0.f ? v : 0.f;     // (32-bit: the store keeps dst as its scalar base)
         }
     }
 }
@@ -238,7 +209,7 @@ __global__ __launch_bounds__(256) void enc_head_kernel(const float *__restrict__
         const int c = col < d ? col : col - d;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int ro = (q & 3) + 8 * (q >> 2) + 4 * h;
+            const int ro = mfma_conv::acc_row(q, h);
             if (ro < live) {
                 const int64_t row = row0 + ro, item = row / pix;
                 const int p = (int)(row - item * pix);
@@ -275,7 +246,7 @@ int run_pass(const geo_image_encoder_desc *e, const Shape &s, const float *x, in
 extern "C" size_t geo_image_encode_workspace_bytes(const geo_image_encoder_desc *enc, int64_t n) {
     Shape s;
     if (!make_shape(enc, &s) || n < 0) return 0;
-    return encode_bytes(s, n < 1 ? 1 : (n < ITEMS_PER_PASS ? n : ITEMS_PER_PASS));
+    return geo::pass_query_bytes(s.per_item, 3, ITEMS_PER_PASS, n);
 }
 
 extern "C" int geo_image_encode(const geo_image_encoder_desc *enc, const float *x, int64_t n, float *mu_out, float *logvar_out,
@@ -288,29 +259,19 @@ extern "C" int geo_image_encode(const geo_image_encoder_desc *enc, const float *
     GEO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "geo_image_encode: n %lld", (long long)n);
     if (n == 0) return GEO_OK;
     GEO_REQUIRE(x && mu_out && logvar_out && ws, "geo_image_encode: null pointer");
-    const int64_t pb = pass_items(s, n, ws_bytes);
-    if (pb < 1) {
-        geo::set_error("geo_image_encode: workspace of %zu bytes is below the minimum of %zu", ws_bytes, encode_bytes(s, 1));
-        return GEO_E_WORKSPACE;
-    }
-    geo::Arena ar(ws, ws_bytes);
-    float *buf1 = ar.take<float>((size_t)pb * s.n1);
-    float *buf2 = ar.take<float>((size_t)pb * s.n2);
-    float *buf3 = ar.take<float>((size_t)pb * s.n3);
-    if (!buf1 || !buf2 || !buf3) {
-        geo::set_error("geo_image_encode: workspace too small");
-        return GEO_E_WORKSPACE;
-    }
+    int64_t pb;
+    float *buf[3];
+    int rc = geo::plan_passes("geo_image_encode", s.per_item, 3, ITEMS_PER_PASS, n, ws, ws_bytes, &pb, buf);
+    if (rc != GEO_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t nin = (size_t)s.C * s.S * s.S, nout = (size_t)s.d * (s.spatial ? 16 : 1);
     for (int64_t p0 = 0; p0 < n; p0 += pb) {
         const int64_t cnt = n - p0 < pb ? n - p0 : pb;
-        int rc;
         if (s.e1 == 64)
-            rc = run_pass<64, 128, 256>(enc, s, x + (size_t)p0 * nin, cnt, buf1, buf2, buf3, mu_out + (size_t)p0 * nout,
+            rc = run_pass<64, 128, 256>(enc, s, x + (size_t)p0 * nin, cnt, buf[0], buf[1], buf[2], mu_out + (size_t)p0 * nout,
                                         logvar_out + (size_t)p0 * nout, st);
         else
-            rc = run_pass<32, 64, 128>(enc, s, x + (size_t)p0 * nin, cnt, buf1, buf2, buf3, mu_out + (size_t)p0 * nout,
+            rc = run_pass<32, 64, 128>(enc, s, x + (size_t)p0 * nin, cnt, buf[0], buf[1], buf[2], mu_out + (size_t)p0 * nout,
                                        logvar_out + (size_t)p0 * nout, st);
         if (rc != GEO_OK) return rc;
     }

@@ -61,6 +61,45 @@ struct Arena {
     }
 };
 
+// ---- passes over a caller's workspace.  An entry point that keeps per-item buffers of 4-byte elements in the workspace cuts its
+// n items into passes of at most `cap`: the largest pass whose buffers fit, found by shrinking from min(n, cap).  The
+// *_workspace_bytes query and the carve use the one byte formula, so they cannot drift apart.
+static inline int64_t shrink_pass(int64_t items) { return items > 64 ? items - items / 8 : items - 1; }
+
+// Bytes of the `nb` buffers of a pass of `items` items, buffer b holding per_item[b] 4-byte elements per item.
+static inline size_t pass_bytes(const size_t *per_item, int nb, int64_t items) {
+    size_t bytes = 0;
+    for (int b = 0; b < nb; ++b) bytes += align_up((size_t)items * per_item[b] * 4);
+    return bytes;
+}
+
+// What a *_workspace_bytes function answers for n >= 0 items: the buffers of one full pass (of one item for n = 0).
+static inline size_t pass_query_bytes(const size_t *per_item, int nb, int64_t cap, int64_t n) {
+    return pass_bytes(per_item, nb, n < 1 ? 1 : (n < cap ? n : cap));
+}
+
+// The pass size for n >= 1 items in a workspace of ws_bytes and the buffers carved from it, or GEO_E_WORKSPACE with the
+// error text prefixed by the entry point's name `who`.
+static inline int plan_passes(const char *who, const size_t *per_item, int nb, int64_t cap, int64_t n, void *ws, size_t ws_bytes,
+                              int64_t *items, float **bufs) {
+    int64_t pb = n < cap ? n : cap;
+    while (pb >= 1 && pass_bytes(per_item, nb, pb) > ws_bytes) pb = shrink_pass(pb);
+    if (pb < 1) {
+        set_error("%s: workspace of %zu bytes is below the minimum of %zu", who, ws_bytes, pass_bytes(per_item, nb, 1));
+        return GEO_E_WORKSPACE;
+    }
+    Arena ar(ws, ws_bytes);
+    for (int b = 0; b < nb; ++b) {
+        bufs[b] = ar.take<float>((size_t)pb * per_item[b]);
+        if (!bufs[b]) {
+            set_error("%s: workspace too small", who);
+            return GEO_E_WORKSPACE;
+        }
+    }
+    *items = pb;
+    return GEO_OK;
+}
+
 // Exclusive prefix sum of int32 counts into int32 offsets (out[n] = total); returns total on host
 // when total_host != nullptr (synchronises in that case).  tmp: >= scan_tmp_bytes(n).
 size_t scan_tmp_bytes(int64_t n);

@@ -26,10 +26,11 @@
 // split across workgroups.  (u0 - u1)^2 is the same bits as (u1 - u0)^2, so a pair's result does not depend on which image is
 // x0, nor on n, its position, the pass or workspace size, the stream or the run.
 #include "geo_common.h"
+#include "mfma_conv.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mfma_conv::f32x16;
 
 constexpr int64_t PAIRS_PER_PASS = 4096;
 constexpr int WAVE = 64;
@@ -40,18 +41,7 @@ constexpr size_t N1 = (size_t)P1 * C1, N2 = (size_t)P2 * C2, N3 = (size_t)P3 * C
 constexpr int DIST_PIX = P1 + P2 + 3 * P3;                   // 301 pixels of the five layers
 constexpr int DIST_WAVES = 16;
 
-size_t lpips_bytes(int64_t pairs) {
-    using geo::align_up;
-    const size_t im = 2 * (size_t)pairs * 4;
-    return align_up(im * N1) + align_up(im * N2) + align_up(im * N3) + align_up(im * N4) + align_up(im * N5);
-}
-
-// Pairs per pass that fit the workspace (0: not even one).
-int64_t pass_pairs(int64_t n, size_t ws_bytes) {
-    int64_t pb = n < PAIRS_PER_PASS ? n : PAIRS_PER_PASS;
-    while (pb >= 1 && lpips_bytes(pb) > ws_bytes) pb = pb > 64 ? pb - pb / 8 : pb - 1;
-    return pb;
-}
+constexpr size_t PER_PAIR[5] = {2 * N1, 2 * N2, 2 * N3, 2 * N4, 2 * N5};     // floats of a pair's two images in the five buffers
 
 // ---- layer 1.  w1p: [(c 11 + ky)][h][co 64][8]: element s < 6 = conv1.weight[co][c][ky][2 s + h] (0 for kx = 11), 0 for
 // s = 6, 7; lane half h of the MFMA takes the even (h = 0) or odd (h = 1) kx.  The chain of an output value runs over c, ky
@@ -104,7 +94,7 @@ __global__ __launch_bounds__(512) void lpips_conv1_kernel(const float *__restric
     float *dst = f1 + (size_t)im * N1;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const int ro = wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+        const int ro = mfma_conv::acc_row(q, h, wave * 32);
         if (ro < P1) {
             const float v0 = acc0[q] + bias0, v1 = acc1[q] + bias1;
             dst[(size_t)ro * C1 + j] = v0 > 0.f ? v0 : 0.f;
@@ -115,10 +105,10 @@ __global__ __launch_bounds__(512) void lpips_conv1_kernel(const float *__restric
 
 // ---- layers 2 to 5: Conv(CIN, COUT, k KS, s1, p KS / 2) on S x S pixels of G images per group.  SRC is the side of the
 // input as stored: SRC == S reads it as it is, SRC == 2 S + 1 takes the 3 x 3 stride-2 maximum while staging.  LDS rows are
-// [image, pixel][CIN] padded by four floats, plus one row of zeros.  The group's MT x NT tiles of 32 x 32 are spread over
-// gridDim.y workgroups of NW waves, one tile per wave (every workgroup stages the group's input).  wp: [tap][CIN / 4][COUT][4],
-// element (tap, q, co, r) = weight[co][4 q + r][ky][kx], tap = KS ky + kx.  The chain runs over the taps, then the input
-// channels in blocks of 8 (within a block in the order 0 4 1 5 2 6 3 7), from 0; the bias is added last.
+// [image, pixel][CIN] in mfma_conv.h's layout.  The group's MT x NT tiles of 32 x 32 are spread over gridDim.y workgroups of NW
+// waves, one tile per wave (every workgroup stages the group's input).  wp: [tap][CIN / 4][COUT][4], element (tap, q, co, r) =
+// weight[co][4 q + r][ky][kx], tap = KS ky + kx.  The chain runs over the taps, then the 8-channel blocks, from 0; the bias is
+// added last.
 template <int CIN, int COUT, int KS, int S, int SRC, int G, int NW>
 __global__ __launch_bounds__(NW * 64) void lpips_conv_kernel(const float *__restrict__ in, float *__restrict__ out, int64_t n_img,
                                                              const float *__restrict__ wp, const float *__restrict__ bias) {
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(NW * 64) void lpips_conv_kernel(const float *__rest
         }
         *reinterpret_cast<float4 *>(lds + (size_t)row * LD + ci) = v;
     }
-    for (int k = tid; k < LD; k += NTHR) lds[(size_t)ZR * LD + k] = 0.f;
+    mfma_conv::fill_zero_row<NTHR>(lds, ZR, LD, tid);
     __syncthreads();
 
     const int lane = tid & 63, wave = tid >> 6;
@@ -165,32 +155,21 @@ __global__ __launch_bounds__(NW * 64) void lpips_conv_kernel(const float *__rest
     const int g = rv ? r / P : 0, pq = rv ? r - g * P : 0;
     const int oy = pq / S, ox = pq - oy * S;
     const int co = nt * 32 + j;
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    f32x16 acc[1];
+    mfma_conv::clear(acc);
     for (int tap = 0; tap < KS * KS; ++tap) {
         const int ky = tap / KS, kx = tap - ky * KS;
-        const int iy = oy - PAD + ky, ix = ox - PAD + kx;
-        const bool ok = rv && iy >= 0 && iy < S && ix >= 0 && ix < S;
-        const float *ap = lds + (size_t)(ok ? g * P + iy * S + ix : ZR) * LD + 4 * h;
+        const float *ap[1] = {mfma_conv::tap_row(lds, LD, ZR, rv, g, oy - PAD + ky, ox - PAD + kx, S, P, h)};
         const float4 *bp = reinterpret_cast<const float4 *>(wp) + ((size_t)tap * (CIN / 4) + h) * COUT + co;
-#pragma unroll 4
-        for (int cb = 0; cb < CIN / 8; ++cb) {
-            const float4 bv = bp[(size_t)cb * 2 * COUT];
-            const float4 av = *reinterpret_cast<const float4 *>(ap + cb * 8);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-        }
+        mfma_conv::k_chain<1, 4>(acc, ap, bp, CIN / 8, COUT);
     }
     const float b = bias[co];
     float *dst = out + (size_t)item0 * P * COUT;                    // row r of the group = (image, pixel), contiguous
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const int ro = mt * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+        const int ro = mfma_conv::acc_row(q, h, mt * 32);
         if (ro < rows) {
-            const float v = acc[q] + b;
+            const float v = acc[0][q] + b;
             dst[(size_t)ro * COUT + co] = v > 0.f ? v : 0.f;
         }
     }
@@ -287,7 +266,7 @@ int run_pass(const geo_lpips_alex_desc *net, const float *x0, const float *x1, i
 
 extern "C" size_t geo_lpips_alex_workspace_bytes(int64_t n) {
     if (n < 0) return 0;
-    return lpips_bytes(n < 1 ? 1 : (n < PAIRS_PER_PASS ? n : PAIRS_PER_PASS));
+    return geo::pass_query_bytes(PER_PAIR, 5, PAIRS_PER_PASS, n);
 }
 
 extern "C" int geo_lpips_alex(const geo_lpips_alex_desc *net, const float *x0, const float *x1, int64_t n, double *total_out,
@@ -299,26 +278,15 @@ extern "C" int geo_lpips_alex(const geo_lpips_alex_desc *net, const float *x0, c
     GEO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "geo_lpips_alex: n %lld", (long long)n);
     if (n == 0) return GEO_OK;
     GEO_REQUIRE(x0 && x1 && total_out && ws, "geo_lpips_alex: null pointer");
-    const int64_t pb = pass_pairs(n, ws_bytes);
-    if (pb < 1) {
-        geo::set_error("geo_lpips_alex: workspace of %zu bytes is below the minimum of %zu", ws_bytes, lpips_bytes(1));
-        return GEO_E_WORKSPACE;
-    }
-    geo::Arena ar(ws, ws_bytes);
+    int64_t pb;
     float *f[5];
-    const size_t per[5] = {N1, N2, N3, N4, N5};
-    for (int l = 0; l < 5; ++l) {
-        f[l] = ar.take<float>(2 * (size_t)pb * per[l]);
-        if (!f[l]) {
-            geo::set_error("geo_lpips_alex: workspace too small");
-            return GEO_E_WORKSPACE;
-        }
-    }
+    int rc = geo::plan_passes("geo_lpips_alex", PER_PAIR, 5, PAIRS_PER_PASS, n, ws, ws_bytes, &pb, f);
+    if (rc != GEO_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     for (int64_t p0 = 0; p0 < n; p0 += pb) {
         const int64_t cnt = n - p0 < pb ? n - p0 : pb;
-        const int rc = run_pass(net, x0 + (size_t)p0 * IMG, x1 + (size_t)p0 * IMG, cnt, f, total_out + p0,
-                                layer_out ? layer_out + p0 * 5 : nullptr, st);
+        rc = run_pass(net, x0 + (size_t)p0 * IMG, x1 + (size_t)p0 * IMG, cnt, f, total_out + p0,
+                      layer_out ? layer_out + p0 * 5 : nullptr, st);
         if (rc != GEO_OK) return rc;
     }
     return GEO_OK;

@@ -23,10 +23,11 @@
 // the exact-f32 matrix instruction.  Every value is a fixed-order fmaf chain of its own row, no atomics: a length does not
 // depend on the pass size, the position in a pass, the entry point, the run or the stream.  dz = 0 gives exactly 0.
 #include "geo_common.h"
+#include "mfma_conv.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mfma_conv::f32x16;
 
 constexpr int MAX_D = 128;
 constexpr int64_t EDGES_PER_PASS = 2048;        // at most this many edges (twice as many items) per pass
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(256) void vj_front_kernel(Ends s, int count, int d,
         for (int m = 0; m < 2; ++m) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int row = m * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int row = mfma_conv::acc_row(q, h, m * 32);
                 const int64_t p = tile0 + row;
                 const float x = m ? acc1[q] : acc0[q];
                 if (EDGE) {
@@ -145,10 +146,9 @@ __global__ __launch_bounds__(256) void vj_front_kernel(Ends s, int count, int d,
     }
 }
 
-// ---- mid: ConvT2 of G items.  The items' inputs ([pixel][c1], masked for the tangent) are staged in LDS with rows padded by
-// four floats (conflict-free 16-byte reads) plus one zero row for taps outside the image.  8 waves: wave = (N tile, M tiles);
-// K runs over (tap, 8-channel block): lane half h takes channels 4h .. 4h+3 of the block, one 16-byte read each of A and B
-// feeds four MFMAs.  w2p: [parity][tap][c1 / 4][c2][4] so that the B read is 16 bytes per lane, consecutive over co.
+// ---- mid: ConvT2 of G items.  The items' inputs ([pixel][c1], masked for the tangent) are staged in LDS in mfma_conv.h's
+// layout.  8 waves: wave = (N tile, M tiles sharing the B read); K runs over (tap, 8-channel block).
+// w2p: [parity][tap][c1 / 4][c2][4].
 // MASKS = false (the image decode, primal only): no sign bits, mask1 / mask2 may be null.
 template <int C1, int C2, bool TANGENT, bool MASKS = true>
 __global__ __launch_bounds__(512) void vj_mid_kernel(const float *__restrict__ in, float *__restrict__ out,
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(512) void vj_mid_kernel(const float *__restrict__ i
             *reinterpret_cast<float4 *>(lds + (size_t)(g * P + pix) * LD + ci) = v;
         }
     }
-    for (int k = tid; k < LD; k += 512) lds[(size_t)ZR * LD + k] = 0.f;
+    mfma_conv::fill_zero_row<512>(lds, ZR, LD, tid);
     __syncthreads();
 
     const int lane = tid & 63, wave = tid >> 6;
@@ -212,38 +212,21 @@ __global__ __launch_bounds__(512) void vj_mid_kernel(const float *__restrict__ i
     for (int par = 0; par < 4; ++par) {
         const int py = par >> 1, px = par & 1;
         f32x16 acc[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[m][q] = 0.f;
+        mfma_conv::clear(acc);
         for (int tap = 0; tap < 4; ++tap) {
             const int a = tap >> 1, b = tap & 1;
             const float *ap[MT];
 #pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                const int iy = ry[m] + py - a, ix = rx[m] + px - b;
-                const bool ok = rv[m] && iy >= 0 && iy < s1 && ix >= 0 && ix < s1;
-                ap[m] = lds + (size_t)(ok ? rg[m] * P + iy * s1 + ix : ZR) * LD + 4 * h;
-            }
+            for (int m = 0; m < MT; ++m)
+                ap[m] = mfma_conv::tap_row(lds, LD, ZR, rv[m], rg[m], ry[m] + py - a, rx[m] + px - b, s1, P, h);
             const float4 *wp = reinterpret_cast<const float4 *>(w2p) + ((size_t)(par * 4 + tap) * (C1 / 4) + h) * C2 + co;
-#pragma unroll 4
-            for (int cb = 0; cb < C1 / 8; ++cb) {
-                const float4 bv = wp[(size_t)cb * 2 * C2];
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    const float4 av = *reinterpret_cast<const float4 *>(ap[m] + cb * 8);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[m], 0, 0, 0);
-                }
-            }
+            mfma_conv::k_chain<MT, 4>(acc, ap, wp, C1 / 8, C2);
         }
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int r = (m0 + m * WPN) * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int r = mfma_conv::acc_row(q, h, (m0 + m * WPN) * 32);
                 const int g = r < rows ? r / P : 0;
                 const int64_t slot = r < rows ? slot_s[g] : -1;
                 const bool valid = slot >= 0;
@@ -287,12 +270,8 @@ __global__ __launch_bounds__(256) void vj_back_kernel(const float *__restrict__ 
         const int64_t slot = TANGENT ? item_slot(s, resident, blockIdx.x, side) : slot0 + it;
         float *sg = sigp + (size_t)slot * nout;
         __syncthreads();
-        const float4 *src = reinterpret_cast<const float4 *>(in + (size_t)it * n2);
-        for (int q = tid; q < n2 / 4; q += 256) {
-            const int pix = (q * 4) / C2, ci = (q * 4) % C2;
-            *reinterpret_cast<float4 *>(lds + (size_t)pix * LD + ci) = src[q];
-        }
-        for (int k = tid; k < LD; k += 256) lds[(size_t)ZR * LD + k] = 0.f;
+        mfma_conv::stage_rows<C2, 256>(lds, in + (size_t)it * n2, P2, tid);
+        mfma_conv::fill_zero_row<256>(lds, ZR, LD, tid);
         __syncthreads();
         float ss = 0.f;
         for (int par = 0; par < 4; ++par) {
@@ -382,7 +361,7 @@ int run(const geo_vanilla_decoder_desc *dc, const Shape &sh, const float *zA, co
         int64_t n_resident, int64_t n_edges, float *len_out, void *ws, size_t ws_bytes, hipStream_t st, const char *who) {
     const int resident = n_resident > 0;
     int64_t eb = n_edges < EDGES_PER_PASS ? n_edges : EDGES_PER_PASS;
-    while (eb >= 1 && layout_bytes(sh, resident ? n_resident : 2 * eb, eb) > ws_bytes) eb = eb > 64 ? eb - eb / 8 : eb - 1;
+    while (eb >= 1 && layout_bytes(sh, resident ? n_resident : 2 * eb, eb) > ws_bytes) eb = geo::shrink_pass(eb);
     if (eb < 1) {
         geo::set_error("%s: workspace of %zu bytes is below the minimum of %zu", who, ws_bytes,
                        layout_bytes(sh, resident ? n_resident : 2, 1));
@@ -449,10 +428,6 @@ constexpr int SD_MAX_D = 64;
 constexpr int SD_MAX_DP = (SD_MAX_D + 1 + 7) & ~7;      // latent channels + the constant-one channel, in 8-channel K blocks
 constexpr int SD_ITEMS = MID_ROWS / 16;                 // 16 grids of 4 x 4 per first-stage workgroup
 
-size_t decode_bytes(size_t n1, size_t n2, int64_t items) {
-    return geo::align_up((size_t)items * n1 * 4) + geo::align_up((size_t)items * n2 * 4);
-}
-
 // ---- ConvT3 of one item per workgroup, as vj_back_kernel's point pass computes the logit (the same chain: b3, then taps
 // 0..3, channels in order), written to logits [C][So][So], So = 2 s2 - 2 crop: output rows and columns crop .. 2 s2 - crop - 1
 // (crop = 2 is the spatial decoder's padding 3 at 28 px: exactly the 32-px output without a border of two).
@@ -464,12 +439,8 @@ __global__ __launch_bounds__(256) void vj_image_kernel(const float *__restrict__
     const int P2 = s2 * s2, S = 2 * s2, So = S - 2 * crop, n2 = P2 * C2, ZR = P2;
     const int tid = threadIdx.x;
     float *img = logits + (size_t)blockIdx.x * CO * So * So;
-    const float4 *src = reinterpret_cast<const float4 *>(in + (size_t)blockIdx.x * n2);
-    for (int q = tid; q < n2 / 4; q += 256) {
-        const int pix = (q * 4) / C2, ci = (q * 4) % C2;
-        *reinterpret_cast<float4 *>(lds + (size_t)pix * LD + ci) = src[q];
-    }
-    for (int k = tid; k < LD; k += 256) lds[(size_t)ZR * LD + k] = 0.f;
+    mfma_conv::stage_rows<C2, 256>(lds, in + (size_t)blockIdx.x * n2, P2, tid);
+    mfma_conv::fill_zero_row<256>(lds, ZR, LD, tid);
     __syncthreads();
     for (int par = 0; par < 4; ++par) {
         const int py = par >> 1, px = par & 1;
@@ -547,10 +518,7 @@ __global__ __launch_bounds__(512) void sd_front_kernel(const float *__restrict__
     for (int par = 0; par < 4; ++par) {
         const int py = par >> 1, px = par & 1;
         f32x16 acc[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[m][q] = 0.f;
+        mfma_conv::clear(acc);
         for (int tap = 0; tap < 4; ++tap) {
             const int a = tap >> 1, b = tap & 1;
             const float *ap[MT];
@@ -562,23 +530,13 @@ __global__ __launch_bounds__(512) void sd_front_kernel(const float *__restrict__
                 ap[m] = lds + (size_t)(ok ? (r & ~15) + iy * 4 + ix : ZR) * LD + 4 * h;
             }
             const float4 *wp = reinterpret_cast<const float4 *>(w1p) + ((size_t)(par * 4 + tap) * (dp / 4) + h) * C1 + co;
-            for (int cb = 0; cb < dp / 8; ++cb) {
-                const float4 bv = wp[(size_t)cb * 2 * C1];
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    const float4 av = *reinterpret_cast<const float4 *>(ap[m] + cb * 8);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[m], 0, 0, 0);
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[m], 0, 0, 0);
-                }
-            }
+            for (int cb = 0; cb < dp / 8; ++cb) mfma_conv::k_block<MT>(acc, ap, cb, wp[(size_t)cb * 2 * C1]);
         }
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int r = (m0 + m * WPN) * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int r = mfma_conv::acc_row(q, h, (m0 + m * WPN) * 32);
                 const int g = r >> 4, y = (r >> 2) & 3, x = r & 3;
                 if (g < live) {
                     const int opix = (2 * y + py) * 8 + 2 * x + px;
@@ -611,16 +569,9 @@ int decode_tail(int c1, int c2, int co, int s1, int crop, const float *w2p, cons
     return GEO_OK;
 }
 
-// Items per pass that fit the workspace (0: not even one).
-int64_t decode_pass_items(size_t n1, size_t n2, int64_t n, size_t ws_bytes) {
-    int64_t pb = n < ITEMS_PER_PASS ? n : ITEMS_PER_PASS;
-    while (pb >= 1 && decode_bytes(n1, n2, pb) > ws_bytes) pb = pb > 64 ? pb - pb / 8 : pb - 1;
-    return pb;
-}
-
 struct SpatialShape {
     int d, dp, c1, c2, co, So, crop;
-    size_t n1, n2;
+    size_t per_item[2];        // floats per item of the two activation buffers
 };
 
 bool make_spatial_shape(const geo_spatial_image_decoder_desc *dc, SpatialShape *s) {
@@ -636,8 +587,8 @@ bool make_spatial_shape(const geo_spatial_image_decoder_desc *dc, SpatialShape *
     s->co = dc->out_channels;
     s->So = dc->out_size;
     s->crop = (32 - s->So) / 2;
-    s->n1 = (size_t)64 * s->c1;
-    s->n2 = (size_t)256 * s->c2;
+    s->per_item[0] = (size_t)64 * s->c1;
+    s->per_item[1] = (size_t)256 * s->c2;
     return true;
 }
 
@@ -690,7 +641,8 @@ extern "C" int geo_vanilla_jvp_edges(const geo_vanilla_decoder_desc *dec, const 
 extern "C" size_t geo_vanilla_decode_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n) {
     Shape sh;
     if (!make_shape(dec, &sh) || n < 0) return 0;
-    return decode_bytes(sh.n1, sh.n2, n < 1 ? 1 : (n < ITEMS_PER_PASS ? n : ITEMS_PER_PASS));
+    const size_t per_item[2] = {(size_t)sh.n1, (size_t)sh.n2};      // the two activation buffers of the image decode
+    return geo::pass_query_bytes(per_item, 2, ITEMS_PER_PASS, n);
 }
 
 extern "C" int geo_vanilla_decode(const geo_vanilla_decoder_desc *dec, const float *z, const int32_t *index, int64_t n,
@@ -701,26 +653,19 @@ extern "C" int geo_vanilla_decode(const geo_vanilla_decoder_desc *dec, const flo
     GEO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "geo_vanilla_decode: n %lld", (long long)n);
     if (n == 0) return GEO_OK;
     GEO_REQUIRE(z && logits_out && ws, "geo_vanilla_decode: null pointer");
-    const int64_t pb = decode_pass_items(sh.n1, sh.n2, n, ws_bytes);
-    if (pb < 1) {
-        geo::set_error("geo_vanilla_decode: workspace of %zu bytes is below the minimum of %zu", ws_bytes, decode_bytes(sh.n1, sh.n2, 1));
-        return GEO_E_WORKSPACE;
-    }
-    geo::Arena ar(ws, ws_bytes);
-    float *buf1 = ar.take<float>((size_t)pb * sh.n1);
-    float *buf2 = ar.take<float>((size_t)pb * sh.n2);
-    if (!buf1 || !buf2) {
-        geo::set_error("geo_vanilla_decode: workspace too small");
-        return GEO_E_WORKSPACE;
-    }
+    const size_t per_item[2] = {(size_t)sh.n1, (size_t)sh.n2};
+    int64_t pb;
+    float *buf[2];
+    rc = geo::plan_passes("geo_vanilla_decode", per_item, 2, ITEMS_PER_PASS, n, ws, ws_bytes, &pb, buf);
+    if (rc != GEO_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     for (int64_t p0 = 0; p0 < n; p0 += pb) {
         const int64_t cnt = n - p0 < pb ? n - p0 : pb;
         const Ends e{z, z, index, nullptr, p0, (int)cnt};
         const dim3 grid((unsigned)((cnt + FRONT_ROWS - 1) / FRONT_ROWS), FRONT_SPLIT);
-        vj_front_kernel<false, false><<<grid, 256, 0, st>>>(e, (int)cnt, sh.d, sh.dp, sh.n1, dec->At, dec->c, buf1, nullptr, 0);
+        vj_front_kernel<false, false><<<grid, 256, 0, st>>>(e, (int)cnt, sh.d, sh.dp, sh.n1, dec->At, dec->c, buf[0], nullptr, 0);
         GEO_LAUNCH_CHECK();
-        rc = decode_tail(sh.c1, sh.c2, sh.co, sh.s1, 0, dec->w2p, dec->scale2, dec->shift2, dec->w3p, dec->b3, buf1, buf2, cnt,
+        rc = decode_tail(sh.c1, sh.c2, sh.co, sh.s1, 0, dec->w2p, dec->scale2, dec->shift2, dec->w3p, dec->b3, buf[0], buf[1], cnt,
                          logits_out + (size_t)p0 * sh.nout, st);
         if (rc != GEO_OK) return rc;
     }
@@ -730,7 +675,7 @@ extern "C" int geo_vanilla_decode(const geo_vanilla_decoder_desc *dec, const flo
 extern "C" size_t geo_spatial_decode_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int64_t n) {
     SpatialShape sh;
     if (!make_spatial_shape(dec, &sh) || n < 0) return 0;
-    return decode_bytes(sh.n1, sh.n2, n < 1 ? 1 : (n < ITEMS_PER_PASS ? n : ITEMS_PER_PASS));
+    return geo::pass_query_bytes(sh.per_item, 2, ITEMS_PER_PASS, n);
 }
 
 extern "C" int geo_spatial_decode(const geo_spatial_image_decoder_desc *dec, const float *z, const float *table, const int32_t *codes,
@@ -744,30 +689,22 @@ extern "C" int geo_spatial_decode(const geo_spatial_image_decoder_desc *dec, con
     GEO_REQUIRE((z != nullptr) != (table != nullptr || codes != nullptr) && (table != nullptr) == (codes != nullptr),
                 "geo_spatial_decode: give either z or (table, codes), not both and not neither");
     GEO_REQUIRE(logits_out && ws, "geo_spatial_decode: null pointer");
-    const int64_t pb = decode_pass_items(sh.n1, sh.n2, n, ws_bytes);
-    if (pb < 1) {
-        geo::set_error("geo_spatial_decode: workspace of %zu bytes is below the minimum of %zu", ws_bytes, decode_bytes(sh.n1, sh.n2, 1));
-        return GEO_E_WORKSPACE;
-    }
-    geo::Arena ar(ws, ws_bytes);
-    float *buf1 = ar.take<float>((size_t)pb * sh.n1);
-    float *buf2 = ar.take<float>((size_t)pb * sh.n2);
-    if (!buf1 || !buf2) {
-        geo::set_error("geo_spatial_decode: workspace too small");
-        return GEO_E_WORKSPACE;
-    }
+    int64_t pb;
+    float *buf[2];
+    int rc = geo::plan_passes("geo_spatial_decode", sh.per_item, 2, ITEMS_PER_PASS, n, ws, ws_bytes, &pb, buf);
+    if (rc != GEO_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t nout = (size_t)sh.co * sh.So * sh.So;
     for (int64_t p0 = 0; p0 < n; p0 += pb) {
         const int64_t cnt = n - p0 < pb ? n - p0 : pb;
         const unsigned grid = (unsigned)((cnt + SD_ITEMS - 1) / SD_ITEMS);
         if (sh.c1 == 128)
-            sd_front_kernel<128><<<grid, 512, 0, st>>>(z, table, codes, p0, cnt, sh.d, sh.dp, dec->w1p, dec->scale1, dec->shift1, buf1);
+            sd_front_kernel<128><<<grid, 512, 0, st>>>(z, table, codes, p0, cnt, sh.d, sh.dp, dec->w1p, dec->scale1, dec->shift1, buf[0]);
         else
-            sd_front_kernel<64><<<grid, 512, 0, st>>>(z, table, codes, p0, cnt, sh.d, sh.dp, dec->w1p, dec->scale1, dec->shift1, buf1);
+            sd_front_kernel<64><<<grid, 512, 0, st>>>(z, table, codes, p0, cnt, sh.d, sh.dp, dec->w1p, dec->scale1, dec->shift1, buf[0]);
         GEO_LAUNCH_CHECK();
-        int rc = decode_tail(sh.c1, sh.c2, sh.co, 8, sh.crop, dec->w2p, dec->scale2, dec->shift2, dec->w3p, dec->b3, buf1, buf2, cnt,
-                             logits_out + (size_t)p0 * nout, st);
+        rc = decode_tail(sh.c1, sh.c2, sh.co, 8, sh.crop, dec->w2p, dec->scale2, dec->shift2, dec->w3p, dec->b3, buf[0], buf[1], cnt,
+                         logits_out + (size_t)p0 * nout, st);
         if (rc != GEO_OK) return rc;
     }
     return GEO_OK;

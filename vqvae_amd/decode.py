@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import device, ptr, stream_ptr, workspace
+from ._device import device, ptr, stream_ptr
+from ._export import capped_workspace, eval_mode
 from .spatial_decoder import SpatialImageDecoderExport, looks_like_spatial_decoder, spatial_image_kernels_cover
 from .vanilla_decoder import VanillaDecoderExport, looks_like_vanilla_decoder, vanilla_kernels_cover
 
@@ -85,12 +86,7 @@ def _native(export, spatial: bool, z, table, codes, n: int, max_workspace_bytes)
     codes = None if codes is None else codes.to(dev, torch.int32).contiguous()
     query = lib.geo_spatial_decode_workspace_bytes if spatial else lib.geo_vanilla_decode_workspace_bytes
     with torch.cuda.device(dev):
-        nbytes = query(export.desc, n)
-        if nbytes == 0:
-            raise _lib.GeoHipError("decode: decoder configuration not supported by the HIP path")
-        if max_workspace_bytes is not None:
-            nbytes = min(nbytes, int(max_workspace_bytes))
-        ws = workspace(nbytes, dev)[:nbytes]
+        ws = capped_workspace(query(export.desc, n), max_workspace_bytes, dev, "decode: decoder")
         if spatial:
             _lib.check(lib.geo_spatial_decode(export.desc, ptr(z), ptr(table), ptr(codes), n, ptr(out), ptr(ws), ws.numel(),
                                               stream_ptr()), "geo_spatial_decode")
@@ -106,9 +102,7 @@ def _torch_route(decoder: nn.Module, spatial: bool, z, table, codes, n: int) -> 
     quantized latents first, grids as contiguous NCHW tensors (a convolution library may sum a channels-last view of the same
     values in another order)."""
     dev = next(decoder.parameters()).device
-    modes = [(m, m.training) for m in decoder.modules()]
-    decoder.eval()
-    try:
+    with eval_mode(decoder):
         out = []
         for i in range(0, n, _TORCH_BATCH):
             if z is not None:
@@ -122,9 +116,6 @@ def _torch_route(decoder: nn.Module, spatial: bool, z, table, codes, n: int) -> 
             probe = z[:0] if z is not None else table.new_zeros((0, table.shape[1]) + ((4, 4) if spatial else ()))
             out.append(decoder(probe.to(dev, torch.float32)).float())
         return torch.cat(out)
-    finally:
-        for m, mode in modes:
-            m.training = mode
 
 
 def decode_logits(decoder_or_export, z: Optional[torch.Tensor] = None, *, table: Optional[torch.Tensor] = None,

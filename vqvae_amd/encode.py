@@ -19,7 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import device, ptr, stream_ptr, workspace
+from ._device import device, ptr, stream_ptr
+from ._export import capped_workspace, eval_mode
 from .image_encoder import ImageEncoderExport, encoder_kernels_cover
 
 _last_encode_path = None
@@ -50,12 +51,7 @@ def _native(export: ImageEncoderExport, x: torch.Tensor, max_workspace_bytes) ->
         raise ValueError(f"{n} images: the encode takes fewer than 2^31")
     x = x.detach().to(dev, torch.float32).contiguous()
     with torch.cuda.device(dev):
-        nbytes = lib.geo_image_encode_workspace_bytes(export.desc, n)
-        if nbytes == 0:
-            raise _lib.GeoHipError("encode: encoder configuration not supported by the HIP path")
-        if max_workspace_bytes is not None:
-            nbytes = min(nbytes, int(max_workspace_bytes))
-        ws = workspace(nbytes, dev)[:nbytes]
+        ws = capped_workspace(lib.geo_image_encode_workspace_bytes(export.desc, n), max_workspace_bytes, dev, "encode: encoder")
         _lib.check(lib.geo_image_encode(export.desc, ptr(x), n, ptr(mu), ptr(logvar), ptr(ws), ws.numel(), stream_ptr()),
                    "geo_image_encode")
     return mu, logvar
@@ -65,9 +61,7 @@ def _native(export: ImageEncoderExport, x: torch.Tensor, max_workspace_bytes) ->
 def _torch_route(encoder: nn.Module, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """The module itself in eval() (its layers' own modes are put back afterwards), in batches of 512."""
     dev = next(encoder.parameters()).device
-    modes = [(m, m.training) for m in encoder.modules()]
-    encoder.eval()
-    try:
+    with eval_mode(encoder):
         mus, logvars = [], []
         for i in range(0, int(x.shape[0]), _TORCH_BATCH):
             mu, logvar = encoder(x[i:i + _TORCH_BATCH].to(dev, torch.float32))
@@ -76,9 +70,6 @@ def _torch_route(encoder: nn.Module, x: torch.Tensor) -> Tuple[torch.Tensor, tor
             mu, logvar = encoder(x.new_zeros((1,) + tuple(x.shape[1:])).to(dev, torch.float32))
             mus.append(mu.float()[:0]), logvars.append(logvar.float()[:0])
         return torch.cat(mus), torch.cat(logvars)
-    finally:
-        for m, mode in modes:
-            m.training = mode
 
 
 def encode_latents(encoder_or_export, x: torch.Tensor, *, max_workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:

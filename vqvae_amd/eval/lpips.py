@@ -19,7 +19,6 @@ The function (normalize=False, spatial=False), for x0, x1 f32 [n, 3, H, W] in [-
 
 Passing a module packs its weights on every call; a caller that evaluates repeatedly builds `LPIPSExport` once.
 """
-import ctypes
 from typing import Optional, Union
 
 import torch
@@ -27,6 +26,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
+from .._export import capped_workspace, fill_desc
+from .._export import conv_taps as _taps
 
 SHIFT = (-.030, -.088, -.188)
 SCALE = (.458, .448, .450)
@@ -151,12 +152,6 @@ def native_lpips_covers(x: torch.Tensor) -> bool:
             and tuple(x.shape[1:]) == (3, NATIVE_SIZE, NATIVE_SIZE))
 
 
-def _taps(w: torch.Tensor) -> torch.Tensor:
-    """Conv2d weight [cout][cin][k][k] -> [tap k ky + kx][cin / 4][cout][4]: element (tap, q, co, r) = w[co][4 q + r][ky][kx]."""
-    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
-    return w.permute(2, 3, 1, 0).reshape(k * k, cin // 4, 4, cout).permute(0, 1, 3, 2)
-
-
 def _first(w: torch.Tensor) -> torch.Tensor:
     """conv1.weight [64][3][11][11] -> [c 11 + ky][h][co][8]: element s < 6 = w[co][c][ky][2 s + h], 0 where kx = 11, s = 6, 7."""
     wk = torch.zeros(64, 3, 11, 16, dtype=w.dtype)
@@ -181,14 +176,11 @@ class LPIPSExport:
                 host[f"lin{k}"] = lin.detach().to("cpu", torch.float32)
         self.tensors = {k: v.contiguous().to(dev) for k, v in host.items()}
         self.device = torch.device(dev)
-        desc = _lib.LPIPSAlexDesc()
-        for name, t in self.tensors.items():
-            setattr(desc, name, ctypes.c_void_p(t.data_ptr()))
-        self.desc = desc
+        self.desc = fill_desc(_lib.LPIPSAlexDesc(), self.tensors)
 
 
 def _native(export: LPIPSExport, x0: torch.Tensor, x1: torch.Tensor, per_layer: bool, max_workspace_bytes) -> torch.Tensor:
-    from .._device import ptr, stream_ptr, workspace
+    from .._device import ptr, stream_ptr
     lib = _lib.load()
     dev = export.device
     n = int(x0.shape[0])
@@ -201,10 +193,7 @@ def _native(export: LPIPSExport, x0: torch.Tensor, x1: torch.Tensor, per_layer: 
     x0 = x0.detach().to(dev).contiguous()
     x1 = x1.detach().to(dev).contiguous()
     with torch.cuda.device(dev):
-        nbytes = lib.geo_lpips_alex_workspace_bytes(n)
-        if max_workspace_bytes is not None:
-            nbytes = min(nbytes, int(max_workspace_bytes))
-        ws = workspace(nbytes, dev)[:nbytes]
+        ws = capped_workspace(lib.geo_lpips_alex_workspace_bytes(n), max_workspace_bytes, dev, "lpips: network")
         _lib.check(lib.geo_lpips_alex(export.desc, ptr(x0), ptr(x1), n, ptr(total), ptr(layers), ptr(ws), ws.numel(), stream_ptr()),
                    "geo_lpips_alex")
     return layers if per_layer else total

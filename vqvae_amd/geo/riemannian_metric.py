@@ -16,6 +16,7 @@ import torch
 
 from .. import _lib
 from .._device import device, ptr, stream_ptr, workspace
+from .._export import capped_workspace
 from ..spatial_decoder import DecoderExport, hip_kernels_cover, looks_like_spatial_decoder
 from ..vanilla_decoder import VanillaDecoderExport, vanilla_kernels_cover
 
@@ -67,13 +68,6 @@ def edge_lengths_graph_device(export: DecoderExport, z: torch.Tensor, src: torch
     return out
 
 
-def _vanilla_workspace(query_bytes: int, max_workspace_bytes, what: str, dev: torch.device) -> torch.Tensor:
-    if query_bytes == 0:
-        raise _lib.GeoHipError(f"{what}: decoder configuration not supported by the HIP path")
-    nbytes = query_bytes if max_workspace_bytes is None else min(query_bytes, int(max_workspace_bytes))
-    return workspace(nbytes, dev)[:nbytes]
-
-
 def edge_lengths_vanilla_device(export: VanillaDecoderExport, z_start: torch.Tensor, z_end: torch.Tensor,
                                 max_workspace_bytes=None) -> torch.Tensor:
     """Vanilla-decoder HIP path on explicit endpoint arrays (f32, contiguous, on the export's device).  The edges are cut
@@ -87,8 +81,8 @@ def edge_lengths_vanilla_device(export: VanillaDecoderExport, z_start: torch.Ten
     if E == 0:
         return out
     with torch.cuda.device(dev):
-        ws = _vanilla_workspace(lib.geo_vanilla_jvp_workspace_bytes(export.desc, E), max_workspace_bytes,
-                                "geo_vanilla_jvp_workspace_bytes", dev)
+        ws = capped_workspace(lib.geo_vanilla_jvp_workspace_bytes(export.desc, E), max_workspace_bytes, dev,
+                              "geo_vanilla_jvp_workspace_bytes: decoder")
         _lib.check(lib.geo_vanilla_jvp_pairs(export.desc, ptr(z_start), ptr(z_end), E, 0, ptr(out), ptr(ws), ws.numel(),
                                              stream_ptr()), "geo_vanilla_jvp_pairs")
     return out
@@ -110,8 +104,8 @@ def edge_lengths_vanilla_graph_device(export: VanillaDecoderExport, z: torch.Ten
     if int(lo) < 0 or int(hi) >= N:
         raise ValueError(f"edge endpoints outside [0, {N})")
     with torch.cuda.device(dev):
-        ws = _vanilla_workspace(lib.geo_vanilla_jvp_edges_workspace_bytes(export.desc, N, E), max_workspace_bytes,
-                                "geo_vanilla_jvp_edges_workspace_bytes", dev)
+        ws = capped_workspace(lib.geo_vanilla_jvp_edges_workspace_bytes(export.desc, N, E), max_workspace_bytes, dev,
+                              "geo_vanilla_jvp_edges_workspace_bytes: decoder")
         _lib.check(lib.geo_vanilla_jvp_edges(export.desc, ptr(z), N, ptr(src), ptr(dst), E, 0, ptr(out), ptr(ws), ws.numel(),
                                              stream_ptr()), "geo_vanilla_jvp_edges")
     return out

@@ -8,14 +8,13 @@ FIXED statistics -- eval-mode BatchNorm with running statistics, or no normalisa
 `ImageEncoderExport` folds each norm and its convolution's bias into one scale and one shift per channel in fp64, lays the
 weights out as the kernels read them (the vanilla head permuted from the module's channel-major flatten to the activations'
 pixel-major order), rounds once to f32 and holds the `geo_image_encoder_desc` of include/geo_hip.h over those tensors."""
-import ctypes
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .vanilla_decoder import _fixed_statistics, _fold
+from ._export import _fixed_statistics, _fold, conv_taps, f64, fill_desc, pack_k_quads
 
 COVERED_ENC_WIDTHS = ((64, 128, 256), (32, 64, 128))          # enc_channels the kernels are compiled for
 COVERED_INPUTS = {1: 28, 3: 32}                               # in_channels -> image size
@@ -96,12 +95,6 @@ def encoder_kernels_cover(m: nn.Module, in_size: Optional[int] = None) -> bool:
     return 1 <= d <= (MAX_VANILLA_LATENT_DIM if vanilla else MAX_SPATIAL_LATENT_DIM)
 
 
-def _taps(w: torch.Tensor) -> torch.Tensor:
-    """Conv2d(k3) weight [cout][cin][3][3] -> [tap 3 ky + kx][cin / 4][cout][4]: element (tap, q, co, r) = w[co][4 q + r][ky][kx]."""
-    cout, cin = w.shape[:2]
-    return w.permute(2, 3, 1, 0).reshape(9, cin // 4, 4, cout).permute(0, 1, 3, 2)
-
-
 class ImageEncoderExport:
     """A covered encoder as geo_image_encode reads it: f32 tensors on `dev` plus the ctypes descriptor over them.  `host` keeps
     the same arrays in fp64, before the one rounding: "w1p" [9 C][e1], "w2p" [9][e1 / 4][e2][4], "w3p" [9][e2 / 4][e3][4],
@@ -118,23 +111,19 @@ class ImageEncoderExport:
         C, e1, e2, e3 = conv1.in_channels, conv1.out_channels, conv2.out_channels, conv3.out_channels
         d = enc.fc_mu.out_channels if self.spatial else enc.fc_mu.out_features
         npad = (2 * d + 31) // 32 * 32
-
-        def f64(t):
-            return t.detach().double().cpu()
-
         host = {}
         with torch.no_grad():
             for tag, (conv, norm) in zip("123", stages):
                 scale, shift = _fold(norm, conv.out_channels)
                 host["scale" + tag], host["shift" + tag] = scale, shift + scale * f64(conv.bias)
             host["w1p"] = f64(conv1.weight).permute(1, 2, 3, 0).reshape(9 * C, e1)
-            host["w2p"], host["w3p"] = _taps(f64(conv2.weight)), _taps(f64(conv3.weight))
+            host["w2p"], host["w3p"] = conv_taps(f64(conv2.weight)), conv_taps(f64(conv3.weight))
             wh = torch.cat([f64(enc.fc_mu.weight).reshape(d, -1), f64(enc.fc_logvar.weight).reshape(d, -1)])    # [2 d][K]
             nseg = 1 if self.spatial else 16
             wh = wh.view(2 * d, e3, nseg).permute(2, 1, 0)                 # [segment = pixel][channel][column]
             whp = torch.zeros(nseg, e3, npad, dtype=torch.float64)
             whp[:, :, :2 * d] = wh
-            host["whp"] = whp.reshape(nseg, e3 // 4, 4, npad).permute(0, 1, 3, 2)
+            host["whp"] = pack_k_quads(whp)
             bh = torch.zeros(npad, dtype=torch.float64)
             bh[:2 * d] = torch.cat([f64(enc.fc_mu.bias), f64(enc.fc_logvar.bias)])
             host["bh"] = bh
@@ -144,6 +133,4 @@ class ImageEncoderExport:
         desc = _lib.ImageEncoderDesc()
         desc.in_channels, desc.in_size, desc.e1, desc.e2, desc.e3 = C, self.in_size, e1, e2, e3
         desc.latent_dim, desc.spatial_head = d, int(self.spatial)
-        for name, t in self.tensors.items():
-            setattr(desc, name, ctypes.c_void_p(t.data_ptr()))
-        self.desc = desc
+        self.desc = fill_desc(desc, self.tensors)

@@ -8,14 +8,14 @@ reference's own SpatialDecoder instances are accepted by duck typing) and the ex
 weights into the `geo_decoder_desc` of include/geo_hip.h.  Encoder, losses and training are out
 of scope.
 """
-import ctypes
 from typing import Mapping, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .vanilla_decoder import COVERED_WIDTHS, _fixed_statistics, _fold, _parity_taps
+from ._export import _fixed_statistics, _fold, _parity_taps, f32, f64, fill_desc, pack_k_quads
+from .vanilla_decoder import COVERED_WIDTHS
 
 MAX_IMAGE_LATENT_DIM = 64
 
@@ -157,9 +157,7 @@ class DecoderExport:
                                    and norm.momentum is not None)
         d.update_running = 1 if self.tracks_running else 0
         d.momentum = float(norm.momentum) if self.tracks_running else 0.0
-        for name, t in self.tensors.items():
-            setattr(d, name, None if t is None else ctypes.c_void_p(t.data_ptr()))
-        self.desc = d
+        self.desc = fill_desc(d, self.tensors)
 
     def commit_running_stats(self, n_calls: int) -> None:
         """After a JVP run over `n_calls` decoder calls (2 per chunk): write the updated statistics back when the export
@@ -215,9 +213,6 @@ class SpatialImageDecoderExport:
         conv1, norm1, conv2, norm2, out = seq[0], seq[1], seq[3], seq[4], seq[6]
         d, c0, c1, c2, C = dec.conv_in.in_channels, dec.conv_in.out_channels, conv1.out_channels, conv2.out_channels, out.out_channels
 
-        def f64(t):
-            return t.detach().double().cpu()
-
         with torch.no_grad():
             aug = torch.cat([f64(dec.conv_in.weight).view(c0, d), f64(dec.conv_in.bias)[:, None]], 1)      # [c0][d + 1]
             W = torch.einsum("ck,ptco->ptko", aug, _parity_taps(f64(conv1.weight)))                        # [4][4][d + 1][c1]
@@ -226,21 +221,16 @@ class SpatialImageDecoderExport:
             dp = (d + 1 + 7) // 8 * 8
             w1p = torch.zeros(4, 4, dp, c1, dtype=torch.float64)
             w1p[:, :, :d + 1] = W
-            w1p = w1p.reshape(4, 4, dp // 4, 4, c1).permute(0, 1, 2, 4, 3)                                 # [4][4][dp / 4][c1][4]
+            w1p = pack_k_quads(w1p)                                                                        # [4][4][dp / 4][c1][4]
             scale2, shift2 = _fold(norm2, c2)
             shift2 = shift2 + scale2 * f64(conv2.bias)
-            w2p = _parity_taps(f64(conv2.weight)).reshape(4, 4, c1 // 4, 4, c2).permute(0, 1, 2, 4, 3)     # [4][4][c1 / 4][c2][4]
+            w2p = pack_k_quads(_parity_taps(f64(conv2.weight)))                                            # [4][4][c1 / 4][c2][4]
             w3p = _parity_taps(f64(out.weight)).permute(0, 1, 3, 2)                                        # [4][4][C][c2]
-
-        def f32(t):
-            return t.to(torch.float32).contiguous().to(dev)
-
         self.host = {"W": W, "scale1": scale1, "shift1": shift1}
-        self.tensors = {"w1p": f32(w1p), "scale1": f32(scale1), "shift1": f32(shift1), "w2p": f32(w2p), "scale2": f32(scale2),
-                        "shift2": f32(shift2), "w3p": f32(w3p), "b3": f32(f64(out.bias))}
+        packed = {"w1p": w1p, "scale1": scale1, "shift1": shift1, "w2p": w2p, "scale2": scale2, "shift2": shift2, "w3p": w3p,
+                  "b3": f64(out.bias)}
+        self.tensors = {k: f32(v, dev) for k, v in packed.items()}
         self.latent_dim, self.out_channels, self.out_size = d, C, {1: 32, 3: 28}[out.padding[0]]
         desc = _lib.SpatialImageDecoderDesc()
         desc.latent_dim, desc.c1, desc.c2, desc.out_channels, desc.out_size = d, c1, c2, C, self.out_size
-        for name, t in self.tensors.items():
-            setattr(desc, name, ctypes.c_void_p(t.data_ptr()))
-        self.desc = desc
+        self.desc = fill_desc(desc, self.tensors)

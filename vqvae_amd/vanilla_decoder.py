@@ -8,13 +8,12 @@ With fixed statistics everything up to the first norm's scale and shift is affin
 once in fp64 (pre1 = A z + c, rounded to f32), folds the second norm into a scale and a shift, re-lays the two k4 transposed
 convolutions out by output-pixel parity and tap, and holds the `geo_vanilla_decoder_desc` of include/geo_hip.h over those
 tensors.  DESIGN.md section 15."""
-import ctypes
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from ._export import _fixed_statistics, _fold, _parity_taps, f32, f64, fill_desc, pack_k_quads  # noqa: F401 (re-exported)
 
 MAX_LATENT_DIM = 128
 COVERED_WIDTHS = ((128, 64), (64, 32))          # (dec_channels[1], dec_channels[2]) the kernels are compiled for
@@ -52,14 +51,6 @@ def looks_like_vanilla_decoder(m: nn.Module) -> bool:
     return len(kinds) == 1 and kinds <= {nn.BatchNorm2d, nn.GroupNorm, nn.Identity}
 
 
-def _fixed_statistics(norm: nn.Module) -> bool:
-    if isinstance(norm, nn.Identity):
-        return True
-    # torch normalises with the running statistics exactly when the LAYER is in eval mode and tracks them
-    return (isinstance(norm, nn.BatchNorm2d) and not norm.training and norm.running_mean is not None
-            and norm.running_var is not None)
-
-
 def vanilla_kernels_cover(m: nn.Module) -> bool:
     """Whether csrc/vanilla_jvp.hip implements this module (else the caller differentiates it with autograd).  Exactly:
     looks_like_vanilla_decoder(m), and
@@ -81,30 +72,6 @@ def vanilla_kernels_cover(m: nn.Module) -> bool:
             and m.output_layer.out_channels in (1, 3))
 
 
-def _fold(norm: nn.Module, channels: int):
-    """(scale, shift) in fp64 on the CPU of a fixed-statistics norm layer: y = scale x + shift."""
-    if isinstance(norm, nn.Identity):
-        return torch.ones(channels, dtype=torch.float64), torch.zeros(channels, dtype=torch.float64)
-    rm, rv = norm.running_mean.detach().double().cpu(), norm.running_var.detach().double().cpu()
-    scale = 1.0 / torch.sqrt(rv + norm.eps)
-    if norm.weight is not None:
-        scale = scale * norm.weight.detach().double().cpu()
-    shift = -rm * scale
-    if norm.bias is not None:
-        shift = shift + norm.bias.detach().double().cpu()
-    return scale, shift
-
-
-def _parity_taps(w: torch.Tensor) -> torch.Tensor:
-    """ConvTranspose2d(k4, s2, p1) weight [cin][cout][4][4] -> [parity 2 py + px][tap 2 a + b][cin][cout]: output pixel
-    (2 y + py, 2 x + px) reads input pixel (y + py - a, x + px - b) through kernel element (2 a + 1 - py, 2 b + 1 - px)."""
-    rows = []
-    for py in (0, 1):
-        for px in (0, 1):
-            rows.append(torch.stack([w[:, :, 2 * a + 1 - py, 2 * b + 1 - px] for a in (0, 1) for b in (0, 1)]))
-    return torch.stack(rows)
-
-
 class VanillaDecoderExport:
     """The composed front, the folded second norm and the re-laid-out convolutions of a covered decoder as f32 tensors on
     `dev`, plus the ctypes descriptor over them.  `A` [n1, d] and `c` [n1] are the composed front (n = pixel * c1 + channel).
@@ -118,10 +85,6 @@ class VanillaDecoderExport:
         out = dec.output_layer
         d, c1, c2, C = dec.fc.in_features, conv1.out_channels, conv2.out_channels, out.out_channels
         s1 = 7 + conv1.output_padding[0]
-
-        def f64(t):
-            return t.detach().double().cpu()
-
         with torch.no_grad():
             # the affine front on the zero latent and the d unit latents, in fp64
             basis = torch.cat([torch.zeros(1, d, dtype=torch.float64), torch.eye(d, dtype=torch.float64)])
@@ -136,21 +99,14 @@ class VanillaDecoderExport:
             At[:d] = h[1:] - c
             scale2, shift2 = _fold(norm2, c2)
             shift2 = shift2 + scale2 * f64(conv2.bias)
-            w2p = _parity_taps(f64(conv2.weight))                                    # [4][4][c1][c2]
-            w2p = w2p.reshape(4, 4, c1 // 4, 4, c2).permute(0, 1, 2, 4, 3)           # [4][4][c1 / 4][c2][4]
+            w2p = pack_k_quads(_parity_taps(f64(conv2.weight)))                      # [4][4][c1 / 4][c2][4]
             w3p = _parity_taps(f64(out.weight)).permute(0, 1, 3, 2)                  # [4][4][C][c2]
-
-        def f32(t):
-            return t.to(torch.float32).contiguous().to(dev)
-
-        self.tensors = {"At": f32(At), "c": f32(c), "w2p": f32(w2p), "scale2": f32(scale2), "shift2": f32(shift2),
-                        "w3p": f32(w3p), "b3": f32(f64(out.bias))}
+        host = {"At": At, "c": c, "w2p": w2p, "scale2": scale2, "shift2": shift2, "w3p": w3p, "b3": f64(out.bias)}
+        self.tensors = {k: f32(v, dev) for k, v in host.items()}
         self.latent_dim, self.out_size, self.n1 = d, 4 * s1, s1 * s1 * c1
         desc = _lib.VanillaDecoderDesc()
         desc.latent_dim, desc.c1, desc.c2, desc.out_channels, desc.out_size = d, c1, c2, C, 4 * s1
-        for name, t in self.tensors.items():
-            setattr(desc, name, ctypes.c_void_p(t.data_ptr()))
-        self.desc = desc
+        self.desc = fill_desc(desc, self.tensors)
 
     @property
     def A(self) -> torch.Tensor:
