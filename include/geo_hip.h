@@ -314,11 +314,27 @@ size_t geo_jvp_workspace_bytes(const geo_decoder_desc *dec, int64_t n_edges, int
  * 0.75 * latent_dim edges per latent the call goes one step further and computes the decoder Jacobian once per latent (its
  * latent_dim columns, n_nodes * latent_dim * 32 or 192 floats of this workspace), each edge end from those columns: same
  * quantity, another summation order (within 1e-6 of the per-edge-end lengths; option jvp_node_jacobian = 0 turns it off).
- * A workspace of geo_jvp_workspace_bytes() still works: the call then takes the per-edge-end path. */
+ * A workspace of geo_jvp_workspace_bytes() still works: the call then takes the per-edge-end path.
+ * The edges-per-latent rule counts the edges of the call.  A caller that computes a graph's lengths in several calls (the ranks of
+ * a sharded build, or slices in one process) uses the *_part forms below and tells each call the edge count of the whole build:
+ * the two routes differ in their last bits, and only then do all parts take the route the whole graph would. */
 size_t geo_jvp_edges_workspace_bytes(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size);
 int geo_decoder_jvp_edges(const geo_decoder_desc *dec, const float *z, int64_t n_nodes,
                           const int32_t *src, const int32_t *dst, int64_t n_edges, int32_t batch_size,
                           float *len_out, void *ws, size_t ws_bytes, void *stream);
+/* The same call for n_edges edges that are a part of a build of build_edges edges over the same latents (build_edges >= n_edges,
+ * else GEO_E_ARG before any launch; build_edges = n_edges is geo_decoder_jvp_edges itself).  build_edges enters the
+ * edges-per-latent rule above and nothing else: passes, slots and the workspace are sized by the call's own n_edges.  For decoders
+ * with fixed statistics the lengths then do not depend on how the edges of a build are divided among calls or ranks, provided every
+ * call is told the build's edge count AND is given at least the workspace its own geo_jvp_edges_part_workspace_bytes query sizes
+ * (the route also depends on ws_bytes: a part with less room, e.g. geo_jvp_workspace_bytes() only, falls back to the per-edge-end
+ * path whatever the build's count): both routes compute an edge from its own two latents alone.  (Train-mode BatchNorm never
+ * takes the Jacobian route; its lengths depend on the chunks, which a caller keeps whole.) */
+size_t geo_jvp_edges_part_workspace_bytes(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int64_t build_edges,
+                                          int32_t batch_size);
+int geo_decoder_jvp_edges_part(const geo_decoder_desc *dec, const float *z, int64_t n_nodes,
+                               const int32_t *src, const int32_t *dst, int64_t n_edges, int64_t build_edges, int32_t batch_size,
+                               float *len_out, void *ws, size_t ws_bytes, void *stream);
 
 /* Which kernels a geo_decoder_jvp_edges (graph_edges != 0) or geo_decoder_jvp_pairs (graph_edges = 0, n_nodes ignored) call with
  * these sizes runs under the current options: the decision the call itself makes, host arithmetic only (no GPU call).
@@ -346,6 +362,9 @@ int geo_decoder_jvp_edges(const geo_decoder_desc *dec, const float *z, int64_t n
 #define GEO_JVP_PLAN_PASSES(p) ((p) >> 16)              /* passes over the (pseudo-)edges, capped at 32767 */
 int geo_jvp_plan(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size, int32_t graph_edges,
                  size_t ws_bytes);
+/* ... of a geo_decoder_jvp_edges_part call (graph_edges != 0; build_edges >= n_edges, else GEO_E_ARG) */
+int geo_jvp_plan_part(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int64_t build_edges, int32_t batch_size,
+                      int32_t graph_edges, size_t ws_bytes);
 
 /* Same quantity for explicit endpoint arrays (edge_lengths_riemannian's own signature):
  * z_start / z_end f32 [E][d]. */

@@ -1,7 +1,8 @@
 """One rank of the multi-rank GPU test (tests/test_gpu_multirank.py starts N fresh copies of this script, all on the
 box's GPU(s), rendezvous over gloo on 127.0.0.1): the sharded hot path on HIP kernels -- gather_latents, sharded kNN,
 sharded edge lengths (whole BatchNorm chunks per rank), the replicated k-means++ chain, sharded assignment solve --
-on C1 (2 048 latents, d=16, k=20, K=64).  Writes this rank's results to <out_dir>/rank<r>.npz."""
+on C1 (2 048 latents, d=16, k=20, K=64; GEO_TEST_SHAPE), with a train-mode BatchNorm decoder or one with fixed statistics
+(GEO_TEST_DECODER).  Writes this rank's results to <out_dir>/rank<r>.npz."""
 import os
 import sys
 
@@ -11,6 +12,9 @@ import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+# GEO_TEST_DECODER -> (norm layer, decoder.training); test_gpu_multirank.py builds its single-process decoder from the same table
+DECODERS = {"batch_train": ("batch", True), "batch_eval": ("batch", False), "none": ("none", False)}
 
 
 def main(out_dir):
@@ -31,10 +35,11 @@ def main(out_dir):
     try:
         n, d, K = (int(v) for v in os.environ.get("GEO_TEST_SHAPE", "2048,16,64").split(","))
         z_h = syn.gauss_latents(n, d, 0)
-        sd = om.make_decoder_state(0, d, 1, norm_type="batch")
-        dec = SpatialDecoder(1, (256, 128, 64), d, 28, "batch")
+        norm, training = DECODERS[os.environ.get("GEO_TEST_DECODER", "batch_train")]      # default: train-mode BatchNorm
+        sd = om.make_decoder_state(0, d, 1, norm_type=norm)
+        dec = SpatialDecoder(1, (256, 128, 64), d, 28, norm)
         dec.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
-        dec = dec.to(dev).train()
+        dec = dec.to(dev).train(training)
         if os.environ.get("GEO_TEST_MODE") == "in_flight":
             # five latent sets of different sizes, three sharded builds in flight on every rank (ticket-ordered collectives)
             from vqvae_amd.scripts.build_codebook import build_codebooks_pipelined

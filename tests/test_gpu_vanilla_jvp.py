@@ -105,6 +105,28 @@ def test_graph_entry_equals_pairs_entry(name):
         edge_lengths_vanilla_graph_device(ex, z, src, dst.clamp(min=300))
 
 
+@pytest.mark.parametrize("name", ["wide-bn-28", "narrow-none-32x3-d5"])
+def test_graph_entry_in_slices_equals_the_whole_call(name):
+    """geo_vanilla_jvp_edges works per latent when n_nodes <= 2 n_edges and per edge end otherwise, and promises the same bits
+    either way.  The 1500 edges of test_graph_entry_equals_pairs_entry over its 300 latents, whole (per latent) and in 15
+    slices of 100 through the edges entry (300 > 200: per edge end, every slice with the workspace its own query sizes):
+    the slices put together are the whole call and the pairs entry, bit for bit."""
+    from vqvae_amd.geo.riemannian_metric import edge_lengths_vanilla_device, edge_lengths_vanilla_graph_device
+    from vqvae_amd.vanilla_decoder import VanillaDecoderExport
+    dev = torch.device("cuda", 0)
+    ex = VanillaDecoderExport(V.case(name)[0], dev)
+    z, src, dst = (t.to(dev) for t in V.small_graph(ex.latent_dim))
+    n_nodes, n_edges, step = z.shape[0], src.numel(), 100
+    assert n_nodes <= 2 * n_edges and n_nodes > 2 * step and n_edges % step == 0
+    whole = edge_lengths_vanilla_graph_device(ex, z, src, dst).cpu().numpy()
+    pairs = edge_lengths_vanilla_device(ex, z[src.long()].contiguous(), z[dst.long()].contiguous()).cpu().numpy()
+    sliced = torch.cat([edge_lengths_vanilla_graph_device(ex, z, src[e0:e0 + step].contiguous(), dst[e0:e0 + step].contiguous())
+                        for e0 in range(0, n_edges, step)]).cpu().numpy()
+    assert sliced.shape == whole.shape and np.all(np.isfinite(sliced))
+    np.testing.assert_array_equal(sliced, whole)
+    np.testing.assert_array_equal(sliced, pairs)
+
+
 @pytest.mark.parametrize("mode", ["full", "subset"])
 def test_legacy_builder_re_weighting_native_against_autograd(mode, monkeypatch):
     """reweight_graph_device on 600 x 16 latents with an eval-BatchNorm decoder: same structure as with the predicate forced

@@ -167,3 +167,97 @@ def test_refused_decoders_report_the_run_s_verdict(lib, decoder, message):
     for graph in (False, True):
         assert plan(lib, decoder, "dense", graph) == E_ARG
         assert message in lib.geo_last_error()
+
+
+# (n_nodes, E) of k = 20 union graphs over Gaussian latents (14 to 16 edges per latent; the last near the C2 graph), then a graph
+# one edge below 0.75 d edges per latent (d = 16: 12) and one exactly on it
+BUILD_GRAPHS = [(512, 7350), (2048, 30354), (60000, 948000), (512, 6143), (512, 6144)]
+PART_BS = 512
+
+
+def part_plan(lib, decoder, n_nodes, n_edges, build_edges):
+    from vqvae_amd import _lib
+    code = lib.geo_jvp_plan_part(C.descriptor(decoder), n_nodes, n_edges, build_edges, PART_BS, 1, 0)
+    assert code >= 0, (decoder, n_nodes, n_edges, build_edges, lib.geo_last_error())
+    return _lib.decode_jvp_plan(code)
+
+
+def rank_slices(n_edges, world):
+    from vqvae_amd import parallel
+    out = [parallel.chunk_range(n_edges, PART_BS, rank, world) for rank in range(world)]
+    assert out[0][0] == 0 and out[-1][1] == n_edges and all(a[1] == b[0] for a, b in zip(out, out[1:]))
+    return [(e0, e1) for e0, e1 in out if e1 > e0]
+
+
+@pytest.mark.parametrize("n_nodes,n_edges", BUILD_GRAPHS)
+@pytest.mark.parametrize("decoder", ["fm_bn_eval", "fm_none", "fm_group"])
+def test_every_part_of_a_build_takes_the_route_of_the_whole(lib, decoder, n_nodes, n_edges):
+    """Fixed statistics, d = 16: a rank's share of the edges, told the build's edge count (geo_jvp_plan_part), carries the
+    node_jacobian flag of the whole graph for every world size; asked about its own edges alone (geo_jvp_plan) at least one
+    rank of two answers differently -- these graphs sit where a sharded build used to leave the single-process route."""
+    from vqvae_amd import _lib
+    desc = C.descriptor(decoder)
+    whole = _lib.decode_jvp_plan(lib.geo_jvp_plan(desc, n_nodes, n_edges, PART_BS, 1, 0))
+    assert whole["node_jacobian"] == (4 * n_edges >= 3 * n_nodes * 16) and whole["per_node"]
+    assert part_plan(lib, decoder, n_nodes, n_edges, n_edges) == whole
+    for world in (1, 2, 3, 8):
+        alone = []
+        for e0, e1 in rank_slices(n_edges, world):
+            part = part_plan(lib, decoder, n_nodes, e1 - e0, n_edges)
+            assert part["node_jacobian"] == whole["node_jacobian"], (world, e0, e1)
+            assert part["per_node"] and (part["front"], part["mid"], part["back"]) == (whole["front"], whole["mid"], whole["back"])
+            alone.append(_lib.decode_jvp_plan(lib.geo_jvp_plan(desc, n_nodes, e1 - e0, PART_BS, 1, 0))["node_jacobian"])
+            # the workspace is the call's own: what the part query sizes is what the part plan assumes, and enough for the run
+            ws = lib.geo_jvp_edges_part_workspace_bytes(desc, n_nodes, e1 - e0, n_edges, PART_BS)
+            assert ws > 0 and _lib.decode_jvp_plan(lib.geo_jvp_plan_part(desc, n_nodes, e1 - e0, n_edges, PART_BS, 1, ws)) == part
+        if world == 2 and whole["node_jacobian"]:
+            assert not all(alone), alone
+        if not whole["node_jacobian"]:
+            assert not any(alone), alone
+    e0, e1 = rank_slices(n_edges, 2)[0]
+    assert lib.geo_jvp_plan_part(desc, n_nodes, e1 - e0, e1 - e0 - 1, PART_BS, 1, 0) == E_ARG
+    assert b"build_edges" in lib.geo_last_error()
+    assert lib.geo_jvp_edges_part_workspace_bytes(desc, n_nodes, e1 - e0, e1 - e0 - 1, PART_BS) == 0
+
+
+@pytest.mark.parametrize("n_nodes,n_edges", BUILD_GRAPHS)
+@pytest.mark.parametrize("decoder,want", [("cf32_bn_eval", ("all_tangent", "per_node", True, False, False)),
+                                          ("fm_bn_train", ("pipe_dedup", "dedup", False, False, True))])
+def test_build_edges_changes_nothing_where_the_jacobian_route_does_not_apply(lib, decoder, want, n_nodes, n_edges):
+    """d = 32 and train-mode BatchNorm never take the per-latent Jacobian, whatever the build's edge count; train mode keeps
+    its start-side dedup.  The plan of a part is the plan of the same call on its own."""
+    from vqvae_amd import _lib
+    desc = C.descriptor(decoder)
+    for world in (1, 2, 3, 8):
+        for e0, e1 in rank_slices(n_edges, world):
+            part = part_plan(lib, decoder, n_nodes, e1 - e0, n_edges)
+            assert (part["mid"], part["back"], part["per_node"], part["node_jacobian"], part["dedup"]) == want
+            assert part == _lib.decode_jvp_plan(lib.geo_jvp_plan(desc, n_nodes, e1 - e0, PART_BS, 1, 0))
+            assert (lib.geo_jvp_edges_part_workspace_bytes(desc, n_nodes, e1 - e0, n_edges, PART_BS)
+                    == lib.geo_jvp_edges_workspace_bytes(desc, n_nodes, e1 - e0, PART_BS))
+    assert lib.geo_jvp_plan_part(desc, n_nodes, n_edges, n_edges - 1, PART_BS, 1, 0) == E_ARG
+
+
+def test_the_plain_queries_are_the_part_queries_with_the_call_s_own_count(lib):
+    for dn in ("fm_bn_eval", "fm_group", "fm_bn_train", "cf32_bn_eval", "c1_48"):
+        desc = C.descriptor(dn)
+        for n_nodes, n_edges, bs in C.SIZES.values():
+            assert (lib.geo_jvp_edges_part_workspace_bytes(desc, n_nodes, n_edges, n_edges, bs)
+                    == lib.geo_jvp_edges_workspace_bytes(desc, n_nodes, n_edges, bs))
+            for graph in (0, 1):
+                assert (lib.geo_jvp_plan_part(desc, n_nodes, n_edges, n_edges, bs, graph, 0)
+                        == lib.geo_jvp_plan(desc, n_nodes, n_edges, bs, graph, 0))
+
+
+def test_the_run_entry_refuses_a_build_smaller_than_the_call_before_anything_else(lib):
+    """geo_decoder_jvp_edges_part itself, not only its queries: build_edges < n_edges is GEO_E_ARG ahead of every other check --
+    with null buffers the answer names build_edges, not the null pointers, and nothing is launched (no GPU here)."""
+    desc = C.descriptor("fm_bn_eval")
+    for n_edges, build_edges in ((7350, 7349), (512, 0), (1, -1)):
+        assert lib.geo_decoder_jvp_edges_part(desc, None, 512, None, None, n_edges, build_edges, 512, None, None, 0, None) == E_ARG
+        assert b"build_edges" in lib.geo_last_error(), lib.geo_last_error()
+    # a valid count gets as far as the next check
+    assert lib.geo_decoder_jvp_edges_part(desc, None, 512, None, None, 7350, 7350, 512, None, None, 0, None) == E_ARG
+    assert b"null pointer" in lib.geo_last_error()
+    assert lib.geo_decoder_jvp_edges(desc, None, 512, None, None, 7350, 512, None, None, 0, None) == E_ARG
+    assert b"null pointer" in lib.geo_last_error()

@@ -2074,11 +2074,17 @@ bool route_error(Route *r, int status, const char *fmt, ...) {
 
 // ws_bytes = nullptr: the workspace is what the matching query returns.  The sizes are filled in whenever the shape parses, also for a
 // decoder the run refuses (status != GEO_OK): the queries answer for those as they always have.
-bool make_route(const geo_decoder_desc *dc, const geo::Options &o, bool graph_edges, int64_t n_nodes, int64_t n_edges, int batch,
-                const size_t *ws_bytes, Route *r) {
+// build_edges: the edges of the whole build this call computes a part of (>= n_edges; the plain entry points pass n_edges).  It
+// enters in one place, the edges-per-latent rule of node_jacobian, so that every part of a build takes the route the whole takes;
+// passes, slots and workspace are the call's own.
+bool make_route(const geo_decoder_desc *dc, const geo::Options &o, bool graph_edges, int64_t n_nodes, int64_t n_edges,
+                int64_t build_edges, int batch, const size_t *ws_bytes, Route *r) {
     *r = Route{};
     if (!dc) return route_error(r, GEO_E_ARG, "geo_decoder_jvp: null pointer");
     if (batch <= 0) return route_error(r, GEO_E_ARG, "geo_decoder_jvp: batch_size must be positive");
+    if (build_edges < n_edges)
+        return route_error(r, GEO_E_ARG, "geo_decoder_jvp: build_edges %lld < n_edges %lld", (long long)build_edges,
+                           (long long)n_edges);
     Plan base;
     if (n_edges < 0 || n_nodes < 0 || !make_plan(dc, n_edges, batch, &base))
         return route_error(r, GEO_E_ARG, "geo_decoder_jvp: unsupported decoder (out_size %d, c2=%d must divide %d)", dc->out_size,
@@ -2109,7 +2115,7 @@ bool make_route(const geo_decoder_desc *dc, const geo::Options &o, bool graph_ed
     const int64_t n_pseudo = (n_nodes + 1) / 2 * s.d;
     size_t jac_bytes = 0;
     if (per_node_kernels && n_nodes > 0 && n_edges > 0 && s.d <= 16 && o.jvp_node_jacobian != 0 &&
-        (o.jvp_node_jacobian != 1 || 4 * n_edges >= 3 * n_nodes * s.d) && n_pseudo < (int64_t)1 << 31 &&
+        (o.jvp_node_jacobian != 1 || 4 * build_edges >= 3 * n_nodes * s.d) && n_pseudo < (int64_t)1 << 31 &&
         make_plan(dc, n_pseudo, batch, &jpl) && node_slots <= jpl.pass_slots()) {
         r->jac_np = (size_t)r->back_nt * 32;
         r->jac_extra_bytes = 2 * geo::align_up((size_t)n_pseudo * 4) + geo::align_up((size_t)n_nodes * s.d * r->jac_np * 4);
@@ -2501,13 +2507,13 @@ int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t 
 
 // validation shared by the two entry points, then the route and the run
 int decoder_jvp(const geo_decoder_desc *dc, const geo::Options &opt, bool graph_edges, const float *z, int64_t n_nodes,
-                const int32_t *src, const int32_t *dst, const float *z_start, const float *z_end, int64_t n_edges, int32_t batch,
-                float *len_out, void *ws, size_t ws_bytes, void *stream) {
+                const int32_t *src, const int32_t *dst, const float *z_start, const float *z_end, int64_t n_edges,
+                int64_t build_edges, int32_t batch, float *len_out, void *ws, size_t ws_bytes, void *stream) {
     GEO_REQUIRE(dc && len_out && ws, "geo_decoder_jvp: null pointer");
     GEO_REQUIRE(batch > 0, "geo_decoder_jvp: batch_size must be positive");
     if (n_edges == 0) return GEO_OK;
     Route r;
-    if (!make_route(dc, opt, graph_edges, n_nodes, n_edges, batch, &ws_bytes, &r)) {
+    if (!make_route(dc, opt, graph_edges, n_nodes, n_edges, build_edges, batch, &ws_bytes, &r)) {
         geo::set_error("%s", r.error);
         return r.status;
     }
@@ -2526,35 +2532,55 @@ extern "C" int geo_debug_mid_prof(unsigned long long *out, int reset) {
 extern "C" size_t geo_jvp_workspace_bytes(const geo_decoder_desc *dec, int64_t n_edges, int32_t batch_size) {
     const geo::Options opt = geo::options();
     Route r;
-    make_route(dec, opt, false, 0, n_edges, batch_size, nullptr, &r);
+    make_route(dec, opt, false, 0, n_edges, n_edges, batch_size, nullptr, &r);
+    return r.bytes;
+}
+
+extern "C" size_t geo_jvp_edges_part_workspace_bytes(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges,
+                                                     int64_t build_edges, int32_t batch_size) {
+    const geo::Options opt = geo::options();
+    Route r;
+    make_route(dec, opt, true, n_nodes, n_edges, build_edges, batch_size, nullptr, &r);
     return r.bytes;
 }
 
 extern "C" size_t geo_jvp_edges_workspace_bytes(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges,
                                                 int32_t batch_size) {
-    const geo::Options opt = geo::options();
-    Route r;
-    make_route(dec, opt, true, n_nodes, n_edges, batch_size, nullptr, &r);
-    return r.bytes;
+    return geo_jvp_edges_part_workspace_bytes(dec, n_nodes, n_edges, n_edges, batch_size);
 }
 
-extern "C" int geo_jvp_plan(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size,
-                            int32_t graph_edges, size_t ws_bytes) {
+extern "C" int geo_jvp_plan_part(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int64_t build_edges,
+                                 int32_t batch_size, int32_t graph_edges, size_t ws_bytes) {
     const geo::Options opt = geo::options();
     Route r;
-    if (!make_route(dec, opt, graph_edges != 0, graph_edges ? n_nodes : 0, n_edges, batch_size, ws_bytes ? &ws_bytes : nullptr, &r)) {
+    if (!make_route(dec, opt, graph_edges != 0, graph_edges ? n_nodes : 0, n_edges, build_edges, batch_size,
+                    ws_bytes ? &ws_bytes : nullptr, &r)) {
         geo::set_error("%s", r.error);
         return r.status;
     }
     return encode_route(r);
 }
 
+extern "C" int geo_jvp_plan(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size,
+                            int32_t graph_edges, size_t ws_bytes) {
+    return geo_jvp_plan_part(dec, n_nodes, n_edges, n_edges, batch_size, graph_edges, ws_bytes);
+}
+
+extern "C" int geo_decoder_jvp_edges_part(const geo_decoder_desc *dec, const float *z, int64_t n_nodes, const int32_t *src,
+                                          const int32_t *dst, int64_t n_edges, int64_t build_edges, int32_t batch_size,
+                                          float *len_out, void *ws, size_t ws_bytes, void *stream) {
+    GEO_REQUIRE(build_edges >= n_edges, "geo_decoder_jvp_edges_part: build_edges %lld < n_edges %lld", (long long)build_edges,
+                (long long)n_edges);
+    GEO_REQUIRE(n_edges == 0 || (z && src && dst && n_nodes > 0), "geo_decoder_jvp_edges: null pointer");
+    const geo::Options opt = geo::options();
+    return decoder_jvp(dec, opt, true, z, n_nodes, src, dst, nullptr, nullptr, n_edges, build_edges, batch_size, len_out, ws,
+                       ws_bytes, stream);
+}
+
 extern "C" int geo_decoder_jvp_edges(const geo_decoder_desc *dec, const float *z, int64_t n_nodes, const int32_t *src,
                                      const int32_t *dst, int64_t n_edges, int32_t batch_size, float *len_out, void *ws,
                                      size_t ws_bytes, void *stream) {
-    GEO_REQUIRE(n_edges == 0 || (z && src && dst && n_nodes > 0), "geo_decoder_jvp_edges: null pointer");
-    const geo::Options opt = geo::options();
-    return decoder_jvp(dec, opt, true, z, n_nodes, src, dst, nullptr, nullptr, n_edges, batch_size, len_out, ws, ws_bytes, stream);
+    return geo_decoder_jvp_edges_part(dec, z, n_nodes, src, dst, n_edges, n_edges, batch_size, len_out, ws, ws_bytes, stream);
 }
 
 extern "C" int geo_decoder_jvp_pairs(const geo_decoder_desc *dec, const float *z_start, const float *z_end,
@@ -2562,6 +2588,6 @@ extern "C" int geo_decoder_jvp_pairs(const geo_decoder_desc *dec, const float *z
                                      void *stream) {
     GEO_REQUIRE(n_edges == 0 || (z_start && z_end), "geo_decoder_jvp_pairs: null pointer");
     const geo::Options opt = geo::options();
-    return decoder_jvp(dec, opt, false, nullptr, 0, nullptr, nullptr, z_start, z_end, n_edges, batch_size, len_out, ws, ws_bytes,
-                       stream);
+    return decoder_jvp(dec, opt, false, nullptr, 0, nullptr, nullptr, z_start, z_end, n_edges, n_edges, batch_size, len_out, ws,
+                       ws_bytes, stream);
 }

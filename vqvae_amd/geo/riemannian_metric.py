@@ -48,22 +48,30 @@ def edge_lengths_device(export: DecoderExport, z_start: torch.Tensor, z_end: tor
 
 
 def edge_lengths_graph_device(export: DecoderExport, z: torch.Tensor, src: torch.Tensor, dst: torch.Tensor,
-                              batch_size: int = 512) -> torch.Tensor:
-    """HIP path on an edge list over resident latents: len[e] for (src[e], dst[e]) without gathers in HBM."""
+                              batch_size: int = 512, build_edges=None) -> torch.Tensor:
+    """HIP path on an edge list over resident latents: len[e] for (src[e], dst[e]) without gathers in HBM.
+    `build_edges`: the edge count of the whole graph when (src, dst) is a part of it -- a rank's share, or one slice of several
+    in one process (None: the call's own count).  Decoders with fixed statistics pick the per-latent Jacobian route from the
+    edges per latent, and the two routes differ in their last bits: told the build's count, every part takes the route the
+    whole graph takes, so the lengths do not depend on how the edges are divided."""
     lib = _lib.load()
     dev = z.device
     E = int(src.numel())
+    build_edges = E if build_edges is None else int(build_edges)
+    if build_edges < E:
+        raise ValueError(f"build_edges {build_edges} < {E} edges of the call")
     out = torch.empty(E, dtype=torch.float32, device=dev)
     if E == 0:
         return out
     # (with the per-latent buffers: decoders with fixed statistics run their primal pass once per latent, not per edge end)
-    nbytes = lib.geo_jvp_edges_workspace_bytes(export.desc, int(z.shape[0]), E, int(batch_size))
+    nbytes = lib.geo_jvp_edges_part_workspace_bytes(export.desc, int(z.shape[0]), E, build_edges, int(batch_size))
     if nbytes == 0:
-        raise _lib.GeoHipError("geo_jvp_edges_workspace_bytes: decoder configuration not supported by the HIP path")
+        raise _lib.GeoHipError("geo_jvp_edges_part_workspace_bytes: decoder configuration not supported by the HIP path")
     ws = workspace(nbytes, dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.geo_decoder_jvp_edges(export.desc, ptr(z), z.shape[0], ptr(src), ptr(dst), E, int(batch_size),
-                                             ptr(out), ptr(ws), ws.numel(), stream_ptr()), "geo_decoder_jvp_edges")
+        _lib.check(lib.geo_decoder_jvp_edges_part(export.desc, ptr(z), z.shape[0], ptr(src), ptr(dst), E, build_edges,
+                                                  int(batch_size), ptr(out), ptr(ws), ws.numel(), stream_ptr()),
+                   "geo_decoder_jvp_edges_part")
     export.commit_running_stats(2 * ((E + int(batch_size) - 1) // int(batch_size)))
     return out
 

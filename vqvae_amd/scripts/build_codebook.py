@@ -56,10 +56,12 @@ def build_codebook_device(z_flat: torch.Tensor, decoder, *, k: int = 20, sym: st
         export = DecoderExport(decoder, dev)
         fold = RunningStatFold(export, group)           # multi-rank: BatchNorm running statistics as one process leaves them
         fold.start()
-        # whole chunks of `batch_size` edges per rank: every BatchNorm batch stays intact
+        # whole chunks of `batch_size` edges per rank: every BatchNorm batch stays intact; every rank is told the build's edge
+        # count, so a decoder with fixed statistics takes the route one process takes
         lengths = sharded_edge_lengths(
             int(src.numel()), batch_size,
-            lambda e0, e1: edge_lengths_graph_device(export, z_flat, src[e0:e1], dst[e0:e1], batch_size), group)
+            lambda e0, e1: edge_lengths_graph_device(export, z_flat, src[e0:e1], dst[e0:e1], batch_size,
+                                                     build_edges=int(src.numel())), group)
         fold.finish(int(src.numel()), batch_size)
     else:       # e.g. GroupNorm: no kernel, autograd on the GPU (the reference's own method)
         lengths = edge_lengths_riemannian(decoder, z_flat[src.long()], z_flat[dst.long()], batch_size).contiguous()
