@@ -1,7 +1,8 @@
 """Numpy restatement of the GPU k-means rules, independent of the project's code.
 
 Not a test module (no test_ prefix): tests/test_kmeans_host.py checks it against the fixture and tests/test_gpu_kmeans.py
-uses its exact key as the arbiter of near ties.  tools/gen_golden_kmeans.py uses it to measure each fixture case's margins.
+uses its exact key as the arbiter of near ties.  tools/gen_golden_kmeans.py uses it to measure each fixture case's margins,
+and tools/gen_golden_kmeans_edges.py also reads each case's stated property from `lloyd`'s trace and stores its centres.
 
   key(x, c)    fp64 fma chain of (x_k - c_k)^2 over k ascending (fma emulated exactly where it matters: `fma_key_rows`)
   seeding      sklearn's _kmeans_plusplus with closest = f32(key), fp64 cumulative sums, pots = f32(fp64 sum)
@@ -89,8 +90,10 @@ def kmeans_plusplus(X: np.ndarray, n_clusters: int, first: int, u: np.ndarray):
     return idx, draw_gap, pot_gap
 
 
-def lloyd(X: np.ndarray, init: np.ndarray, max_iter: int, tol: float):
-    """One Lloyd run (X already centred, init f32 [K][d]).  Returns centres, labels, inertia, n_iter, strict, relocations."""
+def lloyd(X: np.ndarray, init: np.ndarray, max_iter: int, tol: float, trace: list = None):
+    """One Lloyd run (X already centred, init f32 [K][d]).  Returns centres, labels, inertia, n_iter, strict, relocations.
+    A list given as `trace` receives one dict per iteration: "moved" [(row, donor, new cluster)] in the order of the moves,
+    "left_empty" (clusters with no row after the moves, ascending) and "big" (the biggest cluster then, first maximum)."""
     n, d = X.shape
     K = len(init)
     centers = init.astype(np.float32).copy()
@@ -104,6 +107,7 @@ def lloyd(X: np.ndarray, init: np.ndarray, max_iter: int, tol: float):
         sums = np.zeros((K, d), dtype=np.float64)
         np.add.at(sums, lab, X64)
         empty = np.nonzero(counts == 0)[0]
+        moved = []
         if len(empty) and keys.max() > 0:
             order = np.lexsort((np.arange(n), -keys))[:len(empty)]
             for e, r in zip(empty, order):
@@ -113,10 +117,13 @@ def lloyd(X: np.ndarray, init: np.ndarray, max_iter: int, tol: float):
                 counts[e] = 1
                 counts[old] -= 1
                 relocations += 1
+                moved.append((int(r), int(old), int(e)))
         new = np.where(counts[:, None] > 0, sums / np.maximum(counts, 1)[:, None], 0).astype(np.float32)
         big = int(np.argmax(counts))                  # sklearn _average_centers: empty -> the biggest cluster's row as it
         for e in np.nonzero(counts <= 0)[0]:          # stands in the ascending loop (still the sum when it comes later)
             new[e] = (sums[big] if e < big else sums[big] / counts[big]).astype(np.float32)
+        if trace is not None:
+            trace.append({"moved": moved, "left_empty": [int(e) for e in np.nonzero(counts <= 0)[0]], "big": big})
         shift2 = ((new.astype(np.float64) - centers.astype(np.float64)) ** 2).sum(1)
         centers = new
         if np.array_equal(lab, labels_old):

@@ -73,6 +73,88 @@ def test_restatement_reproduces_full_fit_fixture(fx, name):
     np.testing.assert_allclose(got["centers"], fx[tag + "_centers"], rtol=1e-5, atol=1e-6)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# tests/golden/kmeans_edges.npz (tools/gen_golden_kmeans_edges.py): the rules reproduce every case
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def fxe(golden):
+    return golden("kmeans_edges")
+
+
+def test_edges_fixture_has_every_case(fxe):
+    import gen_golden_kmeans_edges as G
+    for name in G.LLOYD_CASES:
+        for part in ("meta", "labels", "centers", "inertia", "n_iter", "rules_centers", "rules_inertia"):
+            assert f"lloyd_{name}_{part}" in fxe.files
+        assert int(fxe[f"lloyd_{name}_rules_only"]) == 0
+    for name in G.TIE_CASES:                       # the rules' result only: scikit-learn's pick among equal keys is arbitrary
+        assert int(fxe[f"lloyd_{name}_rules_only"]) == 1 and f"lloyd_{name}_centers" not in fxe.files
+    for name in G.PP_CASES:
+        dg, pg = fxe[name + "_margins"]
+        n = int(fxe[name + "_meta"][0])
+        assert float(fxe[name + "_draw_bound"]) == (2.0 ** -28 if n > 1 << 20 else 2.0 ** -20)
+        assert dg >= float(fxe[name + "_draw_bound"]) and pg >= 2.0 ** -20
+    lloyd = {k for k in fxe.files if k.startswith("lloyd_") and k.endswith("_meta")}
+    assert len(lloyd) == len(G.LLOYD_CASES) + len(G.TIE_CASES)
+    assert len([k for k in fxe.files if k.startswith("pp_") and k.endswith("_meta")]) == len(G.PP_CASES)
+
+
+def _edges_lloyd_names():
+    import gen_golden_kmeans_edges as G
+    return list(G.LLOYD_CASES)
+
+
+@pytest.mark.parametrize("name", _edges_lloyd_names())
+def test_restatement_reproduces_edges_lloyd_fixture(fxe, name):
+    import gen_golden_kmeans_edges as G
+    tag = f"lloyd_{name}"
+    n, d, K, seed, max_iter = (int(v) for v in fxe[tag + "_meta"])
+    X, init, max_iter, tol = G.lloyd_case(name, seed)
+    assert X.shape == (n, d) and init.shape == (K, d)
+    mean = X.mean(axis=0)
+    trace = []
+    c, lab, inertia, n_iter, strict, reloc = R.lloyd(X - mean, init - mean, max_iter, tol, trace)
+    np.testing.assert_array_equal(lab, fxe[tag + "_labels"].astype(np.int32))
+    assert n_iter == int(fxe[tag + "_n_iter"]) and len(trace) == n_iter
+    np.testing.assert_allclose(c + mean, fxe[tag + "_centers"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(inertia, float(fxe[tag + "_inertia"]), rtol=1e-5)
+    np.testing.assert_array_equal(c, fxe[tag + "_rules_centers"])
+    assert inertia == float(fxe[tag + "_rules_inertia"]) and reloc == int(fxe[tag + "_relocations"])
+    assert G.lloyd_property(name, trace, K), name       # the route the case exists for is the one it takes
+
+
+@pytest.mark.parametrize("name", ["tie_rows", "tie_rounds", "zero_keys"])
+def test_restatement_reproduces_relocation_tie_fixture(fxe, name):
+    import gen_golden_kmeans_edges as G
+    tag = f"lloyd_{name}"
+    X, init = G.tie_case(name)
+    trace = []
+    c, lab, inertia, n_iter, strict, reloc = R.lloyd(X, init, 1, 0.0, trace)
+    np.testing.assert_array_equal(lab, fxe[tag + "_labels"].astype(np.int32))
+    np.testing.assert_array_equal(c, fxe[tag + "_rules_centers"])
+    assert n_iter == int(fxe[tag + "_n_iter"]) == 1
+    np.testing.assert_array_equal(np.array(trace[0]["moved"]), fxe[tag + "_moved"])
+    G.check_tie_case(name, X, init, trace[0]["moved"])
+    for row, donor, new in trace[0]["moved"]:            # a moved row is its new cluster's only member: the centre is the row
+        np.testing.assert_array_equal(c[new], X[row])
+
+
+def test_restatement_reproduces_edges_seeding_fixture(fxe):
+    import gen_golden_kmeans_edges as G
+    from vqvae_amd.cluster import seeding_draws
+    for name in G.PP_CASES:
+        n, d, K, seed, L, S = (int(v) for v in fxe[name + "_meta"])
+        X, K2, L2, S2 = G.pp_input(name, seed)
+        assert (X.shape, K2, L2, S2) == ((n, d), K, L, S)
+        first, u = seeding_draws(np.random.RandomState(seed), n, K, S, L)
+        runs = [R.kmeans_plusplus(X, K, int(first[s]), u[s]) for s in range(S)]
+        np.testing.assert_array_equal(np.stack([r[0] for r in runs]), fxe[name + "_indices"], err_msg=name)
+        np.testing.assert_allclose([min(r[1] for r in runs), min(r[2] for r in runs)], fxe[name + "_margins"], rtol=1e-6,
+                                   err_msg=name)
+        if K == n:
+            assert sorted(runs[0][0]) == list(range(n))   # every row is a centre, once
+
+
 def test_host_stream_model_matches_sklearn_kmeans_plusplus():
     skc = pytest.importorskip("sklearn.cluster")
     from vqvae_amd.cluster import n_local_trials_for, seeding_draws
