@@ -181,8 +181,24 @@ int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neighbors, int3
                  int64_t row0, int64_t row1, int32_t *idx_out, double *d2_out,
                  void *ws, size_t ws_bytes, void *stream);
 
-/* The path the calling thread's last geo_knn_topk call took (host state only, no GPU call; 0 before any call, after an
- * empty row range or an argument error):
+/* geo_knn_query: the same search for queries that are NOT rows of the corpus (sklearn's kneighbors(X)): for each of the m rows
+ * of q (f32 [m][d]) the n_neighbors corpus rows of z with the smallest fp64 key, ordered by (key, corpus index).  The key is
+ * the fma chain geo_knn_topk forms for `form` with the query in the place of the corpus' own row: form 0  sum (q - x)^2,
+ * form 1  (|q|^2 + (-2 q.x)) + |x|^2 clamped at 0 with the fma-chain norms -- a query that is a copy of corpus row r gets
+ * exactly row r's list of geo_knn_topk.  Same limits (d <= 128, n_neighbors <= min(GEO_KNN_MAX_NEIGHBORS, n), n, m < 2^31;
+ * m = 0 is GEO_OK without a launch) and the same paths, chosen from n, d, n_neighbors and the option knn_filter alone.
+ * The corpus is prepared once per call; the queries are prepared and searched in slices of as many rows as the workspace holds
+ * behind the corpus side (candidate lists are per slice row, not per corpus row).  The result does not depend on ws_bytes.
+ * geo_knn_query_workspace_bytes(n, m, d): one slice for all m queries; geo_knn_query_min_workspace_bytes(n, d): the corpus side
+ * and one slice of 128 queries -- less is GEO_E_WORKSPACE before any launch. */
+size_t geo_knn_query_workspace_bytes(int64_t n, int64_t m, int32_t d);
+size_t geo_knn_query_min_workspace_bytes(int64_t n, int32_t d);
+int geo_knn_query(const float *z, int64_t n, const float *q, int64_t m, int32_t d, int32_t n_neighbors, int32_t form,
+                  int32_t *idx_out, double *d2_out, void *ws, size_t ws_bytes, void *stream);
+
+/* The path the calling thread's last geo_knn_topk or geo_knn_query call took (host state only, no GPU call; 0 before any call,
+ * after an empty row range / m = 0 or an argument error).  A geo_knn_query call that ran in several slices reports one path:
+ * the one-level filter if any slice's first level overflowed, the OVERFLOW flag if any slice fell back to the exact scan.  The paths:
  *   GEO_KNN_PATH_EXACT        the exact fp64 scan of every pair (n_neighbors <= 64);
  *   GEO_KNN_PATH_EXACT_WIDE   the exact scan with lists of two or four entries per lane (n_neighbors > 64);
  *   GEO_KNN_PATH_FILTER_BF16  thresholds from a strided corpus subset (a bound), bf16 hi/lo matrix-core scan, fp64 refinement;

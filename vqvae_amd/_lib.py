@@ -79,6 +79,9 @@ _SIGNATURES = {
     "geo_kpp_chain": (ctypes.c_int, [c_p, c_p, c_p, i32, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, c_p, sz, c_p, c_p]),
     "geo_knn_workspace_bytes": (sz, [i64, i32]),
     "geo_knn_topk": (ctypes.c_int, [c_p, i64, i32, i32, i32, i64, i64, c_p, c_p, c_p, sz, c_p]),
+    "geo_knn_query_workspace_bytes": (sz, [i64, i64, i32]),
+    "geo_knn_query_min_workspace_bytes": (sz, [i64, i32]),
+    "geo_knn_query": (ctypes.c_int, [c_p, i64, c_p, i64, i32, i32, i32, c_p, c_p, c_p, sz, c_p]),
     "geo_knn_last_path": (ctypes.c_int, []),
     "geo_knn_thresholds": (ctypes.c_int, [c_p, i64, i32, i32, i32, i64, i64, i32, c_p, c_p, sz, c_p]),
     "geo_symmetrize_workspace_bytes": (sz, [i32, i32]),

@@ -949,10 +949,10 @@ int launch_knn(bool expansion, const float *zp32, const double *zq64, const doub
 
 // lists longer than one wave (64 < kq <= 256): 2 or 4 list registers per lane, 4 queries per wave
 template <int DCH>
-int launch_knn_wide(bool expansion, const float *zp32, const double *zq64, const double *nrm, int64_t n, int nch, int kq,
-                    int64_t row0, int64_t row1, int32_t *idx_out, double *d2_out, hipStream_t s) {
-    if (kq <= 128) return launch_knn<DCH, 4, 2>(expansion, zp32, zq64, nrm, nrm, n, nch, kq, row0, row1, idx_out, d2_out, s);
-    return launch_knn<DCH, 4, 4>(expansion, zp32, zq64, nrm, nrm, n, nch, kq, row0, row1, idx_out, d2_out, s);
+int launch_knn_wide(bool expansion, const float *zp32, const double *zq64, const double *nrm, const double *nrm_q, int64_t n,
+                    int nch, int kq, int64_t row0, int64_t row1, int32_t *idx_out, double *d2_out, hipStream_t s) {
+    if (kq <= 128) return launch_knn<DCH, 4, 2>(expansion, zp32, zq64, nrm, nrm_q, n, nch, kq, row0, row1, idx_out, d2_out, s);
+    return launch_knn<DCH, 4, 4>(expansion, zp32, zq64, nrm, nrm_q, n, nch, kq, row0, row1, idx_out, d2_out, s);
 }
 
 int launch_knn_bound(const KnnPlan &p, bool expansion, const float *zs32, const double *zq64, const double *nrm_s,
@@ -979,6 +979,224 @@ bool filter_applies(int64_t n, int dp) {
     // worth it from ~40 000 rows at 16 dimensions; the exact scan costs in proportion to the dimension
     const int64_t n_min = 640000 / dp > 16384 ? 640000 / dp : 16384;
     return n >= n_min && (dp == 8 || dp == 16 || dp == 32 || dp == 64);
+}
+
+// ---- one dispatch for both entry points ---------------------------------------------------------------------------------
+// geo_knn_topk (queries = rows of the corpus) and geo_knn_query (queries of their own) differ in where the query side of the
+// kernels points, nothing else: the corpus side is prepared once (KnnCorpus), a range of query rows is described by KnnQuery
+// and searched by search_rows, which picks the path from n, dp, kq and the knn_filter option alone.
+struct KnnCorpus {
+    const float *zp32;                 // [n][dp] zero padded
+    const double *nrm;                 // [n]
+    int64_t n;
+    // the filter paths (prepare_filter_corpus)
+    int S, dpb;
+    int64_t m, m0, n_pad, m_pad;       // subset rows (every S-th), subset of the subset, rows padded to whole scan tiles
+    bool bf16_scan, two_level;
+    double eps;
+    float *zs32; double *nrm_s;        // [m][dp], [m]
+    unsigned short *zb; float *negn;   // [n_pad][2][dpb], [n_pad]
+    float *zs0; double *nrm_s0;        // [m0][dp], [m0]                 (two levels)
+    unsigned short *zb_s; float *negn_s;
+};
+
+// query rows [row0, row1) of the arrays below; outputs and the per-query buffers are indexed from row0
+struct KnnQuery {
+    const double *zq64;                // [..][dp]
+    const double *nrm_q;
+    const unsigned short *zbq;         // [..][2][dpb] (bf16 scan)
+    int64_t row0, row1;
+    int64_t f32_row0;                  // the row of corpus.zp32 where query row0's float32 copy lies: knn_scan_kernel reads its
+};                                     // queries from the corpus array (row0 itself in a self-search)
+
+struct KnnLists { double *u; int32_t *cnt, *list, *overflow; };      // per query row of a range: [rows], [rows], [rows][FILTER_CAP]
+
+// the filter's corpus-side arrays out of the arena, in geo_knn_topk's order (its u / cnt / list lie between nrm_s and overflow)
+bool carve_filter_corpus(geo::Arena &ar, const KnnPlan &p, int64_t n, int kq, KnnCorpus &c, KnnLists &lists, int64_t list_rows) {
+    c.S = filter_stride(kq);
+    c.m = (n + c.S - 1) / c.S;
+    c.zs32 = ar.take<float>((size_t)c.m * p.dp);
+    c.nrm_s = ar.take<double>((size_t)c.m);
+    if (list_rows > 0) {                                  // (geo_knn_query keeps them per slice, behind the corpus)
+        lists.u = ar.take<double>((size_t)list_rows);
+        lists.cnt = ar.take<int32_t>((size_t)list_rows);
+        lists.list = ar.take<int32_t>((size_t)list_rows * FILTER_CAP);
+    }
+    lists.overflow = ar.take<int32_t>(16);
+    c.dpb = p.dp < 16 ? 16 : p.dp;
+    c.bf16_scan = geo::options().knn_filter != 2;         // 2: the float32 matrix-core scan (comparison runs)
+    c.n_pad = (n + 255) / 256 * 256;                      // the scan reads whole tiles
+    c.m_pad = (c.m + 255) / 256 * 256;
+    c.zb = ar.take<unsigned short>((size_t)c.n_pad * 2 * c.dpb);
+    c.negn = ar.take<float>((size_t)c.n_pad);
+    const size_t m0w = ((size_t)c.m + c.S - 1) / c.S;
+    c.zs0 = ar.take<float>(m0w * p.dp);
+    c.nrm_s0 = ar.take<double>(m0w);
+    c.zb_s = ar.take<unsigned short>((size_t)c.m_pad * 2 * c.dpb);
+    c.negn_s = ar.take<float>((size_t)c.m_pad);
+    if (!c.zs0 || !c.nrm_s0 || !c.zb_s || !c.negn_s) c.zs0 = nullptr;   // (a caller with a smaller workspace: one level)
+    // a d-term float32 dot product errs by < (d + 2) 2^-24 |x||y|, |x||y| <= (|x|^2 + |y|^2) / 2, and the float32
+    // test adds a few more roundings of the same size: 16x margin
+    // (the bf16 scan keeps 16 bits of every coordinate: its products err by < 2^-16 (|x|^2 + |y|^2) on top, 4x margin)
+    c.eps = 16.0 * (p.dp + 2) * 5.9604644775390625e-08 + (c.bf16_scan ? 4.0 * 1.52587890625e-05 : 0.0);
+    // Large inputs: the pass over every S-th row is itself N^2 / S fp64 work (S = 16: 100 ms of 255 at a million latents).
+    // Two levels instead: thresholds from every S-th row of every S-th row (knn_bound_kernel), with them the SAME filter +
+    // refinement over the every-S-th-row subset gives the exact kq-th distance to that subset -- at least as tight as the
+    // threshold of the one-level scheme; the same candidate counts at both levels.
+    c.m0 = (c.m + c.S - 1) / c.S;
+    c.two_level = c.bf16_scan && c.zs0 && n >= TWO_LEVEL_MIN && c.m0 >= kq;
+    return c.zs32 && c.nrm_s && lists.overflow && c.zb && c.negn && (list_rows <= 0 || (lists.u && lists.cnt && lists.list));
+}
+
+// the corpus-side launches of the filter paths: the threshold subset(s) and the bf16 parts
+int prepare_filter_corpus(const KnnPlan &p, const KnnCorpus &c, hipStream_t stream) {
+    knn_subset_kernel<<<geo::grid_for(c.m * p.dp, 256, 4096), 256, 0, stream>>>(c.zp32, c.nrm, c.n, p.dp, c.S, c.m, c.zs32, c.nrm_s);
+    GEO_LAUNCH_CHECK();
+    if (c.bf16_scan) {
+        knn_split_kernel<<<geo::grid_for(c.n_pad * c.dpb, 256, 4096), 256, 0, stream>>>(c.zp32, c.nrm, c.n, c.n_pad, p.dp, c.dpb, c.eps,
+                                                                                          c.zb, c.negn);
+        GEO_LAUNCH_CHECK();
+    }
+    if (c.two_level) {
+        knn_subset_kernel<<<geo::grid_for(c.m0 * p.dp, 256, 4096), 256, 0, stream>>>(c.zs32, c.nrm_s, c.m, p.dp, c.S, c.m0, c.zs0, c.nrm_s0);
+        GEO_LAUNCH_CHECK();
+        knn_split_kernel<<<geo::grid_for(c.m_pad * c.dpb, 256, 4096), 256, 0, stream>>>(c.zs32, c.nrm_s, c.m, c.m_pad, p.dp, c.dpb, c.eps,
+                                                                                          c.zb_s, c.negn_s);
+        GEO_LAUNCH_CHECK();
+    }
+    return GEO_OK;
+}
+
+// The kq nearest corpus rows of the query rows q, into idx_out / d2_out [row1 - row0][kq]; *path = the GEO_KNN_PATH_* taken.
+// l = the range's candidate buffers when the filter applies (corpus prepared by prepare_filter_corpus), else null.
+int search_rows(const KnnPlan &p, bool ex, int kq, const KnnCorpus &c, const KnnQuery &q, const KnnLists *l, int32_t *idx_out,
+                double *d2_out, hipStream_t stream, int32_t *path) {
+    const int64_t row0 = q.row0, row1 = q.row1, rows = row1 - row0, n = c.n;
+    if (kq > 64) {                                // no float32 filter here: its candidate lists are sized for kq <= 64
+        *path = GEO_KNN_PATH_EXACT_WIDE;
+        if (p.dch == 8) return launch_knn_wide<8>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
+        if (p.dch == 16) return launch_knn_wide<16>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
+        return launch_knn_wide<32>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
+    }
+    if (l) {
+        const int dpb = c.dpb;
+        const double eps = c.eps;
+        double *u = l->u;
+        int32_t *cnt = l->cnt, *list = l->list, *overflow = l->overflow;
+        GEO_HIP_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
+        const unsigned rgrid = (unsigned)((rows + KNN_WAVES - 1) / KNN_WAVES);
+        auto splits_for = [&](int64_t corpus) {                // corpus slices per 128-query block: enough workgroups, tiles to spare
+            const int64_t qb = (rows + 127) / 128;
+            int64_t sp = 16384 / qb;
+            if (sp > 64) sp = 64;
+            if (sp > (corpus + 255) / 256) sp = (corpus + 255) / 256;
+            return (int)(sp > 1 ? sp : 1);
+        };
+#define GEO_REFINE(DCHV, EXV, ZC, NRMC) \
+    knn_refine_kernel<DCHV, EXV><<<rgrid, 256, 0, stream>>>(ZC, q.zq64, NRMC, q.nrm_q, p.nch, kq, row0, rows, cnt, list, \
+                                                          idx_out, d2_out, overflow)
+#define GEO_REFINE_ANY(ZC, NRMC)                                                                                   \
+    do {                                                                                                           \
+        if (p.dch == 8) { if (ex) GEO_REFINE(8, true, ZC, NRMC); else GEO_REFINE(8, false, ZC, NRMC); }              \
+        else if (p.dch == 16) { if (ex) GEO_REFINE(16, true, ZC, NRMC); else GEO_REFINE(16, false, ZC, NRMC); }      \
+        else { if (ex) GEO_REFINE(32, true, ZC, NRMC); else GEO_REFINE(32, false, ZC, NRMC); }                       \
+    } while (0)
+        int rc = 0;
+        bool tau_done = false;
+        if (c.two_level) {
+            rc = launch_knn_bound(p, ex, c.zs0, q.zq64, c.nrm_s0, q.nrm_q, c.m0, kq, row0, row1, eps, u, cnt, nullptr, stream);
+            if (rc) return rc;
+            const int sp1 = splits_for(c.m);
+            const unsigned g1 = (unsigned)((rows + 127) / 128) * (unsigned)sp1;
+            if (dpb == 16) knn_scan_bf16_kernel<16, 256><<<g1, 256, 0, stream>>>(c.zb_s, q.zbq, c.negn_s, u, c.m, row0, rows, sp1, cnt, list);
+            else if (dpb == 32) knn_scan_bf16_kernel<32, 256><<<g1, 256, 0, stream>>>(c.zb_s, q.zbq, c.negn_s, u, c.m, row0, rows, sp1, cnt, list);
+            else knn_scan_bf16_kernel<64, 128><<<g1, 256, 0, stream>>>(c.zb_s, q.zbq, c.negn_s, u, c.m, row0, rows, sp1, cnt, list);
+            GEO_LAUNCH_CHECK();
+            GEO_REFINE_ANY(c.zs32, c.nrm_s);                   // kq smallest exact distances to the subset -> d2_out
+            GEO_LAUNCH_CHECK();
+            int32_t h_over0 = 0;
+            GEO_HIP_CHECK(hipMemcpyAsync(&h_over0, overflow, 4, hipMemcpyDeviceToHost, stream));
+            GEO_HIP_CHECK(hipStreamSynchronize(stream));
+            tau_done = h_over0 == 0;
+            if (tau_done) *path = GEO_KNN_PATH_TWO_LEVEL;
+            if (!tau_done) GEO_HIP_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
+        }
+        if (tau_done) {                                        // the subset's exact kq-th distances, left in d2_out by the refinement
+            knn_tau_kernel<<<geo::grid_for(rows, 256, 4096), 256, 0, stream>>>(d2_out, q.nrm_q, row0, rows, kq, eps, u, cnt);
+            GEO_LAUNCH_CHECK();
+        } else {
+            *path = c.bf16_scan ? GEO_KNN_PATH_FILTER_BF16 : GEO_KNN_PATH_FILTER_F32;
+            rc = launch_knn_bound(p, ex, c.zs32, q.zq64, c.nrm_s, q.nrm_q, c.m, kq, row0, row1, eps, u, cnt, nullptr, stream);
+            if (rc) return rc;
+        }
+        const int splits = splits_for(n);
+        const unsigned sgrid = (unsigned)((rows + 127) / 128) * (unsigned)splits;
+        if (c.bf16_scan) {
+            if (dpb == 16) knn_scan_bf16_kernel<16, 256><<<sgrid, 256, 0, stream>>>(c.zb, q.zbq, c.negn, u, n, row0, rows, splits, cnt, list);
+            else if (dpb == 32) knn_scan_bf16_kernel<32, 256><<<sgrid, 256, 0, stream>>>(c.zb, q.zbq, c.negn, u, n, row0, rows, splits, cnt, list);
+            else knn_scan_bf16_kernel<64, 128><<<sgrid, 256, 0, stream>>>(c.zb, q.zbq, c.negn, u, n, row0, rows, splits, cnt, list);
+        } else
+        if (p.dp == 8) knn_scan_kernel<8, 256><<<sgrid, 256, 0, stream>>>(c.zp32, c.nrm, u, n, q.f32_row0, rows, eps, splits, cnt, list);
+        else if (p.dp == 16) knn_scan_kernel<16, 256><<<sgrid, 256, 0, stream>>>(c.zp32, c.nrm, u, n, q.f32_row0, rows, eps, splits, cnt, list);
+        else if (p.dp == 32) knn_scan_kernel<32, 256><<<sgrid, 256, 0, stream>>>(c.zp32, c.nrm, u, n, q.f32_row0, rows, eps, splits, cnt, list);
+        else knn_scan_kernel<64, 128><<<sgrid, 256, 0, stream>>>(c.zp32, c.nrm, u, n, q.f32_row0, rows, eps, splits, cnt, list);
+        GEO_LAUNCH_CHECK();
+        GEO_REFINE_ANY(c.zp32, c.nrm);
+#undef GEO_REFINE_ANY
+#undef GEO_REFINE
+        GEO_LAUNCH_CHECK();
+        int32_t h_over = 0;
+        GEO_HIP_CHECK(hipMemcpyAsync(&h_over, overflow, 4, hipMemcpyDeviceToHost, stream));
+        GEO_HIP_CHECK(hipStreamSynchronize(stream));
+        if (h_over == 0) return GEO_OK;
+        // some query kept more than FILTER_CAP candidates (masses of near-duplicates): exact scan for everything
+        *path |= GEO_KNN_PATH_OVERFLOW;
+    } else {
+        *path = GEO_KNN_PATH_EXACT;
+    }
+    const bool small = rows < 16384;              // fewer queries per wave keeps the chip busy on small inputs
+    int rc;
+    if (p.dch == 8)
+        rc = small ? launch_knn<8, 4>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream)
+                   : launch_knn<8, 16>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
+    else if (p.dch == 16)
+        rc = small ? launch_knn<16, 4>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream)
+                   : launch_knn<16, 16>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
+    else
+        rc = small ? launch_knn<32, 4>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream)
+                   : launch_knn<32, 16>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
+    return rc;
+}
+
+// what one query row of a slice keeps in geo_knn_query's workspace, in 4-byte elements (geo::plan_passes): the padded
+// float32 row (first: it continues the corpus array, see KnnQuery::f32_row0), the fp64 row, the norm; on the filter paths the
+// bf16 parts, the split kernel's unused norm column, u, cnt and the candidate list
+constexpr int QUERY_BUFS = 8;
+int query_per_item(const KnnPlan &p, bool filter, size_t *per_item) {
+    const size_t dpb = p.dp < 16 ? 16 : p.dp;
+    per_item[0] = (size_t)p.dp; per_item[1] = 2 * (size_t)p.dp; per_item[2] = 2;
+    if (!filter) return 3;
+    per_item[3] = dpb; per_item[4] = 1; per_item[5] = 2; per_item[6] = 1; per_item[7] = FILTER_CAP;
+    return QUERY_BUFS;
+}
+constexpr int64_t QUERY_MIN_SLICE = 128, QUERY_PREP_CHUNK = 65536;
+
+// the corpus side of geo_knn_query's workspace: what geo_knn_topk keeps without its fp64 copy and per-row buffers, a
+// QUERY_PREP_CHUNK-row fp64 scratch for knn_prep_kernel instead, the padded float32 corpus last
+size_t query_corpus_bytes(int64_t n, const KnnPlan &p) {
+    const size_t chunk = (size_t)(n < QUERY_PREP_CHUNK ? n : QUERY_PREP_CHUNK);
+    size_t b = geo::align_up((size_t)n * sizeof(double)) + geo::align_up(chunk * p.dp * sizeof(double));
+    if (filter_applies(n, p.dp)) {
+        const size_t m = ((size_t)n + FILTER_STRIDE_MIN - 1) / FILTER_STRIDE_MIN;     // the densest subset (longest lists)
+        const size_t dpb = p.dp < 16 ? 16 : p.dp;
+        const size_t n_pad = ((size_t)n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;
+        const size_t m0 = (m + FILTER_STRIDE_MIN - 1) / FILTER_STRIDE_MIN;
+        b += geo::align_up(m * p.dp * sizeof(float)) + geo::align_up(m * sizeof(double)) + 256 +
+             geo::align_up(n_pad * 2 * dpb * sizeof(unsigned short)) + geo::align_up(n_pad * sizeof(float)) +
+             geo::align_up(m0 * p.dp * sizeof(float)) + geo::align_up(m0 * sizeof(double)) +
+             geo::align_up(m_pad * 2 * dpb * sizeof(unsigned short)) + geo::align_up(m_pad * sizeof(float));
+    }
+    return b + geo::align_up((size_t)n * p.dp * sizeof(float));
 }
 
 }  // namespace
@@ -1025,140 +1243,136 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
     }
     knn_prep_kernel<<<geo::grid_for(n, 256, 4096), 256, 0, stream>>>(z, n, d, p.dp, zp32, zq64, nrm);
     GEO_LAUNCH_CHECK();
-    const bool ex = form != 0;
-    const int64_t rows = row1 - row0;
-    if (n_neighbors > 64) {                       // no float32 filter here: its candidate lists are sized for kq <= 64
-        g_last_path = GEO_KNN_PATH_EXACT_WIDE;
-        if (p.dch == 8) return launch_knn_wide<8>(ex, zp32, zq64, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
-        if (p.dch == 16) return launch_knn_wide<16>(ex, zp32, zq64, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
-        return launch_knn_wide<32>(ex, zp32, zq64, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
-    }
+    KnnCorpus c = {};
+    c.zp32 = zp32; c.nrm = nrm; c.n = n;
+    KnnLists lists = {};
     const int S = filter_stride(n_neighbors);
-    if (filter_applies(n, p.dp) && (n + S - 1) / S >= n_neighbors) {
-        const int64_t m = (n + S - 1) / S;
-        float *zs32 = ar.take<float>((size_t)m * p.dp);
-        double *nrm_s = ar.take<double>((size_t)m);
-        double *u = ar.take<double>((size_t)n);
-        int32_t *cnt = ar.take<int32_t>((size_t)n);
-        int32_t *list = ar.take<int32_t>((size_t)n * FILTER_CAP);
-        int32_t *overflow = ar.take<int32_t>(16);
-        const int dpb = p.dp < 16 ? 16 : p.dp;
-        const bool bf16_scan = geo::options().knn_filter != 2;         // 2: the float32 matrix-core scan (comparison runs)
-        const int64_t n_pad = (n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;      // the scan reads whole tiles
-        unsigned short *zb = ar.take<unsigned short>((size_t)n_pad * 2 * dpb);
-        float *negn = ar.take<float>((size_t)n_pad);
-        const size_t m0w = ((size_t)m + S - 1) / S;
-        float *zs0 = ar.take<float>(m0w * p.dp);
-        double *nrm_s0 = ar.take<double>(m0w);
-        unsigned short *zb_s = ar.take<unsigned short>((size_t)m_pad * 2 * dpb);
-        float *negn_s = ar.take<float>((size_t)m_pad);
-        if (!zs0 || !nrm_s0 || !zb_s || !negn_s) zs0 = nullptr;   // (a caller with a smaller workspace: one level)
-        if (!zs32 || !nrm_s || !u || !cnt || !list || !overflow || !zb || !negn) {
+    const bool filter = n_neighbors <= 64 && filter_applies(n, p.dp) && (n + S - 1) / S >= n_neighbors;
+    if (filter) {
+        if (!carve_filter_corpus(ar, p, n, n_neighbors, c, lists, n)) {
             geo::set_error("geo_knn_topk: workspace %zu too small", ws_bytes);
             return GEO_E_WORKSPACE;
         }
-        // a d-term float32 dot product errs by < (d + 2) 2^-24 |x||y|, |x||y| <= (|x|^2 + |y|^2) / 2, and the float32
-        // test adds a few more roundings of the same size: 16x margin
-        // (the bf16 scan keeps 16 bits of every coordinate: its products err by < 2^-16 (|x|^2 + |y|^2) on top, 4x margin)
-        const double eps = 16.0 * (p.dp + 2) * 5.9604644775390625e-08 + (bf16_scan ? 4.0 * 1.52587890625e-05 : 0.0);
-        GEO_HIP_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
-        knn_subset_kernel<<<geo::grid_for(m * p.dp, 256, 4096), 256, 0, stream>>>(zp32, nrm, n, p.dp, S, m, zs32, nrm_s);
-        GEO_LAUNCH_CHECK();
-        if (bf16_scan) {
-            knn_split_kernel<<<geo::grid_for(n_pad * dpb, 256, 4096), 256, 0, stream>>>(zp32, nrm, n, n_pad, p.dp, dpb, eps, zb, negn);
-            GEO_LAUNCH_CHECK();
-        }
-        const unsigned rgrid = (unsigned)((rows + KNN_WAVES - 1) / KNN_WAVES);
-        auto splits_for = [&](int64_t corpus) {                // corpus slices per 128-query block: enough workgroups, tiles to spare
-            const int64_t qb = (rows + 127) / 128;
-            int64_t sp = 16384 / qb;
-            if (sp > 64) sp = 64;
-            if (sp > (corpus + 255) / 256) sp = (corpus + 255) / 256;
-            return (int)(sp > 1 ? sp : 1);
-        };
-#define GEO_REFINE(DCHV, EXV, ZC, NRMC) \
-    knn_refine_kernel<DCHV, EXV><<<rgrid, 256, 0, stream>>>(ZC, zq64, NRMC, nrm, p.nch, n_neighbors, row0, rows, cnt, list, \
-                                                          idx_out, d2_out, overflow)
-#define GEO_REFINE_ANY(ZC, NRMC)                                                                                   \
-    do {                                                                                                           \
-        if (p.dch == 8) { if (ex) GEO_REFINE(8, true, ZC, NRMC); else GEO_REFINE(8, false, ZC, NRMC); }              \
-        else if (p.dch == 16) { if (ex) GEO_REFINE(16, true, ZC, NRMC); else GEO_REFINE(16, false, ZC, NRMC); }      \
-        else { if (ex) GEO_REFINE(32, true, ZC, NRMC); else GEO_REFINE(32, false, ZC, NRMC); }                       \
-    } while (0)
-        int rc = 0;
-        bool tau_done = false;
-        // Large inputs: the pass over every S-th row is itself N^2 / S fp64 work (S = 16: 100 ms of 255 at a million latents).
-        // Two levels instead: thresholds from every S-th row of every S-th row (knn_bound_kernel), with them the SAME filter +
-        // refinement over the every-S-th-row subset gives the exact kq-th distance to that subset -- at least as tight as the
-        // threshold of the one-level scheme; the same candidate counts at both levels.
-        const int64_t m0 = (m + S - 1) / S;
-        if (bf16_scan && zs0 && n >= TWO_LEVEL_MIN && m0 >= n_neighbors) {
-            knn_subset_kernel<<<geo::grid_for(m0 * p.dp, 256, 4096), 256, 0, stream>>>(zs32, nrm_s, m, p.dp, S, m0, zs0, nrm_s0);
-            GEO_LAUNCH_CHECK();
-            rc = launch_knn_bound(p, ex, zs0, zq64, nrm_s0, nrm, m0, n_neighbors, row0, row1, eps, u, cnt, nullptr, stream);
-            if (rc) return rc;
-            knn_split_kernel<<<geo::grid_for(m_pad * dpb, 256, 4096), 256, 0, stream>>>(zs32, nrm_s, m, m_pad, p.dp, dpb, eps, zb_s, negn_s);
-            GEO_LAUNCH_CHECK();
-            const int sp1 = splits_for(m);
-            const unsigned g1 = (unsigned)((rows + 127) / 128) * (unsigned)sp1;
-            if (dpb == 16) knn_scan_bf16_kernel<16, 256><<<g1, 256, 0, stream>>>(zb_s, zb, negn_s, u, m, row0, rows, sp1, cnt, list);
-            else if (dpb == 32) knn_scan_bf16_kernel<32, 256><<<g1, 256, 0, stream>>>(zb_s, zb, negn_s, u, m, row0, rows, sp1, cnt, list);
-            else knn_scan_bf16_kernel<64, 128><<<g1, 256, 0, stream>>>(zb_s, zb, negn_s, u, m, row0, rows, sp1, cnt, list);
-            GEO_LAUNCH_CHECK();
-            GEO_REFINE_ANY(zs32, nrm_s);                       // kq smallest exact distances to the subset -> d2_out
-            GEO_LAUNCH_CHECK();
-            int32_t h_over0 = 0;
-            GEO_HIP_CHECK(hipMemcpyAsync(&h_over0, overflow, 4, hipMemcpyDeviceToHost, stream));
-            GEO_HIP_CHECK(hipStreamSynchronize(stream));
-            tau_done = h_over0 == 0;
-            if (tau_done) g_last_path = GEO_KNN_PATH_TWO_LEVEL;
-            if (!tau_done) GEO_HIP_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
-        }
-        if (tau_done) {                                        // the subset's exact kq-th distances, left in d2_out by the refinement
-            knn_tau_kernel<<<geo::grid_for(rows, 256, 4096), 256, 0, stream>>>(d2_out, nrm, row0, rows, n_neighbors, eps, u, cnt);
-            GEO_LAUNCH_CHECK();
-        } else {
-            g_last_path = bf16_scan ? GEO_KNN_PATH_FILTER_BF16 : GEO_KNN_PATH_FILTER_F32;
-            rc = launch_knn_bound(p, ex, zs32, zq64, nrm_s, nrm, m, n_neighbors, row0, row1, eps, u, cnt, nullptr, stream);
-            if (rc) return rc;
-        }
-        const int splits = splits_for(n);
-        const unsigned sgrid = (unsigned)((rows + 127) / 128) * (unsigned)splits;
-        if (bf16_scan) {
-            if (dpb == 16) knn_scan_bf16_kernel<16, 256><<<sgrid, 256, 0, stream>>>(zb, zb, negn, u, n, row0, rows, splits, cnt, list);
-            else if (dpb == 32) knn_scan_bf16_kernel<32, 256><<<sgrid, 256, 0, stream>>>(zb, zb, negn, u, n, row0, rows, splits, cnt, list);
-            else knn_scan_bf16_kernel<64, 128><<<sgrid, 256, 0, stream>>>(zb, zb, negn, u, n, row0, rows, splits, cnt, list);
-        } else
-        if (p.dp == 8) knn_scan_kernel<8, 256><<<sgrid, 256, 0, stream>>>(zp32, nrm, u, n, row0, rows, eps, splits, cnt, list);
-        else if (p.dp == 16) knn_scan_kernel<16, 256><<<sgrid, 256, 0, stream>>>(zp32, nrm, u, n, row0, rows, eps, splits, cnt, list);
-        else if (p.dp == 32) knn_scan_kernel<32, 256><<<sgrid, 256, 0, stream>>>(zp32, nrm, u, n, row0, rows, eps, splits, cnt, list);
-        else knn_scan_kernel<64, 128><<<sgrid, 256, 0, stream>>>(zp32, nrm, u, n, row0, rows, eps, splits, cnt, list);
-        GEO_LAUNCH_CHECK();
-        GEO_REFINE_ANY(zp32, nrm);
-#undef GEO_REFINE_ANY
-#undef GEO_REFINE
-        GEO_LAUNCH_CHECK();
-        int32_t h_over = 0;
-        GEO_HIP_CHECK(hipMemcpyAsync(&h_over, overflow, 4, hipMemcpyDeviceToHost, stream));
-        GEO_HIP_CHECK(hipStreamSynchronize(stream));
-        if (h_over == 0) return GEO_OK;
-        // some query kept more than FILTER_CAP candidates (masses of near-duplicates): exact scan for everything
-        g_last_path |= GEO_KNN_PATH_OVERFLOW;
-    } else {
-        g_last_path = GEO_KNN_PATH_EXACT;
+        const int rc = prepare_filter_corpus(p, c, stream);
+        if (rc) return rc;
     }
-    const bool small = rows < 16384;              // fewer queries per wave keeps the chip busy on small inputs
-    int rc;
-    if (p.dch == 8)
-        rc = small ? launch_knn<8, 4>(ex, zp32, zq64, nrm, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream)
-                   : launch_knn<8, 16>(ex, zp32, zq64, nrm, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
-    else if (p.dch == 16)
-        rc = small ? launch_knn<16, 4>(ex, zp32, zq64, nrm, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream)
-                   : launch_knn<16, 16>(ex, zp32, zq64, nrm, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
-    else
-        rc = small ? launch_knn<32, 4>(ex, zp32, zq64, nrm, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream)
-                   : launch_knn<32, 16>(ex, zp32, zq64, nrm, nrm, n, p.nch, n_neighbors, row0, row1, idx_out, d2_out, stream);
+    const KnnQuery q = {zq64, nrm, c.zb, row0, row1, row0};     // the corpus' own rows
+    int32_t path = 0;
+    const int rc = search_rows(p, form != 0, n_neighbors, c, q, filter ? &lists : nullptr, idx_out, d2_out, stream, &path);
+    g_last_path = path;
     return rc;
+}
+
+extern "C" size_t geo_knn_query_min_workspace_bytes(int64_t n, int32_t d) {
+    if (n <= 0 || d <= 0) return 1024;
+    const KnnPlan p = plan_for(d);
+    size_t per_item[QUERY_BUFS];
+    const int nb = query_per_item(p, filter_applies(n, p.dp), per_item);
+    return query_corpus_bytes(n, p) + geo::pass_bytes(per_item, nb, QUERY_MIN_SLICE);
+}
+
+extern "C" size_t geo_knn_query_workspace_bytes(int64_t n, int64_t m, int32_t d) {
+    if (n <= 0 || d <= 0) return 1024;
+    const KnnPlan p = plan_for(d);
+    size_t per_item[QUERY_BUFS];
+    const int nb = query_per_item(p, filter_applies(n, p.dp), per_item);
+    return query_corpus_bytes(n, p) + geo::pass_bytes(per_item, nb, m > QUERY_MIN_SLICE ? m : QUERY_MIN_SLICE);
+}
+
+extern "C" int geo_knn_query(const float *z, int64_t n, const float *q, int64_t m, int32_t d, int32_t n_neighbors, int32_t form,
+                             int32_t *idx_out, double *d2_out, void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    g_last_path = 0;
+    GEO_REQUIRE(z && q && idx_out && d2_out && ws, "geo_knn_query: null pointer");
+    GEO_REQUIRE(n > 0 && n < (int64_t)1 << 31, "geo_knn_query: n=%lld out of range", (long long)n);
+    GEO_REQUIRE(m >= 0 && m < (int64_t)1 << 31, "geo_knn_query: m=%lld out of range", (long long)m);
+    GEO_REQUIRE(d > 0 && d <= 128, "geo_knn_query: d=%d not in [1,128]", d);
+    GEO_REQUIRE(n_neighbors > 0 && n_neighbors <= GEO_KNN_MAX_NEIGHBORS && n_neighbors <= n,
+                "geo_knn_query: n_neighbors=%d not in [1, min(%d, n)]", n_neighbors, GEO_KNN_MAX_NEIGHBORS);
+    if (m == 0) return GEO_OK;
+    const KnnPlan p = plan_for(d);
+    const size_t need = geo_knn_query_min_workspace_bytes(n, d);
+    if (ws_bytes < need) {
+        geo::set_error("geo_knn_query: workspace of %zu bytes is below the minimum of %zu", ws_bytes, need);
+        return GEO_E_WORKSPACE;
+    }
+    // corpus side, prepared once for all slices
+    geo::Arena ar(ws, ws_bytes);
+    const int64_t chunk = n < QUERY_PREP_CHUNK ? n : QUERY_PREP_CHUNK;
+    double *nrm = ar.take<double>((size_t)n);
+    double *z64_scratch = ar.take<double>((size_t)chunk * p.dp);          // knn_prep_kernel's fp64 rows: the corpus' are not read
+    KnnCorpus c = {};
+    c.n = n;
+    const int S = filter_stride(n_neighbors);
+    const bool filter_ws = filter_applies(n, p.dp);                       // what the workspace was sized for
+    const bool filter = n_neighbors <= 64 && filter_ws && (n + S - 1) / S >= n_neighbors;
+    KnnLists lists = {};
+    bool ok = nrm && z64_scratch;
+    if (ok && filter) ok = carve_filter_corpus(ar, p, n, n_neighbors, c, lists, 0);
+    // the padded float32 corpus ends where the slices' buffers begin: the float32 scan reads its queries from this array
+    const size_t zp_bytes = (size_t)n * p.dp * sizeof(float);
+    char *zp_block = ok ? reinterpret_cast<char *>(ar.take<float>((size_t)n * p.dp)) : nullptr;
+    if (!zp_block) {
+        geo::set_error("geo_knn_query: workspace %zu too small", ws_bytes);
+        return GEO_E_WORKSPACE;
+    }
+    float *zp32 = reinterpret_cast<float *>(zp_block + (geo::align_up(zp_bytes) - zp_bytes));   // (a multiple of 32 bytes: dp >= 8)
+    c.zp32 = zp32; c.nrm = nrm;
+    // query side: slices of the rows that fit what is left
+    size_t per_item[QUERY_BUFS];
+    const int nb = query_per_item(p, filter_ws, per_item);
+    int64_t slice = 0;
+    float *bufs[QUERY_BUFS] = {};
+    int rc = geo::plan_passes("geo_knn_query", per_item, nb, m, m, static_cast<char *>(ws) + ar.off, ws_bytes - ar.off, &slice, bufs);
+    if (rc) return rc;
+    float *qz32 = bufs[0];
+    double *qz64 = reinterpret_cast<double *>(bufs[1]);
+    double *nrm_q = reinterpret_cast<double *>(bufs[2]);
+    unsigned short *zbq = filter ? reinterpret_cast<unsigned short *>(bufs[3]) : nullptr;
+    float *negn_q = filter ? bufs[4] : nullptr;
+    if (filter) {
+        lists.u = reinterpret_cast<double *>(bufs[5]);
+        lists.cnt = reinterpret_cast<int32_t *>(bufs[6]);
+        lists.list = reinterpret_cast<int32_t *>(bufs[7]);
+    }
+    if (qz32 != zp32 + (size_t)n * p.dp) {
+        geo::set_error("geo_knn_query: internal: the query rows do not continue the corpus array");
+        return GEO_E_ARG;
+    }
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int64_t cr = n - c0 < chunk ? n - c0 : chunk;
+        knn_prep_kernel<<<geo::grid_for(cr, 256, 4096), 256, 0, stream>>>(z + c0 * d, cr, d, p.dp, zp32 + c0 * p.dp, z64_scratch, nrm + c0);
+        GEO_LAUNCH_CHECK();
+    }
+    if (filter) {
+        rc = prepare_filter_corpus(p, c, stream);
+        if (rc) return rc;
+    }
+    int32_t path_all = 0;
+    for (int64_t s0 = 0; s0 < m; s0 += slice) {
+        const int64_t rows = m - s0 < slice ? m - s0 : slice;
+        knn_prep_kernel<<<geo::grid_for(rows, 256, 4096), 256, 0, stream>>>(q + s0 * d, rows, d, p.dp, qz32, qz64, nrm_q);
+        GEO_LAUNCH_CHECK();
+        if (filter && c.bf16_scan) {                           // the queries' bf16 parts: no padding rows (the scan clamps its queries)
+            knn_split_kernel<<<geo::grid_for(rows * c.dpb, 256, 4096), 256, 0, stream>>>(qz32, nrm_q, rows, rows, p.dp, c.dpb, c.eps, zbq, negn_q);
+            GEO_LAUNCH_CHECK();
+        }
+        const KnnQuery qs = {qz64, nrm_q, zbq, 0, rows, n};
+        int32_t path = 0;
+        rc = search_rows(p, form != 0, n_neighbors, c, qs, filter ? &lists : nullptr, idx_out + s0 * n_neighbors,
+                         d2_out + s0 * n_neighbors, stream, &path);
+        if (rc) return rc;
+        // one answer for the call: a slice whose first level overflowed makes it the one-level path, any fallback sets the flag
+        if (s0 == 0) path_all = path;
+        else {
+            const int32_t over = (path_all | path) & GEO_KNN_PATH_OVERFLOW;
+            int32_t base = path_all & ~GEO_KNN_PATH_OVERFLOW;
+            if ((path & ~GEO_KNN_PATH_OVERFLOW) != base) base = GEO_KNN_PATH_FILTER_BF16;
+            path_all = base | over;
+        }
+    }
+    g_last_path = path_all;
+    return GEO_OK;
 }
 
 extern "C" int geo_knn_last_path(void) { return g_last_path; }

@@ -2,12 +2,12 @@
 `src.geo` package (src/geo/__init__.py:5-8 re-exports the same two names), plus the K sweep of the
 k-medoids analysis (fit_kmedoids_path, an extension) and the Riemannian graph experiments of the reference's
 experiments/geo scripts (vqvae_amd.geo.experiments)."""
-from .knn_graph_optimized import build_knn_graph
+from .knn_graph_optimized import build_knn_graph, kneighbors, knn_query_device
 from .geo_shortest_paths import dijkstra_multi_source
 from .kmeans_optimized import fit_kmedoids_path
 from .experiments import (mean_shortest_path, mean_shortest_path_device, pick_sources_from_lcc, reweight_edges_symmetric_device,
                           riemann_graph_effects, riemann_sanity, stratified_edge_sample)
 
-__all__ = ["build_knn_graph", "dijkstra_multi_source", "fit_kmedoids_path", "mean_shortest_path", "mean_shortest_path_device",
-           "pick_sources_from_lcc", "reweight_edges_symmetric_device", "riemann_graph_effects", "riemann_sanity",
+__all__ = ["build_knn_graph", "dijkstra_multi_source", "fit_kmedoids_path", "kneighbors", "knn_query_device", "mean_shortest_path",
+           "mean_shortest_path_device", "pick_sources_from_lcc", "reweight_edges_symmetric_device", "riemann_graph_effects", "riemann_sanity",
            "stratified_edge_sample"]

@@ -42,6 +42,64 @@ def knn_search_device(z: torch.Tensor, n_neighbors: int, row0: int = 0, row1: Op
     return idx, d2
 
 
+def _check_query_shapes(z_shape, q_shape, n_neighbors: int) -> None:
+    """The ValueErrors of a query search, from shapes alone (raised before the library is loaded)."""
+    if len(z_shape) != 2 or len(q_shape) != 2:
+        raise ValueError(f"corpus and queries must be 2-D, got shapes {tuple(z_shape)} and {tuple(q_shape)}")
+    (n, d), (_, dq) = z_shape, q_shape
+    if dq != d:
+        raise ValueError(f"queries have {dq} columns, the corpus {d}")
+    if not 1 <= d <= 128:
+        raise ValueError(f"latent dimension {d} outside the supported range [1, 128]")
+    if not 1 <= n_neighbors <= min(MAX_NEIGHBORS, n):
+        raise ValueError(f"n_neighbors = {n_neighbors} outside [1, min({MAX_NEIGHBORS}, n = {n})]")
+
+
+def knn_query_device(z: torch.Tensor, q: torch.Tensor, n_neighbors: int, form: Optional[int] = None,
+                     max_workspace_bytes: Optional[int] = None):
+    """(idx int32 [m, n_neighbors], d2 float64 [m, n_neighbors]): for every row of the resident queries q (f32 [m, d]) the
+    n_neighbors nearest rows of the resident corpus z (f32 [n, d]), ordered by (fp64 key, corpus index) -- sklearn's
+    NearestNeighbors.fit(z).kneighbors(q), by the kernels and paths of knn_search_device (geo_knn_query).  form: 0 = sum of
+    squared differences, 1 = norm expansion, None = the rule of knn_search_device (d > 15 -> expansion).
+    max_workspace_bytes caps the workspace (never below the library's minimum): the queries then run in slices; the result
+    does not depend on it."""
+    _check_query_shapes(z.shape, q.shape, n_neighbors)
+    if z.dtype != torch.float32 or q.dtype != torch.float32:
+        raise ValueError(f"corpus and queries must be float32, got {z.dtype} and {q.dtype}")
+    if q.device != z.device:
+        raise ValueError(f"corpus on {z.device}, queries on {q.device}")
+    from .._export import capped_workspace
+    lib = _lib.load()
+    (n, d), m = z.shape, int(q.shape[0])
+    z, q = z.contiguous(), q.contiguous()
+    idx = torch.empty((m, n_neighbors), dtype=torch.int32, device=z.device)
+    d2 = torch.empty((m, n_neighbors), dtype=torch.float64, device=z.device)
+    if m == 0:
+        return idx, d2
+    if form is None:
+        form = 1 if d > 15 else 0
+    cap = None if max_workspace_bytes is None else max(int(max_workspace_bytes), lib.geo_knn_query_min_workspace_bytes(n, d))
+    with torch.cuda.device(z.device):
+        ws = capped_workspace(lib.geo_knn_query_workspace_bytes(n, m, d), cap, z.device, "knn_query_device:")
+        _lib.check(lib.geo_knn_query(ptr(z), n, ptr(q), m, d, n_neighbors, int(form), ptr(idx), ptr(d2), ptr(ws), ws.numel(),
+                                     stream_ptr()), "geo_knn_query")
+    return idx, d2
+
+
+def kneighbors(z: np.ndarray, q: np.ndarray, k: int, metric: str = "euclidean"):
+    """sklearn's NearestNeighbors(n_neighbors=k).fit(z).kneighbors(q) on the GPU: (distances f64 [m, k], indices int64 [m, k]),
+    nearest first, equal distances by corpus index.  Euclidean only."""
+    if metric != "euclidean":
+        raise ValueError(f"Metric '{metric}' not supported by kneighbors. Use 'euclidean'.")
+    z, q = np.asarray(z), np.asarray(q)
+    _check_query_shapes(z.shape, q.shape, int(k))
+    dev = device()
+    z_dev = torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(dev)
+    q_dev = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(dev)
+    idx, d2 = knn_query_device(z_dev, q_dev, int(k))
+    return torch.sqrt(d2).cpu().numpy(), idx.cpu().numpy().astype(np.int64)
+
+
 def symmetrize_device(nbr_idx: torch.Tensor, nbr_w: Optional[torch.Tensor], sym: str) -> DeviceCSR:
     """Directed neighbour lists (int32 [N,k], optional f32 weights) -> canonical symmetric CSR."""
     lib = _lib.load()
