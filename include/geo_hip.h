@@ -586,9 +586,10 @@ int geo_prior_attention_bwd(const float *qkv, const float *probs, const uint8_t 
                             int32_t B, int32_t T, int32_t H, int32_t head_dim, float *dqkv, void *stream);
 /* torch.optim.AdamW's update (train_transformer.py:39-43,64-66: decoupled weight decay, bias-corrected moments) over ONE
  * flat buffer of n floats in a single pass.  lr_dev f32 [1] and step_dev i64 [1] (the 1-based step count of THIS update) are
- * read on the device, so the launch does not change from step to step.  Asynchronous on `stream`. */
+ * read on the device, so the launch does not change from step to step.  The hyper-parameters are doubles, as torch holds
+ * them: 1 - beta is formed in double before it is rounded to float.  Asynchronous on `stream`. */
 int geo_prior_adamw(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev,
-                    const int64_t *step_dev, float beta1, float beta2, float eps, float weight_decay, void *stream);
+                    const int64_t *step_dev, double beta1, double beta2, double eps, double weight_decay, void *stream);
 
 /* ---- sampling from the code prior (src/scripts/generate_samples.py:12-31: sample, top_k_logits) ----
  * The model: dims, the flat f32 parameter arena (vqvae_amd/prior/transformer.py, Transformer.layout) and the float offsets of

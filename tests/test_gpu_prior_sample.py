@@ -1,5 +1,5 @@
 """The KV-cached HIP decode of the code prior (csrc/prior_sample.hip) on the MI355X: teacher-forced logits against
-Transformer.forward, greedy sequences against the reference (tests/golden/prior_sample.npz), the draw rule on explicit
+Transformer.forward and against a float64 restatement of it, greedy sequences against the reference (tests/golden/prior_sample.npz), the draw rule on explicit
 uniforms, the distribution of draws, reproducibility across seeds and concurrent streams, the fallback for non-standard
 masks, and the generate_samples CLI end to end."""
 import threading
@@ -8,12 +8,14 @@ import numpy as np
 import pytest
 import torch
 
+from prior_cases import forward_fp64
 from test_prior_sample_host import check_cli_outputs, fixture_inputs, fixture_model, tiny_setup
 
 pytestmark = pytest.mark.gpu
 
 # f32 end to end; the decode sums in another order than the GEMMs under Transformer.forward.  Measured on the MI355X: max
 # |diff| / max |logit| 4.9e-7 .. 1.41e-6 over the shapes and batch sizes below (the test prints it); the bound leaves ~14x.
+# Against the float64 restatement (prior_cases.forward_fp64, no kernel of this project): 3.9e-7 .. 1.32e-6.
 LOGIT_TOL = 2e-5
 SHAPES = {
     "prior_hd16": dict(num_classes=10, num_tokens=64, embed_dim=64, n_layers=2, n_head=4, max_seq_len=16),
@@ -57,8 +59,13 @@ def test_teacher_forced_logits_equal_forward(shape, B, labelled):
     with torch.no_grad():
         want = model(x[:, :T - 1], y=y)
     err = float((logits - want).abs().max() / want.abs().max())
-    print(f"{shape} B={B} labelled={labelled}: max |diff| / max |logit| = {err:.2e}")
+    # ... and against the float64 restatement, which runs no kernel of this project (the forward above runs csrc/prior.hip's
+    # attention, so an error the two attention kernels shared would cancel in `err`); all rows, float64 on the GPU
+    want64 = forward_fp64(model, x[:, :T - 1], y)
+    err64 = float((logits.double() - want64).abs().max() / want64.abs().max())
+    print(f"{shape} B={B} labelled={labelled}: max |diff| / max |logit| = {err:.2e} (forward), {err64:.2e} (float64)")
     assert err < LOGIT_TOL
+    assert err64 < LOGIT_TOL
 
 
 @pytest.mark.parametrize("name", ["prior", "prior_nolabel", "fm", "vanilla", "vanilla_nolabel", "limit", "nonstd"])
@@ -102,6 +109,8 @@ def test_explicit_uniforms_follow_the_draw_rule(temperature, top_k):
     with torch.no_grad():
         fwd = model(tokens[:, :-1], y=y)[:, T0 - 1:]
     assert float((drawn - fwd).abs().max() / fwd.abs().max()) < LOGIT_TOL
+    fwd64 = forward_fp64(model, tokens[:, :-1], y)[:, T0 - 1:]           # no kernel of this project on the reference side
+    assert float((drawn.double() - fwd64).abs().max() / fwd64.abs().max()) < LOGIT_TOL
     near = 0
     for s in range(steps):
         want = draw_rule(drawn[:, s], u[:, s], temperature, top_k)

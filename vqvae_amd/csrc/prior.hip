@@ -155,16 +155,19 @@ __global__ __launch_bounds__(64 * WPB) void prior_attention_bwd_kernel(const flo
 }
 
 // torch.optim.AdamW's step on one flat buffer (decoupled weight decay, bias-corrected moments); lr and step on the device.
+// The hyper-parameters arrive as the doubles torch holds them in: 1 - beta is formed in double and rounded once, as torch
+// does.  (From a float beta2 = 0.999f, 1 - beta2 is 1.3e-5 short of 0.001, and exp_avg_sq with it.)
 __global__ __launch_bounds__(256) void prior_adamw_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                          float *__restrict__ v, int64_t n, const float *__restrict__ lr_dev,
-                                                         const int64_t *__restrict__ step_dev, float beta1, float beta2, float eps,
-                                                         float weight_decay) {
+                                                         const int64_t *__restrict__ step_dev, double beta1_, double beta2_, double eps_,
+                                                         double weight_decay) {
     const double lr = (double)lr_dev[0];
     const double step = (double)step_dev[0];
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    const float decay = (float)(1.0 - lr * (double)weight_decay);
+    const double bc1 = 1.0 - pow(beta1_, step), bc2 = 1.0 - pow(beta2_, step);
+    const float decay = (float)(1.0 - lr * weight_decay);
     const float step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-    const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
+    const float w1 = (float)(1.0 - beta1_), w2 = (float)(1.0 - beta2_);
+    const float beta2 = (float)beta2_, eps = (float)eps_;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float gi = g[i];
         const float pi = p[i] * decay;
@@ -214,7 +217,7 @@ extern "C" int geo_prior_attention_bwd(const float *qkv, const float *probs, con
 }
 
 extern "C" int geo_prior_adamw(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev,
-                               const int64_t *step_dev, float beta1, float beta2, float eps, float weight_decay, void *stream_) {
+                               const int64_t *step_dev, double beta1, double beta2, double eps, double weight_decay, void *stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(param && grad && exp_avg && exp_avg_sq && lr_dev && step_dev && n > 0, "geo_prior_adamw: bad arguments");
     prior_adamw_kernel<<<geo::grid_for(n, 256, 2048), 256, 0, stream>>>(param, grad, exp_avg, exp_avg_sq, n, lr_dev, step_dev, beta1,
