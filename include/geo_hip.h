@@ -166,6 +166,34 @@ int geo_attach_argmin(const float *Dt, int64_t ld, int32_t K, const int32_t *nbr
                       int64_t n_new, float *dist_out, int32_t *arg_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cell-restricted medoid costs (extension; DESIGN.md "Cell-restricted medoid update"): the medoid update without the
+ * all-pairs matrix, at any graph size.  (indptr, indices, weights): symmetric pull CSR, float32 weights >= 0, n < 2^27 nodes,
+ * nnz < 2^31.  assign i32 [n] in [-1, K); order / offsets as for geo_cluster_costs: the members of cell c are
+ * order[offsets[c] .. offsets[c+1]), ascending node index, offsets[K] = nodes with assign >= 0 (a node with assign < 0 is in
+ * no cell).  The CUT graph keeps the entries whose two ends share a cell; d_c(i, j) is the shortest path in it under
+ * geo_sssp_multi's rule (fp64 sums source-outward, run to the fixed point, rounded to float32, +inf when j cannot be
+ * reached inside the cell).  cost_out f64 [n]: cost[i] = sum over the members j of i's cell, ascending, of
+ * (double)d_c(i, j)^power with geo_cluster_costs's summation tree -- bit for bit geo_cluster_costs over the all-pairs matrix
+ * of the cut graph -- and +inf for assign[i] < 0.  The unit of work is (cell, tile of geo_cell_costs_tile() sources); cells
+ * of at most resident_nodes_max nodes (0 = geo_cell_costs_resident_max_nodes(), also the most it can be) keep a unit's
+ * distance rows in LDS, larger cells in a slice of ws.  cost_out does not depend on the run, the stream, ws_bytes or
+ * resident_nodes_max.  status_out (host i32 [4]): cells solved in LDS, cells solved through the workspace, most sweeps
+ * of a unit, 0.  Before any launch: GEO_E_ARG for a null pointer, power outside {1, 2}, K < 1, n outside [1, 2^27);
+ * GEO_E_WORKSPACE below geo_cell_costs_min_workspace_bytes(n, nnz, K, 0).  After the plan (one synchronisation): GEO_E_ARG when offsets[K] > n
+ * or order / offsets / assign contradict each other, GEO_E_WORKSPACE below geo_cell_costs_min_workspace_bytes for the
+ * largest cell found (one slice; geo_cell_costs_workspace_bytes sizes a slice for every workgroup in flight -- fewer slices
+ * mean fewer large-cell units in flight, never another result).  GEO_E_NOCONV when a unit needs more than 65 536 sweeps (a
+ * cell of m nodes needs at most m).  A failed call writes nothing to cost_out.  Synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int32_t geo_cell_costs_tile(void);
+int32_t geo_cell_costs_resident_max_nodes(void);
+size_t geo_cell_costs_workspace_bytes(int32_t n, int64_t nnz, int32_t K, int32_t max_cell);
+size_t geo_cell_costs_min_workspace_bytes(int32_t n, int64_t nnz, int32_t K, int32_t max_cell);
+int geo_cell_costs(const int32_t *indptr, const int32_t *indices, const float *weights, int32_t n, int64_t nnz,
+                   const int32_t *assign, const int32_t *order, const int32_t *offsets, int32_t K, int32_t power,
+                   int32_t resident_nodes_max, double *cost_out, void *ws, size_t ws_bytes, int32_t *status_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * kNN search.  Replaces sklearn NearestNeighbors.kneighbors as called from
  * src/geo/knn_graph_optimized.py:40-42: exact n_neighbors nearest corpus rows (self included) of the
  * query rows [row0,row1) of z, ranked on fp64 squared distances, ties ordered by index.

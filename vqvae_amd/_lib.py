@@ -75,6 +75,11 @@ _SIGNATURES = {
     "geo_rows_argmin": (ctypes.c_int, [c_p, i64, c_p, i32, i32, c_p, c_p, c_p]),
     "geo_pam_swap_deltas": (ctypes.c_int, [c_p, i64, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, c_p, c_p, c_p]),
     "geo_attach_argmin": (ctypes.c_int, [c_p, i64, i32, c_p, c_p, i32, i64, c_p, c_p, c_p]),
+    "geo_cell_costs_tile": (i32, []),
+    "geo_cell_costs_resident_max_nodes": (i32, []),
+    "geo_cell_costs_workspace_bytes": (sz, [i32, i64, i32, i32]),
+    "geo_cell_costs_min_workspace_bytes": (sz, [i32, i64, i32, i32]),
+    "geo_cell_costs": (ctypes.c_int, [c_p, c_p, c_p, i32, i64, c_p, c_p, c_p, i32, i32, i32, c_p, c_p, sz, c_p, c_p]),
     "geo_kpp_resident_max_nodes": (i32, []),
     "geo_kpp_chain": (ctypes.c_int, [c_p, c_p, c_p, i32, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, c_p, sz, c_p, c_p]),
     "geo_knn_workspace_bytes": (sz, [i64, i32]),

@@ -19,7 +19,8 @@ import torch
 from scipy import sparse
 
 from .. import _lib
-from .._device import DeviceCSR, device, ptr, stream_ptr, workspace
+from .._device import DeviceCSR, device, ptr, ptr_or_stand_in, stream_ptr, workspace
+from .._export import capped_workspace
 from .geo_shortest_paths import nearest_source_device, _pull_structure, ensure_valid_graph, sssp_multi_device
 
 
@@ -465,12 +466,25 @@ def medoid_update_device(D: torch.Tensor, assign: torch.Tensor, medoids: torch.T
     with torch.cuda.device(dev):
         _lib.check(lib.geo_cluster_costs(ptr(D), D.stride(0), ptr(a32), ptr(order), ptr(offsets), n, int(power),
                                          ptr(cost), stream_ptr()), "geo_cluster_costs")
+    new, _ = _select_medoids(cost, a64, torch.arange(n, dtype=torch.int64, device=dev), medoids, n)
+    return new, cost
+
+
+def _select_medoids(cost: torch.Tensor, a64: torch.Tensor, nodes: torch.Tensor, medoids: torch.Tensor, n: int,
+                    keep_all_inf: bool = False):
+    """The medoid selection both updates share, two scatter-min passes: entry e is node nodes[e] of cluster a64[e] with cost
+    cost[e]; per cluster the node with the smallest cost, lowest node index on ties; a cluster without an entry keeps its
+    medoid.  keep_all_inf: a cluster whose costs are all +inf keeps its medoid too (otherwise its first node wins, as
+    np.argmin has it).  Returns (new medoids i32 [K], smallest cost per cluster f64 [K], +inf for a cluster without an entry)."""
+    dev, K = cost.device, int(medoids.numel())
     cmin = torch.full((K,), float("inf"), dtype=torch.float64, device=dev).scatter_reduce(0, a64, cost, "amin")
-    idx = torch.arange(n, dtype=torch.int64, device=dev)
-    cand = torch.where(cost == cmin[a64], idx, torch.full_like(idx, n))
+    hit = cost == cmin[a64]
+    if keep_all_inf:
+        hit = hit & torch.isfinite(cost)
+    cand = torch.where(hit, nodes, torch.full_like(nodes, n))
     first = torch.full((K,), n, dtype=torch.int64, device=dev).scatter_reduce(0, a64, cand, "amin")
     new = torch.where(first < n, first, medoids.to(torch.int64)).to(torch.int32)
-    return new, cost
+    return new, cmin
 
 
 def assign_from_rows_device(D: torch.Tensor, medoids: torch.Tensor):
@@ -517,6 +531,125 @@ def fit_kmedoids_voronoi(W, K: int = 512, init: str = "kpp", seed: int = 42, max
     _print_sizes(assign_h, len(medoids))
     print(f"[kmedoids] Voronoi iterations: {len(history) - 1}, qe {history[0]:.3f} -> {history[-1]:.3f}")
     return medoids, assign_h, history[-1], history
+
+
+# ---- extension: medoid update inside the cells, without any matrix (csrc/cell.hip) ----------------------------------------
+def _as_i32(x, dev) -> torch.Tensor:
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def cell_medoid_update_device(G, assign, medoids, power: int = 2, *, resident_nodes_max: Optional[int] = None,
+                              max_workspace_bytes: Optional[int] = None, info: Optional[dict] = None):
+    """One medoid update on the CUT graph (DESIGN.md "Cell-restricted medoid update"): G without the entries whose two ends
+    have different `assign`; a node with assign < 0 is in no cell.  cost[i] = sum over the members j of i's cell of
+    d_c(i, j)^power, d_c the shortest path inside the cell (geo_cell_costs: bit for bit geo_cluster_costs over the all-pairs
+    matrix of the cut graph, which is never formed), +inf for assign[i] < 0.  Per cell the member with the smallest cost,
+    lowest node index on ties; an empty cell and a cell whose costs are all +inf keep their medoid.
+    G: symmetric weighted DeviceCSR (or a scipy matrix); assign i32 [n] in [-1, K); medoids i32 [K] in [0, n).
+    resident_nodes_max: cells up to this size keep their distance rows in LDS (None: the library's bound); max_workspace_bytes
+    caps the scratch (fewer large cells in flight); neither changes a bit of the result.
+    Returns (new medoids i32 [K], cost f64 [n]).  `info`, if given, receives resident_cells, workspace_cells, max_sweeps,
+    kept_cells (cells with members whose costs are all +inf) and tile (sources per unit of work)."""
+    if power not in (1, 2):
+        raise ValueError(f"power must be 1 or 2, got {power!r}")
+    if resident_nodes_max is not None and int(resident_nodes_max) < 1:
+        raise ValueError(f"resident_nodes_max must be at least 1, got {resident_nodes_max!r}")
+    G = _to_device_graph(G)
+    if G.data is None:
+        raise ValueError("cell_medoid_update_device needs a weighted graph")
+    dev, n = G.indptr.device, G.n
+    a32, med = _as_i32(assign, dev), _as_i32(medoids, dev)
+    K = int(med.numel())
+    if a32.dim() != 1 or int(a32.numel()) != n:
+        raise ValueError(f"assign must have one entry per node ({n}), got shape {tuple(a32.shape)}")
+    if med.dim() != 1 or K < 1:
+        raise ValueError("medoids must be a non-empty vector")
+    if n and (int(a32.max()) >= K or int(a32.min()) < -1):
+        raise ValueError(f"assign must lie in [-1, {K}), got [{int(a32.min())}, {int(a32.max())}]")
+    if int(med.min()) < 0 or int(med.max()) >= n:
+        raise ValueError(f"medoids must lie in [0, {n}), got [{int(med.min())}, {int(med.max())}]")
+    lib = _lib.load()
+    a64 = a32.to(torch.int64)
+    keys = torch.where(a32 >= 0, a64, torch.full_like(a64, K))                  # nodes of no cell sort behind every cell
+    order64 = torch.argsort(keys, stable=True)                                  # members ascending inside a cell
+    counts = torch.bincount(keys, minlength=K + 1)[:K]
+    offsets = torch.zeros(K + 1, dtype=torch.int32, device=dev)
+    offsets[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    order = order64.to(torch.int32).contiguous()
+    members, max_cell = int(offsets[K]), int(counts.max())
+    ws = capped_workspace(lib.geo_cell_costs_workspace_bytes(n, G.nnz, K, max_cell), max_workspace_bytes, dev, "cell medoid update")
+    cost = torch.empty(n, dtype=torch.float64, device=dev)
+    status = np.zeros(4, dtype=np.int32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.geo_cell_costs(ptr(G.indptr), ptr_or_stand_in(G.indices), ptr_or_stand_in(G.data), n, G.nnz, ptr(a32),
+                                      ptr(order), ptr(offsets), K, int(power), int(resident_nodes_max or 0), ptr(cost), ptr(ws),
+                                      ws.numel(), status.ctypes.data, stream_ptr()), "geo_cell_costs")
+    nodes = order64[:members]
+    new, cmin = _select_medoids(cost[nodes], a64[nodes], nodes, med, n, keep_all_inf=True)
+    if info is not None:
+        info.update(resident_cells=int(status[0]), workspace_cells=int(status[1]), max_sweeps=int(status[2]),
+                    kept_cells=int(((counts > 0) & torch.isinf(cmin)).sum()), tile=int(lib.geo_cell_costs_tile()))
+    return new, cost
+
+
+def _objective(dmin: torch.Tensor, power: int) -> float:
+    """sum of dmin^power over the finite entries, fp64 (numpy's sum of the host copy: the value a host loop computes)."""
+    d = dmin.cpu().numpy().astype(np.float64)
+    d = d[np.isfinite(d)]
+    return float(np.sum(d * d if power == 2 else d))
+
+
+def refine_voronoi_graph(G: DeviceCSR, medoids0, max_iter: int = 10, power: int = 2):
+    """The rounds of fit_kmedoids_voronoi_graph from given medoids (the seeded state).  Returns (medoids i32 [K], dmin f32 [n],
+    assign i32 [n] -- all on the GPU -- accepted objectives, one counter dict per update run, whether the guard fired)."""
+    dev = G.indptr.device
+    med = torch.from_numpy(np.asarray(medoids0, dtype=np.int32)).to(dev)
+    dmin, assign = _assign_device(G, np.asarray(medoids0))
+    history, updates, rejected = [_objective(dmin, power)], [], False
+    for _ in range(max_iter):
+        step = {}
+        in_cell = torch.where(torch.isfinite(dmin), assign, torch.full_like(assign, -1))
+        new, _ = cell_medoid_update_device(G, in_cell, med, power, info=step)
+        updates.append(step)
+        if bool((new == med).all()):
+            break
+        dmin_new, assign_new = _assign_device(G, new.cpu().numpy())
+        objective = _objective(dmin_new, power)
+        if not objective < history[-1]:
+            rejected = True
+            print(f"[kmedoids] update {len(updates)} not accepted: objective {objective:.3f} >= {history[-1]:.3f}")
+            break
+        med, dmin, assign = new, dmin_new, assign_new
+        history.append(objective)
+    return med, dmin, assign, history, updates, rejected
+
+
+def fit_kmedoids_voronoi_graph(W, K: int = 512, init: str = "kpp", seed: int = 42, max_iter: int = 10, power: int = 2,
+                               info: Optional[dict] = None):
+    """fit_kmedoids_optimized followed by cell-restricted medoid updates (at most max_iter): refinement at any graph size,
+    no all-pairs matrix (fit_kmedoids_voronoi needs one, about 230 000 nodes at most).
+
+    Each round: the update inside the cells (cell_medoid_update_device; unreachable nodes, dmin = inf, belong to no cell);
+    stop if no medoid moved; re-assign with one label-carrying solve (nearest_source_device); the objective is the sum of
+    dmin^power over the finite entries in fp64.  A round is accepted only if the objective is strictly below the last
+    accepted one, otherwise the previous state is kept and the fit stops: the cell-restricted cost of the old medoid equals
+    its global cost except where float32 ties hand a path node to another medoid, so an update can, rarely, not pay off.
+    Returns (medoids, assign, qe, history): history = the accepted objectives, the seeded state first; qe = the reference's
+    quantisation error of the final distances.  `info`, if given, receives iterations, rejected (the guard fired) and
+    updates (one dict of cell_medoid_update_device's counters per update run)."""
+    if power not in (1, 2):
+        raise ValueError(f"power must be 1 or 2, got {power!r}")
+    G = _to_device_graph(W)
+    medoids0, _, _ = fit_kmedoids_optimized(G, K=K, init=init, seed=seed)
+    med, dmin, assign, history, updates, rejected = refine_voronoi_graph(G, medoids0, max_iter, power)
+    medoids = med.cpu().numpy().astype(int)
+    assign_h = assign.cpu().numpy().astype(int)
+    _print_sizes(assign_h, len(medoids))
+    print(f"[kmedoids] Voronoi iterations (cell-restricted): {len(history) - 1}, objective {history[0]:.3f} -> {history[-1]:.3f}")
+    if info is not None:
+        info.update(iterations=len(history) - 1, rejected=rejected, updates=updates)
+    return medoids, assign_h, _qe_from(dmin.cpu().numpy()), history
 
 
 

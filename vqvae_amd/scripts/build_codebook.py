@@ -21,7 +21,7 @@ import torch
 from scipy import sparse
 
 from .._device import DeviceCSR, device
-from ..geo.kmeans_optimized import fit_kmedoids_optimized
+from ..geo.kmeans_optimized import fit_kmedoids_optimized, fit_kmedoids_voronoi_graph
 from ..geo.knn_graph_optimized import (compact_device, knn_graph_device, lcc_mask_device, reweight_device,
                                        upper_edges_device)
 from ..geo.riemannian_metric import edge_lengths_graph_device, edge_lengths_riemannian
@@ -31,11 +31,15 @@ from ..spatial_decoder import DecoderExport, hip_kernels_cover, load_decoder_fro
 
 def build_codebook_device(z_flat: torch.Tensor, decoder, *, k: int = 20, sym: str = "union", K: int = 512,
                           init: str = "kpp", seed: int = 42, batch_size: int = 512,
-                          timers: Optional[Dict[str, float]] = None, group=None) -> dict:
+                          timers: Optional[Dict[str, float]] = None, group=None, refine_iters: int = 0,
+                          refine_power: int = 2) -> dict:
     """The hot path on resident data.  z_flat: f32 [n_nodes, d] on the GPU, rows in (n, h, w) order.
     Returns device/host results; `timers` (if given) receives per-stage seconds (synchronised).
     Under an initialised torch.distributed group the kNN rows and the JVP chunks are sharded over the
-    ranks (vqvae_amd/parallel.py); every rank ends with the full result."""
+    ranks (vqvae_amd/parallel.py); every rank ends with the full result.
+    refine_iters > 0 (extension): the seeded codebook is refined by up to that many cell-restricted medoid updates
+    (fit_kmedoids_voronoi_graph, objective sum of distance^refine_power) and the result gains the key "refine" = {history,
+    iterations, info}.  Every rank refines its full copy: the refinement is deterministic, so the ranks agree."""
     dev = z_flat.device
 
     def tick(name, t0):
@@ -81,16 +85,26 @@ def build_codebook_device(z_flat: torch.Tensor, decoder, *, k: int = 20, sym: st
         W_lcc, z_lcc = W_geo, z_flat
     t0 = tick("lcc", t0)
 
-    medoids, assign_lcc, qe = fit_kmedoids_optimized(W_lcc, K=K, init=init, seed=seed)
+    refine = None
+    if refine_iters > 0:
+        refine_info = {}
+        medoids, assign_lcc, qe, history = fit_kmedoids_voronoi_graph(W_lcc, K=K, init=init, seed=seed, max_iter=refine_iters,
+                                                                      power=refine_power, info=refine_info)
+        refine = {"history": history, "iterations": len(history) - 1, "info": refine_info}
+    else:
+        medoids, assign_lcc, qe = fit_kmedoids_optimized(W_lcc, K=K, init=init, seed=seed)
     t0 = tick("kmedoids", t0)
 
     mask_h = mask.cpu().numpy()
     assign_flat = np.full(z_flat.shape[0], -1, dtype=np.int32)
     assign_flat[mask_h] = assign_lcc
     z_medoid = z_lcc[torch.from_numpy(medoids).to(dev)].cpu()
-    return {"W_lcc": W_lcc, "mask_lcc": mask_h, "medoids": medoids, "assign_flat": assign_flat, "qe": qe,
-            "z_medoid": z_medoid, "n_edges": int(src.numel()), "edge_lengths": lengths, "edges": (src, dst),
-            "sharded": sharded}
+    res = {"W_lcc": W_lcc, "mask_lcc": mask_h, "medoids": medoids, "assign_flat": assign_flat, "qe": qe,
+           "z_medoid": z_medoid, "n_edges": int(src.numel()), "edge_lengths": lengths, "edges": (src, dst),
+           "sharded": sharded}
+    if refine is not None:
+        res["refine"] = refine
+    return res
 
 
 def build_codebooks_pipelined(latent_sets, decoder, *, depth: int = 3, **kwargs) -> list:
@@ -141,7 +155,8 @@ def main(args):
 
     print(f"Building k-NN graph: N={z_flat.shape[0]}, k={args.k}, method=hip")
     res = build_codebook_device(z_flat, decoder, k=args.k, sym=args.sym, K=args.K, init=args.init, seed=args.seed,
-                                batch_size=args.batch_size)
+                                batch_size=args.batch_size, refine_iters=getattr(args, "refine_iters", 0),
+                                refine_power=getattr(args, "refine_power", 2))
 
     sparse.save_npz(out_dir / "knn_graph_geodesic.npz", res["W_lcc"].to_scipy())
     codes = res["assign_flat"].reshape(N, H, W)
@@ -155,6 +170,10 @@ def main(args):
     }
     torch.save(codebook, out_dir / "codebook.pt")
     np.save(out_dir / "codes.npy", codes)
+    if "refine" in res:                                 # --refine_iters N: a fourth artefact, the other three keep their format
+        import json
+        with open(out_dir / "refine.json", "w") as f:
+            json.dump({"refine_iters": args.refine_iters, "refine_power": args.refine_power, "qe": res["qe"], **res["refine"]}, f, indent=1)
     print(f"Quantization error: {res['qe']:.3f}")
     print(f"Saved artifacts to: {out_dir}")
     return res
@@ -177,6 +196,9 @@ def make_parser() -> argparse.ArgumentParser:
     parser.add_argument("--init", type=str, default="kpp")
     parser.add_argument("--seed", type=int, default=42)
     parser.add_argument("--batch_size", type=int, default=512)
+    # extension: cell-restricted medoid updates after the seeding (0: the reference's codebook, artefacts unchanged)
+    parser.add_argument("--refine_iters", type=int, default=0)
+    parser.add_argument("--refine_power", type=int, default=2, choices=(1, 2))
     return parser
 
 
