@@ -409,6 +409,10 @@ int geo_jvp_plan(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, 
 /* ... of a geo_decoder_jvp_edges_part call (graph_edges != 0; build_edges >= n_edges, else GEO_E_ARG) */
 int geo_jvp_plan_part(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int64_t build_edges, int32_t batch_size,
                       int32_t graph_edges, size_t ws_bytes);
+/* Does that call (workspace as sized by the matching query) run ConvT3 with head_stream_kernel?  1: the 16-output head without
+ * GroupNorm on back route MFMA or DEDUP with option jvp_head_stream != 0 (default; GEO_JVP_HEAD_STREAM); 0: back_mfma_kernel /
+ * back_kernel.  Both compute the same bits.  Negative (GEO_E_*) where geo_jvp_plan is.  The plan code has no free bit for it. */
+int geo_jvp_head_stream(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size, int32_t graph_edges);
 
 /* Same quantity for explicit endpoint arrays (edge_lengths_riemannian's own signature):
  * z_start / z_end f32 [E][d]. */

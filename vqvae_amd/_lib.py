@@ -102,6 +102,7 @@ _SIGNATURES = {
     "geo_jvp_workspace_bytes": (sz, [ctypes.POINTER(DecoderDesc), i64, i32]),
     "geo_jvp_edges_workspace_bytes": (sz, [ctypes.POINTER(DecoderDesc), i64, i64, i32]),
     "geo_jvp_plan": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), i64, i64, i32, i32, sz]),
+    "geo_jvp_head_stream": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), i64, i64, i32, i32]),
     "geo_decoder_jvp_edges": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, i64, c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
     "geo_jvp_edges_part_workspace_bytes": (sz, [ctypes.POINTER(DecoderDesc), i64, i64, i64, i32]),
     "geo_jvp_plan_part": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), i64, i64, i64, i32, i32, sz]),

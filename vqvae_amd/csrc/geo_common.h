@@ -40,7 +40,8 @@ struct Options {
         jvp_back_valu = 0, jvp_front_valu = 0, jvp_per_node = 1 /* fixed-statistics decoders: primal ConvT2 / ConvT3 once per latent */,
         jvp_node_jacobian = 1 /* fixed statistics, d <= 16: decoder Jacobian once per latent, edge ends from its columns (1: when the graph has enough edges per latent, 2: always, 0: never) */,
         jvp_start_dedup = 1 /* train-mode BatchNorm, graph edges: each chunk's start-side primal ConvT2 / ConvT3 rows once per run of equal src (0: once per slot) */,
-        jvp_front_once = 1 /* on that route with the vector first layer: the tangent row once per edge, the start-side primal row once per run (0: every row of both sides) */;
+        jvp_front_once = 1 /* on that route with the vector first layer: the tangent row once per edge, the start-side primal row once per run (0: every row of both sides) */,
+        jvp_head_stream = 1 /* 16-output ConvT3 head without GroupNorm: head_stream_kernel, the next K block's rows in flight while one is converted and multiplied (0: back_mfma_kernel; same bits) */;
 };
 Options &options();
 

@@ -29,6 +29,8 @@
 //   back   norm2 + ReLU, ConvT3, sigmoid', squared norm per sample.
 //            back_mfma_kernel      c2 = 64 and 16 or 192 outputs: MODE 0 primal + tangent; MODE 2 then 1: the primal rows once
 //                                  (per latent: per_node; per run of equal src: dedup), then the tangents
+//            head_stream_kernel    the 16-output head without GroupNorm, per slot and the dedup route's end side / start tangents
+//                                  (jvp_head_stream): back_mfma_kernel's arithmetic with the next K block's rows in flight
 //            back_kernel (VALU)    every other head, or jvp_back_valu
 //   node_jacobian: the per_node kernels over unit tangents, then jacobian_lengths_kernel.
 #include "geo_common.h"
@@ -1869,6 +1871,177 @@ __global__ __launch_bounds__(256, 2) void back_mfma_kernel(const float *__restri
     }
 }
 
+// The 16-output head without GroupNorm (route `head_stream`): back_mfma_kernel<1, false, MODE>'s staged values, products and epilogue
+// bit for bit, scheduled so that the rows stream.  MODE 0: primal + tangent per slot (side_only as above).  MODE 1: the start-side
+// tangents of the dedup route -- ReLU mask from the compact primal row (row_map), sigmoid' from sg_compact.
+//   staging map   lane l of wave w stages channels 4 (l & 15) .. + 3 of pixel (l >> 4) & 1 of the K block, for the rows
+//                 8 w + 2 i + (l >> 5), i = 0..3: one 16-byte load per row and operand, a wave's load covers two whole 512-byte row
+//                 segments, and the four NormConst stay in registers for the tile (channel = k mod 64, the same in all 8 blocks).
+//   loads         block kb + 1's rows are requested into a second register set while block kb is converted (rows 0, 1 before, rows
+//                 2, 3 half way, into what rows 0, 1 of block kb leave free); the weights of block kb are requested before that, so
+//                 waiting for them leaves the rows in flight (loads return in order).  Nothing is requested past the tile's own
+//                 rows: block 7 prefetches nothing.
+template <int MODE>
+__global__ __launch_bounds__(256, 3) void head_stream_kernel(const float *__restrict__ pre2, const float *__restrict__ tpre2,
+                                                         const NormConst *__restrict__ consts2, int consts_per_group,
+                                                         int tiles_per_group, int co_n, int s_out,
+                                                         const unsigned short *__restrict__ W3b, const float *__restrict__ b3,
+                                                         float *__restrict__ norms, const float *__restrict__ sg_compact,
+                                                         const int32_t *__restrict__ row_map, int side_only) {
+    constexpr int C2 = 64, KB = 128, LDK = KB + 8, NP = 32, N2 = 16 * C2;
+    __shared__ __attribute__((aligned(16))) unsigned short A3[3][2][TS][LDK];     // 52 KB, reused for the reduction
+    const int tile = side_only ? (((int)blockIdx.x / tiles_per_group) * 2 + side_only - 1) * tiles_per_group +
+                                     (int)blockIdx.x % tiles_per_group
+                               : (int)blockIdx.x;
+    const int group = tile / tiles_per_group;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int P = co_n * s_out * s_out;
+    const size_t slot0 = (size_t)tile * TS;
+
+    const int c0 = (lane & 15) * 4, kcol = ((lane >> 4) & 1) * C2 + c0, row0 = wave * 8 + (lane >> 5);
+    NormConst kn[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) kn[c] = consts2[(size_t)(consts_per_group ? group : 0) * C2 + c0 + c];
+    // Buffer descriptors (scalar) and one 32-bit lane offset each.  Tangents and MODE 0's primal: the tile's 32 rows.  MODE 1's primal:
+    // the start group's rows, where row_map points (make_route keeps a group's rows below 2 GB).  The weights: W3b.
+    const __amdgpu_buffer_rsrc_t t_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tpre2 + slot0 * N2), 0, TS * N2 * 4, 0x00020000);
+    const size_t g0 = (size_t)group * tiles_per_group * TS;
+    const __amdgpu_buffer_rsrc_t p_src = MODE == 1
+        ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pre2 + g0 * N2), 0, tiles_per_group * TS * N2 * 4, 0x00020000)
+        : __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pre2 + slot0 * N2), 0, TS * N2 * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t b_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(W3b), 0, 16 * C2 * NP * 3 * 2, 0x00020000);
+    const unsigned t_lane = (unsigned)(row0 * N2 + kcol) * 4u;                    // row i: + i * 2 rows
+    unsigned p_lane[MODE == 1 ? 4 : 1];
+    if (MODE == 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            p_lane[MODE == 1 ? i : 0] = (unsigned)(((size_t)row_map[slot0 + row0 + 2 * i] - g0) * N2 + kcol) * 4u;
+    }
+    auto load_rows = [&](int kb, int i0, float4 (&p)[4], float4 (&t)[4]) {     // rows i0, i0 + 1 of block kb
+#pragma unroll
+        for (int i = i0; i < i0 + 2; ++i) {
+            const int soff = (i * 2 * N2 + kb * KB) * 4;
+            p[i] = MODE == 1 ? __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(p_src, p_lane[MODE == 1 ? i : 0], kb * KB * 4, 0))
+                             : __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(p_src, t_lane, soff, 0));
+            t[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(t_src, t_lane, soff, 0));
+        }
+    };
+
+    f32x16 accp, acct;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { accp[i] = 0.f; acct[i] = 0.f; }
+    const int r = lane & 31, h = lane >> 5;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    const unsigned b_lane = (unsigned)(h * NP * 8 + r * 8) * 2u;
+
+    // one K block: `p`, `t` hold its rows, `pn`, `tn` take the next block's
+    auto block = [&](int kb, const float4 (&p)[4], const float4 (&t)[4], float4 (&pn)[4], float4 (&tn)[4]) {
+        const bool more = kb + 1 < 8;
+        bf16x8 b[2][3];
+        __builtin_amdgcn_sched_barrier(0);                        // (not among the previous block's products: registers)
+#pragma unroll
+        for (int kq = 0; kq < 2; ++kq)
+#pragma unroll
+            for (int part = 0; part < 3; ++part)
+                b[kq][part] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                    b_src, b_lane, (((kb * 3 + part) * 8 + wave_s * 2 + kq) * 2 * NP * 8) * 2, 0));
+        if (more) load_rows(kb + 1, 0, pn, tn);
+        __syncthreads();                                          // the previous block's operand reads are done
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i == 2) {                                         // rows 0, 1 are converted: their registers take the other half
+                __builtin_amdgcn_sched_barrier(0);
+                if (more) load_rows(kb + 1, 2, pn, tn);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            float a[4], ta[4];
+            norm_relu(kn[0], p[i].x, t[i].x, &a[0], &ta[0]);
+            norm_relu(kn[1], p[i].y, t[i].y, &a[1], &ta[1]);
+            norm_relu(kn[2], p[i].z, t[i].z, &a[2], &ta[2]);
+            norm_relu(kn[3], p[i].w, t[i].w, &a[3], &ta[3]);
+            const int row = row0 + 2 * i;
+            unsigned lo[3], hi[3];
+            if (MODE != 1) {
+                split3_pair(a[0], a[1], lo[0], lo[1], lo[2]);
+                split3_pair(a[2], a[3], hi[0], hi[1], hi[2]);
+#pragma unroll
+                for (int part = 0; part < 3; ++part)
+                    *reinterpret_cast<uint2 *>(&A3[part][0][row][kcol]) = make_uint2(lo[part], hi[part]);
+            }
+            split3_pair(ta[0], ta[1], lo[0], lo[1], lo[2]);
+            split3_pair(ta[2], ta[3], hi[0], hi[1], hi[2]);
+#pragma unroll
+            for (int part = 0; part < 3; ++part)
+                *reinterpret_cast<uint2 *>(&A3[part][1][row][kcol]) = make_uint2(lo[part], hi[part]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kq = 0; kq < 2; ++kq) {
+            const int ks = wave * 2 + kq;                         // this wave's 16-deep steps of the block
+            bf16x8 ap[3], at[3];
+#pragma unroll
+            for (int part = 0; part < 3; ++part) {
+                if (MODE != 1) ap[part] = *reinterpret_cast<const bf16x8 *>(&A3[part][0][r][ks * 16 + h * 8]);
+                at[part] = *reinterpret_cast<const bf16x8 *>(&A3[part][1][r][ks * 16 + h * 8]);
+            }
+            if (MODE != 1) accp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[2], b[kq][0], accp, 0, 0, 0);
+            acct = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at[2], b[kq][0], acct, 0, 0, 0);
+            if (MODE != 1) accp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0], b[kq][2], accp, 0, 0, 0);
+            acct = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at[0], b[kq][2], acct, 0, 0, 0);
+            if (MODE != 1) accp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[1], b[kq][1], accp, 0, 0, 0);
+            acct = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at[1], b[kq][1], acct, 0, 0, 0);
+            if (MODE != 1) accp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[1], b[kq][0], accp, 0, 0, 0);
+            acct = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at[1], b[kq][0], acct, 0, 0, 0);
+            if (MODE != 1) accp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0], b[kq][1], accp, 0, 0, 0);
+            acct = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at[0], b[kq][1], acct, 0, 0, 0);
+            if (MODE != 1) accp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0], b[kq][0], accp, 0, 0, 0);
+            acct = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at[0], b[kq][0], acct, 0, 0, 0);
+        }
+    };
+
+    float4 pa[4], ta[4], pb[4], tb[4];
+    load_rows(0, 0, pa, ta);
+    load_rows(0, 2, pa, ta);
+#pragma unroll                                                    // (unrolled: the register sets alternate by name, no copies)
+    for (int kb = 0; kb < 8; kb += 2) {
+        block(kb, pa, ta, pb, tb);
+        block(kb + 1, pb, tb, pa, ta);
+    }
+
+    // sum the four waves' partial tiles through LDS, then sigmoid' and the norm (back_mfma_kernel's epilogue for NT = 1)
+    float *red = reinterpret_cast<float *>(&A3[0][0][0][0]);     // [wave 4][p|t 2][32 rows][33]
+    const int row = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
+    const size_t nrow = MODE == 1 ? (size_t)row_map[slot0 + row] : slot0 + row;   // sg_compact row: the slot's compact row
+    double sumsq = 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int rr = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+        if (MODE != 1) red[((wave * 2 + 0) * 32 + rr) * 33 + (lane & 31)] = accp[q];
+        red[((wave * 2 + 1) * 32 + rr) * 33 + (lane & 31)] = acct[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int o = c4 + c;
+        if (o < P) {
+            float x = b3[o / (s_out * s_out)], t = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                if (MODE != 1) x += red[((w * 2 + 0) * 32 + row) * 33 + c4 + c];
+                t += red[((w * 2 + 1) * 32 + row) * 33 + c4 + c];
+            }
+            const float sg = MODE == 1 ? sg_compact[nrow * NP + o] : 1.0f / (1.0f + expf(-x));
+            const float j = t * sg * (1.0f - sg);
+            sumsq += (double)(j * j);
+        }
+    }
+    sumsq += __shfl_xor(sumsq, 1, 64);
+    sumsq += __shfl_xor(sumsq, 2, 64);
+    sumsq += __shfl_xor(sumsq, 4, 64);
+    if ((threadIdx.x & 7) == 0) norms[slot0 + row] = (float)sqrt(sumsq);
+}
+
 __global__ __launch_bounds__(256) void combine_kernel(const float *__restrict__ norms, int64_t e_base, int64_t e_count,
                                                      int batch, int slots_per_group, float *__restrict__ len_out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e_count; i += (int64_t)gridDim.x * blockDim.x) {
@@ -2058,6 +2231,7 @@ struct Route {
     int back_nt = 0;                                            // 32-column output tiles of the matrix-core ConvT3 (1 or 6)
     int parts2 = 16;                 // partial-sum rows per tile that the ConvT2 kernel leaves for finalize_batch_kernel
     bool per_node = false, node_jacobian = false, dedup = false, front_once = false;
+    bool head_stream = false;        // ConvT3 of the 16-output head without GroupNorm: head_stream_kernel (geo_jvp_head_stream)
     size_t back_lds = 0;             // dynamic LDS of back_kernel
     size_t jac_np = 0, jac_extra_bytes = 0;                     // node_jacobian: padded outputs per column; pseudo-edge lists + columns
     size_t bytes = 0;                // workspace as the matching *_workspace_bytes query sizes it (0: no answer)
@@ -2148,6 +2322,10 @@ bool make_route(const geo_decoder_desc *dc, const geo::Options &o, bool graph_ed
                          : GEO_JVP_MID_CHUNK;
     r->parts2 = mid_pipe && !r->per_node ? 4 : (mid_all ? 1 : 16);
     r->back = r->dedup ? GEO_JVP_BACK_DEDUP : r->per_node ? GEO_JVP_BACK_PER_NODE : back_mfma ? GEO_JVP_BACK_MFMA : GEO_JVP_BACK_VALU;
+    // the streaming 16-output head: per slot (mfma), and on the dedup route the end side and the start-side tangents
+    r->head_stream = back_mfma && r->back_nt == 1 && !r->group_norm && (r->back == GEO_JVP_BACK_DEDUP || r->back == GEO_JVP_BACK_MFMA) &&
+                     o.jvp_head_stream != 0 &&
+                     (!r->dedup || (size_t)base.slots_per_group * s.n2 * 4 < ((size_t)1 << 31));   // (one descriptor per group's rows)
     r->back_lds = ((size_t)2 * BACK_TS * 16 * (s.c2 + 4) + (size_t)16 * s.co * (s.c2 + 4) + (size_t)BACK_TS * s.p_out) * 4;
 
     // ---- what the run refuses
@@ -2343,6 +2521,22 @@ int launch_back(const Route &r, const geo_decoder_desc *dc, const Pass &p, const
         return GEO_OK;
     }
     const unsigned tiles = (unsigned)p.tiles, side_tiles = (unsigned)(p.tiles / 2), chunks = (unsigned)(p.groups() / 2);
+    if (r.head_stream) {                          // (make_route: 16 outputs, no GroupNorm, back dedup or mfma)
+        if (p.back == GEO_JVP_BACK_DEDUP) {       // as below, the compact primal rows stay on back_mfma_kernel
+            head_stream_kernel<0><<<side_tiles, 256, 0, stream>>>(p.back_pre2, b.tpre2, b.k2, 1, p.tiles_per_group, s.co, s.s_out, b.W3b,
+                                                                  dc->b3, b.norms, nullptr, nullptr, 2);
+            back_mfma_kernel<1, false, 2><<<chunks, 256, 0, stream>>>(
+                p.back_pre2, b.tpre2, b.k2, 1, p.tiles_per_group, s.co, s.s_out, b.W3b, dc->b3, b.norms, nullptr, b.sg_compact, nullptr,
+                nullptr, 0, 0, 1, nullptr, 0, nullptr, b.n_compact, 1);
+            head_stream_kernel<1><<<side_tiles, 256, 0, stream>>>(p.back_pre2, b.tpre2, b.k2, 1, p.tiles_per_group, s.co, s.s_out, b.W3b,
+                                                                  dc->b3, b.norms, b.sg_compact, b.row_map, 1);
+        } else {
+            head_stream_kernel<0><<<tiles, 256, 0, stream>>>(p.back_pre2, b.tpre2, b.k2, p.stat, p.tiles_per_group, s.co, s.s_out, b.W3b,
+                                                             dc->b3, b.norms, nullptr, nullptr, 0);
+        }
+        GEO_LAUNCH_CHECK();
+        return GEO_OK;
+    }
     pick_int<1, 6>(r.back_nt, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
         if (p.back == GEO_JVP_BACK_DEDUP) {       // end side per slot; start side: the compact primal rows, then the tangents
@@ -2564,6 +2758,17 @@ extern "C" int geo_jvp_plan_part(const geo_decoder_desc *dec, int64_t n_nodes, i
 extern "C" int geo_jvp_plan(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size,
                             int32_t graph_edges, size_t ws_bytes) {
     return geo_jvp_plan_part(dec, n_nodes, n_edges, n_edges, batch_size, graph_edges, ws_bytes);
+}
+
+extern "C" int geo_jvp_head_stream(const geo_decoder_desc *dec, int64_t n_nodes, int64_t n_edges, int32_t batch_size,
+                                   int32_t graph_edges) {
+    const geo::Options opt = geo::options();
+    Route r;
+    if (!make_route(dec, opt, graph_edges != 0, graph_edges ? n_nodes : 0, n_edges, n_edges, batch_size, nullptr, &r)) {
+        geo::set_error("%s", r.error);
+        return r.status;
+    }
+    return r.head_stream ? 1 : 0;
 }
 
 extern "C" int geo_decoder_jvp_edges_part(const geo_decoder_desc *dec, const float *z, int64_t n_nodes, const int32_t *src,
