@@ -253,6 +253,39 @@ int geo_knn_thresholds(const float *z, int64_t n, int32_t d, int32_t n_neighbors
                        void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Bridging the components of a kNN graph (extension: the reference keeps the largest component and drops the rest).
+ * z f32 [n][d], labels i32 [n] component numbers, form as for geo_knn_topk.  The PAIR KEY of nodes a != b is the fp64 key
+ * geo_knn_topk gives corpus row hi = max(a, b) in the list of query row lo = min(a, b): form 0 the fma chain of
+ * (lo_c - hi_c)^2, form 1 (|lo|^2 + (-2 lo.hi)) + |hi|^2 clamped at 0 -- in form 1 the norm added first is the one of the
+ * lower index, whichever end asks.  Pairs are totally ordered by (key, lo, hi).
+ *
+ * geo_nearest_foreign: for each of the m query rows q = rows[i] (i32, any order, repeats allowed) the node x with
+ * labels[x] != labels[q] that minimises (pair key, x): nbr_out i32 [m], key_out f64 [m]; a query whose label is every
+ * node's gets -1 and +inf.  An exact fp64 scan of all m n pairs with knn_kernel's mapping (one wave owns a few queries,
+ * every lane one candidate per 64-candidate step, one running (key, index) minimum per lane and query, a wave reduction at
+ * the end).  Limits as geo_knn_topk: d <= 128, n < 2^31; m = 0 is GEO_OK without a launch; rows outside [0, n) are the
+ * caller's error (not checked).  Workspace: geo_nearest_foreign_workspace_bytes(n, d), GEO_E_WORKSPACE below it.  The result
+ * does not depend on ws_bytes, the stream or the run.
+ *
+ * geo_bridge_components: the edges of the minimum spanning tree of the component graph under that order (Kruskal over all
+ * pairs with different labels): exactly C - 1 undirected edges, edges_out i32 [C-1][2] = (lo, hi) and keys_out f64 [C-1]
+ * (both on the device), sorted by (key, lo, hi).  Computed by Boruvka rounds that leave the currently largest component
+ * (lowest label on ties) out of the queries: query list from the current labels, geo_nearest_foreign's kernel, a
+ * per-component (key, lo, hi) minimum with 64-bit integer atomicMin (key bits first, then the packed pair: no float
+ * atomics, the same bits every run), one small read per round, union-find over the component numbers on the host, a
+ * relabel on the device; at most ceil(log2 C) rounds.  labels must lie in [0, C) (GEO_E_ARG otherwise, found by the plan's
+ * histogram before any output is written), every label in [0, C) must occur.  status_out i32 [4] ON THE HOST: rounds,
+ * queries of the first round, queries of all rounds, 0.  C = 1: no edge, status 0 0 0 0.  Synchronises.  A failed call
+ * writes nothing to the outputs.  Workspace: geo_bridge_components_workspace_bytes(n, d, C).
+ * ------------------------------------------------------------------------------------------ */
+size_t geo_nearest_foreign_workspace_bytes(int64_t n, int32_t d);
+int geo_nearest_foreign(const float *z, int64_t n, int32_t d, int32_t form, const int32_t *labels, const int32_t *rows,
+                        int64_t m, int32_t *nbr_out, double *key_out, void *ws, size_t ws_bytes, void *stream);
+size_t geo_bridge_components_workspace_bytes(int64_t n, int32_t d, int32_t C);
+int geo_bridge_components(const float *z, int64_t n, int32_t d, int32_t form, const int32_t *labels, int32_t C,
+                          int32_t *edges_out, double *keys_out, int32_t *status_out, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Symmetrisation.  Replaces csr_matrix(...) + W.maximum/minimum(W.T) + setdiag(0) +
  * eliminate_zeros() of src/geo/knn_graph_optimized.py:54-66.
  * nbr_idx i32 [n][k] / nbr_w f32 [n][k] (NULL = connectivity, all ones) are the directed lists.
@@ -319,6 +352,24 @@ int geo_csr_compact_count(const int32_t *indptr, const int32_t *indices, const f
 int geo_csr_compact_fill(const int32_t *indptr, const int32_t *indices, const float *data, int32_t n,
                          const uint8_t *keep_node, int32_t drop_zero, const int32_t *new_index,
                          const int32_t *indptr_new, int32_t *indices_out, float *data_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Inserting a few undirected edges into a canonical CSR (the bridges of geo_bridge_components).  src / dst i32 [E] and
+ * w f32 [E] on the device; both directions of every edge are merged into the rows: columns stay ascending, existing
+ * entries keep their weights, a pair that is already stored adds nothing, an edge listed twice counts once (its first
+ * weight).  src == dst or an index outside [0, n) is GEO_E_ARG before any launch (the E edges are read back first: E is
+ * tiny, nnz is not).  Two calls like symmetrize: geo_csr_insert_count fills indptr_out [n+1] and returns the new nnz through
+ * nnz_out [host] (synchronises); geo_csr_insert_fill, with the same workspace (its contents carry over), writes
+ * indices_out / data_out in one pass over the rows (data NULL = all ones).  E = 0 copies the graph.
+ * Workspace: geo_csr_insert_workspace_bytes(n, E), GEO_E_WORKSPACE below it.
+ * ------------------------------------------------------------------------------------------ */
+size_t geo_csr_insert_workspace_bytes(int32_t n, int64_t E);
+int geo_csr_insert_count(const int32_t *indptr, const int32_t *indices, int32_t n, const int32_t *src, const int32_t *dst,
+                         const float *w, int64_t E, int32_t *indptr_out, int64_t *nnz_out,
+                         void *ws, size_t ws_bytes, void *stream);
+int geo_csr_insert_fill(const int32_t *indptr, const int32_t *indices, const float *data, int32_t n, int64_t E,
+                        const int32_t *indptr_new, int32_t *indices_out, float *data_out,
+                        void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Decoder pull-back edge lengths.  Replaces torch.autograd.functional.jvp through SpatialDecoder

@@ -89,6 +89,13 @@ _SIGNATURES = {
     "geo_knn_query": (ctypes.c_int, [c_p, i64, c_p, i64, i32, i32, i32, c_p, c_p, c_p, sz, c_p]),
     "geo_knn_last_path": (ctypes.c_int, []),
     "geo_knn_thresholds": (ctypes.c_int, [c_p, i64, i32, i32, i32, i64, i64, i32, c_p, c_p, sz, c_p]),
+    "geo_nearest_foreign_workspace_bytes": (sz, [i64, i32]),
+    "geo_nearest_foreign": (ctypes.c_int, [c_p, i64, i32, i32, c_p, c_p, i64, c_p, c_p, c_p, sz, c_p]),
+    "geo_bridge_components_workspace_bytes": (sz, [i64, i32, i32]),
+    "geo_bridge_components": (ctypes.c_int, [c_p, i64, i32, i32, c_p, i32, c_p, c_p, c_p, c_p, sz, c_p]),
+    "geo_csr_insert_workspace_bytes": (sz, [i32, i64]),
+    "geo_csr_insert_count": (ctypes.c_int, [c_p, c_p, i32, c_p, c_p, c_p, i64, c_p, c_p, c_p, sz, c_p]),
+    "geo_csr_insert_fill": (ctypes.c_int, [c_p, c_p, c_p, i32, i64, c_p, c_p, c_p, c_p, sz, c_p]),
     "geo_symmetrize_workspace_bytes": (sz, [i32, i32]),
     "geo_symmetrize_count": (ctypes.c_int, [c_p, c_p, i32, i32, i32, c_p, c_p, c_p, sz, c_p]),
     "geo_symmetrize_fill": (ctypes.c_int, [c_p, c_p, i32, i32, i32, c_p, c_p, c_p, c_p, sz, c_p]),

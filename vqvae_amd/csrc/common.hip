@@ -170,7 +170,7 @@ int exclusive_scan_i32(const int32_t *in, int32_t *out, int64_t n, void *tmp, si
 
 }  // namespace geo
 
-extern "C" int geo_version(void) { return 113; }   // 1.0.13: + option jvp_head_stream, geo_jvp_head_stream; 1.0.12: + geo_cell_costs, geo_cell_costs_workspace_bytes, geo_cell_costs_min_workspace_bytes, geo_cell_costs_tile, geo_cell_costs_resident_max_nodes; 1.0.11: + geo_knn_query, geo_knn_query_workspace_bytes, geo_knn_query_min_workspace_bytes; 1.0.10: + geo_decoder_jvp_edges_part, geo_jvp_edges_part_workspace_bytes, geo_jvp_plan_part; 1.0.9: + geo_lpips_alex; 1.0.8: + geo_image_encode; 1.0.7: + geo_vanilla_decode, geo_spatial_decode; 1.0.6: + geo_path_stats, geo_csr_set_symmetric; 1.0.5: + option jvp_front_once, GEO_JVP_FRONT_ONCE in geo_jvp_plan (1.0.4: geo_vanilla_jvp_*; 1.0.3: geo_sssp_nearest_source, geo_jvp_edges_workspace_bytes, geo_pam_swap_deltas, prior kernels)
+extern "C" int geo_version(void) { return 114; }   // 1.0.13: + option jvp_head_stream, geo_jvp_head_stream; 1.0.12: + geo_cell_costs, geo_cell_costs_workspace_bytes, geo_cell_costs_min_workspace_bytes, geo_cell_costs_tile, geo_cell_costs_resident_max_nodes; 1.0.11: + geo_knn_query, geo_knn_query_workspace_bytes, geo_knn_query_min_workspace_bytes; 1.0.10: + geo_decoder_jvp_edges_part, geo_jvp_edges_part_workspace_bytes, geo_jvp_plan_part; 1.0.9: + geo_lpips_alex; 1.0.8: + geo_image_encode; 1.0.7: + geo_vanilla_decode, geo_spatial_decode; 1.0.6: + geo_path_stats, geo_csr_set_symmetric; 1.0.5: + option jvp_front_once, GEO_JVP_FRONT_ONCE in geo_jvp_plan (1.0.4: geo_vanilla_jvp_*; 1.0.3: geo_sssp_nearest_source, geo_jvp_edges_workspace_bytes, geo_pam_swap_deltas, prior kernels)
 extern "C" const char *geo_last_error(void) { return geo::g_err; }
 
 extern "C" int geo_set_option(const char *name, int32_t value) {

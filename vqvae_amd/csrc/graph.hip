@@ -8,6 +8,9 @@
 //   W[mask][:, mask]                                                     src/scripts/build_codebook.py:59
 #include "geo_common.h"
 
+#include <algorithm>
+#include <vector>
+
 namespace {
 
 constexpr int WPB = 4;   // waves (= rows) per 256-thread block
@@ -336,6 +339,74 @@ __global__ __launch_bounds__(256) void compact_fill_kernel(const int32_t *__rest
     }
 }
 
+// ------------------------------------------------------------------------------------ insertion
+// add_row / add_col / add_w [A]: the directed entries to merge, sorted by (row, col) and distinct, padded with row = n.
+// The count leaves add_keep (the pair is not stored yet) and add_pre (kept entries before it in its row) for the fill.
+__device__ __forceinline__ int32_t lower_bound_i32(const int32_t *__restrict__ a, int32_t lo, int32_t hi, int32_t x) {
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void insert_count_kernel(const int32_t *__restrict__ indptr,
+                                                          const int32_t *__restrict__ indices, int32_t n,
+                                                          const int32_t *__restrict__ add_row,
+                                                          const int32_t *__restrict__ add_col, int32_t A,
+                                                          int32_t *__restrict__ add_keep, int32_t *__restrict__ add_pre,
+                                                          int32_t *__restrict__ row_cnt) {
+    for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
+        const int32_t b = indptr[r], e = indptr[r + 1];
+        const int32_t a0 = lower_bound_i32(add_row, 0, A, r), a1 = lower_bound_i32(add_row, a0, A, r + 1);
+        int32_t kept = 0;
+        for (int32_t a = a0; a < a1; ++a) {
+            const int32_t p = lower_bound_i32(indices, b, e, add_col[a]);
+            const int32_t keep = (p == e || indices[p] != add_col[a]) ? 1 : 0;
+            add_keep[a] = keep;
+            add_pre[a] = kept;
+            kept += keep;
+        }
+        row_cnt[r] = e - b + kept;
+    }
+}
+
+// one wave per row: a row without additions is a copy; otherwise every stored entry moves up by the kept additions
+// left of it and every kept addition lands behind the stored entries left of it
+__global__ __launch_bounds__(256) void insert_fill_kernel(const int32_t *__restrict__ indptr,
+                                                         const int32_t *__restrict__ indices,
+                                                         const float *__restrict__ data, int32_t n,
+                                                         const int32_t *__restrict__ add_row,
+                                                         const int32_t *__restrict__ add_col,
+                                                         const float *__restrict__ add_w,
+                                                         const int32_t *__restrict__ add_keep,
+                                                         const int32_t *__restrict__ add_pre, int32_t A,
+                                                         const int32_t *__restrict__ indptr_new,
+                                                         int32_t *__restrict__ indices_out, float *__restrict__ data_out) {
+    const int lane = threadIdx.x & 63;
+    const int32_t r = blockIdx.x * WPB + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const int32_t b = indptr[r], e = indptr[r + 1], base = indptr_new[r];
+    const int32_t kept_all = indptr_new[r + 1] - base - (e - b);
+    const int32_t a0 = lower_bound_i32(add_row, 0, A, r), a1 = lower_bound_i32(add_row, a0, A, r + 1);
+    for (int32_t i = b + lane; i < e; i += 64) {
+        const int32_t c = indices[i];
+        int32_t shift = 0;
+        if (a1 > a0) {
+            const int32_t a = lower_bound_i32(add_col, a0, a1, c);
+            shift = a < a1 ? add_pre[a] : kept_all;
+        }
+        indices_out[base + (i - b) + shift] = c;
+        data_out[base + (i - b) + shift] = data ? data[i] : 1.0f;
+    }
+    for (int32_t a = a0 + lane; a < a1; a += 64) {
+        if (!add_keep[a]) continue;
+        const int32_t p = lower_bound_i32(indices, b, e, add_col[a]);
+        indices_out[base + (p - b) + add_pre[a]] = add_col[a];
+        data_out[base + (p - b) + add_pre[a]] = add_w[a];
+    }
+}
+
 unsigned rows_grid(int32_t n) { return (unsigned)((n + WPB - 1) / WPB); }
 
 // The ABI's rule (geo_hip.h): a workspace smaller than the size query that belongs to the call is refused before any launch.
@@ -533,6 +604,103 @@ extern "C" int geo_csr_compact_fill(const int32_t *indptr, const int32_t *indice
     GEO_REQUIRE(indptr && indices && new_index && indptr_new && indices_out && n > 0, "geo_csr_compact_fill: bad argument");
     compact_fill_kernel<<<rows_grid(n), 256, 0, s>>>(indptr, indices, data, n, new_index, drop_zero, indptr_new,
                                                      indices_out, data_out);
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+extern "C" size_t geo_csr_insert_workspace_bytes(int32_t n, int64_t E) {
+    if (n <= 0 || E < 0) return 1024;
+    return 5 * geo::align_up((size_t)(2 * E + 1) * 4) + geo::align_up(((size_t)n + 1) * 4) +
+           geo::align_up(geo::scan_tmp_bytes((int64_t)n + 1)) + 4096;
+}
+
+namespace {
+
+struct InsertWs {
+    int32_t *add_row, *add_col, *add_keep, *add_pre, *row_cnt;
+    float *add_w;
+    void *scan_tmp;
+    size_t scan_bytes;
+};
+
+void carve_insert(void *ws, size_t ws_bytes, int32_t n, int64_t E, InsertWs *o) {
+    geo::Arena ar(ws, ws_bytes);
+    const size_t A = (size_t)(2 * E + 1);
+    o->add_row = ar.take<int32_t>(A);
+    o->add_col = ar.take<int32_t>(A);
+    o->add_w = ar.take<float>(A);
+    o->add_keep = ar.take<int32_t>(A);
+    o->add_pre = ar.take<int32_t>(A);
+    o->row_cnt = ar.take<int32_t>((size_t)n + 1);
+    o->scan_bytes = geo::scan_tmp_bytes((int64_t)n + 1);
+    o->scan_tmp = ar.take<char>(o->scan_bytes);
+}
+
+struct AddEntry { int32_t row, col; float w; };
+
+}  // namespace
+
+extern "C" int geo_csr_insert_count(const int32_t *indptr, const int32_t *indices, int32_t n, const int32_t *src,
+                                    const int32_t *dst, const float *w, int64_t E, int32_t *indptr_out, int64_t *nnz_out,
+                                    void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    GEO_REQUIRE(indptr && indices && src && dst && w && indptr_out && nnz_out && ws && n > 0, "geo_csr_insert_count: bad argument");
+    GEO_REQUIRE(E >= 0 && E < ((int64_t)1 << 28), "geo_csr_insert_count: E=%lld out of range", (long long)E);
+    GEO_REQUIRE_WORKSPACE("geo_csr_insert_count", ws_bytes, geo_csr_insert_workspace_bytes(n, E));
+    // the edges are few: read them back, refuse a bad one before anything is launched, order both directions by (row, col)
+    std::vector<int32_t> hs((size_t)E), hd((size_t)E);
+    std::vector<float> hw((size_t)E);
+    if (E > 0) {
+        GEO_HIP_CHECK(hipMemcpyAsync(hs.data(), src, (size_t)E * 4, hipMemcpyDeviceToHost, s));
+        GEO_HIP_CHECK(hipMemcpyAsync(hd.data(), dst, (size_t)E * 4, hipMemcpyDeviceToHost, s));
+        GEO_HIP_CHECK(hipMemcpyAsync(hw.data(), w, (size_t)E * 4, hipMemcpyDeviceToHost, s));
+        GEO_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    for (int64_t e = 0; e < E; ++e) {
+        GEO_REQUIRE(hs[e] >= 0 && hs[e] < n && hd[e] >= 0 && hd[e] < n, "geo_csr_insert_count: edge %lld (%d, %d) outside [0, %d)",
+                    (long long)e, hs[e], hd[e], n);
+        GEO_REQUIRE(hs[e] != hd[e], "geo_csr_insert_count: edge %lld is a self edge (%d)", (long long)e, hs[e]);
+    }
+    std::vector<AddEntry> add;
+    add.reserve((size_t)(2 * E));
+    for (int64_t e = 0; e < E; ++e) {
+        add.push_back({hs[e], hd[e], hw[e]});
+        add.push_back({hd[e], hs[e], hw[e]});
+    }
+    std::stable_sort(add.begin(), add.end(),
+                     [](const AddEntry &a, const AddEntry &b) { return a.row != b.row ? a.row < b.row : a.col < b.col; });
+    const size_t A = (size_t)(2 * E);
+    std::vector<int32_t> hrow(A + 1, n), hcol(A + 1, 0);       // an edge listed twice counts once: the tail is padding (row n)
+    std::vector<float> hww(A + 1, 0.0f);
+    size_t u = 0;
+    for (size_t a = 0; a < add.size(); ++a) {
+        if (a > 0 && add[a].row == add[a - 1].row && add[a].col == add[a - 1].col) continue;
+        hrow[u] = add[a].row; hcol[u] = add[a].col; hww[u] = add[a].w; ++u;
+    }
+    InsertWs o;
+    carve_insert(ws, ws_bytes, n, E, &o);
+    if (A > 0) {
+        GEO_HIP_CHECK(hipMemcpyAsync(o.add_row, hrow.data(), A * 4, hipMemcpyHostToDevice, s));
+        GEO_HIP_CHECK(hipMemcpyAsync(o.add_col, hcol.data(), A * 4, hipMemcpyHostToDevice, s));
+        GEO_HIP_CHECK(hipMemcpyAsync(o.add_w, hww.data(), A * 4, hipMemcpyHostToDevice, s));
+    }
+    insert_count_kernel<<<geo::grid_for(n, 256, 2048), 256, 0, s>>>(indptr, indices, n, o.add_row, o.add_col, (int32_t)A, o.add_keep,
+                                                                  o.add_pre, o.row_cnt);
+    GEO_LAUNCH_CHECK();
+    return geo::exclusive_scan_i32(o.row_cnt, indptr_out, n, o.scan_tmp, o.scan_bytes, nnz_out, s);   // synchronises: the host vectors may go
+}
+
+extern "C" int geo_csr_insert_fill(const int32_t *indptr, const int32_t *indices, const float *data, int32_t n, int64_t E,
+                                   const int32_t *indptr_new, int32_t *indices_out, float *data_out, void *ws, size_t ws_bytes,
+                                   void *stream_) {
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    GEO_REQUIRE(indptr && indices && indptr_new && indices_out && data_out && ws && n > 0, "geo_csr_insert_fill: bad argument");
+    GEO_REQUIRE(E >= 0 && E < ((int64_t)1 << 28), "geo_csr_insert_fill: E=%lld out of range", (long long)E);
+    GEO_REQUIRE_WORKSPACE("geo_csr_insert_fill", ws_bytes, geo_csr_insert_workspace_bytes(n, E));
+    InsertWs o;
+    carve_insert(ws, ws_bytes, n, E, &o);
+    insert_fill_kernel<<<rows_grid(n), 256, 0, s>>>(indptr, indices, data, n, o.add_row, o.add_col, o.add_w, o.add_keep, o.add_pre,
+                                                    (int32_t)(2 * E), indptr_new, indices_out, data_out);
     GEO_LAUNCH_CHECK();
     return GEO_OK;
 }

@@ -15,7 +15,9 @@
 // steps (k * ln(N/k) per query), the loop is bound by the fp64 FMA rate.
 #include "geo_common.h"
 
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 namespace {
 
@@ -922,6 +924,179 @@ __global__ __launch_bounds__(256) void knn_refine_kernel(const float *__restrict
     }
 }
 
+// ---- nearest node of another component (geo_nearest_foreign, geo_bridge_components) -------------------------------------------
+// knn_kernel's mapping with the k-list replaced by ONE running (key, index) minimum per lane and query: the wave's Q queries
+// are gathered through `rows`, their coordinates stay wave-uniform fp64 through the scalar cache, every lane owns one candidate
+// per 64-candidate step.  Candidates arrive in ascending index, so `<` keeps the lowest index among equal keys; a butterfly by
+// (key, index) closes each query.  The pair key is the one geo_knn_topk gives row max(q, x) in the list of row min(q, x): the
+// fma chains are symmetric in the two rows, only the order of the two norms of the expansion form is not -- the norm of the
+// LOWER index is added first.  A 64-candidate step lies wholly below or wholly above the query row except the one that holds
+// it, so the order is a wave-uniform branch and costs a per-lane select in that one step only.
+// What keeps a candidate out:
+//  - a lane past the corpus' end: its key is made +inf by the arithmetic itself, as in knn_bound_kernel (no select per query);
+//  - a candidate of the query's own component: when the wave's Q queries share one label (always at Q = 1; runs of one
+//    component in a query list) the same +inf, one compare per candidate for all Q queries; otherwise one v_cmp_ne_u32 against
+//    the query's label in an SGPR, and-ed into the update mask on the scalar unit.
+// The update itself is one v_cmp_lt_f64 and three v_cndmask per candidate and query against ~DCH v_fma_f64.
+template <int DCH, int Q, bool EXPANSION>
+__global__ __launch_bounds__(256) void nearest_foreign_kernel(const float *__restrict__ zp32, const double *__restrict__ zq64,
+                                                             const double *__restrict__ nrm, const int32_t *__restrict__ labels,
+                                                             const int32_t *__restrict__ rows, int64_t m, int64_t n, int nch,
+                                                             int32_t *__restrict__ nbr_out, double *__restrict__ key_out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t q0 = ((int64_t)blockIdx.x * KNN_WAVES + wave) * Q;
+    if (q0 >= m) return;
+    const int dp = nch * DCH;
+    int32_t qrow[Q], ql[Q];                                    // wave-uniform (the queries' norms are re-read through the scalar
+    bool uniform = true;                                       // cache where they are used, as in knn_kernel: 2 Q SGPRs less)
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const int64_t qi = q0 + q < m ? q0 + q : m - 1;        // (a padded slot repeats the last query)
+        qrow[q] = __builtin_amdgcn_readfirstlane(rows[qi]);
+        ql[q] = __builtin_amdgcn_readfirstlane(labels[qrow[q]]);
+        uniform = uniform && ql[q] == ql[0];
+    }
+    double bk[Q];
+    int32_t bi[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) { bk[q] = inf64(); bi[q] = -1; }
+
+    // (n < 2^31: 32-bit step and row numbers keep the order test below on the scalar unit, which compares no 64-bit integers)
+    const uint32_t n32 = (uint32_t)n;
+    for (uint32_t c0 = 0; c0 < n32; c0 += 64) {
+        const uint32_t j = c0 + (uint32_t)lane;
+        const bool valid = j < n32;
+        const int64_t jc = valid ? j : n32 - 1;
+        const int32_t lab = labels[jc];
+        const double nrm_j = EXPANSION ? nrm[jc] : 0.0;        // requested before the fma chains, not behind a branch after them
+        const bool out = !valid || (uniform && lab == ql[0]);
+        double acc[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) acc[q] = (!EXPANSION && out) ? inf64() : 0.0;
+        for (int ch = 0; ch < nch; ++ch) {
+            double cj[DCH];
+            const float4 *src = reinterpret_cast<const float4 *>(zp32 + jc * dp + ch * DCH);
+#pragma unroll
+            for (int v = 0; v < DCH / 4; ++v) {
+                const float4 f = src[v];
+                cj[4 * v] = (double)f.x; cj[4 * v + 1] = (double)f.y;
+                cj[4 * v + 2] = (double)f.z; cj[4 * v + 3] = (double)f.w;
+            }
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const double *__restrict__ qv = zq64 + (int64_t)qrow[q] * dp + ch * DCH;     // wave-uniform address
+#pragma unroll
+                for (int k = 0; k < DCH; ++k) {
+                    if (EXPANSION) {
+                        acc[q] = fma(qv[k], cj[k], acc[q]);
+                    } else {
+                        const double t = qv[k] - cj[k];
+                        acc[q] = fma(t, t, acc[q]);
+                    }
+                }
+            }
+        }
+        const double nj = out ? inf64() : nrm_j;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            double d2 = acc[q];
+            if (EXPANSION) {
+                const double t = -2.0 * d2;
+                const uint32_t qr = (uint32_t)qrow[q];
+                const double nq = nrm[qrow[q]];
+                if (c0 > qr) d2 = (nq + t) + nj;                               // the query is the lower row of every pair
+                else if (c0 + 63 < qr) d2 = (nj + t) + nq;                     // ... the higher row of every pair
+                else d2 = j < qr ? (nj + t) + nq : (nq + t) + nj;
+                if (!(d2 > 0.0)) d2 = 0.0;
+            }
+            bool upd = d2 < bk[q];
+            if (!uniform) upd = upd && lab != ql[q];
+            bk[q] = upd ? d2 : bk[q];
+            bi[q] = upd ? (int32_t)j : bi[q];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        double k = bk[q];
+        int32_t i = bi[q];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double ok = __shfl_xor(k, off, 64);
+            const int32_t oi = __shfl_xor(i, off, 64);
+            if (ok < k || (ok == k && oi < i)) { k = ok; i = oi; }
+        }
+        if (lane == 0 && q0 + q < m) {
+            nbr_out[q0 + q] = i;
+            key_out[q0 + q] = k;
+        }
+    }
+}
+
+// ---- Boruvka bookkeeping of geo_bridge_components (everything but the scan: O(n) per round) ---------------------------------------
+__global__ __launch_bounds__(256) void bridge_hist_kernel(const int32_t *__restrict__ labels, int64_t n, int32_t C,
+                                                         int32_t *__restrict__ cur, int32_t *__restrict__ sizes,
+                                                         int32_t *__restrict__ bad) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t l = labels[i];
+        cur[i] = l;
+        if (l < 0 || l >= C) *bad = 1;
+        else atomicAdd(&sizes[l], 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void bridge_flag_kernel(const int32_t *__restrict__ cur, int64_t n, int32_t big,
+                                                         int32_t *__restrict__ flag) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        flag[i] = cur[i] != big ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void bridge_rows_kernel(const int32_t *__restrict__ flag, const int32_t *__restrict__ pos,
+                                                         int64_t n, int32_t *__restrict__ rows) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        if (flag[i]) rows[pos[i]] = (int32_t)i;
+}
+
+// keys are >= +0 or +inf: their bit patterns order as unsigned integers
+__global__ __launch_bounds__(256) void bridge_minkey_kernel(const int32_t *__restrict__ cur, const int32_t *__restrict__ rows,
+                                                           const double *__restrict__ key, int64_t m,
+                                                           unsigned long long *__restrict__ minkey) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+        atomicMin(&minkey[cur[rows[i]]], (unsigned long long)__double_as_longlong(key[i]));
+}
+
+__global__ __launch_bounds__(256) void bridge_minedge_kernel(const int32_t *__restrict__ cur, const int32_t *__restrict__ rows,
+                                                            const int32_t *__restrict__ nbr, const double *__restrict__ key,
+                                                            int64_t m, const unsigned long long *__restrict__ minkey,
+                                                            unsigned long long *__restrict__ minedge) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t a = rows[i], b = nbr[i], c = cur[a];
+        if (b < 0 || (unsigned long long)__double_as_longlong(key[i]) != minkey[c]) continue;
+        const unsigned lo = (unsigned)(a < b ? a : b), hi = (unsigned)(a < b ? b : a);
+        atomicMin(&minedge[c], ((unsigned long long)lo << 32) | hi);
+    }
+}
+
+// the component at the other end of every component's chosen edge (one writer per component: the edge's own end)
+__global__ __launch_bounds__(256) void bridge_other_kernel(const int32_t *__restrict__ cur, const int32_t *__restrict__ rows,
+                                                          const int32_t *__restrict__ nbr, const double *__restrict__ key,
+                                                          int64_t m, const unsigned long long *__restrict__ minkey,
+                                                          const unsigned long long *__restrict__ minedge,
+                                                          int32_t *__restrict__ other) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t a = rows[i], b = nbr[i], c = cur[a];
+        if (b < 0 || (unsigned long long)__double_as_longlong(key[i]) != minkey[c]) continue;
+        const unsigned lo = (unsigned)(a < b ? a : b), hi = (unsigned)(a < b ? b : a);
+        if ((((unsigned long long)lo << 32) | hi) == minedge[c]) other[c] = cur[b];
+    }
+}
+
+__global__ __launch_bounds__(256) void bridge_relabel_kernel(int32_t *__restrict__ cur, int64_t n,
+                                                            const int32_t *__restrict__ map) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        cur[i] = map[cur[i]];
+}
+
 struct KnnPlan { int dch, nch, dp; };
 
 KnnPlan plan_for(int d) {
@@ -1405,4 +1580,235 @@ extern "C" int geo_knn_thresholds(const float *z, int64_t n, int32_t d, int32_t 
     knn_subset_kernel<<<geo::grid_for(m * p.dp, 256, 4096), 256, 0, stream>>>(zp32, nrm, n, p.dp, stride, m, zs32, nrm_s);
     GEO_LAUNCH_CHECK();
     return launch_knn_bound(p, form != 0, zs32, zq64, nrm_s, nrm, m, n_neighbors, row0, row1, 0.0, nullptr, nullptr, tau_out, stream);
+}
+
+// ---- nearest foreign node / component bridges -----------------------------------------------------------------------------------
+namespace {
+
+// few queries: one per wave fills more of the chip (and every wave's label is trivially uniform); many: 4, then 8 per wave.
+// Not knn_kernel's 16: the gathered rows cost an address pair, a row number and a label in SGPRs per query, and at 16 the
+// scalar registers spill -- measured on 74 679 / 217 456 queries of 960 000 x 16 / 800 000 x 32 latents, in 10^12 fp64 FMA/s:
+// Q = 4: 6.9 / 6.8, Q = 8: 10.9 / 9.7, Q = 16: 9.1 / 6.7 (knn_kernel's exact scan of as many rows: 11.4 / 13.3).
+template <int DCH>
+int launch_nearest_foreign_d(bool ex, const float *zp32, const double *zq64, const double *nrm, const int32_t *labels,
+                             const int32_t *rows, int64_t m, int64_t n, int nch, int32_t *nbr, double *key, hipStream_t s) {
+    const int Q = m <= 2048 ? 1 : (m < 16384 ? 4 : 8);
+    const int64_t waves = (m + Q - 1) / Q;
+    const unsigned grid = (unsigned)((waves + KNN_WAVES - 1) / KNN_WAVES);
+#define GEO_NF(QV)                                                                                                          \
+    do {                                                                                                                    \
+        if (ex) nearest_foreign_kernel<DCH, QV, true><<<grid, 256, 0, s>>>(zp32, zq64, nrm, labels, rows, m, n, nch, nbr, key); \
+        else nearest_foreign_kernel<DCH, QV, false><<<grid, 256, 0, s>>>(zp32, zq64, nrm, labels, rows, m, n, nch, nbr, key);   \
+    } while (0)
+    if (Q == 1) GEO_NF(1); else if (Q == 4) GEO_NF(4); else GEO_NF(8);
+#undef GEO_NF
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+int launch_nearest_foreign(const KnnPlan &p, bool ex, const float *zp32, const double *zq64, const double *nrm,
+                           const int32_t *labels, const int32_t *rows, int64_t m, int64_t n, int32_t *nbr, double *key,
+                           hipStream_t s) {
+    if (p.dch == 8) return launch_nearest_foreign_d<8>(ex, zp32, zq64, nrm, labels, rows, m, n, p.nch, nbr, key, s);
+    if (p.dch == 16) return launch_nearest_foreign_d<16>(ex, zp32, zq64, nrm, labels, rows, m, n, p.nch, nbr, key, s);
+    return launch_nearest_foreign_d<32>(ex, zp32, zq64, nrm, labels, rows, m, n, p.nch, nbr, key, s);
+}
+
+size_t foreign_corpus_bytes(int64_t n, const KnnPlan &p) {
+    return geo::align_up((size_t)n * p.dp * sizeof(float)) + geo::align_up((size_t)n * p.dp * sizeof(double)) +
+           geo::align_up((size_t)n * sizeof(double));
+}
+
+struct BridgeEdge {
+    double key;
+    int32_t lo, hi;
+    bool operator<(const BridgeEdge &o) const {
+        if (key != o.key) return key < o.key;
+        if (lo != o.lo) return lo < o.lo;
+        return hi < o.hi;
+    }
+};
+
+int32_t uf_find(int32_t *par, int32_t a) {
+    while (par[a] != a) { par[a] = par[par[a]]; a = par[a]; }
+    return a;
+}
+
+}  // namespace
+
+extern "C" size_t geo_nearest_foreign_workspace_bytes(int64_t n, int32_t d) {
+    if (n <= 0 || d <= 0) return 1024;
+    return foreign_corpus_bytes(n, plan_for(d)) + 1024;
+}
+
+extern "C" int geo_nearest_foreign(const float *z, int64_t n, int32_t d, int32_t form, const int32_t *labels, const int32_t *rows,
+                                   int64_t m, int32_t *nbr_out, double *key_out, void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    GEO_REQUIRE(z && labels && rows && nbr_out && key_out && ws, "geo_nearest_foreign: null pointer");
+    GEO_REQUIRE(n > 0 && n < (int64_t)1 << 31, "geo_nearest_foreign: n=%lld out of range", (long long)n);
+    GEO_REQUIRE(m >= 0 && m < (int64_t)1 << 31, "geo_nearest_foreign: m=%lld out of range", (long long)m);
+    GEO_REQUIRE(d > 0 && d <= 128, "geo_nearest_foreign: d=%d not in [1,128]", d);
+    if (m == 0) return GEO_OK;
+    const size_t need = geo_nearest_foreign_workspace_bytes(n, d);
+    if (ws_bytes < need) {
+        geo::set_error("geo_nearest_foreign: workspace of %zu bytes is below the %zu needed", ws_bytes, need);
+        return GEO_E_WORKSPACE;
+    }
+    const KnnPlan p = plan_for(d);
+    geo::Arena ar(ws, ws_bytes);
+    float *zp32 = ar.take<float>((size_t)n * p.dp);
+    double *zq64 = ar.take<double>((size_t)n * p.dp);
+    double *nrm = ar.take<double>((size_t)n);
+    knn_prep_kernel<<<geo::grid_for(n, 256, 4096), 256, 0, stream>>>(z, n, d, p.dp, zp32, zq64, nrm);
+    GEO_LAUNCH_CHECK();
+    return launch_nearest_foreign(p, form != 0, zp32, zq64, nrm, labels, rows, m, n, nbr_out, key_out, stream);
+}
+
+extern "C" size_t geo_bridge_components_workspace_bytes(int64_t n, int32_t d, int32_t C) {
+    if (n <= 0 || d <= 0 || C <= 0) return 1024;
+    const size_t c = (size_t)C;
+    return foreign_corpus_bytes(n, plan_for(d)) + 5 * geo::align_up(((size_t)n + 1) * 4) + geo::align_up((size_t)n * 8) +
+           geo::align_up(c * 20 + 64) + 2 * geo::align_up(c * 4 + 64) + geo::align_up(geo::scan_tmp_bytes(n + 1)) + 1024;
+}
+
+extern "C" int geo_bridge_components(const float *z, int64_t n, int32_t d, int32_t form, const int32_t *labels, int32_t C,
+                                     int32_t *edges_out, double *keys_out, int32_t *status_out, void *ws, size_t ws_bytes,
+                                     void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    GEO_REQUIRE(z && labels && edges_out && keys_out && status_out && ws, "geo_bridge_components: null pointer");
+    GEO_REQUIRE(n > 0 && n < (int64_t)1 << 31, "geo_bridge_components: n=%lld out of range", (long long)n);
+    GEO_REQUIRE(d > 0 && d <= 128, "geo_bridge_components: d=%d not in [1,128]", d);
+    GEO_REQUIRE(C >= 1 && C <= n, "geo_bridge_components: C=%d not in [1, n]", C);
+    const size_t need = geo_bridge_components_workspace_bytes(n, d, C);
+    if (ws_bytes < need) {
+        geo::set_error("geo_bridge_components: workspace of %zu bytes is below the %zu needed", ws_bytes, need);
+        return GEO_E_WORKSPACE;
+    }
+    const KnnPlan p = plan_for(d);
+    geo::Arena ar(ws, ws_bytes);
+    float *zp32 = ar.take<float>((size_t)n * p.dp);
+    double *zq64 = ar.take<double>((size_t)n * p.dp);
+    double *nrm = ar.take<double>((size_t)n);
+    int32_t *cur = ar.take<int32_t>((size_t)n + 1);
+    int32_t *flag = ar.take<int32_t>((size_t)n + 1);
+    int32_t *pos = ar.take<int32_t>((size_t)n + 1);
+    int32_t *rows = ar.take<int32_t>((size_t)n + 1);
+    int32_t *nbr = ar.take<int32_t>((size_t)n + 1);
+    double *key = ar.take<double>((size_t)n);
+    // what a round reads back, in one block: minkey u64 [C], minedge u64 [C], other i32 [C]
+    char *sel = ar.take<char>((size_t)C * 20 + 64);
+    int32_t *sizes = ar.take<int32_t>((size_t)C + 16);         // sizes [C], then the bad-label flag
+    int32_t *map = ar.take<int32_t>((size_t)C + 16);
+    const size_t sb = geo::scan_tmp_bytes(n + 1);
+    void *st = ar.take<char>(sb);
+    if (!zp32 || !zq64 || !nrm || !cur || !flag || !pos || !rows || !nbr || !key || !sel || !sizes || !map || !st) {
+        geo::set_error("geo_bridge_components: workspace %zu too small", ws_bytes);
+        return GEO_E_WORKSPACE;
+    }
+    // the plan: labels in range, component sizes
+    const int gn = geo::grid_for(n, 256, 4096);
+    GEO_HIP_CHECK(hipMemsetAsync(sizes, 0, ((size_t)C + 1) * 4, stream));
+    bridge_hist_kernel<<<gn, 256, 0, stream>>>(labels, n, C, cur, sizes, sizes + C);
+    GEO_LAUNCH_CHECK();
+    int32_t *h_sizes = static_cast<int32_t *>(malloc(((size_t)C + 1) * 4 * 3));      // sizes + bad, parents, map
+    char *h_sel = static_cast<char *>(malloc((size_t)C * 20));
+    BridgeEdge *found = static_cast<BridgeEdge *>(malloc(((size_t)C + 1) * 2 * sizeof(BridgeEdge)));
+    struct Free { void *a, *b, *c; ~Free() { free(a); free(b); free(c); } } guard = {h_sizes, h_sel, found};
+    if (!h_sizes || !h_sel || !found) {
+        geo::set_error("geo_bridge_components: out of host memory");
+        return GEO_E_ARG;
+    }
+    int32_t *par = h_sizes + (C + 1), *h_map = par + (C + 1);
+    GEO_HIP_CHECK(hipMemcpyAsync(h_sizes, sizes, ((size_t)C + 1) * 4, hipMemcpyDeviceToHost, stream));
+    GEO_HIP_CHECK(hipStreamSynchronize(stream));
+    GEO_REQUIRE(h_sizes[C] == 0, "geo_bridge_components: a label lies outside [0, %d)", C);
+    for (int32_t c = 0; c < C; ++c) GEO_REQUIRE(h_sizes[c] > 0, "geo_bridge_components: label %d does not occur", c);
+    int32_t status[4] = {0, 0, 0, 0};
+    int64_t n_found = 0;
+    if (C > 1) {
+        knn_prep_kernel<<<gn, 256, 0, stream>>>(z, n, d, p.dp, zp32, zq64, nrm);
+        GEO_LAUNCH_CHECK();
+    }
+    int32_t cc = C;                                            // components left
+    while (cc > 1) {
+        int32_t big = 0;
+        for (int32_t c = 1; c < cc; ++c)
+            if (h_sizes[c] > h_sizes[big]) big = c;            // lowest label among the largest
+        const int64_t m = n - h_sizes[big];
+        bridge_flag_kernel<<<gn, 256, 0, stream>>>(cur, n, big, flag);
+        GEO_LAUNCH_CHECK();
+        if (int rc = geo::exclusive_scan_i32(flag, pos, n, st, sb, nullptr, stream)) return rc;
+        bridge_rows_kernel<<<gn, 256, 0, stream>>>(flag, pos, n, rows);
+        GEO_LAUNCH_CHECK();
+        if (int rc = launch_nearest_foreign(p, form != 0, zp32, zq64, nrm, cur, rows, m, n, nbr, key, stream)) return rc;
+        unsigned long long *minkey = reinterpret_cast<unsigned long long *>(sel), *minedge = minkey + cc;
+        int32_t *other = reinterpret_cast<int32_t *>(minedge + cc);
+        GEO_HIP_CHECK(hipMemsetAsync(sel, 0xff, (size_t)cc * 20, stream));
+        const int gm = geo::grid_for(m, 256, 4096);
+        bridge_minkey_kernel<<<gm, 256, 0, stream>>>(cur, rows, key, m, minkey);
+        GEO_LAUNCH_CHECK();
+        bridge_minedge_kernel<<<gm, 256, 0, stream>>>(cur, rows, nbr, key, m, minkey, minedge);
+        GEO_LAUNCH_CHECK();
+        bridge_other_kernel<<<gm, 256, 0, stream>>>(cur, rows, nbr, key, m, minkey, minedge, other);
+        GEO_LAUNCH_CHECK();
+        GEO_HIP_CHECK(hipMemcpyAsync(h_sel, sel, (size_t)cc * 20, hipMemcpyDeviceToHost, stream));
+        GEO_HIP_CHECK(hipStreamSynchronize(stream));
+        status[0] += 1;
+        if (status[0] == 1) status[1] = (int32_t)m;
+        status[2] += (int32_t)m;
+        const unsigned long long *h_minkey = reinterpret_cast<const unsigned long long *>(h_sel), *h_minedge = h_minkey + cc;
+        const int32_t *h_other = reinterpret_cast<const int32_t *>(h_minedge + cc);
+        for (int32_t c = 0; c < cc; ++c) par[c] = c;
+        for (int32_t c = 0; c < cc; ++c) {
+            if (c == big) continue;
+            const int32_t o = h_other[c];
+            if (o < 0 || o >= cc || o == c || h_minedge[c] == ~0ull) {
+                geo::set_error("geo_bridge_components: internal: component %d found no foreign node", c);
+                return GEO_E_ARG;
+            }
+            const int32_t ra = uf_find(par, c), rb = uf_find(par, o);
+            if (ra != rb) {                                    // (equal: the other end chose the same edge earlier in this loop)
+                if (ra < rb) par[rb] = ra; else par[ra] = rb;  // the root is the lowest label: numbering by lowest node stays
+                long long kb = (long long)h_minkey[c];
+                BridgeEdge e;
+                memcpy(&e.key, &kb, 8);
+                e.lo = (int32_t)(h_minedge[c] >> 32);
+                e.hi = (int32_t)(h_minedge[c] & 0xffffffffu);
+                found[n_found++] = e;
+            }
+        }
+        int32_t next = 0;
+        for (int32_t c = 0; c < cc; ++c)
+            if (par[c] == c) h_map[c] = next++;
+        for (int32_t c = 0; c < cc; ++c) {
+            const int32_t r = uf_find(par, c);
+            if (r != c) { h_map[c] = h_map[r]; h_sizes[r] += h_sizes[c]; }
+        }
+        for (int32_t c = 0; c < cc; ++c)
+            if (par[c] == c) h_sizes[h_map[c]] = h_sizes[c];   // h_map[c] <= c: never overwrites a root still to be read
+        GEO_HIP_CHECK(hipMemcpyAsync(map, h_map, (size_t)cc * 4, hipMemcpyHostToDevice, stream));
+        bridge_relabel_kernel<<<gn, 256, 0, stream>>>(cur, n, map);
+        GEO_LAUNCH_CHECK();
+        GEO_HIP_CHECK(hipStreamSynchronize(stream));           // h_map is rewritten next round
+        if (next >= cc) {
+            geo::set_error("geo_bridge_components: internal: a round merged nothing");
+            return GEO_E_ARG;
+        }
+        cc = next;
+    }
+    if (n_found != (int64_t)C - 1) {
+        geo::set_error("geo_bridge_components: internal: %lld edges for %d components", (long long)n_found, C);
+        return GEO_E_ARG;
+    }
+    if (C > 1) {
+        std::sort(found, found + n_found);
+        int32_t *h_edges = reinterpret_cast<int32_t *>(h_sel);           // 20 C bytes: 8 (C - 1) + 8 (C - 1) fit
+        double *h_keys = reinterpret_cast<double *>(h_sel + (size_t)(C - 1) * 8);
+        for (int64_t e = 0; e < n_found; ++e) { h_edges[2 * e] = found[e].lo; h_edges[2 * e + 1] = found[e].hi; h_keys[e] = found[e].key; }
+        GEO_HIP_CHECK(hipMemcpyAsync(edges_out, h_edges, (size_t)(C - 1) * 8, hipMemcpyHostToDevice, stream));
+        GEO_HIP_CHECK(hipMemcpyAsync(keys_out, h_keys, (size_t)(C - 1) * 8, hipMemcpyHostToDevice, stream));
+        GEO_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    for (int i = 0; i < 4; ++i) status_out[i] = status[i];
+    return GEO_OK;
 }

@@ -264,6 +264,151 @@ def compact_device(G: DeviceCSR, keep: Optional[torch.Tensor], drop_zero: bool) 
     return DeviceCSR(n, indptr_new[: n + 1].contiguous(), indices, data), new_index
 
 
+# --------------------------------------------------------------------------------- bridging the components (extension)
+def _key_form(d: int, form: Optional[int]) -> int:
+    """The key form knn_search_device uses at this dimension (sklearn "auto") unless one is given."""
+    return (1 if d > 15 else 0) if form is None else int(form)
+
+
+def _check_latents(z: torch.Tensor, n: int) -> None:
+    if z.dim() != 2 or z.dtype != torch.float32:
+        raise ValueError(f"latents must be a float32 [n, d] tensor, got {z.dtype} {tuple(z.shape)}")
+    if z.shape[0] != n:
+        raise ValueError(f"{z.shape[0]} latents for {n} nodes")
+    if not 1 <= z.shape[1] <= 128:
+        raise ValueError(f"latent dimension {z.shape[1]} outside the supported range [1, 128]")
+
+
+def nearest_foreign_device(z: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, form: Optional[int] = None):
+    """(nbr int32 [m], key float64 [m]): for every query row q = rows[i] of the resident latents z (f32 [n, d]) the node x
+    with labels[x] != labels[q] that minimises (pair key, x) -- the pair key is the fp64 key knn_search_device gives row
+    max(q, x) in the list of row min(q, x) (geo_nearest_foreign).  A query whose label is every node's gets -1 and +inf.
+    form: 0 = sum of squared differences, 1 = norm expansion, None = the rule of knn_search_device."""
+    _check_latents(z, int(labels.numel()))
+    lib = _lib.load()
+    n, d = z.shape
+    dev = z.device
+    z = z.contiguous()
+    labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+    rows = rows.to(device=dev, dtype=torch.int32).contiguous()
+    m = int(rows.numel())
+    nbr = torch.empty(m, dtype=torch.int32, device=dev)
+    key = torch.empty(m, dtype=torch.float64, device=dev)
+    if m == 0:
+        return nbr, key
+    if int(rows.min()) < 0 or int(rows.max()) >= n:
+        raise ValueError(f"query rows outside [0, {n})")
+    with torch.cuda.device(dev):
+        ws = workspace(lib.geo_nearest_foreign_workspace_bytes(n, d), dev)
+        _lib.check(lib.geo_nearest_foreign(ptr(z), n, d, _key_form(d, form), ptr(labels), ptr(rows), m, ptr(nbr), ptr(key),
+                                           ptr(ws), ws.numel(), stream_ptr()), "geo_nearest_foreign")
+    return nbr, key
+
+
+def bridge_edges_device(z: torch.Tensor, labels: torch.Tensor, n_components: int, form: Optional[int] = None,
+                        extra_workspace_bytes: int = 0):
+    """(edges int32 [C-1, 2], keys float64 [C-1], info): the bridges of the components `labels` (int32 [n] in [0, C)) of the
+    resident latents z -- the minimum spanning tree of the component graph under the order (pair key, lo, hi), sorted by it
+    (geo_bridge_components).  info: components, rounds, queries_first_round, queries.  extra_workspace_bytes enlarges the
+    workspace beyond the library's size (tests: the result does not depend on it)."""
+    _check_latents(z, int(labels.numel()))
+    lib = _lib.load()
+    n, d = z.shape
+    dev = z.device
+    C = int(n_components)
+    z = z.contiguous()
+    labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+    edges = torch.empty((max(C - 1, 0), 2), dtype=torch.int32, device=dev)
+    keys = torch.empty(max(C - 1, 0), dtype=torch.float64, device=dev)
+    status = np.zeros(4, dtype=np.int32)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.geo_bridge_components_workspace_bytes(n, d, C) + int(extra_workspace_bytes), dev)
+        nbytes = ws.numel() if extra_workspace_bytes else lib.geo_bridge_components_workspace_bytes(n, d, C)
+        _lib.check(lib.geo_bridge_components(ptr(z), n, d, _key_form(d, form), ptr(labels), C, ptr_or_stand_in(edges),
+                                             ptr_or_stand_in(keys), status.ctypes.data, ptr(ws), nbytes, stream_ptr()),
+                   "geo_bridge_components")
+    info = {"components": C, "rounds": int(status[0]), "queries_first_round": int(status[1]), "queries": int(status[2])}
+    return edges, keys, info
+
+
+def csr_insert_device(G: DeviceCSR, src: torch.Tensor, dst: torch.Tensor, w: torch.Tensor) -> DeviceCSR:
+    """The canonical CSR G with both directions of the E undirected edges (src, dst int32 [E], w f32 [E]) merged in:
+    columns ascending, existing entries keep their weights, a pair already stored adds nothing (geo_csr_insert_*).
+    A graph without data is taken as all ones."""
+    lib = _lib.load()
+    dev = G.indptr.device
+    E = int(src.numel())
+    src = src.to(device=dev, dtype=torch.int32).contiguous()
+    dst = dst.to(device=dev, dtype=torch.int32).contiguous()
+    w = w.to(device=dev, dtype=torch.float32).contiguous()
+    indptr_new = torch.empty(G.n + 1, dtype=torch.int32, device=dev)
+    nnz = np.zeros(1, dtype=np.int64)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.geo_csr_insert_workspace_bytes(G.n, E), dev)
+        _lib.check(lib.geo_csr_insert_count(ptr(G.indptr), ptr_or_stand_in(G.indices), G.n, ptr_or_stand_in(src),
+                                            ptr_or_stand_in(dst), ptr_or_stand_in(w), E, ptr(indptr_new), nnz.ctypes.data,
+                                            ptr(ws), ws.numel(), stream_ptr()), "geo_csr_insert_count")
+        indices = torch.empty(int(nnz[0]), dtype=torch.int32, device=dev)
+        data = torch.empty(int(nnz[0]), dtype=torch.float32, device=dev)
+        _lib.check(lib.geo_csr_insert_fill(ptr(G.indptr), ptr_or_stand_in(G.indices), ptr(G.data), G.n, E, ptr(indptr_new),
+                                           ptr_or_stand_in(indices), ptr_or_stand_in(data), ptr(ws), ws.numel(), stream_ptr()),
+                   "geo_csr_insert_fill")
+    return DeviceCSR(G.n, indptr_new, indices, data)
+
+
+_FLT_MIN = float(np.finfo(np.float32).tiny)
+
+
+def bridge_components_device(G: DeviceCSR, z: torch.Tensor, *, mode: str = "connectivity", form: Optional[int] = None):
+    """Connect the components of the resident, structurally symmetric graph G over the latents z (f32 [n, d]):
+    (G2, edges int32 [C-1, 2], keys float64 [C-1], info).  The bridges are the C - 1 edges of the minimum spanning tree of
+    the component graph under the order (pair key, lo, hi) (bridge_edges_device; labels from connected_components_device);
+    each is inserted as two symmetric entries of weight 1 (mode "connectivity") or float32(sqrt(key)) (mode "distance";
+    FLT_MIN where that is 0 -- duplicate rows in different components -- so that the entry is a stored one).  No existing
+    entry changes.  C == 1 returns G itself.  info: components, rounds, queries_first_round, queries.
+    form must be the key form the graph was built with (None: the rule of knn_search_device)."""
+    if mode not in ("connectivity", "distance"):
+        raise ValueError(f"Invalid mode: {mode}")
+    _check_latents(z, G.n)
+    C, labels = connected_components_device(G)
+    if C <= 1:
+        dev = G.indptr.device
+        return (G, torch.empty((0, 2), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float64, device=dev),
+                {"components": C, "rounds": 0, "queries_first_round": 0, "queries": 0})
+    edges, keys, info = bridge_edges_device(z, labels, C, form)
+    if mode == "distance":
+        w = torch.sqrt(keys).to(torch.float32)
+        w = torch.where(w == 0, torch.full_like(w, _FLT_MIN), w)
+    else:
+        w = torch.ones(C - 1, dtype=torch.float32, device=edges.device)
+    G2 = csr_insert_device(G, edges[:, 0], edges[:, 1], w)
+    return G2, edges, keys, info
+
+
+def connect_components(W: sparse.csr_matrix, z: np.ndarray, mode: str = "distance", metric: str = "euclidean"):
+    """scipy in, scipy out: the symmetric kNN graph W of build_knn_graph(z, ...) with its components bridged
+    (bridge_components_device): (W2 csr_matrix float32, info).  info carries components, rounds, the query counts and the
+    bridges ("edges" int64 [C-1, 2], "keys" float64 [C-1] squared distances).  Euclidean graphs only."""
+    if metric != "euclidean":
+        raise ValueError(f"Metric '{metric}' not supported by connect_components. Use 'euclidean'.")
+    if mode not in ("connectivity", "distance"):
+        raise ValueError(f"Invalid mode: {mode}")
+    z = np.asarray(z)
+    W = sparse.csr_matrix(W)
+    if z.ndim != 2 or z.shape[0] != W.shape[0]:
+        raise ValueError(f"latents of shape {z.shape} for a graph of {W.shape[0]} nodes")
+    if W.shape[0] == 0:
+        return W.astype(np.float32), {"components": 0, "rounds": 0, "queries_first_round": 0, "queries": 0,
+                                      "edges": np.empty((0, 2), np.int64), "keys": np.empty(0, np.float64)}
+    dev = device()
+    W.sort_indices()
+    G = DeviceCSR.from_scipy(W, dev)
+    z_dev = torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(dev)
+    G2, edges, keys, info = bridge_components_device(G, z_dev, mode=mode)
+    info = dict(info, edges=edges.cpu().numpy().astype(np.int64), keys=keys.cpu().numpy())
+    return G2.to_scipy(), info
+
+
 def upper_edges_device(G: DeviceCSR):
     """(src, dst int32 [E], entry_edge int32 [nnz]): stored entries with row < col in row-major order
     (build_codebook.py:43-45) and, for every entry, the index of its undirected edge."""

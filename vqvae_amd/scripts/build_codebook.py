@@ -1,5 +1,6 @@
 """Build a geodesic spatial codebook on the MI355X -- drop-in for the reference CLI
-src/scripts/build_codebook.py (main :14-106, flags :108-134; same flags, same three artefacts).
+src/scripts/build_codebook.py (main :14-106, flags :108-134; same flags, same three artefacts;
+--connect_components, an extension, bridges the graph's components and adds bridges.json).
 
     python -m vqvae_amd.scripts.build_codebook --latents_path z.pt --out_dir out --vae_ckpt_path best.pt \
         --in_channels 1 --output_image_size 28 --latent_dim 16 --enc_channels 64 128 256 \
@@ -22,8 +23,8 @@ from scipy import sparse
 
 from .._device import DeviceCSR, device
 from ..geo.kmeans_optimized import fit_kmedoids_optimized, fit_kmedoids_voronoi_graph
-from ..geo.knn_graph_optimized import (compact_device, knn_graph_device, lcc_mask_device, reweight_device,
-                                       upper_edges_device)
+from ..geo.knn_graph_optimized import (bridge_components_device, compact_device, knn_graph_device, lcc_mask_device,
+                                       reweight_device, upper_edges_device)
 from ..geo.riemannian_metric import edge_lengths_graph_device, edge_lengths_riemannian
 from ..parallel import RunningStatFold, sharded_edge_lengths, world_info
 from ..spatial_decoder import DecoderExport, hip_kernels_cover, load_decoder_from_checkpoint
@@ -32,14 +33,22 @@ from ..spatial_decoder import DecoderExport, hip_kernels_cover, load_decoder_fro
 def build_codebook_device(z_flat: torch.Tensor, decoder, *, k: int = 20, sym: str = "union", K: int = 512,
                           init: str = "kpp", seed: int = 42, batch_size: int = 512,
                           timers: Optional[Dict[str, float]] = None, group=None, refine_iters: int = 0,
-                          refine_power: int = 2) -> dict:
+                          refine_power: int = 2, connect_components: bool = False) -> dict:
     """The hot path on resident data.  z_flat: f32 [n_nodes, d] on the GPU, rows in (n, h, w) order.
     Returns device/host results; `timers` (if given) receives per-stage seconds (synchronised).
     Under an initialised torch.distributed group the kNN rows and the JVP chunks are sharded over the
     ranks (vqvae_amd/parallel.py); every rank ends with the full result.
     refine_iters > 0 (extension): the seeded codebook is refined by up to that many cell-restricted medoid updates
     (fit_kmedoids_voronoi_graph, objective sum of distance^refine_power) and the result gains the key "refine" = {history,
-    iterations, info}.  Every rank refines its full copy: the refinement is deterministic, so the ranks agree."""
+    iterations, info}.  Every rank refines its full copy: the refinement is deterministic, so the ranks agree.
+    connect_components (extension, off by default): the components of the kNN graph are bridged (bridge_components_device:
+    the C - 1 minimum-spanning-tree edges of the component graph) right after the search, so the bridges get pull-back
+    lengths through the JVP like every other edge and every latent gets a code; the result gains the key "bridges" =
+    {edges, keys, components, rounds}.  Everything downstream is untouched, the zero-length drop and the largest-component
+    rule included: a bridge between exact duplicates that gets pull-back length 0 is removed by the zero rule and the
+    largest-component rule then applies as before.  Every rank bridges its full copy (deterministic: the ranks agree).
+    With train-mode BatchNorm the extra edges move the chunk boundaries, so the other lengths change as with any change of
+    the edge list."""
     dev = z_flat.device
 
     def tick(name, t0):
@@ -50,6 +59,10 @@ def build_codebook_device(z_flat: torch.Tensor, decoder, *, k: int = 20, sym: st
 
     t0 = time.perf_counter()
     G, _, _ = knn_graph_device(z_flat, k, mode="connectivity", sym=sym, group=group, need_dist=False)
+    bridges = None
+    if connect_components:
+        G, b_edges, b_keys, b_info = bridge_components_device(G, z_flat, mode="connectivity")
+        bridges = {"edges": b_edges, "keys": b_keys, "components": b_info["components"], "rounds": b_info["rounds"]}
     src, dst, entry_edge = upper_edges_device(G)
     t0 = tick("knn", t0)
 
@@ -104,6 +117,8 @@ def build_codebook_device(z_flat: torch.Tensor, decoder, *, k: int = 20, sym: st
            "sharded": sharded}
     if refine is not None:
         res["refine"] = refine
+    if bridges is not None:
+        res["bridges"] = bridges
     return res
 
 
@@ -156,7 +171,8 @@ def main(args):
     print(f"Building k-NN graph: N={z_flat.shape[0]}, k={args.k}, method=hip")
     res = build_codebook_device(z_flat, decoder, k=args.k, sym=args.sym, K=args.K, init=args.init, seed=args.seed,
                                 batch_size=args.batch_size, refine_iters=getattr(args, "refine_iters", 0),
-                                refine_power=getattr(args, "refine_power", 2))
+                                refine_power=getattr(args, "refine_power", 2),
+                                connect_components=getattr(args, "connect_components", False))
 
     sparse.save_npz(out_dir / "knn_graph_geodesic.npz", res["W_lcc"].to_scipy())
     codes = res["assign_flat"].reshape(N, H, W)
@@ -174,6 +190,17 @@ def main(args):
         import json
         with open(out_dir / "refine.json", "w") as f:
             json.dump({"refine_iters": args.refine_iters, "refine_power": args.refine_power, "qe": res["qe"], **res["refine"]}, f, indent=1)
+    if "bridges" in res:                                # --connect_components: bridges.json, the other three keep their format
+        import json
+        b = res["bridges"]
+        src, dst = res["edges"]
+        n_nodes = int(z_flat.shape[0])
+        edge_key = src.long() * n_nodes + dst.long()    # ascending: the upper edges are in row-major order
+        at = torch.searchsorted(edge_key, b["edges"][:, 0].long() * n_nodes + b["edges"][:, 1].long())
+        with open(out_dir / "bridges.json", "w") as f:
+            json.dump({"connect_components": True, "components": b["components"], "rounds": b["rounds"],
+                       "edges": b["edges"].cpu().tolist(), "keys": b["keys"].cpu().tolist(),
+                       "lengths": res["edge_lengths"][at].cpu().tolist()}, f, indent=1)
     print(f"Quantization error: {res['qe']:.3f}")
     print(f"Saved artifacts to: {out_dir}")
     return res
@@ -199,6 +226,8 @@ def make_parser() -> argparse.ArgumentParser:
     # extension: cell-restricted medoid updates after the seeding (0: the reference's codebook, artefacts unchanged)
     parser.add_argument("--refine_iters", type=int, default=0)
     parser.add_argument("--refine_power", type=int, default=2, choices=(1, 2))
+    # extension: bridge the kNN graph's components so that every latent gets a code (writes bridges.json as well)
+    parser.add_argument("--connect_components", action='store_true')
     return parser
 
 
