@@ -596,6 +596,48 @@ def test_near_far_push_solve_forced_on_every_graph_equals_oracle(delta, order, r
     assert np.isinf(D[:20, 3000:]).all() and np.isinf(D[20:, :3000]).all()
 
 
+def _check_small_chunked_route(request, W, layout, **opts):
+    """40 sources (one repeated) on a 3000-node graph with `sssp_sb=16` (the chunked layout below 12 289 nodes) and `opts`:
+    D, column minimum and first-row argmin equal the oracle's, and the call reports `layout`."""
+    import torch
+    from oracle import sssp as osp
+    from vqvae_amd import _lib
+    from vqvae_amd._device import DeviceCSR, device
+    from vqvae_amd.geo.geo_shortest_paths import dijkstra_multi_source, sssp_multi_device
+    _set_options(request, sssp_sb=16, sssp_push=0, sssp_group=2, **opts)
+    src = np.random.RandomState(8).choice(W.shape[0], 40, replace=False)
+    src[-1] = src[2]                                                # a duplicate source: ties for the first-row argmin
+    Do = osp.dijkstra_multi_source(W, src)
+    np.testing.assert_array_equal(dijkstra_multi_source(W, src), Do)
+    assert _lib.load().geo_sssp_last_profile(None, None) == layout
+    G = DeviceCSR.from_scipy(W, device())
+    _, _, dmin, arg, sweeps = sssp_multi_device(G, torch.from_numpy(src.astype(np.int32)).to(device()), want_D=False, want_min=True)
+    assert _lib.load().geo_sssp_last_profile(None, None) == layout
+    np.testing.assert_array_equal(dmin.cpu().numpy(), Do.min(axis=0))
+    np.testing.assert_array_equal(arg.cpu().numpy(), Do.argmin(axis=0))
+    assert sweeps >= 8                                              # the first group of 4, then the restarted solve's groups
+
+
+def test_ordered_fp64_chunk_sweeps_without_the_push_solve(request):
+    """`sssp_push=0, sssp_u32=0, sssp_group=2` on a small forced-chunked swiss roll: after its first group the fp64 chunk sweep
+    orders the sources along the landmark distances and starts over with the grouped grid cap (layout 1016)."""
+    from oracle import knn as okn
+    W, _ = okn.build_knn_graph(swiss_roll_latents(3000, 16, 3), k=6, mode="distance", sym="union")
+    _check_small_chunked_route(request, W.tocsr(), 1016, sssp_u32=0)
+
+
+def test_fixed_point_solve_restarts_ordered_by_hop_counts(request):
+    """`sssp_push=0, sssp_group=2, sssp_order=2`, weights of one binade: the fixed-point solve orders the sources by two
+    landmark hop counts after its first group, starts over and answers (layout 2032)."""
+    from oracle import knn as okn
+    from oracle.synthetic import formula_weights
+    W, _ = okn.build_knn_graph(swiss_roll_latents(3000, 16, 3), k=6, mode="connectivity", sym="union")
+    W = W.tocsr()
+    rows = np.repeat(np.arange(3000), np.diff(W.indptr))
+    W.data = formula_weights(np.minimum(rows, W.indices), np.maximum(rows, W.indices)).astype(np.float32)   # symmetric
+    _check_small_chunked_route(request, W, 2032, sssp_order=2)
+
+
 def _nearest_both_ways(W, sources, unweighted=False):
     """(dmin, argmin) from the ONE-solve nearest-source kernel and from the K-source solve, plus the layout the former took."""
     import torch

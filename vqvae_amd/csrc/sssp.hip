@@ -769,12 +769,6 @@ __global__ __launch_bounds__(256) void weight_sum_kernel(const float *__restrict
     if ((threadIdx.x & 63) == 0) atomicAdd(out, acc);
 }
 
-size_t push_bytes(int32_t n, int64_t nnz, int32_t nb) {
-    const size_t cs = ((size_t)nb + 31) / 32 * 32, per = (size_t)nb * n;
-    const size_t cap = (size_t)n + (size_t)(nnz / 16) + 16;                     // chunks of the graph (upper bound)
-    return geo::align_up(2 * (size_t)nb * cap * 4) + geo::align_up(3 * per * 4) + 2 * geo::align_up(per * 4) +
-           geo::align_up(3 * cs * 4) * 2 + geo::align_up(2 * cs * 4) + geo::align_up(2 * cs * 8) + 512 + 256 + 4096;
-}
 
 __device__ __forceinline__ double units_to_f64(uint32_t u, double unit) { return u == U_INF ? inf64() : (double)u * unit; }
 
@@ -1073,12 +1067,6 @@ __global__ __launch_bounds__(256) void cell_adjacency_kernel(const int32_t *__re
 }
 constexpr int32_t CELL_ORDER_MAX_SOURCES = 16384;       // quotient graph as a bitmap: 32 MB at this size
 
-struct MultiWs {
-    double *dist;
-    int32_t *pred;
-    int32_t *flags;
-    int32_t *src_pad;
-};
 
 // sources per batch.  64 (one 512-byte row per node and wave, CSR row through the scalar cache) is the
 // fastest layout measured on MI355X at every graph size: a 16-source batch would fit one XCD's L2 at
@@ -1104,645 +1092,782 @@ int choose_sb(int32_t n, int32_t n_sources, int forced_here) {
     return 64;
 }
 
-size_t chunk_bytes(int32_t n, int64_t nnz, int32_t nb) {
-    const size_t max_chunks = (size_t)n + (size_t)(nnz / 16) + 16;
-    const size_t words = ((size_t)n + 3) / 4;
-    return 2 * geo::align_up(((size_t)n + 1) * 4) + 2 * geo::align_up(max_chunks * 4) +
-           geo::align_up(geo::scan_tmp_bytes((int64_t)n + 1)) + geo::align_up(3 * (size_t)nb * words * 4) +
-           geo::align_up(4 * (((size_t)nb + 31) / 32 * 32) * 4) + geo::align_up((size_t)n * 8) + geo::align_up(2 * (size_t)nb * 16 * 4) +
-           geo::align_up((size_t)(nnz > 0 ? nnz : 1) * 4) + 256 + 256 + geo::align_up((size_t)n * 4) + 1024 + push_bytes(n, nnz, nb) +
-           geo::align_up((size_t)std::min(nb * 16, CELL_ORDER_MAX_SOURCES) * ((std::min(nb * 16, CELL_ORDER_MAX_SOURCES) + 31) / 32) * 4);
+// ---- the plan: what a call will run, decided once from the sizes and the options ---------------------------------------
+struct MultiPlan {
+    int32_t sb, nb;     // sources per batch, batches
+    int32_t cs;         // row stride of the flag / count rings
+    bool chunked;       // 16-edge chunk work items (see sweep_chunk16_kernel); their 32-bit row offsets need n * 128 bytes < 2^32
+    bool u32;           // the 32-bit fixed-point solve exists at these sizes (what geo_sssp_plan reports) ...
+    bool try_u32;       // ... and goes first (`sssp_push=2` sends every graph to the near-far push solve instead)
+    bool replan64;      // a graph this large took 16-source batches only for the fixed-point solve: fp64 runs 64 per batch
+};
+
+MultiPlan make_plan(int32_t n, int32_t n_sources, int force_sb) {
+    const geo::Options &opt = geo::options();
+    MultiPlan p;
+    p.sb = choose_sb(n, n_sources, force_sb);
+    p.nb = (n_sources + p.sb - 1) / p.sb;
+    // rows of the flag / count rings start on their own 128-byte lines: every block reads the previous sweep's row while
+    // the current sweep's row takes stores and atomics (a shared line made alternate sweeps 3x slower at nb = 16)
+    p.cs = ((p.nb + 31) / 32) * 32;
+    p.chunked = p.sb == 16 && n_sources > 16 && n < ROW128_MAX_NODES;
+    p.u32 = p.chunked && n_sources >= 32 && opt.sssp_u32 != 0;
+    p.try_u32 = p.u32 && opt.sssp_push != 2;
+    p.replan64 = p.try_u32 && force_sb == 0 && opt.sssp_sb != 16 && opt.sssp_sb != 64 && (size_t)n * 128 > ((size_t)12 << 20);
+    return p;
 }
+
+// ---- the layout: every buffer of a solve, in workspace order ------------------------------------------------------------
+struct MultiBufs {
+    double *dist;                       // [nb][n][sb] fp64; the fixed-point solve keeps uint32 [nb32][n][32] in the same bytes
+    int32_t *pred, *flags, *src_pad;
+    int32_t *row_of;                    // (batch, slot) -> row of the caller's `sources`
+    // chunked plans only
+    int32_t words;                      // need-map: one byte per node, in 4-byte words
+    size_t max_chunks, scan_bytes;
+    uint32_t *bits;                     // need-map ring [3][nb][words]
+    int32_t *counts;                    // improvement-count ring [4][cs]
+    int32_t *chunk_cnt, *chunk_off, *row_order, *chunk_node, *chunk_start;
+    char *scan_tmp;
+    double *lm_d;                       // a landmark's distances (n doubles); the BFS orderings keep label[n], level_of[n] here
+    float *lm_key;
+    int32_t *lm_flags;                  // [0..3] solve flags, [8..9] the landmark eccentricity (u64)
+    uint32_t *wunits, *wrange;          // 32-bit fixed-point weights / their range
+    PushState push;
+    uint32_t *cell_adj;
+    double *wsum;
+};
+
+// Over a workspace it hands out the buffers, over none (base == nullptr) it only adds up their sizes.
+struct Carver {
+    char *base;
+    size_t off = 0;
+    template <typename T>
+    void take(T *&p, size_t count) {
+        p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += geo::align_up(count * sizeof(T));
+    }
+};
 
 // slots of a solve: whole batches of `sb` sources, and (for the 32-source fixed-point layout of the same buffers) of 32
 size_t padded_slots(int32_t nb, int32_t sb) { return ((size_t)nb * sb + 31) / 32 * 32; }
 
-size_t multi_bytes(int32_t n, int32_t nb, int32_t sb, bool with_pred) {
-    const size_t slots = padded_slots(nb, sb);
-    size_t b = geo::align_up(slots * n * sizeof(double));
-    if (with_pred) b += geo::align_up(slots * n * sizeof(int32_t));
-    b += geo::align_up(3 * (((size_t)nb + 31) / 32 * 32) * sizeof(int32_t)) + 2 * geo::align_up(slots * sizeof(int32_t));
-    return b;
+// The one description of the layout: the buffers of plan `p` carved from `ws` (or only measured); returns their bytes.
+size_t lay_out(const MultiPlan &p, int32_t n, int64_t nnz, bool with_pred, void *ws, MultiBufs &b) {
+    Carver c{static_cast<char *>(ws)};
+    b = MultiBufs{};
+    const size_t slots = padded_slots(p.nb, p.sb), nb = (size_t)p.nb, cs = (size_t)p.cs;
+    c.take(b.dist, slots * n);
+    if (with_pred) c.take(b.pred, slots * n);
+    c.take(b.flags, 3 * cs);
+    c.take(b.src_pad, slots);
+    c.take(b.row_of, slots);
+    if (!p.chunked) return c.off;
+    b.words = (n + 3) / 4;
+    b.max_chunks = (size_t)n + (size_t)(nnz / 16) + 16;
+    b.scan_bytes = geo::scan_tmp_bytes((int64_t)n + 1);
+    c.take(b.bits, 3 * nb * b.words);
+    c.take(b.counts, 4 * cs);
+    c.take(b.chunk_cnt, (size_t)n + 1);
+    c.take(b.chunk_off, (size_t)n + 1);
+    c.take(b.row_order, (size_t)n);
+    c.take(b.chunk_node, b.max_chunks);
+    c.take(b.chunk_start, b.max_chunks);
+    c.take(b.scan_tmp, b.scan_bytes);
+    c.take(b.lm_d, (size_t)n);
+    c.take(b.lm_key, 2 * nb * p.sb);
+    c.take(b.lm_flags, 16);
+    c.take(b.wunits, (size_t)(nnz > 0 ? nnz : 1));
+    c.take(b.wrange, 4);
+    PushState &push = b.push;
+    push.cs = p.cs;
+    push.cap = (int32_t)b.max_chunks;
+    push.chunk_off = b.chunk_off;
+    push.chunk_node = b.chunk_node;
+    push.chunk_start = b.chunk_start;
+    push.words = (n + 31) / 32;
+    c.take(push.near_lists, 2 * nb * b.max_chunks);
+    c.take(push.far_lists, 3 * nb * n);
+    c.take(push.near_bits, 2 * nb * push.words);
+    c.take(push.far_bits, nb * push.words);
+    c.take(push.near_cnt, 3 * cs);
+    c.take(push.far_cnt, 3 * cs);
+    c.take(push.far_slot, 2 * cs);
+    c.take(push.theta, 2 * cs);
+    c.take(push.active, 64);
+    const size_t S = (size_t)std::min(p.nb * 16, CELL_ORDER_MAX_SOURCES);
+    c.take(b.cell_adj, S * ((S + 31) / 32));
+    c.take(b.wsum, 8);
+    return c.off;
 }
 
 }  // namespace
 
+// Covers every plan the options can select after the query: both batch widths (chunked where 16 per batch is), predecessors wanted.
 extern "C" size_t geo_sssp_workspace_bytes(int32_t n, int64_t nnz, int32_t n_sources) {
     if (n < 0 || n_sources < 0 || nnz < 0) return 0;
     const int32_t nn = n > 0 ? n : 1, ss = n_sources > 0 ? n_sources : 1;
-    size_t multi = 0;
-    for (int sb : {16, 64}) {
-        const size_t m = multi_bytes(nn, (ss + sb - 1) / sb, sb, true);
-        multi = m > multi ? m : multi;
-    }
-    multi += chunk_bytes(nn, nnz, (ss + 15) / 16);
-    size_t single = geo::align_up((size_t)nn * sizeof(double)) + 256;
-    return (multi > single ? multi : single) + 1024;
+    size_t bytes = geo::align_up((size_t)nn * sizeof(double)) + 256;          // geo_sssp_single_update: d[n], 4 flags
+    MultiBufs b;
+    for (int sb : {16, 64}) bytes = std::max(bytes, lay_out(make_plan(nn, ss, sb), nn, nnz, true, nullptr, b));
+    return bytes;
 }
 
+namespace {
+
+// One geo_sssp_multi call: the caller's arguments, the plan and its buffers, and the order the sources are solved in.
+struct MultiCall {
+    const int32_t *indptr, *indices;
+    const float *weights;
+    int32_t n;
+    int64_t nnz;
+    const int32_t *sources;
+    int32_t n_sources;
+    float *D_out;
+    int32_t *P_out;
+    float *dmin_out;
+    int32_t *argmin_out;
+    hipStream_t stream;
+    const geo::Options &opt;
+    MultiPlan plan;
+    MultiBufs buf;
+    int64_t n_chunks;
+    std::vector<int32_t> host_sources, order;        // order[i]: the caller's row solved in slot i
+    bool grouped;                                    // the order puts neighbouring sources into one batch
+};
+
+// Plan `c.plan`'s buffers from the caller's workspace.
+int carve(MultiCall &c, void *ws, size_t ws_bytes) {
+    const size_t need = lay_out(c.plan, c.n, c.nnz, c.P_out != nullptr, nullptr, c.buf);
+    if (ws_bytes < need) {
+        geo::set_error("geo_sssp_multi: workspace %zu < %zu", ws_bytes, need);
+        return GEO_E_WORKSPACE;
+    }
+    lay_out(c.plan, c.n, c.nnz, c.P_out != nullptr, ws, c.buf);
+    return GEO_OK;
+}
+
+// The 16-edge chunks of the CSR rows (chunk_node, chunk_start; chunk_off[v]: first chunk of row v).
+int build_chunk_index(MultiCall &c) {
+    const MultiBufs &b = c.buf;
+    const int grid = geo::grid_for(c.n, 256, 2048);
+    chunk_count_kernel<<<grid, 256, 0, c.stream>>>(c.indptr, c.n, b.chunk_cnt);
+    GEO_LAUNCH_CHECK();
+    if (int rc = geo::exclusive_scan_i32(b.chunk_cnt, b.chunk_off, c.n, b.scan_tmp, b.scan_bytes, &c.n_chunks, c.stream)) return rc;
+    GEO_REQUIRE((size_t)c.n_chunks <= b.max_chunks, "geo_sssp_multi: nnz=%lld does not match the graph", (long long)c.nnz);
+    chunk_fill_kernel<<<grid, 256, 0, c.stream>>>(c.indptr, c.n, b.chunk_off, b.chunk_node, b.chunk_start);
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// The caller's sources on the host, checked; the solve starts in the caller's order.
+int fetch_sources(MultiCall &c) {
+    c.host_sources.resize(c.n_sources);
+    GEO_HIP_CHECK(hipMemcpyAsync(c.host_sources.data(), c.sources, (size_t)c.n_sources * 4, hipMemcpyDeviceToHost, c.stream));
+    GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+    for (int32_t i = 0; i < c.n_sources; ++i)
+        GEO_REQUIRE(c.host_sources[i] >= 0 && c.host_sources[i] < c.n, "geo_sssp_multi: sources[%d] = %d is outside 0..%d", i,
+                    c.host_sources[i], c.n - 1);
+    return GEO_OK;
+}
+
+void identity_order(MultiCall &c) {
+    c.order.resize(c.n_sources);
+    for (int32_t i = 0; i < c.n_sources; ++i) c.order[i] = i;
+    c.grouped = false;
+}
+
+// ---- ordering the sources so that a batch holds neighbouring ones --------------------------------------------------------
+// Sources that lie close together are relaxed together: a row is evaluated whenever ANY of its batch's 16
+// sources moved a neighbour, so with 16 scattered sources every row is re-evaluated as each of 16 fronts
+// passes (and their corrections cascade), with 16 neighbouring sources the fronts pass as one.  On graphs
+// with short geodesics (a few sweeps) this does not matter; when the first sweeps reach only a small part
+// of the graph the solve restarts with the sources ordered by one of the three strategies below.  Results do not
+// depend on the grouping.
+
+// Sort key of a source: the Morton code of two 16-bit landmark coordinates, then the caller's row.
+uint64_t morton_key(uint32_t qa, uint32_t qb, int32_t row) {
+    uint64_t m = 0;
+    for (int bit = 15; bit >= 0; --bit) m = (m << 2) | (uint64_t)(((qa >> bit) & 1u) << 1) | ((qb >> bit) & 1u);
+    return (m << 32) | (uint32_t)row;
+}
+
+void order_by_keys(std::vector<uint64_t> &key, std::vector<int32_t> &order) {
+    std::sort(key.begin(), key.end());
+    for (size_t i = 0; i < key.size(); ++i) order[i] = (int32_t)(key[i] & 0xffffffffu);
+}
+
+// Breadth-first levels from the seeded nodes: one launch per level, `group` levels per host check, the group's last level
+// decides (lm_flags[0]).  `clear_first`: the flag is also cleared ahead of the group.
+int bfs_levels(const MultiCall &c, int32_t *label, int32_t *level_of, int group, bool clear_first) {
+    int32_t *changed = c.buf.lm_flags;
+    int32_t level = 1, hchanged = 1;
+    while (hchanged && level < c.n + 2) {
+        if (clear_first) GEO_HIP_CHECK(hipMemsetAsync(changed, 0, sizeof(int32_t), c.stream));
+        for (int g = 0; g < group; ++g, ++level) {
+            if (g == group - 1) GEO_HIP_CHECK(hipMemsetAsync(changed, 0, sizeof(int32_t), c.stream));
+            cell_grow_kernel<<<geo::grid_for(c.n, 256, 2048), 256, 0, c.stream>>>(c.indptr, c.indices, c.n, label, level_of, level, changed);
+        }
+        GEO_LAUNCH_CHECK();
+        GEO_HIP_CHECK(hipMemcpyAsync(&hchanged, changed, sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+        GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+    }
+    return GEO_OK;
+}
+
+// (a) by the cells of the graph (`sssp_order=1`, experiment): multi-source BFS by hops gives every node the source it is
+//     nearest to; two sources are adjacent when an edge joins their cells; sources are taken in BFS order over that K-node
+//     quotient graph (host).  ~20 launches over the graph and one K x K bitmap: 0.3 ms at 60 000 nodes / 512 sources,
+//     against 5.8 ms for the two exact single-source solves of (b) on the swiss bench graph (288 sweeps each) -- but the
+//     batches it forms are worse: the push solve then takes 36.9 ms instead of 20.5 ms (measured), so (b) is the default.
+int order_by_cells(const MultiCall &c, std::vector<int32_t> &order) {
+    const MultiBufs &b = c.buf;
+    const int32_t n = c.n, n_sources = c.n_sources;
+    int32_t *label = reinterpret_cast<int32_t *>(b.lm_d), *level_of = label + n;
+    const int32_t wordsK = (n_sources + 31) / 32;
+    GEO_HIP_CHECK(hipMemsetAsync(label, 0xff, 2 * (size_t)n * sizeof(int32_t), c.stream));    // -1 everywhere
+    GEO_HIP_CHECK(hipMemsetAsync(b.cell_adj, 0, (size_t)n_sources * wordsK * 4, c.stream));
+    cell_seed_kernel<<<geo::grid_for(n_sources, 256, 64), 256, 0, c.stream>>>(c.sources, n_sources, n, label, level_of, nullptr);
+    GEO_LAUNCH_CHECK();
+    if (int rc = bfs_levels(c, label, level_of, 8, true)) return rc;
+    cell_adjacency_kernel<<<geo::grid_for(n, 256, 2048), 256, 0, c.stream>>>(c.indptr, c.indices, n, label, wordsK, b.cell_adj);
+    GEO_LAUNCH_CHECK();
+    std::vector<uint32_t> adj((size_t)n_sources * wordsK);
+    std::vector<int32_t> cell(n_sources);
+    gather_i32_kernel<<<geo::grid_for(n_sources, 256, 64), 256, 0, c.stream>>>(label, c.sources, n_sources, reinterpret_cast<int32_t *>(b.lm_key));
+    GEO_HIP_CHECK(hipMemcpyAsync(adj.data(), b.cell_adj, adj.size() * 4, hipMemcpyDeviceToHost, c.stream));
+    GEO_HIP_CHECK(hipMemcpyAsync(cell.data(), b.lm_key, (size_t)n_sources * 4, hipMemcpyDeviceToHost, c.stream));
+    GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+    // BFS over the quotient graph from the cell of sources[0]; unreached cells (other components) start new searches
+    std::vector<int32_t> rank(n_sources, -1), queue;
+    queue.reserve(n_sources);
+    int32_t next_rank = 0;
+    auto search = [&](int32_t start) {
+        size_t head = queue.size();
+        queue.push_back(start);
+        rank[start] = next_rank++;
+        while (head < queue.size()) {
+            const uint32_t *row = adj.data() + (size_t)queue[head++] * wordsK;
+            for (int32_t wi = 0; wi < wordsK; ++wi) {
+                uint32_t bits = row[wi];
+                while (bits) {
+                    const int32_t d = wi * 32 + __builtin_ctz(bits);
+                    bits &= bits - 1;
+                    if (d < n_sources && rank[d] < 0) { rank[d] = next_rank++; queue.push_back(d); }
+                }
+            }
+        }
+    };
+    search(cell[0] >= 0 ? cell[0] : 0);
+    for (int32_t i = 0; i < n_sources; ++i) {
+        const int32_t ci = cell[i] >= 0 ? cell[i] : i;
+        if (rank[ci] < 0) search(ci);
+    }
+    std::vector<uint64_t> key(n_sources);
+    for (int32_t i = 0; i < n_sources; ++i) key[i] = ((uint64_t)(uint32_t)rank[cell[i] >= 0 ? cell[i] : i] << 32) | (uint32_t)i;
+    order_by_keys(key, order);
+    return GEO_OK;
+}
+
+// (c) along two landmark HOP counts (`sssp_order=2`): the Morton order of (b) needs two smooth coordinates on the graph,
+//     not exact distances; breadth-first levels from sources[0] and from the source farthest from it (in hops) cost one
+//     cheap launch per level instead of one full relaxation sweep per hop of an exact solve.
+int order_by_hops(const MultiCall &c, std::vector<int32_t> &order) {
+    const MultiBufs &b = c.buf;
+    const int32_t n = c.n, n_sources = c.n_sources;
+    int32_t *label = reinterpret_cast<int32_t *>(b.lm_d), *level_of = label + n;
+    std::vector<int32_t> ka(n_sources), kb(n_sources);
+    auto hops_from = [&](int32_t seed_pos, std::vector<int32_t> &out) -> int {
+        GEO_HIP_CHECK(hipMemsetAsync(label, 0xff, 2 * (size_t)n * sizeof(int32_t), c.stream));
+        cell_seed_kernel<<<1, 64, 0, c.stream>>>(c.sources + seed_pos, 1, n, label, level_of, nullptr);
+        GEO_LAUNCH_CHECK();
+        if (int rc = bfs_levels(c, label, level_of, 16, false)) return rc;
+        gather_i32_kernel<<<geo::grid_for(n_sources, 256, 64), 256, 0, c.stream>>>(level_of, c.sources, n_sources, reinterpret_cast<int32_t *>(b.lm_key));
+        GEO_HIP_CHECK(hipMemcpyAsync(out.data(), b.lm_key, (size_t)n_sources * 4, hipMemcpyDeviceToHost, c.stream));
+        GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+        return GEO_OK;
+    };
+    if (int rc = hops_from(0, ka)) return rc;
+    int32_t far = 0, amax = 0;
+    for (int32_t i = 0; i < n_sources; ++i)
+        if (ka[i] > amax) { amax = ka[i]; far = i; }
+    if (int rc = hops_from(far, kb)) return rc;
+    int32_t bmax = 0;
+    for (int32_t i = 0; i < n_sources; ++i) bmax = std::max(bmax, kb[i]);
+    std::vector<uint64_t> key(n_sources);
+    for (int32_t i = 0; i < n_sources; ++i) {
+        // sources the landmarks cannot reach (other components: level -1) sort last
+        const uint32_t qa = ka[i] >= 0 && amax > 0 ? (uint32_t)(65535.0 * ka[i] / amax) : 65535u;
+        const uint32_t qb = kb[i] >= 0 && bmax > 0 ? (uint32_t)(65535.0 * kb[i] / bmax) : 65535u;
+        key[i] = morton_key(qa, qb, i);
+    }
+    order_by_keys(key, order);
+    return GEO_OK;
+}
+
+// (b) along two landmark distances (`sssp_order=0`, the default): Morton order of (dist from sources[0], dist from the source
+//     farthest from it).  Also yields the eccentricity of sources[0] (the farthest node of its component), which tells the
+//     32-bit solve early that it cannot fit.
+int order_by_landmarks(const MultiCall &c, std::vector<int32_t> &order, double *ecc) {
+    const MultiBufs &b = c.buf;
+    const int32_t n = c.n, n_sources = c.n_sources;
+    int32_t lm_sweeps = 0;
+    std::vector<float> ka(n_sources), kb(n_sources);
+    const int gk = geo::grid_for(n_sources, 256, 64);
+    if (int rc = solve_single(c.indptr, c.indices, c.weights, n, c.host_sources[0], b.lm_d, b.lm_flags, 16, c.stream, &lm_sweeps)) return rc;
+    gather_f32_kernel<<<gk, 256, 0, c.stream>>>(b.lm_d, c.sources, n_sources, b.lm_key);
+    unsigned long long *ecc_dev = reinterpret_cast<unsigned long long *>(b.lm_flags + 8), ecc_bits = 0ull;   // (8-byte aligned scratch)
+    GEO_HIP_CHECK(hipMemsetAsync(ecc_dev, 0, sizeof(unsigned long long), c.stream));
+    max_finite_kernel<<<geo::grid_for(n, 256, 1024), 256, 0, c.stream>>>(b.lm_d, n, ecc_dev);
+    GEO_HIP_CHECK(hipMemcpyAsync(&ecc_bits, ecc_dev, sizeof(ecc_bits), hipMemcpyDeviceToHost, c.stream));
+    GEO_HIP_CHECK(hipMemcpyAsync(ka.data(), b.lm_key, (size_t)n_sources * 4, hipMemcpyDeviceToHost, c.stream));
+    GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+    memcpy(ecc, &ecc_bits, sizeof(*ecc));
+    int32_t far = 0;
+    float amax = 0.f;
+    for (int32_t i = 0; i < n_sources; ++i)
+        if (std::isfinite(ka[i]) && ka[i] > amax) { amax = ka[i]; far = i; }
+    if (int rc = solve_single(c.indptr, c.indices, c.weights, n, c.host_sources[far], b.lm_d, b.lm_flags, 16, c.stream, &lm_sweeps)) return rc;
+    gather_f32_kernel<<<gk, 256, 0, c.stream>>>(b.lm_d, c.sources, n_sources, b.lm_key);
+    GEO_HIP_CHECK(hipMemcpyAsync(kb.data(), b.lm_key, (size_t)n_sources * 4, hipMemcpyDeviceToHost, c.stream));
+    GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+    float bmax = 0.f;
+    for (int32_t i = 0; i < n_sources; ++i)
+        if (std::isfinite(kb[i]) && kb[i] > bmax) bmax = kb[i];
+    std::vector<uint64_t> key(n_sources);
+    for (int32_t i = 0; i < n_sources; ++i) {
+        // sources the landmarks cannot reach (other components) sort last
+        const uint32_t qa = std::isfinite(ka[i]) && amax > 0.f ? (uint32_t)(65535.0f * ka[i] / amax) : 65535u;
+        const uint32_t qb = std::isfinite(kb[i]) && bmax > 0.f ? (uint32_t)(65535.0f * kb[i] / bmax) : 65535u;
+        key[i] = morton_key(qa, qb, i);
+    }
+    order_by_keys(key, order);
+    return GEO_OK;
+}
+
+// Orders the sources by the strategy `sssp_order` names; *ecc: the eccentricity of sources[0] where the strategy finds it, else 0.
+int regroup_sources(MultiCall &c, double *ecc) {
+    *ecc = 0.0;
+    int rc;
+    if (c.opt.sssp_order == 2) rc = order_by_hops(c, c.order);
+    else if (c.opt.sssp_order == 1 && c.n_sources <= CELL_ORDER_MAX_SOURCES) rc = order_by_cells(c, c.order);
+    else rc = order_by_landmarks(c, c.order, ecc);
+    if (rc == GEO_OK) c.grouped = true;
+    return rc;
+}
+
+// ---- what the solves share ------------------------------------------------------------------------------------------
+// The sources into `slots` slots in the current order (-1 = no source in this slot), and a cleared flag ring.
+int upload_sources(const MultiCall &c, size_t slots) {
+    std::vector<int32_t> hsrc(slots, -1), hrow(slots, -1);
+    for (int32_t i = 0; i < c.n_sources; ++i) { hsrc[i] = c.host_sources[c.order[i]]; hrow[i] = c.order[i]; }
+    GEO_HIP_CHECK(hipMemcpyAsync(c.buf.src_pad, hsrc.data(), slots * 4, hipMemcpyHostToDevice, c.stream));
+    GEO_HIP_CHECK(hipMemcpyAsync(c.buf.row_of, hrow.data(), slots * 4, hipMemcpyHostToDevice, c.stream));
+    GEO_HIP_CHECK(hipMemsetAsync(c.buf.flags, 0, 3 * (size_t)c.plan.cs * sizeof(int32_t), c.stream));
+    return GEO_OK;
+}
+
+// Need-map and count rings of a chunked solve over `nbx` batches of `width` sources: empty, then the sources' neighbours flagged.
+int reset_need_map(const MultiCall &c, int32_t nbx, int width) {
+    const MultiBufs &b = c.buf;
+    GEO_HIP_CHECK(hipMemsetAsync(b.counts, 0, 4 * (size_t)c.plan.cs * 4, c.stream));
+    GEO_HIP_CHECK(hipMemsetAsync(b.bits, 0, 3 * (size_t)nbx * b.words * 4, c.stream));
+    source_need_kernel<<<geo::grid_for((int64_t)c.n_sources * 16, 256, 256), 256, 0, c.stream>>>(
+        b.src_pad, c.n_sources, c.n, width, b.words, c.indptr, c.indices, b.bits + 2 * (size_t)nbx * b.words);
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// After the first sweeps: did little of the (node, source) matrix move in the last two (`hc`: their sampled counts)?  Long
+// geodesics -- the solve wants its sources ordered.  `sssp_group`: 2 always.
+bool wants_order(const MultiCall &c, const std::vector<int32_t> &hc, int32_t nbx, int width) {
+    double moved = 0.0;
+    for (int32_t b = 0; b < 2 * nbx; ++b) moved += 16.0 * (hc[b] < 0 ? -hc[b] : hc[b]);
+    return c.opt.sssp_group == 2 || moved < 0.25 * (double)nbx * c.n * width;
+}
+
+// Grid and body switches of a chunked solve over `nbx` batches.
+struct ChunkSweep {
+    int gs, groups;     // batches per group of blocks, groups
+    int cap_all, cap;   // blocks per batch: capped so that one sweep stays <= ~64k blocks; grouped solves run many sweeps that
+                        // touch few rows -- a smaller grid keeps the idle launches cheap ...
+    int sdiv, mdiv;     // sparse body while fewer than n/sdiv rows moved in the previous sweep; map kept below n/mdiv
+                        // (... and grouped solves stay with the flagged-row body whenever the need-map is there)
+};
+ChunkSweep chunk_sweep(const MultiCall &c, int32_t nbx) {
+    const geo::Options &o = c.opt;
+    ChunkSweep s;
+    s.gs = nbx < 8 ? nbx : 8;
+    s.groups = (nbx + s.gs - 1) / s.gs;
+    s.cap_all = 65536 / (s.gs * s.groups);
+    s.cap = (c.grouped && s.cap_all > o.sssp_grouped_cap) ? o.sssp_grouped_cap : s.cap_all;
+    s.sdiv = o.sssp_sparse_div > 0 ? o.sssp_sparse_div : (c.grouped ? 1 : 8);
+    s.mdiv = o.sssp_map_div > 0 ? o.sssp_map_div : (c.grouped ? 1 : 2);
+    return s;
+}
+
+// `sssp_trace` (experiment): sampled improvement counts of sweep `sweep` of a chunked solve
+int trace_counts(const MultiCall &c, const char *tag, int32_t sweep, int32_t nbx, int width) {
+    std::vector<int32_t> tc(nbx);
+    GEO_HIP_CHECK(hipMemcpy(tc.data(), c.buf.counts + (size_t)(sweep % 4) * c.plan.cs, (size_t)nbx * 4, hipMemcpyDeviceToHost));
+    long long tot = 0, neg = 0;
+    for (int32_t b = 0; b < nbx; ++b) { tot += tc[b] < 0 ? -tc[b] : tc[b]; neg += tc[b] < 0; }
+    fprintf(stderr, "[%s] sweep %d: ~%lld improved pairs (%.1f%% of pairs), %lld/%d batches without map\n", tag, sweep, tot * 16,
+            100.0 * tot * 16 / ((double)nbx * c.n * width), neg, nbx);
+    return GEO_OK;
+}
+
+// `group_len` sweeps between two events (enqueue(sweep) launches one), then read_back(sweeps so far) queues the copies the host
+// decides on; synchronises and adds the group's device time to g_last_sweep_ms.
+template <typename Enqueue, typename ReadBack>
+int run_sweep_group(hipStream_t stream, int group_len, int32_t &sweeps, Enqueue &&enqueue, ReadBack &&read_back) {
+    GEO_HIP_CHECK(hipEventRecord(g_ev0, stream));
+    for (int g = 0; g < group_len; ++g, ++sweeps)
+        if (int rc = enqueue(sweeps)) return rc;
+    GEO_HIP_CHECK(hipEventRecord(g_ev1, stream));
+    if (int rc = read_back(sweeps)) return rc;
+    GEO_HIP_CHECK(hipStreamSynchronize(stream));
+    float ms = 0.f;
+    GEO_HIP_CHECK(hipEventElapsedTime(&ms, g_ev0, g_ev1));
+    g_last_sweep_ms += ms;
+    return GEO_OK;
+}
+
+// Flags of the last sweep and the counts of the last two (4-slot ring; `sweeps` already counts them) of a chunked solve.
+int read_flags_and_counts(const MultiCall &c, int32_t sweeps, int32_t nbx, int32_t *hflags, int32_t *hcounts) {
+    const MultiBufs &b = c.buf;
+    const size_t cs = (size_t)c.plan.cs, bytes = (size_t)nbx * sizeof(int32_t);
+    GEO_HIP_CHECK(hipMemcpyAsync(hflags, b.flags + (size_t)((sweeps + 2) % 3) * cs, bytes, hipMemcpyDeviceToHost, c.stream));
+    if (!hcounts) return GEO_OK;
+    GEO_HIP_CHECK(hipMemcpyAsync(hcounts, b.counts + (size_t)((sweeps + 3) % 4) * cs, bytes, hipMemcpyDeviceToHost, c.stream));
+    GEO_HIP_CHECK(hipMemcpyAsync(hcounts + nbx, b.counts + (size_t)((sweeps + 2) % 4) * cs, bytes, hipMemcpyDeviceToHost, c.stream));
+    return GEO_OK;
+}
+
+bool all_zero(const std::vector<int32_t> &flags) {
+    for (int32_t f : flags)
+        if (f) return false;
+    return true;
+}
+
+// ---- exact 32-bit fixed-point solve (32 sources per row) when the weights qualify; see sweep_chunk32u_kernel ------------
+// Do the weights fit?  Normal numbers spanning < 2^28 units of 2^-shift each.
+int fixed_point_units(const MultiCall &c, bool *eligible, int *shift) {
+    *eligible = true;
+    *shift = 0;
+    if (!c.weights) return GEO_OK;
+    const uint32_t init[4] = {0xffffffffu, 0u, 0u, 0u};
+    uint32_t got[4];
+    GEO_HIP_CHECK(hipMemcpyAsync(c.buf.wrange, init, sizeof(init), hipMemcpyHostToDevice, c.stream));
+    weight_range_kernel<<<geo::grid_for(c.nnz, 256 * 16, 512), 256, 0, c.stream>>>(c.weights, c.nnz, c.buf.wrange);
+    GEO_LAUNCH_CHECK();
+    GEO_HIP_CHECK(hipMemcpyAsync(got, c.buf.wrange, sizeof(got), hipMemcpyDeviceToHost, c.stream));
+    GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+    if (got[2]) *eligible = false;                                   // negative, NaN or infinite weight
+    else if (got[0] != 0xffffffffu) {                                // some positive weight
+        const int e_min = (int)(got[0] >> 23) - 127, e_max = (int)(got[1] >> 23) - 127;
+        *eligible = (got[0] >> 23) != 0 && 24 + (e_max - e_min) <= 28;
+        *shift = 23 - e_min;
+    }
+    return GEO_OK;
+}
+
+enum class FixedResult { done, declined, declined_ordered };   // declined_ordered: c.order is ordered, c.grouped set
+
+// done: dist holds uint32 distances in units of *unit, *sweeps_out sweeps ran.  declined: the weights do not qualify, a distance
+// overflowed or the sweep limit passed.  A long-geodesics graph restarts ONCE with the sources ordered (as the fp64 solve
+// does): the fixed-point kernel then sweeps rows of 32 neighbouring sources.
+int solve_fixed_point(MultiCall &c, FixedResult *result, int32_t *sweeps_out, double *unit) {
+    *result = FixedResult::declined;
+    bool eligible;
+    int shift;
+    if (int rc = fixed_point_units(c, &eligible, &shift)) return rc;
+    if (!eligible) return GEO_OK;
+    const MultiBufs &b = c.buf;
+    const geo::Options &opt = c.opt;
+    const int32_t n = c.n, nb32 = (c.n_sources + 31) / 32, words = b.words, cs = c.plan.cs;
+    *unit = std::ldexp(1.0, -shift);
+    uint32_t *dist32 = reinterpret_cast<uint32_t *>(b.dist);
+    weight_units_kernel<<<geo::grid_for(c.nnz, 256, 2048), 256, 0, c.stream>>>(c.weights, c.nnz, shift, b.wunits);
+    row_order_kernel<<<1, 1024, 0, c.stream>>>(b.chunk_cnt, n, b.row_order);
+    GEO_LAUNCH_CHECK();
+    std::vector<int32_t> hf(nb32), hc(2 * (size_t)nb32);
+    int32_t sweeps = 0, sweeps_before = 0;
+    bool done = false, give_up = false;
+    for (int att32 = 0; att32 < 2 && !done && !give_up; ++att32) {
+        bool restart = false;
+        sweeps_before += sweeps;
+        sweeps = 0;
+        if (int rc = upload_sources(c, (size_t)nb32 * 32)) return rc;
+        init_multi32_kernel<<<geo::grid_for((int64_t)nb32 * n * 32, 256 * 8), 256, 0, c.stream>>>(dist32, b.src_pad, n, nb32);
+        if (int rc = reset_need_map(c, nb32, 32)) return rc;
+        const ChunkSweep s = chunk_sweep(c, nb32);
+        const int per_batch = geo::grid_for(n, 8, s.cap > 0 ? s.cap : 1);     // 8 row slots per block
+        const unsigned grid = (unsigned)per_batch * (unsigned)s.gs * (unsigned)s.groups;
+        auto enqueue = [&](int32_t sw) -> int {
+            const int cur = sw % 3, prev = (sw + 2) % 3, next = (sw + 1) % 3;
+            uint32_t *bcur = b.bits + (size_t)cur * nb32 * words, *bprev = b.bits + (size_t)prev * nb32 * words;
+            if (sw > 0) GEO_HIP_CHECK(hipMemsetAsync(bcur, 0, (size_t)nb32 * words * 4, c.stream));
+            sweep_chunk32u_kernel<<<grid, 256, 0, c.stream>>>(c.indptr, c.indices, b.wunits, n, nb32, b.row_order, per_batch, s.gs,
+                                                              dist32, b.flags, b.counts, bprev, bcur, words, prev, cur, next, sw == 0,
+                                                              opt.sssp_act, s.sdiv, s.mdiv, (sw + 2) % 4, (sw + 3) % 4, sw % 4,
+                                                              (sw + 1) % 4, cs);
+            GEO_LAUNCH_CHECK();
+            return opt.sssp_trace ? trace_counts(c, "sssp-u32", sw, nb32, 32) : GEO_OK;
+        };
+        auto read_back = [&](int32_t sw) { return read_flags_and_counts(c, sw, nb32, hf.data(), hc.data()); };
+        int group_len = SWEEP_GROUP;
+        while (!done && !give_up && !restart) {
+            if (int rc = run_sweep_group(c.stream, group_len, sweeps, enqueue, read_back)) return rc;
+            done = all_zero(hf);
+            if (!done && att32 == 0 && !c.grouped && sweeps == SWEEP_GROUP && opt.sssp_group != 0 && wants_order(c, hc, nb32, 32)) {
+                double landmark_ecc;
+                if (int rc = regroup_sources(c, &landmark_ecc)) return rc;
+                restart = true;
+                // some node is landmark_ecc away from sources[0]: if that alone does not fit 32 bits of units the
+                // fixed-point solve would only find out at its end -- the fp64 kernels take the (ordered) sources now
+                if (landmark_ecc / *unit >= 4294967294.0) give_up = true;
+                // ordered by cells or hops (no eccentricity known), or `sssp_push=3`: long geodesics go to the near-far push
+                // solve, which is at least as fast as the ordered fixed-point sweeps and cannot overflow
+                if (opt.sssp_push != 0 && (opt.sssp_order != 0 || opt.sssp_push == 3)) give_up = true;
+            }
+            if (!done && sweeps > (int64_t)n + 2) give_up = true;
+            if (sweeps >= 16 && group_len < 16) group_len *= 2;
+        }
+    }
+    *sweeps_out = sweeps + sweeps_before;
+    int32_t ovf = 0;
+    if (done) {
+        GEO_HIP_CHECK(hipMemsetAsync(b.flags, 0, sizeof(int32_t), c.stream));
+        overflow_scan_kernel<<<geo::grid_for((int64_t)nb32 * n * 32, 256, 2048), 256, 0, c.stream>>>(dist32, (int64_t)nb32 * n * 32, b.flags);
+        GEO_HIP_CHECK(hipMemcpyAsync(&ovf, b.flags, sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+        GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+    }
+    *result = done && !ovf ? FixedResult::done : c.grouped ? FixedResult::declined_ordered : FixedResult::declined;
+    return GEO_OK;
+}
+
+// ---- long geodesics: near-far push solve (see push_sweep_kernel) -------------------------------------------------------
+int solve_push(const MultiCall &c, int32_t *sweeps_out) {
+    const MultiBufs &b = c.buf;
+    const PushState &push = b.push;
+    const geo::Options &opt = c.opt;
+    const int32_t n = c.n, nb = c.plan.nb, cs = c.plan.cs;
+    double mean_w = 1.0;
+    if (c.weights && c.nnz > 0) {
+        GEO_HIP_CHECK(hipMemsetAsync(b.wsum, 0, sizeof(double), c.stream));
+        weight_sum_kernel<<<geo::grid_for(c.nnz, 256, 1024), 256, 0, c.stream>>>(c.weights, c.nnz, b.wsum);
+        GEO_HIP_CHECK(hipMemcpyAsync(&mean_w, b.wsum, sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+        mean_w /= (double)c.nnz;
+    }
+    const double delta = (opt.sssp_delta > 0 ? (double)opt.sssp_delta : 4.0) * (mean_w > 0.0 ? mean_w : 1.0);
+    GEO_HIP_CHECK(hipMemsetAsync(push.near_bits, 0, 2 * (size_t)nb * push.words * 4, c.stream));
+    GEO_HIP_CHECK(hipMemsetAsync(push.far_bits, 0, (size_t)nb * push.words * 4, c.stream));
+    push_init_kernel<<<nb, 256, 0, c.stream>>>(b.src_pad, n, nb, push, delta);
+    GEO_LAUNCH_CHECK();
+    const int64_t limit = 64 * (int64_t)n + 64;
+    const int bpb = opt.sssp_push_blocks > 0 ? opt.sssp_push_blocks : 64;
+    const unsigned grid = (unsigned)(((nb + 7) / 8) * 8) * (unsigned)bpb;        // batch <-> XCD: see push_sweep_kernel
+    auto enqueue = [&](int32_t sw) -> int {
+        if (c.weights) push_sweep_kernel<true><<<grid, 256, 0, c.stream>>>(c.indptr, c.indices, c.weights, n, nb, bpb, b.dist, push, delta, sw);
+        else push_sweep_kernel<false><<<grid, 256, 0, c.stream>>>(c.indptr, c.indices, c.weights, n, nb, bpb, b.dist, push, delta, sw);
+        GEO_LAUNCH_CHECK();
+        if (opt.sssp_trace) {
+            std::vector<int32_t> hn(cs), hfc(3 * (size_t)cs);
+            GEO_HIP_CHECK(hipMemcpy(hn.data(), push.near_cnt + (size_t)((sw + 1) % 3) * cs, (size_t)cs * 4, hipMemcpyDeviceToHost));
+            GEO_HIP_CHECK(hipMemcpy(hfc.data(), push.far_cnt, 3 * (size_t)cs * 4, hipMemcpyDeviceToHost));
+            long long tn = 0, tf = 0, idle = 0;
+            for (int32_t i = 0; i < nb; ++i) {
+                const long long f = std::max(hfc[i], std::max(hfc[cs + i], hfc[2 * cs + i]));
+                tn += hn[i]; tf += f; idle += (hn[i] == 0 && f == 0);
+            }
+            fprintf(stderr, "[sssp-push] sweep %d: next near %lld, far pile <= %lld, idle batches %lld/%d\n", sw, tn, tf, idle, nb);
+        }
+        return GEO_OK;
+    };
+    int32_t sweeps = 0, hact = 1;
+    auto read_back = [&](int32_t sw) -> int {
+        GEO_HIP_CHECK(hipMemcpyAsync(&hact, push.active + (sw + 2) % 3, sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+        return GEO_OK;
+    };
+    int group_len = 8;
+    while (hact) {
+        if (int rc = run_sweep_group(c.stream, group_len, sweeps, enqueue, read_back)) return rc;
+        if (hact && sweeps > limit) {
+            geo::set_error("geo_sssp_multi: near-far solve did not finish within %d sweeps", sweeps);
+            return GEO_E_NOCONV;
+        }
+        if (sweeps >= 32 && group_len < 32) group_len *= 2;
+    }
+    *sweeps_out = sweeps;
+    return GEO_OK;
+}
+
+// ---- fp64 sweeps over the plan's layout ---------------------------------------------------------------------------------
+enum class SweepResult { done, wants_regroup };
+
+// wants_regroup (only when `may_regroup`, after the first group of a chunked solve in the caller's order): few pairs moved.
+int solve_sweeps(const MultiCall &c, bool may_regroup, SweepResult *result, int32_t *sweeps_out) {
+    const MultiBufs &b = c.buf;
+    const geo::Options &opt = c.opt;
+    const int32_t n = c.n, nb = c.plan.nb, sb = c.plan.sb, cs = c.plan.cs, words = b.words;
+    const bool chunked = c.plan.chunked;
+    const ChunkSweep s = chunk_sweep(c, nb);
+    const int nodes_per_block = (64 / sb) * WAVES_PER_BLOCK;
+    const int per_batch = chunked ? geo::grid_for(c.n_chunks, 16, s.cap > 0 ? s.cap : 1)
+                                  : geo::grid_for(n, nodes_per_block, s.cap_all > 0 ? s.cap_all : 1);
+    const unsigned grid = (unsigned)per_batch * (unsigned)s.gs * (unsigned)s.groups;
+    auto enqueue = [&](int32_t sw) -> int {
+        const int cur = sw % 3, prev = (sw + 2) % 3, next = (sw + 1) % 3;
+#define GEO_SWEEP(SBT, WT)                                                                                                \
+    sweep_multi_kernel<SBT, WT><<<grid, 256, 0, c.stream>>>(c.indptr, c.indices, c.weights, n, nb, per_batch, s.gs, b.dist, \
+                                                            b.flags, prev, cur, next, sw == 0, cs)
+#define GEO_SWEEP_CHUNK(WT)                                                                                                \
+    sweep_chunk16_kernel<WT><<<grid, 256, 0, c.stream>>>(c.indptr, c.indices, c.weights, n, nb, b.chunk_node, b.chunk_start, \
+                                                         (int32_t)c.n_chunks, per_batch, s.gs, b.dist, b.flags, b.counts, bprev, \
+                                                         bcur, words, prev, cur, next, sw == 0, opt.sssp_act, s.sdiv, s.mdiv,   \
+                                                         (sw + 2) % 4, (sw + 3) % 4, sw % 4, (sw + 1) % 4, cs)
+        if (chunked) {
+            uint32_t *bcur = b.bits + (size_t)cur * nb * words, *bprev = b.bits + (size_t)prev * nb * words;
+            if (sw > 0) GEO_HIP_CHECK(hipMemsetAsync(bcur, 0, (size_t)nb * words * 4, c.stream));
+            if (c.weights) GEO_SWEEP_CHUNK(true); else GEO_SWEEP_CHUNK(false);
+        } else if (sb == 64) { if (c.weights) GEO_SWEEP(64, true); else GEO_SWEEP(64, false); }
+        else                 { if (c.weights) GEO_SWEEP(16, true); else GEO_SWEEP(16, false); }
+#undef GEO_SWEEP_CHUNK
+#undef GEO_SWEEP
+        GEO_LAUNCH_CHECK();
+        return chunked && opt.sssp_trace ? trace_counts(c, "sssp", sw, nb, 16) : GEO_OK;
+    };
+    std::vector<int32_t> hflags(nb), hcounts(2 * (size_t)nb);
+    auto read_back = [&](int32_t sw) { return read_flags_and_counts(c, sw, nb, hflags.data(), chunked ? hcounts.data() : nullptr); };
+    int32_t sweeps = 0;
+    int group_len = SWEEP_GROUP;
+    *result = SweepResult::wants_regroup;
+    for (bool done = false, regroup = false; !done && !regroup;) {
+        if (int rc = run_sweep_group(c.stream, group_len, sweeps, enqueue, read_back)) return rc;
+        done = all_zero(hflags);
+        if (!done && sweeps > (int64_t)n + 2) {
+            geo::set_error("geo_sssp_multi: no fixed point after %d sweeps", sweeps);
+            return GEO_E_NOCONV;
+        }
+        if (!done && may_regroup && chunked && !c.grouped && opt.sssp_group != 0 && sweeps == SWEEP_GROUP)
+            regroup = wants_order(c, hcounts, nb, 16);
+        if (sweeps >= 16 && group_len < 16) group_len *= 2;      // long solves: fewer host round trips
+        if (done) *result = SweepResult::done;
+    }
+    *sweeps_out = sweeps;
+    return GEO_OK;
+}
+
+// ---- outputs: dist[b][v][s] -> D[row][v] (f32), predecessors, column minimum and the first row attaining it ------------
+int write_outputs_fixed(const MultiCall &c, double unit) {
+    const MultiBufs &b = c.buf;
+    const int32_t n = c.n, nb32 = (c.n_sources + 31) / 32;
+    const uint32_t *dist32 = reinterpret_cast<const uint32_t *>(b.dist);
+    const dim3 tg((unsigned)((n + 63) / 64), (unsigned)nb32);
+    if (c.D_out) transpose_out32_kernel<<<tg, 256, 0, c.stream>>>(dist32, c.D_out, n, c.n_sources, unit, b.row_of);
+    if (c.P_out) {
+        pred_multi32_kernel<<<geo::grid_for((int64_t)nb32 * n * 32, 256, 8192), 256, 0, c.stream>>>(
+            c.indptr, c.indices, b.wunits, n, nb32, dist32, b.src_pad, b.pred);
+        transpose_out_kernel<int32_t, int32_t><<<tg, 256, 0, c.stream>>>(b.pred, c.P_out, n, c.n_sources, 32, b.row_of);
+    }
+    if (c.dmin_out || c.argmin_out)
+        colmin32_kernel<<<(unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), 256, 0, c.stream>>>(
+            dist32, n, c.n_sources, unit, b.row_of, c.dmin_out, c.argmin_out);
+    GEO_LAUNCH_CHECK();
+    GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+    return GEO_OK;
+}
+
+int write_outputs_f64(const MultiCall &c) {
+    const MultiBufs &b = c.buf;
+    const int32_t n = c.n, nb = c.plan.nb, sb = c.plan.sb;
+    const dim3 tg((unsigned)((n + 63) / 64), (unsigned)nb);
+    if (c.D_out) transpose_out_kernel<double, float><<<tg, 256, 0, c.stream>>>(b.dist, c.D_out, n, c.n_sources, sb, b.row_of);
+    if (c.P_out) {
+        const int pg = geo::grid_for((int64_t)nb * n * sb, 256, 8192);
+        if (c.weights) pred_multi_kernel<true><<<pg, 256, 0, c.stream>>>(c.indptr, c.indices, c.weights, n, nb, sb, b.dist, b.src_pad, b.pred);
+        else pred_multi_kernel<false><<<pg, 256, 0, c.stream>>>(c.indptr, c.indices, c.weights, n, nb, sb, b.dist, b.src_pad, b.pred);
+        transpose_out_kernel<int32_t, int32_t><<<tg, 256, 0, c.stream>>>(b.pred, c.P_out, n, c.n_sources, sb, b.row_of);
+    }
+    if (c.dmin_out || c.argmin_out)
+        colmin_kernel<<<(unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), 256, 0, c.stream>>>(
+            b.dist, n, c.n_sources, sb, b.row_of, c.dmin_out, c.argmin_out);
+    GEO_LAUNCH_CHECK();
+    GEO_HIP_CHECK(hipStreamSynchronize(c.stream));
+    return GEO_OK;
+}
+
+// What geo_sssp_last_profile reports: layout code, sweeps (= launches of a sweep kernel) of the solve that answered.
+void report(int32_t layout, int32_t sweeps, int32_t *sweeps_out) {
+    if (sweeps_out) *sweeps_out = sweeps;
+    g_last_sweep_launches = sweeps;
+    g_last_layout = layout;
+}
+
+}  // namespace
+
+// The driver: validate; plan; carve; chunk index; the fixed-point solve if planned (done -> outputs; declined -> fp64 in the
+// caller's order, re-planned to 64 per batch where 16 only carried it; declined with the sources ordered -> the same, but a
+// 16-per-batch plan keeps the order); then attempts {upload; push solve for long geodesics, else sweeps; wants regroup -> order
+// the sources, once more}; outputs.
 static int sssp_multi_impl(const int32_t *indptr, const int32_t *indices, const float *weights, int32_t n,
                            int64_t nnz, const int32_t *sources, int32_t n_sources, float *D_out, int32_t *P_out,
                            float *dmin_out, int32_t *argmin_out, void *ws, size_t ws_bytes,
                            int32_t *sweeps_out, void *stream_, int force_sb) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(n > 0 && n_sources > 0, "geo_sssp_multi: n=%d n_sources=%d must be positive", n, n_sources);
     GEO_REQUIRE(indptr && indices && sources && ws, "geo_sssp_multi: null pointer");
-    const int sb = choose_sb(n, n_sources, force_sb);
-    const int32_t nb = (n_sources + sb - 1) / sb;
-    // 16-edge chunk work items (see sweep_chunk16_kernel); their 32-bit row offsets need n * 128 bytes < 2^32
-    const bool chunked = sb == 16 && n_sources > 16 && n < ROW128_MAX_NODES;
     GEO_REQUIRE(nnz >= 0, "geo_sssp_multi: nnz must be given");
-    if (ws_bytes < multi_bytes(n, nb, sb, P_out != nullptr) + (chunked ? chunk_bytes(n, nnz, nb) : 0)) {
-        geo::set_error("geo_sssp_multi: workspace %zu < %zu", ws_bytes,
-                       multi_bytes(n, nb, sb, P_out != nullptr) + (chunked ? chunk_bytes(n, nnz, nb) : 0));
-        return GEO_E_WORKSPACE;
-    }
-    geo::Arena ar(ws, ws_bytes);
-    MultiWs w;
-    const size_t slots = padded_slots(nb, sb);
-    w.dist = ar.take<double>(slots * n);
-    w.pred = P_out ? ar.take<int32_t>(slots * n) : nullptr;
-    // rows of the flag / count rings start on their own 128-byte lines: every block reads the previous sweep's row while
-    // the current sweep's row takes stores and atomics (a shared line made alternate sweeps 3x slower at nb = 16)
-    const int cs = ((nb + 31) / 32) * 32;
-    w.flags = ar.take<int32_t>(3 * (size_t)cs);
-    w.src_pad = ar.take<int32_t>(slots);
-    int32_t *row_of = ar.take<int32_t>(slots);                    // (batch, slot) -> row of the caller's `sources`
-
-    int32_t *chunk_node = nullptr, *chunk_start = nullptr;
-    uint32_t *bits = nullptr;
-    int32_t *counts = nullptr;
-    double *lm_d = nullptr;
-    float *lm_key = nullptr;
-    int32_t *lm_flags = nullptr;
-    uint32_t *wunits = nullptr, *wrange = nullptr;           // 32-bit fixed-point weights / their range
-    int32_t *chunk_cnt = nullptr, *row_order = nullptr;
-    PushState push{};
-    uint32_t *cell_adj = nullptr;
-    double *wsum = nullptr;
-    const geo::Options &opt = geo::options();
-    const int act_mode = opt.sssp_act;
-    // sparse body while fewer than n/sparse_div rows moved in the previous sweep; map kept below n/map_div
-    const int sparse_div = opt.sssp_sparse_div > 0 ? opt.sssp_sparse_div : 8;
-    const int map_div = opt.sssp_map_div > 0 ? opt.sssp_map_div : 2;
-    const int group_mode = opt.sssp_group;                   // 0 never, 1 auto, 2 always
-    const int32_t words = (n + 3) / 4;                       // need-map: one byte per node, in 4-byte words
-    int64_t n_chunks = 0;
-    if (chunked) {
-        bits = ar.take<uint32_t>(3 * (size_t)nb * words);
-        counts = ar.take<int32_t>(4 * (size_t)cs);
-        int32_t *ccnt = ar.take<int32_t>((size_t)n + 1), *coff = ar.take<int32_t>((size_t)n + 1);
-        chunk_cnt = ccnt;
-        row_order = ar.take<int32_t>((size_t)n);
-        (void)ar.take<int32_t>(256);                          // (layout kept in step with geo_sssp_workspace_bytes)
-        const size_t max_chunks = (size_t)n + (size_t)(nnz / 16) + 16;
-        chunk_node = ar.take<int32_t>(max_chunks);
-        chunk_start = ar.take<int32_t>(max_chunks);
-        const size_t sbytes = geo::scan_tmp_bytes((int64_t)n + 1);
-        void *stmp = ar.take<char>(sbytes);
-        lm_d = ar.take<double>((size_t)n);
-        lm_key = ar.take<float>(2 * (size_t)nb * sb);
-        lm_flags = ar.take<int32_t>(16);                    // [0..3] solve flags, [8..9] the landmark eccentricity (u64)
-        wunits = ar.take<uint32_t>((size_t)(nnz > 0 ? nnz : 1));
-        wrange = ar.take<uint32_t>(4);
-        const size_t per = (size_t)nb * n;
-        push.cs = cs;
-        push.cap = (int32_t)max_chunks;
-        push.chunk_off = coff;
-        push.chunk_node = chunk_node;
-        push.chunk_start = chunk_start;
-        push.near_lists = ar.take<int32_t>(2 * (size_t)nb * max_chunks);
-        push.far_lists = ar.take<int32_t>(3 * per);
-        push.words = (n + 31) / 32;
-        push.near_bits = ar.take<uint32_t>(2 * (size_t)nb * push.words);
-        push.far_bits = ar.take<uint32_t>((size_t)nb * push.words);
-        push.near_cnt = ar.take<int32_t>(3 * (size_t)cs);
-        push.far_cnt = ar.take<int32_t>(3 * (size_t)cs);
-        push.far_slot = ar.take<int32_t>(2 * (size_t)cs);
-        push.theta = ar.take<double>(2 * (size_t)cs);
-        push.active = ar.take<int32_t>(64);
-        (void)ar.take<int32_t>(512);                          // (layout kept in step with geo_sssp_workspace_bytes)
-        {
-            const size_t S = (size_t)std::min(nb * 16, CELL_ORDER_MAX_SOURCES);
-            cell_adj = ar.take<uint32_t>(S * ((S + 31) / 32));
-        }
-        wsum = ar.take<double>(8);
-        GEO_REQUIRE(bits && counts && stmp && lm_d && lm_key && lm_flags && wunits && wrange && push.near_lists &&
-                        push.far_lists && push.near_bits && push.far_bits && push.near_cnt && push.far_cnt && push.far_slot &&
-                        push.theta && push.active && cell_adj && wsum,
-                    "geo_sssp_multi: workspace carve failed");
-        chunk_count_kernel<<<geo::grid_for(n, 256, 2048), 256, 0, stream>>>(indptr, n, ccnt);
-        GEO_LAUNCH_CHECK();
-        int rc = geo::exclusive_scan_i32(ccnt, coff, n, stmp, sbytes, &n_chunks, stream);
-        if (rc) return rc;
-        GEO_REQUIRE((size_t)n_chunks <= max_chunks, "geo_sssp_multi: nnz=%lld does not match the graph", (long long)nnz);
-        chunk_fill_kernel<<<geo::grid_for(n, 256, 2048), 256, 0, stream>>>(indptr, n, coff, chunk_node, chunk_start);
-        GEO_LAUNCH_CHECK();
-    }
-    // blocks per batch: enough to cover the work items, capped so that one sweep stays <= ~64k blocks
-    const int nodes_per_block = (64 / sb) * WAVES_PER_BLOCK;
-    const int gs = nb < 8 ? nb : 8;
-    const int groups = (nb + gs - 1) / gs;
-    const int cap = 65536 / (gs * groups);
-    std::vector<int32_t> hflags(nb), hcounts(2 * (size_t)nb), order(n_sources), hsrc, host_sources(n_sources);
-    for (int32_t i = 0; i < n_sources; ++i) order[i] = i;
-    GEO_HIP_CHECK(hipMemcpyAsync(host_sources.data(), sources, (size_t)n_sources * 4, hipMemcpyDeviceToHost, stream));
-    GEO_HIP_CHECK(hipStreamSynchronize(stream));
-    for (int32_t i = 0; i < n_sources; ++i)
-        GEO_REQUIRE(host_sources[i] >= 0 && host_sources[i] < n, "geo_sssp_multi: sources[%d] = %d is outside 0..%d", i,
-                    host_sources[i], n - 1);
+    MultiCall c{indptr, indices, weights, n, nnz, sources, n_sources, D_out, P_out, dmin_out, argmin_out,
+                static_cast<hipStream_t>(stream_), geo::options(), make_plan(n, n_sources, force_sb), MultiBufs{}, 0, {}, {}, false};
+    if (int rc = carve(c, ws, ws_bytes)) return rc;
+    if (c.plan.chunked)
+        if (int rc = build_chunk_index(c)) return rc;
+    if (int rc = fetch_sources(c)) return rc;
+    identity_order(c);
     if (!g_ev0) {
         GEO_HIP_CHECK(hipEventCreate(&g_ev0));
         GEO_HIP_CHECK(hipEventCreate(&g_ev1));
     }
-    // ---- order the sources so that a batch holds neighbouring ones (see below: "Sources that lie close together ...") ----
-    bool grouped = false;
-    double landmark_ecc = 0.0;
-    // (a) by the cells of the graph (`sssp_order=1`, experiment): multi-source BFS by hops gives every node the source it is
-    //     nearest to; two sources are adjacent when an edge joins their cells; sources are taken in BFS order over that K-node
-    //     quotient graph (host).  ~20 launches over the graph and one K x K bitmap: 0.3 ms at 60 000 nodes / 512 sources,
-    //     against 5.8 ms for the two exact single-source solves of (b) on the swiss bench graph (288 sweeps each) -- but the
-    //     batches it forms are worse: the push solve then takes 36.9 ms instead of 20.5 ms (measured), so (b) is the default.
-    auto order_by_cells = [&]() -> int {
-        int32_t *label = reinterpret_cast<int32_t *>(lm_d), *level_of = label + n;            // lm_d: n doubles
-        const int32_t wordsK = (n_sources + 31) / 32;
-        GEO_HIP_CHECK(hipMemsetAsync(label, 0xff, 2 * (size_t)n * sizeof(int32_t), stream));    // -1 everywhere
-        GEO_HIP_CHECK(hipMemsetAsync(cell_adj, 0, (size_t)n_sources * wordsK * 4, stream));
-        cell_seed_kernel<<<geo::grid_for(n_sources, 256, 64), 256, 0, stream>>>(sources, n_sources, n, label, level_of, nullptr);
-        GEO_LAUNCH_CHECK();
-        int32_t level = 1, hchanged = 1;
-        while (hchanged && level < n + 2) {
-            GEO_HIP_CHECK(hipMemsetAsync(lm_flags, 0, sizeof(int32_t), stream));
-            for (int g = 0; g < 8; ++g, ++level) {
-                if (g == 7) GEO_HIP_CHECK(hipMemsetAsync(lm_flags, 0, sizeof(int32_t), stream));   // the group's last level decides
-                cell_grow_kernel<<<geo::grid_for(n, 256, 2048), 256, 0, stream>>>(indptr, indices, n, label, level_of, level, lm_flags);
-            }
-            GEO_LAUNCH_CHECK();
-            GEO_HIP_CHECK(hipMemcpyAsync(&hchanged, lm_flags, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            GEO_HIP_CHECK(hipStreamSynchronize(stream));
-        }
-        cell_adjacency_kernel<<<geo::grid_for(n, 256, 2048), 256, 0, stream>>>(indptr, indices, n, label, wordsK, cell_adj);
-        GEO_LAUNCH_CHECK();
-        std::vector<uint32_t> adj((size_t)n_sources * wordsK);
-        std::vector<int32_t> cell(n_sources);
-        gather_i32_kernel<<<geo::grid_for(n_sources, 256, 64), 256, 0, stream>>>(label, sources, n_sources, reinterpret_cast<int32_t *>(lm_key));
-        GEO_HIP_CHECK(hipMemcpyAsync(adj.data(), cell_adj, adj.size() * 4, hipMemcpyDeviceToHost, stream));
-        GEO_HIP_CHECK(hipMemcpyAsync(cell.data(), lm_key, (size_t)n_sources * 4, hipMemcpyDeviceToHost, stream));
-        GEO_HIP_CHECK(hipStreamSynchronize(stream));
-        // BFS over the quotient graph from the cell of sources[0]; unreached cells (other components) start new searches
-        std::vector<int32_t> rank(n_sources, -1), queue;
-        queue.reserve(n_sources);
-        int32_t next_rank = 0;
-        auto search = [&](int32_t start) {
-            size_t head = queue.size();
-            queue.push_back(start);
-            rank[start] = next_rank++;
-            while (head < queue.size()) {
-                const int32_t c = queue[head++];
-                const uint32_t *row = adj.data() + (size_t)c * wordsK;
-                for (int32_t wi = 0; wi < wordsK; ++wi) {
-                    uint32_t bits = row[wi];
-                    while (bits) {
-                        const int32_t d = wi * 32 + __builtin_ctz(bits);
-                        bits &= bits - 1;
-                        if (d < n_sources && rank[d] < 0) { rank[d] = next_rank++; queue.push_back(d); }
-                    }
-                }
-            }
-        };
-        search(cell[0] >= 0 ? cell[0] : 0);
-        for (int32_t i = 0; i < n_sources; ++i) {
-            const int32_t c = cell[i] >= 0 ? cell[i] : i;
-            if (rank[c] < 0) search(c);
-        }
-        std::vector<uint64_t> key(n_sources);
-        for (int32_t i = 0; i < n_sources; ++i) key[i] = ((uint64_t)(uint32_t)rank[cell[i] >= 0 ? cell[i] : i] << 32) | (uint32_t)i;
-        std::sort(key.begin(), key.end());
-        for (int32_t i = 0; i < n_sources; ++i) order[i] = (int32_t)(key[i] & 0xffffffffu);
-        grouped = true;
-        return GEO_OK;
-    };
-    // (c) along two landmark HOP counts (`sssp_order=2`): the Morton order of (b) needs two smooth coordinates on the graph,
-    //     not exact distances; breadth-first levels from sources[0] and from the source farthest from it (in hops) cost one
-    //     cheap launch per level instead of one full relaxation sweep per hop of an exact solve.
-    auto order_by_hops = [&]() -> int {
-        int32_t *label = reinterpret_cast<int32_t *>(lm_d), *level_of = label + n;
-        std::vector<int32_t> ka(n_sources), kb(n_sources);
-        auto bfs = [&](int32_t seed_pos, std::vector<int32_t> &out) -> int {
-            GEO_HIP_CHECK(hipMemsetAsync(label, 0xff, 2 * (size_t)n * sizeof(int32_t), stream));
-            cell_seed_kernel<<<1, 64, 0, stream>>>(sources + seed_pos, 1, n, label, level_of, nullptr);
-            GEO_LAUNCH_CHECK();
-            int32_t level = 1, hchanged = 1;
-            while (hchanged && level < n + 2) {
-                for (int g = 0; g < 16; ++g, ++level) {
-                    if (g == 15) GEO_HIP_CHECK(hipMemsetAsync(lm_flags, 0, sizeof(int32_t), stream));   // the group's last level decides
-                    cell_grow_kernel<<<geo::grid_for(n, 256, 2048), 256, 0, stream>>>(indptr, indices, n, label, level_of, level, lm_flags);
-                }
-                GEO_LAUNCH_CHECK();
-                GEO_HIP_CHECK(hipMemcpyAsync(&hchanged, lm_flags, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                GEO_HIP_CHECK(hipStreamSynchronize(stream));
-            }
-            gather_i32_kernel<<<geo::grid_for(n_sources, 256, 64), 256, 0, stream>>>(level_of, sources, n_sources, reinterpret_cast<int32_t *>(lm_key));
-            GEO_HIP_CHECK(hipMemcpyAsync(out.data(), lm_key, (size_t)n_sources * 4, hipMemcpyDeviceToHost, stream));
-            GEO_HIP_CHECK(hipStreamSynchronize(stream));
-            return GEO_OK;
-        };
-        if (int rc = bfs(0, ka)) return rc;
-        int32_t far = 0, amax = 0;
-        for (int32_t i = 0; i < n_sources; ++i)
-            if (ka[i] > amax) { amax = ka[i]; far = i; }
-        if (int rc = bfs(far, kb)) return rc;
-        int32_t bmax = 0;
-        for (int32_t i = 0; i < n_sources; ++i) bmax = std::max(bmax, kb[i]);
-        std::vector<uint64_t> key(n_sources);
-        for (int32_t i = 0; i < n_sources; ++i) {
-            // sources the landmarks cannot reach (other components: level -1) sort last
-            const uint32_t qa = ka[i] >= 0 && amax > 0 ? (uint32_t)(65535.0 * ka[i] / amax) : 65535u;
-            const uint32_t qb = kb[i] >= 0 && bmax > 0 ? (uint32_t)(65535.0 * kb[i] / bmax) : 65535u;
-            uint64_t m = 0;
-            for (int bit = 15; bit >= 0; --bit) m = (m << 2) | (uint64_t)(((qa >> bit) & 1u) << 1) | ((qb >> bit) & 1u);
-            key[i] = (m << 32) | (uint32_t)i;
-        }
-        std::sort(key.begin(), key.end());
-        for (int32_t i = 0; i < n_sources; ++i) order[i] = (int32_t)(key[i] & 0xffffffffu);
-        grouped = true;
-        return GEO_OK;
-    };
-    // (b) along two landmark distances (round 2; `sssp_order=0`, the default): Morton order of (dist from sources[0], dist from the source
-    //     farthest from it).  Also yields the eccentricity of sources[0], which tells the 32-bit solve early that it cannot fit.
-    auto regroup_sources = [&]() -> int {
-        if (opt.sssp_order == 2) return order_by_hops();
-        if (opt.sssp_order == 1 && n_sources <= CELL_ORDER_MAX_SOURCES) return order_by_cells();
-        int32_t lm_sweeps = 0;
-        std::vector<float> ka(n_sources), kb(n_sources);
-        const int gk = geo::grid_for(n_sources, 256, 64);
-        if (int rc = solve_single(indptr, indices, weights, n, host_sources[0], lm_d, lm_flags, 16, stream, &lm_sweeps)) return rc;
-        gather_f32_kernel<<<gk, 256, 0, stream>>>(lm_d, sources, n_sources, lm_key);
-        unsigned long long *ecc_dev = reinterpret_cast<unsigned long long *>(lm_flags + 8), ecc_bits = 0ull;   // (8-byte aligned scratch)
-        GEO_HIP_CHECK(hipMemsetAsync(ecc_dev, 0, sizeof(unsigned long long), stream));
-        max_finite_kernel<<<geo::grid_for(n, 256, 1024), 256, 0, stream>>>(lm_d, n, ecc_dev);
-        GEO_HIP_CHECK(hipMemcpyAsync(&ecc_bits, ecc_dev, sizeof(ecc_bits), hipMemcpyDeviceToHost, stream));
-        GEO_HIP_CHECK(hipMemcpyAsync(ka.data(), lm_key, (size_t)n_sources * 4, hipMemcpyDeviceToHost, stream));
-        GEO_HIP_CHECK(hipStreamSynchronize(stream));
-        {
-            double e;
-            memcpy(&e, &ecc_bits, sizeof(e));
-            landmark_ecc = e;                                  // farthest node from sources[0] (its component)
-        }
-        int32_t far = 0;
-        float amax = 0.f;
-        for (int32_t i = 0; i < n_sources; ++i)
-            if (std::isfinite(ka[i]) && ka[i] > amax) { amax = ka[i]; far = i; }
-        if (int rc = solve_single(indptr, indices, weights, n, host_sources[far], lm_d, lm_flags, 16, stream, &lm_sweeps)) return rc;
-        gather_f32_kernel<<<gk, 256, 0, stream>>>(lm_d, sources, n_sources, lm_key);
-        GEO_HIP_CHECK(hipMemcpyAsync(kb.data(), lm_key, (size_t)n_sources * 4, hipMemcpyDeviceToHost, stream));
-        GEO_HIP_CHECK(hipStreamSynchronize(stream));
-        float bmax = 0.f;
-        for (int32_t i = 0; i < n_sources; ++i)
-            if (std::isfinite(kb[i]) && kb[i] > bmax) bmax = kb[i];
-        std::vector<uint64_t> key(n_sources);
-        for (int32_t i = 0; i < n_sources; ++i) {
-            // sources the landmarks cannot reach (other components) sort last
-            const uint32_t qa = std::isfinite(ka[i]) && amax > 0.f ? (uint32_t)(65535.0f * ka[i] / amax) : 65535u;
-            const uint32_t qb = std::isfinite(kb[i]) && bmax > 0.f ? (uint32_t)(65535.0f * kb[i] / bmax) : 65535u;
-            uint64_t m = 0;
-            for (int bit = 15; bit >= 0; --bit) m = (m << 2) | (uint64_t)(((qa >> bit) & 1u) << 1) | ((qb >> bit) & 1u);
-            key[i] = (m << 32) | (uint32_t)i;
-        }
-        std::sort(key.begin(), key.end());
-        for (int32_t i = 0; i < n_sources; ++i) order[i] = (int32_t)(key[i] & 0xffffffffu);
-        grouped = true;
-        return GEO_OK;
-    };
     g_last_sweep_ms = 0.0;
-    // ---- exact 32-bit fixed-point solve (32 sources per row) when the weights qualify; see sweep_chunk32u_kernel ----
-    if (chunked && n_sources >= 32 && opt.sssp_u32 != 0 && opt.sssp_push != 2) {
-        int shift = 0;
-        bool eligible = true;
-        if (weights) {
-            const uint32_t init[4] = {0xffffffffu, 0u, 0u, 0u};
-            uint32_t got[4];
-            GEO_HIP_CHECK(hipMemcpyAsync(wrange, init, sizeof(init), hipMemcpyHostToDevice, stream));
-            weight_range_kernel<<<geo::grid_for(nnz, 256 * 16, 512), 256, 0, stream>>>(weights, nnz, wrange);
-            GEO_LAUNCH_CHECK();
-            GEO_HIP_CHECK(hipMemcpyAsync(got, wrange, sizeof(got), hipMemcpyDeviceToHost, stream));
-            GEO_HIP_CHECK(hipStreamSynchronize(stream));
-            if (got[2]) eligible = false;                                   // negative, NaN or infinite weight
-            else if (got[0] != 0xffffffffu) {                               // some positive weight
-                const int e_min = (int)(got[0] >> 23) - 127, e_max = (int)(got[1] >> 23) - 127;
-                eligible = (got[0] >> 23) != 0 && 24 + (e_max - e_min) <= 28;    // normal numbers, < 2^28 units each
-                shift = 23 - e_min;
-            }
+    if (c.plan.try_u32) {
+        FixedResult fixed;
+        int32_t sweeps = 0;
+        double unit = 1.0;
+        if (int rc = solve_fixed_point(c, &fixed, &sweeps, &unit)) return rc;
+        if (fixed == FixedResult::done) {
+            report(2032, sweeps, sweeps_out);
+            return write_outputs_fixed(c, unit);
         }
-        if (eligible) {
-            const int32_t nb32 = (n_sources + 31) / 32;
-            const double unit = std::ldexp(1.0, -shift);
-            uint32_t *dist32 = reinterpret_cast<uint32_t *>(w.dist);
-            weight_units_kernel<<<geo::grid_for(nnz, 256, 2048), 256, 0, stream>>>(weights, nnz, shift, wunits);
-            row_order_kernel<<<1, 1024, 0, stream>>>(chunk_cnt, n, row_order);
-            GEO_LAUNCH_CHECK();
-            std::vector<int32_t> hsrc32((size_t)nb32 * 32, -1), hrow32((size_t)nb32 * 32, -1), hf(nb32), hc(2 * (size_t)nb32);
-            int32_t sweeps = 0, sweeps_before = 0;
-            bool done = false, give_up = false;
-            // a long-geodesics graph restarts ONCE with the sources ordered along the landmark distances (as the fp64
-            // solve does): the fixed-point kernel then sweeps rows of 32 neighbouring sources
-            for (int att32 = 0; att32 < 2 && !done && !give_up; ++att32) {
-            bool restart = false;
-            sweeps_before += sweeps;
-            sweeps = 0;
-            for (int32_t i = 0; i < n_sources; ++i) { hsrc32[i] = host_sources[order[i]]; hrow32[i] = order[i]; }
-            GEO_HIP_CHECK(hipMemcpyAsync(w.src_pad, hsrc32.data(), hsrc32.size() * 4, hipMemcpyHostToDevice, stream));
-            GEO_HIP_CHECK(hipMemcpyAsync(row_of, hrow32.data(), hrow32.size() * 4, hipMemcpyHostToDevice, stream));
-            GEO_HIP_CHECK(hipMemsetAsync(w.flags, 0, 3 * (size_t)cs * sizeof(int32_t), stream));
-            init_multi32_kernel<<<geo::grid_for((int64_t)nb32 * n * 32, 256 * 8), 256, 0, stream>>>(dist32, w.src_pad, n, nb32);
-            GEO_HIP_CHECK(hipMemsetAsync(counts, 0, 4 * (size_t)cs * 4, stream));
-            GEO_HIP_CHECK(hipMemsetAsync(bits, 0, 3 * (size_t)nb32 * words * 4, stream));
-            source_need_kernel<<<geo::grid_for((int64_t)n_sources * 16, 256, 256), 256, 0, stream>>>(
-                w.src_pad, n_sources, n, 32, words, indptr, indices, bits + 2 * (size_t)nb32 * words);
-            GEO_LAUNCH_CHECK();
-            const int gs32 = nb32 < 8 ? nb32 : 8, groups32 = (nb32 + gs32 - 1) / gs32;
-            const int cap32_all = 65536 / (gs32 * groups32);
-            // (grouped solves: many sweeps that touch few rows -- a smaller grid and the flagged-row body throughout)
-            const int cap32 = (grouped && cap32_all > opt.sssp_grouped_cap) ? opt.sssp_grouped_cap : cap32_all;
-            const int sdiv32 = grouped && opt.sssp_sparse_div <= 0 ? 1 : sparse_div;
-            const int mdiv32 = grouped && opt.sssp_map_div <= 0 ? 1 : map_div;
-            const int per_batch = geo::grid_for(n, 8, cap32 > 0 ? cap32 : 1);     // 8 row slots per block
-            const unsigned grid = (unsigned)per_batch * (unsigned)gs32 * (unsigned)groups32;
-            int group_len = SWEEP_GROUP;
-            while (!done && !give_up && !restart) {
-                int last_cur = 0;
-                GEO_HIP_CHECK(hipEventRecord(g_ev0, stream));
-                for (int g = 0; g < group_len; ++g, ++sweeps) {
-                    const int cur = sweeps % 3, prev = (sweeps + 2) % 3, next = (sweeps + 1) % 3;
-                    uint32_t *bcur = bits + (size_t)cur * nb32 * words, *bprev = bits + (size_t)prev * nb32 * words;
-                    if (sweeps > 0) GEO_HIP_CHECK(hipMemsetAsync(bcur, 0, (size_t)nb32 * words * 4, stream));
-                    sweep_chunk32u_kernel<<<grid, 256, 0, stream>>>(indptr, indices, wunits, n, nb32, row_order,
-                                                                  per_batch, gs32, dist32, w.flags, counts, bprev,
-                                                                  bcur, words, prev, cur, next, sweeps == 0, act_mode, sdiv32,
-                                                                  mdiv32, (sweeps + 2) % 4, (sweeps + 3) % 4, sweeps % 4,
-                                                                  (sweeps + 1) % 4, cs);
-                    GEO_LAUNCH_CHECK();
-                    if (opt.sssp_trace) {                              // experiment: sampled improvement counts per sweep
-                        std::vector<int32_t> tc(nb32);
-                        GEO_HIP_CHECK(hipMemcpy(tc.data(), counts + (size_t)(sweeps % 4) * cs, (size_t)nb32 * 4, hipMemcpyDeviceToHost));
-                        long long tot = 0, neg = 0;
-                        for (int32_t b = 0; b < nb32; ++b) { tot += tc[b] < 0 ? -tc[b] : tc[b]; neg += tc[b] < 0; }
-                        fprintf(stderr, "[sssp-u32] sweep %d: ~%lld improved pairs (%.1f%% of pairs), %lld/%d batches without map\n", sweeps,
-                                tot * 16, 100.0 * tot * 16 / ((double)nb32 * n * 32), neg, nb32);
-                    }
-                    last_cur = cur;
-                }
-                GEO_HIP_CHECK(hipEventRecord(g_ev1, stream));
-                GEO_HIP_CHECK(hipMemcpyAsync(hf.data(), w.flags + (size_t)last_cur * cs, (size_t)nb32 * 4, hipMemcpyDeviceToHost, stream));
-                GEO_HIP_CHECK(hipMemcpyAsync(hc.data(), counts + (size_t)((sweeps + 3) % 4) * cs, (size_t)nb32 * 4, hipMemcpyDeviceToHost, stream));
-                GEO_HIP_CHECK(hipMemcpyAsync(hc.data() + nb32, counts + (size_t)((sweeps + 2) % 4) * cs, (size_t)nb32 * 4, hipMemcpyDeviceToHost, stream));
-                GEO_HIP_CHECK(hipStreamSynchronize(stream));
-                float ms = 0.f;
-                GEO_HIP_CHECK(hipEventElapsedTime(&ms, g_ev0, g_ev1));
-                g_last_sweep_ms += ms;
-                done = true;
-                for (int32_t b = 0; b < nb32; ++b) done = done && (hf[b] == 0);
-                if (!done && att32 == 0 && !grouped && sweeps == SWEEP_GROUP && group_mode != 0) {
-                    // long geodesics (few pairs moved so far): order the sources, start over
-                    double moved = 0.0;
-                    for (int32_t b = 0; b < 2 * nb32; ++b) moved += 16.0 * (hc[b] < 0 ? -hc[b] : hc[b]);
-                    if (group_mode == 2 || moved < 0.25 * (double)nb32 * n * 32) {
-                        if (int rc = regroup_sources()) return rc;
-                        restart = true;
-                        // some node is landmark_ecc away from sources[0]: if that alone does not fit 32 bits of units the
-                        // fixed-point solve would only find out at its end -- the fp64 kernels take the (ordered) sources now
-                        if (landmark_ecc / unit >= 4294967294.0) give_up = true;
-                        // ordered by cells (no eccentricity known): long geodesics go to the near-far push solve, which is at
-                        // least as fast as the ordered fixed-point sweeps and cannot overflow
-                        if (opt.sssp_push != 0 && (opt.sssp_order != 0 || opt.sssp_push == 3)) give_up = true;
-                    }
-                }
-                if (!done && sweeps > (int64_t)n + 2) give_up = true;
-                if (sweeps >= 16 && group_len < 16) group_len *= 2;
-            }
-            }                                                  // att32
-            sweeps += sweeps_before;
-            if (done) {
-                int32_t ovf = 0;
-                GEO_HIP_CHECK(hipMemsetAsync(w.flags, 0, sizeof(int32_t), stream));
-                overflow_scan_kernel<<<geo::grid_for((int64_t)nb32 * n * 32, 256, 2048), 256, 0, stream>>>(dist32, (int64_t)nb32 * n * 32, w.flags);
-                GEO_HIP_CHECK(hipMemcpyAsync(&ovf, w.flags, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                GEO_HIP_CHECK(hipStreamSynchronize(stream));
-                if (!ovf) {
-                    if (sweeps_out) *sweeps_out = sweeps;
-                    g_last_sweep_launches = sweeps;
-                    g_last_layout = 2032;
-                    const dim3 tg((unsigned)((n + 63) / 64), (unsigned)nb32);
-                    if (D_out) transpose_out32_kernel<<<tg, 256, 0, stream>>>(dist32, D_out, n, n_sources, unit, row_of);
-                    if (P_out) {
-                        pred_multi32_kernel<<<geo::grid_for((int64_t)nb32 * n * 32, 256, 8192), 256, 0, stream>>>(
-                            indptr, indices, wunits, n, nb32, dist32, w.src_pad, w.pred);
-                        transpose_out_kernel<int32_t, int32_t><<<tg, 256, 0, stream>>>(w.pred, P_out, n, n_sources, 32, row_of);
-                    }
-                    if (dmin_out || argmin_out)
-                        colmin32_kernel<<<(unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), 256, 0, stream>>>(
-                            dist32, n, n_sources, unit, row_of, dmin_out, argmin_out);
-                    GEO_LAUNCH_CHECK();
-                    GEO_HIP_CHECK(hipStreamSynchronize(stream));
-                    return GEO_OK;
-                }
-            }
-            g_last_sweep_ms = 0.0;                       // the fp64 solve below is the one that counts
+        g_last_sweep_ms = 0.0;                       // the fp64 solve below is the one that counts
+        if (c.plan.replan64) {
+            c.plan = make_plan(n, n_sources, 64);
+            if (int rc = carve(c, ws, ws_bytes)) return rc;
+            identity_order(c);
         }
-        // a graph this large took 16-source batches only for the fixed-point solve: the fp64 solve runs 64 per batch
-        if (force_sb == 0 && opt.sssp_sb != 16 && opt.sssp_sb != 64 && (size_t)n * 128 > ((size_t)12 << 20))
-            return sssp_multi_impl(indptr, indices, weights, n, nnz, sources, n_sources, D_out, P_out, dmin_out,
-                                   argmin_out, ws, ws_bytes, sweeps_out, stream_, 64);
     }
+    const geo::Options &opt = c.opt;
     int32_t total_sweeps = 0;
     bool pushed = false;
-    // Sources that lie close together are relaxed together: a row is evaluated whenever ANY of its batch's 16
-    // sources moved a neighbour, so with 16 scattered sources every row is re-evaluated as each of 16 fronts
-    // passes (and their corrections cascade), with 16 neighbouring sources the fronts pass as one.  On graphs
-    // with short geodesics (a few sweeps) this does not matter; when the first sweeps reach only a small part
-    // of the graph the solve restarts with the sources ordered along two landmark distances (Morton order of
-    // (dist from sources[0], dist from the source farthest from it)).  Results do not depend on the grouping.
     for (int attempt = 0;; ++attempt) {
-        hsrc.assign((size_t)nb * sb, -1);                           // -1 = no source in this slot
-        std::vector<int32_t> hrow((size_t)nb * sb, -1);
-        for (int32_t i = 0; i < n_sources; ++i) { hsrc[i] = host_sources[order[i]]; hrow[i] = order[i]; }
-        GEO_HIP_CHECK(hipMemcpyAsync(w.src_pad, hsrc.data(), hsrc.size() * 4, hipMemcpyHostToDevice, stream));
-        GEO_HIP_CHECK(hipMemcpyAsync(row_of, hrow.data(), hrow.size() * 4, hipMemcpyHostToDevice, stream));
-        GEO_HIP_CHECK(hipMemsetAsync(w.flags, 0, 3 * (size_t)cs * sizeof(int32_t), stream));
-        init_multi_kernel<<<geo::grid_for((int64_t)nb * n * sb, 256 * 8), 256, 0, stream>>>(w.dist, w.src_pad, n, nb, sb);
-        GEO_LAUNCH_CHECK();
-        if (chunked) {
-            GEO_HIP_CHECK(hipMemsetAsync(counts, 0, 4 * (size_t)cs * 4, stream));
-            GEO_HIP_CHECK(hipMemsetAsync(bits, 0, 3 * (size_t)nb * words * 4, stream));
-            source_need_kernel<<<geo::grid_for((int64_t)n_sources * 16, 256, 256), 256, 0, stream>>>(
-                w.src_pad, n_sources, n, sb, words, indptr, indices, bits + 2 * (size_t)nb * words);
-            GEO_LAUNCH_CHECK();
-        }
-        if (chunked && opt.sssp_push != 0 && (grouped || opt.sssp_push == 2 || group_mode == 2)) {
-            // ---- long geodesics: near-far push solve (see push_sweep_kernel) ----
-            double mean_w = 1.0;
-            if (weights && nnz > 0) {
-                GEO_HIP_CHECK(hipMemsetAsync(wsum, 0, sizeof(double), stream));
-                weight_sum_kernel<<<geo::grid_for(nnz, 256, 1024), 256, 0, stream>>>(weights, nnz, wsum);
-                GEO_HIP_CHECK(hipMemcpyAsync(&mean_w, wsum, sizeof(double), hipMemcpyDeviceToHost, stream));
-                GEO_HIP_CHECK(hipStreamSynchronize(stream));
-                mean_w /= (double)nnz;
-            }
-            const double delta = (opt.sssp_delta > 0 ? (double)opt.sssp_delta : 4.0) * (mean_w > 0.0 ? mean_w : 1.0);
-            auto push_reset = [&]() -> int {
-                GEO_HIP_CHECK(hipMemsetAsync(push.near_bits, 0, 2 * (size_t)nb * push.words * 4, stream));
-                GEO_HIP_CHECK(hipMemsetAsync(push.far_bits, 0, (size_t)nb * push.words * 4, stream));
-                push_init_kernel<<<nb, 256, 0, stream>>>(w.src_pad, n, nb, push, delta);
-                GEO_LAUNCH_CHECK();
-                return GEO_OK;
-            };
-            if (int rc = push_reset()) return rc;
-            const int64_t plimit = 64 * (int64_t)n + 64;
-            const int bpb = opt.sssp_push_blocks > 0 ? opt.sssp_push_blocks : 64;
-            const unsigned pgrid = (unsigned)(((nb + 7) / 8) * 8) * (unsigned)bpb;        // batch <-> XCD: see push_sweep_kernel
-            int32_t sweeps = 0, hact = 1;
-            int group_len = 8;
-            while (hact) {
-                int last = 0;
-                GEO_HIP_CHECK(hipEventRecord(g_ev0, stream));
-                for (int g = 0; g < group_len; ++g, ++sweeps) {
-                    if (weights) push_sweep_kernel<true><<<pgrid, 256, 0, stream>>>(indptr, indices, weights, n, nb, bpb, w.dist, push, delta, sweeps);
-                    else push_sweep_kernel<false><<<pgrid, 256, 0, stream>>>(indptr, indices, weights, n, nb, bpb, w.dist, push, delta, sweeps);
-                    GEO_LAUNCH_CHECK();
-                    if (opt.sssp_trace) {
-                        std::vector<int32_t> hn(cs), hfc(3 * (size_t)cs);
-                        GEO_HIP_CHECK(hipMemcpy(hn.data(), push.near_cnt + (size_t)((sweeps + 1) % 3) * cs, (size_t)cs * 4, hipMemcpyDeviceToHost));
-                        GEO_HIP_CHECK(hipMemcpy(hfc.data(), push.far_cnt, 3 * (size_t)cs * 4, hipMemcpyDeviceToHost));
-                        long long tn = 0, tf = 0, idle = 0;
-                        for (int32_t b = 0; b < nb; ++b) { tn += hn[b]; long long f = std::max(hfc[b], std::max(hfc[cs + b], hfc[2 * cs + b])); tf += f; idle += (hn[b] == 0 && f == 0); }
-                        fprintf(stderr, "[sssp-push] sweep %d: next near %lld, far pile <= %lld, idle batches %lld/%d\n", sweeps, tn, tf, idle, nb);
-                    }
-                    last = sweeps % 3;
-                }
-                GEO_HIP_CHECK(hipEventRecord(g_ev1, stream));
-                GEO_HIP_CHECK(hipMemcpyAsync(&hact, push.active + last, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                GEO_HIP_CHECK(hipStreamSynchronize(stream));
-                float ms = 0.f;
-                GEO_HIP_CHECK(hipEventElapsedTime(&ms, g_ev0, g_ev1));
-                g_last_sweep_ms += ms;
-                if (hact && sweeps > plimit) {
-                    geo::set_error("geo_sssp_multi: near-far solve did not finish within %d sweeps", sweeps);
-                    return GEO_E_NOCONV;
-                }
-                if (sweeps >= 32 && group_len < 32) group_len *= 2;
-            }
-            total_sweeps += sweeps;
-            pushed = true;
-            break;
-        }
-        // grouped solves run many sweeps that touch few rows: a smaller grid keeps the idle launches cheap
-        const int want_cap = opt.sssp_grouped_cap;
-        const int cap_now = (grouped && cap > want_cap) ? want_cap : cap;
-        // ... and stay with the flagged-row body whenever the need-map is there
-        const int sdiv = grouped && opt.sssp_sparse_div <= 0 ? 1 : sparse_div;
-        const int mdiv = grouped && opt.sssp_map_div <= 0 ? 1 : map_div;
-        const int per_batch = chunked ? geo::grid_for(n_chunks, 16, cap_now > 0 ? cap_now : 1)
-                                      : geo::grid_for(n, nodes_per_block, cap > 0 ? cap : 1);
-        const unsigned grid = (unsigned)per_batch * (unsigned)gs * (unsigned)groups;
         int32_t sweeps = 0;
-        bool done = false, regroup = false;
-        const int64_t limit = (int64_t)n + 2;
-        int group_len = SWEEP_GROUP;
-        while (!done && !regroup) {
-            int last_cur = 0;
-            GEO_HIP_CHECK(hipEventRecord(g_ev0, stream));
-            for (int g = 0; g < group_len; ++g, ++sweeps) {
-                const int cur = sweeps % 3, prev = (sweeps + 2) % 3, next = (sweeps + 1) % 3;
-#define GEO_SWEEP(SBT, WT)                                                                                          \
-    sweep_multi_kernel<SBT, WT><<<grid, 256, 0, stream>>>(indptr, indices, weights, n, nb, per_batch, gs, w.dist, w.flags, \
-                                                          prev, cur, next, sweeps == 0, cs)
-                if (chunked) {
-                    uint32_t *bcur = bits + (size_t)cur * nb * words, *bprev = bits + (size_t)prev * nb * words;
-                    if (sweeps > 0) GEO_HIP_CHECK(hipMemsetAsync(bcur, 0, (size_t)nb * words * 4, stream));
-                    if (weights)
-                        sweep_chunk16_kernel<true><<<grid, 256, 0, stream>>>(indptr, indices, weights, n, nb, chunk_node, chunk_start,
-                                                                             (int32_t)n_chunks, per_batch, gs, w.dist, w.flags,
-                                                                             counts, bprev, bcur, words, prev, cur, next, sweeps == 0, act_mode, sdiv, mdiv,
-                                                                             (sweeps + 2) % 4, (sweeps + 3) % 4, sweeps % 4, (sweeps + 1) % 4, cs);
-                    else
-                        sweep_chunk16_kernel<false><<<grid, 256, 0, stream>>>(indptr, indices, weights, n, nb, chunk_node, chunk_start,
-                                                                              (int32_t)n_chunks, per_batch, gs, w.dist, w.flags,
-                                                                              counts, bprev, bcur, words, prev, cur, next, sweeps == 0, act_mode, sdiv, mdiv,
-                                                                             (sweeps + 2) % 4, (sweeps + 3) % 4, sweeps % 4, (sweeps + 1) % 4, cs);
-                } else if (sb == 64) { if (weights) GEO_SWEEP(64, true); else GEO_SWEEP(64, false); }
-                else                 { if (weights) GEO_SWEEP(16, true); else GEO_SWEEP(16, false); }
-#undef GEO_SWEEP
-                GEO_LAUNCH_CHECK();
-                if (chunked && opt.sssp_trace) {            // experiment: sampled improvement counts per sweep
-                    std::vector<int32_t> hc(nb);
-                    GEO_HIP_CHECK(hipMemcpy(hc.data(), counts + (size_t)(sweeps % 4) * cs, (size_t)nb * 4, hipMemcpyDeviceToHost));
-                    long long tot = 0, neg = 0;
-                    for (int32_t b = 0; b < nb; ++b) { tot += hc[b] < 0 ? -hc[b] : hc[b]; neg += hc[b] < 0; }
-                    fprintf(stderr, "[sssp] sweep %d: ~%lld improved pairs (%.1f%% of pairs), %lld/%d batches without map\n", sweeps,
-                            tot * 16, 100.0 * tot * 16 / ((double)nb * n * 16), neg, nb);
-                }
-                last_cur = cur;
-            }
-            GEO_HIP_CHECK(hipEventRecord(g_ev1, stream));
-            GEO_HIP_CHECK(hipMemcpyAsync(hflags.data(), w.flags + (size_t)last_cur * cs, (size_t)nb * sizeof(int32_t),
-                                         hipMemcpyDeviceToHost, stream));
-            if (chunked) {                       // improvement counts of the last two sweeps (4-slot ring)
-                const int c_last = (sweeps + 3) % 4, c_before = (sweeps + 2) % 4;        // `sweeps` already counts them
-                GEO_HIP_CHECK(hipMemcpyAsync(hcounts.data(), counts + (size_t)c_last * cs, (size_t)nb * sizeof(int32_t),
-                                             hipMemcpyDeviceToHost, stream));
-                GEO_HIP_CHECK(hipMemcpyAsync(hcounts.data() + nb, counts + (size_t)c_before * cs, (size_t)nb * sizeof(int32_t),
-                                             hipMemcpyDeviceToHost, stream));
-            }
-            GEO_HIP_CHECK(hipStreamSynchronize(stream));
-            float ms = 0.f;
-            GEO_HIP_CHECK(hipEventElapsedTime(&ms, g_ev0, g_ev1));
-            g_last_sweep_ms += ms;
-            done = true;
-            for (int32_t b = 0; b < nb; ++b) done = done && (hflags[b] == 0);
-            if (!done && sweeps > limit) {
-                geo::set_error("geo_sssp_multi: no fixed point after %d sweeps", sweeps);
-                return GEO_E_NOCONV;
-            }
-            if (!done && chunked && !grouped && group_mode != 0 && attempt == 0 && sweeps == SWEEP_GROUP) {
-                // after the first sweeps: how much of the (node, source) matrix moved in the last two?
-                double moved = 0.0;
-                for (int32_t b = 0; b < 2 * nb; ++b) moved += 16.0 * (hcounts[b] < 0 ? -hcounts[b] : hcounts[b]);
-                regroup = group_mode == 2 || moved < 0.25 * (double)nb * n * 16;
-            }
-            if (sweeps >= 16 && group_len < 16) group_len *= 2;      // long solves: fewer host round trips
-        }
+        if (int rc = upload_sources(c, (size_t)c.plan.nb * c.plan.sb)) return rc;
+        init_multi_kernel<<<geo::grid_for((int64_t)c.plan.nb * n * c.plan.sb, 256 * 8), 256, 0, c.stream>>>(c.buf.dist, c.buf.src_pad, n,
+                                                                                                         c.plan.nb, c.plan.sb);
+        GEO_LAUNCH_CHECK();
+        if (c.plan.chunked)
+            if (int rc = reset_need_map(c, c.plan.nb, c.plan.sb)) return rc;
+        pushed = c.plan.chunked && opt.sssp_push != 0 && (c.grouped || opt.sssp_push == 2 || opt.sssp_group == 2);
+        SweepResult swept = SweepResult::done;
+        if (int rc = pushed ? solve_push(c, &sweeps) : solve_sweeps(c, attempt == 0, &swept, &sweeps)) return rc;
         total_sweeps += sweeps;
-        if (done) break;
-        // ---- order the sources along two landmark distances, then start over ----
-        if (int rc = regroup_sources()) return rc;
+        if (swept == SweepResult::done) break;
+        double ecc;
+        if (int rc = regroup_sources(c, &ecc)) return rc;
     }
-    const int32_t sweeps = total_sweeps;
-    if (sweeps_out) *sweeps_out = sweeps;
-    g_last_sweep_launches = sweeps;
-    g_last_layout = sb + (chunked ? 1000 : 0) + (pushed ? 3000 : 0);   // 4016 near-far push solve
-
-    const dim3 tgrid((unsigned)((n + 63) / 64), (unsigned)nb);
-    if (D_out) {
-        transpose_out_kernel<double, float><<<tgrid, 256, 0, stream>>>(w.dist, D_out, n, n_sources, sb, row_of);
-        GEO_LAUNCH_CHECK();
-    }
-    if (P_out) {
-        const int pg = geo::grid_for((int64_t)nb * n * sb, 256, 8192);
-        if (weights)
-            pred_multi_kernel<true><<<pg, 256, 0, stream>>>(indptr, indices, weights, n, nb, sb, w.dist, w.src_pad, w.pred);
-        else
-            pred_multi_kernel<false><<<pg, 256, 0, stream>>>(indptr, indices, weights, n, nb, sb, w.dist, w.src_pad, w.pred);
-        GEO_LAUNCH_CHECK();
-        transpose_out_kernel<int32_t, int32_t><<<tgrid, 256, 0, stream>>>(w.pred, P_out, n, n_sources, sb, row_of);
-        GEO_LAUNCH_CHECK();
-    }
-    if (dmin_out || argmin_out) {
-        colmin_kernel<<<(unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), 256, 0, stream>>>(
-            w.dist, n, n_sources, sb, row_of, dmin_out, argmin_out);
-        GEO_LAUNCH_CHECK();
-    }
-    GEO_HIP_CHECK(hipStreamSynchronize(stream));
-    return GEO_OK;
+    report(c.plan.sb + (c.plan.chunked ? 1000 : 0) + (pushed ? 3000 : 0), total_sweeps, sweeps_out);   // 4016: near-far push solve
+    return write_outputs_f64(c);
 }
 
 extern "C" int geo_sssp_multi(const int32_t *indptr, const int32_t *indices, const float *weights, int32_t n,
@@ -2046,10 +2171,8 @@ extern "C" int geo_sssp_nearest_source(const int32_t *indptr, const int32_t *ind
 
 extern "C" int geo_sssp_plan(int32_t n, int32_t n_sources) {
     if (n <= 0 || n_sources <= 0) return GEO_E_ARG;
-    const int sb = choose_sb(n, n_sources, 0);
-    const bool chunked = sb == 16 && n_sources > 16 && n < ROW128_MAX_NODES;
-    const bool u32 = chunked && n_sources >= 32 && geo::options().sssp_u32 != 0;
-    return sb + (chunked ? 1000 : 0) + (u32 ? 2000 : 0);
+    const MultiPlan p = make_plan(n, n_sources, 0);
+    return p.sb + (p.chunked ? 1000 : 0) + (p.u32 ? 2000 : 0);
 }
 
 extern "C" int geo_sssp_last_profile(double *sweep_ms, int32_t *sweep_launches) {
