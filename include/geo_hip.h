@@ -471,6 +471,33 @@ int geo_decoder_jvp_pairs(const geo_decoder_desc *dec, const float *z_start, con
                           int64_t n_edges, int32_t batch_size, float *len_out,
                           void *ws, size_t ws_bytes, void *stream);
 
+/* The pull-back metric tensor itself, per latent: G(z) = J(z)^T J(z), J as above (p_out x d, float32 columns from the tangent pass
+ * over the d unit tangents -- the column pass of the per-latent Jacobian route, run on its own), its eigenvalues, the volume
+ * element and the numerical rank.
+ *   G_out      [n][d][d] fp64: G[a][b] = sum over o < p_out of (double)J[a][o] * (double)J[b][o], o ascending (each product is
+ *              exact in fp64); the upper triangle is computed and mirrored, so G[a][b] and G[b][a] are the same bits
+ *   eig_out    [n][d] fp64, ascending: cyclic Jacobi on G in a fixed rotation order (may be null)
+ *   logvol_out [n] fp64: 0.5 * log det G = 0.5 * sum_i log(eig_i) if every eigenvalue is > 0, else -inf (may be null)
+ *   rank_out   [n] int32: #{ i : sqrt(eig_i) > max(p_out, d) * FLT_EPSILON * sqrt(eig_max) }, numpy's matrix_rank rule on the
+ *              singular values of the float32 Jacobian (may be null)
+ * G = 0 gives eig = 0, rank = 0, logvol = -inf.  Float32 columns determine G's entries and its large eigenvalues; where G is nearly
+ * singular (16 outputs from 16 latent dimensions: cond(G) up to 1e9) they do not determine the smallest eigenvalues or logvol.
+ * Covered: what the per-latent Jacobian route covers -- fixed statistics (norm 0, norm 1 with bn_train == 0, norm 2 with 32
+ * groups per layer), latent_dim <= 16, c1 in {32, 64, 128}, c2 == 64, 16, 32 or 192 outputs.  Not covered: train-mode BatchNorm (a
+ * sample's Jacobian depends on its batch), latent_dim > 16, other widths: geo_metric_tensor_workspace_bytes and
+ * geo_metric_tensor_min_workspace_bytes answer 0 and the call returns GEO_E_ARG before any launch, as it does for a null pointer
+ * and for a workspace below geo_metric_tensor_min_workspace_bytes (the columns of one 32-latent slice; a call with n < 32 also
+ * takes its own geo_metric_tensor_workspace_bytes(dec, n)).  The call always runs the column pass: it reads neither the option
+ * jvp_node_jacobian nor an edges-per-latent rule, and where another option switches off a kernel the pass needs (jvp_per_node = 0,
+ * jvp_mid = 2, jvp_back_valu) the queries answer 0 and the call refuses likewise instead of changing route.
+ * Latents are processed in slices sized from ws_bytes (at most 2^18 latents, which is what the query sizes for a larger n).  A
+ * latent's outputs are a function of its own row of z alone: the same bits for any n, position, slice length, stream and earlier
+ * workspace contents.  n == 0 returns GEO_OK without a launch.  No atomics. */
+size_t geo_metric_tensor_workspace_bytes(const geo_decoder_desc *dec, int64_t n);
+size_t geo_metric_tensor_min_workspace_bytes(const geo_decoder_desc *dec);
+int geo_decoder_metric_tensor(const geo_decoder_desc *dec, const float *z, int64_t n, double *G_out, double *eig_out,
+                              double *logvol_out, int32_t *rank_out, void *ws, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * K-quad weights and the chain order, shared by the native pull-back, decode, encode and LPIPS below.
  * A convolution weight read as a matrix [K][N] (K = input channels of one tap, N = output channels) is packed

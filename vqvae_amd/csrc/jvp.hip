@@ -33,8 +33,11 @@
 //                                  (jvp_head_stream): back_mfma_kernel's arithmetic with the next K block's rows in flight
 //            back_kernel (VALU)    every other head, or jvp_back_valu
 //   node_jacobian: the per_node kernels over unit tangents, then jacobian_lengths_kernel.
+//   geo_decoder_metric_tensor: the same column pass over slices of latents, then jacobian_gram_kernel (G = J^T J per latent, fp64)
+//                              and metric_spectrum_kernel (eigenvalues, rank, 0.5 log det G) -- DESIGN.md section 24.
 #include "geo_common.h"
 
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -2106,6 +2109,120 @@ __global__ __launch_bounds__(256) void jacobian_lengths_kernel(const float *__re
     if (live && l == 0) len_out[e] = 0.5f * (end_norm[0] + end_norm[1]);
 }
 
+// ---------------------------------------------------------------------------------- per-latent metric tensor
+// geo_decoder_metric_tensor: the same columns, reduced to G = J^T J per latent instead of to edge lengths.
+// G[a][b] = sum over o < p_out of (double)J[a][o] * (double)J[b][o], o ascending.  The product of two float32 values is exact in
+// fp64 (48 significant bits), so every partial sum is the correctly rounded fp64 sum of exact terms whether or not the compiler
+// contracts the multiply-add.  One workgroup per latent at a time: the d columns staged in LDS (coalesced), one thread per
+// entry of the upper triangle, which also writes the mirrored entry -- G[a][b] and G[b][a] are the same bits.  No atomics; the
+// padding of a column (o >= p_out, up to np) is never read: back_mfma_kernel never wrote it.
+constexpr int GRAM_MAX_D = 16, GRAM_MAX_P = 192, GRAM_LD = GRAM_MAX_P + 1;
+__global__ __launch_bounds__(256) void jacobian_gram_kernel(const float *__restrict__ jac_node, int64_t n_nodes, int d, int p_out,
+                                                           int np, double *__restrict__ G) {
+    __shared__ float Js[GRAM_MAX_D][GRAM_LD];
+    const int n_pairs = d * (d + 1) / 2;
+    int a = 0, b = (int)threadIdx.x;                          // entry threadIdx.x of the upper triangle, rows in order
+    while (a < d && b >= d - a) { b -= d - a; ++a; }
+    b += a;
+    for (int64_t node = blockIdx.x; node < n_nodes; node += gridDim.x) {
+        __syncthreads();                                       // (the last latent's entries are read)
+        const float *J = jac_node + (size_t)node * d * np;
+        for (int i = threadIdx.x; i < d * p_out; i += 256) {
+            const int k = i / p_out, o = i - k * p_out;
+            Js[k][o] = J[(size_t)k * np + o];
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < n_pairs) {
+            double s = 0.0;
+            for (int o = 0; o < p_out; ++o) s += (double)Js[a][o] * (double)Js[b][o];
+            double *Gn = G + (size_t)node * d * d;
+            Gn[a * d + b] = s;
+            Gn[b * d + a] = s;
+        }
+    }
+}
+
+// Spectrum of one G per thread, fp64: cyclic Jacobi on the upper triangle (kept in LDS, [entry][thread]: a thread's entries lie
+// in its own bank pair, and nothing is shared, so the kernel has no barrier).  Fixed order: sweeps over (p, q), p < q, rows in
+// order; a rotation is skipped when the off-diagonal entry is exactly 0 and, from the fifth sweep on, set to 0 when it no longer
+// changes either diagonal entry in fp64; the sweeps end when every off-diagonal entry is exactly 0 (at most SPEC_SWEEPS).  All of
+// it is a function of the matrix alone: the same G gives the same bits on every run.  Eigenvalues sorted ascending;
+//   rank   = #{ i : eig_i > 0 and sqrt(eig_i) > max(p_out, d) * FLT_EPSILON * sqrt(eig_max) }  (numpy's matrix_rank rule on J's
+//            singular values),
+//   logvol = 0.5 * sum_i log(eig_i), ascending, if every eigenvalue is > 0, else -inf.
+// G = 0 gives eig = 0, rank = 0, logvol = -inf; no NaN from a finite G.
+constexpr int SPEC_THREADS = 64, SPEC_TRI = GRAM_MAX_D * (GRAM_MAX_D + 1) / 2, SPEC_SWEEPS = 32;
+__device__ __forceinline__ int tri_at(int i, int j, int d) {      // entry (i, j) = (j, i) of the packed upper triangle
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    return lo * d - lo * (lo - 1) / 2 + (hi - lo);
+}
+__global__ __launch_bounds__(SPEC_THREADS) void metric_spectrum_kernel(const double *__restrict__ G, int64_t n_nodes, int d,
+                                                                      int p_out, double *__restrict__ eig_out,
+                                                                      double *__restrict__ logvol_out,
+                                                                      int32_t *__restrict__ rank_out) {
+    __shared__ double A[SPEC_TRI][SPEC_THREADS];
+    const int t = threadIdx.x;
+    const int64_t node = (int64_t)blockIdx.x * SPEC_THREADS + t;
+    if (node >= n_nodes) return;
+    const double *Gn = G + (size_t)node * d * d;
+    for (int i = 0; i < d; ++i)
+        for (int j = i; j < d; ++j) A[tri_at(i, j, d)][t] = Gn[i * d + j];
+    for (int sweep = 0; sweep < SPEC_SWEEPS; ++sweep) {
+        double off = 0.0;
+        for (int p = 0; p < d - 1; ++p)
+            for (int q = p + 1; q < d; ++q) off += fabs(A[tri_at(p, q, d)][t]);
+        if (off == 0.0) break;
+        for (int p = 0; p < d - 1; ++p)
+            for (int q = p + 1; q < d; ++q) {
+                const int ipq = tri_at(p, q, d), ipp = tri_at(p, p, d), iqq = tri_at(q, q, d);
+                const double apq = A[ipq][t];
+                if (apq == 0.0) continue;
+                const double app = A[ipp][t], aqq = A[iqq][t], g = 100.0 * fabs(apq);
+                if (sweep >= 4 && fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) { A[ipq][t] = 0.0; continue; }
+                const double h = aqq - app;
+                double tn;                                      // tan of the rotation angle, the smaller root
+                if (fabs(h) + g == fabs(h)) tn = apq / h;
+                else {
+                    const double theta = 0.5 * h / apq;
+                    tn = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+                    if (theta < 0.0) tn = -tn;
+                }
+                const double c = 1.0 / sqrt(tn * tn + 1.0), s = tn * c, tau = s / (1.0 + c);
+                A[ipp][t] = app - tn * apq;
+                A[iqq][t] = aqq + tn * apq;
+                A[ipq][t] = 0.0;
+                for (int k = 0; k < d; ++k) {
+                    if (k == p || k == q) continue;
+                    const int ikp = tri_at(k, p, d), ikq = tri_at(k, q, d);
+                    const double akp = A[ikp][t], akq = A[ikq][t];
+                    A[ikp][t] = akp - s * (akq + akp * tau);
+                    A[ikq][t] = akq + s * (akp - akq * tau);
+                }
+            }
+    }
+    // the diagonal into entries 0 .. d-1 (row 0: of these only entry 0 is a diagonal entry, and it stays), insertion sort
+    for (int i = 1; i < d; ++i) A[i][t] = A[tri_at(i, i, d)][t];
+    for (int i = 1; i < d; ++i) {
+        const double v = A[i][t];
+        int j = i - 1;
+        while (j >= 0 && A[j][t] > v) { A[j + 1][t] = A[j][t]; --j; }
+        A[j + 1][t] = v;
+    }
+    const double emax = A[d - 1][t];
+    const double tol = (double)(p_out > d ? p_out : d) * (double)FLT_EPSILON * (emax > 0.0 ? sqrt(emax) : 0.0);
+    int rank = 0;
+    bool positive = true;
+    double logdet = 0.0;
+    for (int i = 0; i < d; ++i) {
+        const double e = A[i][t];
+        if (eig_out) eig_out[(size_t)node * d + i] = e;
+        if (e > 0.0) { logdet += log(e); if (sqrt(e) > tol) ++rank; }
+        else positive = false;
+    }
+    if (rank_out) rank_out[node] = rank;
+    if (logvol_out) logvol_out[node] = positive ? 0.5 * logdet : -(double)INFINITY;
+}
+
 // ---------------------------------------------------------------------------------- host side: shape, plan, route
 bool make_shape(const geo_decoder_desc *dc, Shape *s) {
     s->d = dc->latent_dim; s->c0 = dc->c0; s->c1 = dc->c1; s->c2 = dc->c2; s->co = dc->out_channels;
@@ -2580,10 +2697,14 @@ int launch_pass(const Route &r, const geo_decoder_desc *dc, const Pass &p, const
 }
 
 // ---------------------------------------------------------------------------------- host side: the run
-// graph edges (z, src, dst) or explicit end points (z_start, z_end); `r` is make_route's answer for exactly this call
+// what geo_decoder_metric_tensor keeps of a slice of latents (eig / logvol / rank: all three null = no spectrum)
+struct MetricOut { double *G, *eig, *logvol; int32_t *rank; };
+
+// graph edges (z, src, dst) or explicit end points (z_start, z_end); `r` is make_route's answer for exactly this call.
+// metric (node_jacobian routes only): no edges are read and no lengths written; the columns are reduced to G and its spectrum.
 int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t n_nodes, const int32_t *src, const int32_t *dst,
             const float *z_start, const float *z_end, int64_t n_edges, float *len_out, void *ws, size_t ws_bytes,
-            hipStream_t stream) {
+            hipStream_t stream, const MetricOut *metric = nullptr) {
     const Plan &pl = r.pl;
     const Shape &s = pl.sh;
     const int batch = pl.batch;
@@ -2690,7 +2811,15 @@ int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t 
             GEO_LAUNCH_CHECK();
         }
     }
-    if (r.node_jacobian) {                                      // each edge end from its latent's columns
+    if (r.node_jacobian && metric) {                            // G = J^T J per latent, then its spectrum
+        jacobian_gram_kernel<<<geo::grid_for(n_nodes, 1), 256, 0, stream>>>(b.jac, n_nodes, s.d, s.p_out, (int)r.jac_np, metric->G);
+        GEO_LAUNCH_CHECK();
+        if (metric->eig || metric->logvol || metric->rank) {
+            metric_spectrum_kernel<<<(unsigned)((n_nodes + SPEC_THREADS - 1) / SPEC_THREADS), SPEC_THREADS, 0, stream>>>(
+                metric->G, n_nodes, s.d, s.p_out, metric->eig, metric->logvol, metric->rank);
+            GEO_LAUNCH_CHECK();
+        }
+    } else if (r.node_jacobian) {                               // each edge end from its latent's columns
         const int64_t teams = (n_edges * 16 + 255) / 256;
         GEO_REQUIRE(teams < ((int64_t)1 << 31), "geo_decoder_jvp_edges: too many edges for one launch (%lld)", (long long)n_edges);
         jacobian_lengths_kernel<<<(unsigned)teams, 256, 0, stream>>>(z, src, dst, n_edges, s.d, s.p_out, (int)r.jac_np, b.jac, len_out);
@@ -2712,6 +2841,89 @@ int decoder_jvp(const geo_decoder_desc *dc, const geo::Options &opt, bool graph_
         return r.status;
     }
     return run_jvp(dc, r, z, n_nodes, src, dst, z_start, z_end, n_edges, len_out, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+// ---------------------------------------------------------------------------------- host side: metric tensor per latent
+// The column pass of the node_jacobian route on its own, over slices of latents sized from the workspace.  The route of a slice is
+// make_route's for a graph over the slice's latents with the Jacobian route forced (the edges-per-latent rule and the option
+// jvp_node_jacobian do not enter); every other option acts as it does on geo_decoder_jvp_edges, and where one switches off a
+// kernel the pass needs the call refuses instead of changing route.
+constexpr int METRIC_BATCH = 512;                     // pseudo-edges per chunk (fixed statistics: tiling only)
+constexpr int64_t METRIC_MAX_SLICE = 1 << 18;         // latents per slice at most (d = 1: one pass of slots holds them)
+constexpr int64_t METRIC_MIN_SLICE = TS;              // the slice geo_metric_tensor_min_workspace_bytes sizes
+
+bool metric_route(const geo_decoder_desc *dc, const geo::Options &o, int64_t n_slice, const size_t *ws_bytes, Route *r) {
+    geo::Options forced = o;
+    forced.jvp_node_jacobian = 2;
+    return make_route(dc, forced, true, n_slice, 1, 1, METRIC_BATCH, ws_bytes, r) && r->node_jacobian && r->per_node;
+}
+
+// whether the call takes this decoder under these options; if not, why: status and text in `r`
+bool metric_covers(const geo_decoder_desc *dc, const geo::Options &o, Route *r) {
+    *r = Route{};
+    if (!dc) return route_error(r, GEO_E_ARG, "geo_decoder_metric_tensor: null pointer");
+    if (dc->norm == 1 && dc->bn_train)
+        return route_error(r, GEO_E_ARG, "geo_decoder_metric_tensor: train-mode BatchNorm is not covered (a sample's Jacobian "
+                                         "depends on its batch)");
+    if (dc->latent_dim < 1 || dc->latent_dim > GRAM_MAX_D)
+        return route_error(r, GEO_E_ARG, "geo_decoder_metric_tensor: latent_dim %d not in [1,%d]", dc->latent_dim, GRAM_MAX_D);
+    if (metric_route(dc, o, METRIC_MIN_SLICE, nullptr, r) && r->pl.sh.p_out <= GRAM_MAX_P) return true;
+    if (r->status != GEO_OK) { r->status = GEO_E_ARG; return false; }        // (make_route's text)
+    return route_error(r, GEO_E_ARG, "geo_decoder_metric_tensor: no per-latent column pass for this decoder (c2 == 64 and 16, 32 or "
+                                     "192 outputs), or an option (jvp_per_node, jvp_mid, jvp_back_valu) switches it off");
+}
+
+size_t metric_slice_bytes(const geo_decoder_desc *dc, const geo::Options &o, int64_t n_slice) {
+    Route r;
+    return metric_route(dc, o, n_slice, nullptr, &r) ? r.bytes : 0;
+}
+
+int decoder_metric_tensor(const geo_decoder_desc *dc, const float *z, int64_t n, const MetricOut &out, void *ws, size_t ws_bytes,
+                          hipStream_t stream) {
+    const geo::Options opt = geo::options();
+    Route probe;
+    if (!metric_covers(dc, opt, &probe)) {
+        geo::set_error("%s", probe.error);
+        return probe.status;
+    }
+    GEO_REQUIRE(n >= 0, "geo_decoder_metric_tensor: n %lld < 0", (long long)n);
+    if (n == 0) return GEO_OK;
+    GEO_REQUIRE(z && out.G && ws, "geo_decoder_metric_tensor: null pointer");
+    const int d = dc->latent_dim;
+
+    // ---- the slice length: everything (up to the cap) when it fits, else the largest whole number of tiles that does
+    const int64_t cap = n < METRIC_MAX_SLICE ? n : METRIC_MAX_SLICE;
+    int64_t slice = cap;
+    const size_t cap_bytes = metric_slice_bytes(dc, opt, cap);
+    if (!cap_bytes || ws_bytes < cap_bytes) {
+        const size_t min_bytes = metric_slice_bytes(dc, opt, METRIC_MIN_SLICE);
+        GEO_REQUIRE(min_bytes && ws_bytes >= min_bytes, "geo_decoder_metric_tensor: workspace of %zu bytes is below the minimum of %zu",
+                    ws_bytes, min_bytes);
+        int64_t lo = 1, hi = (cap + TS - 1) / TS;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) / 2;
+            const size_t bytes = metric_slice_bytes(dc, opt, mid * TS);
+            if (bytes && bytes <= ws_bytes) lo = mid; else hi = mid - 1;
+        }
+        slice = lo * TS;
+    }
+    // ---- the routes of a whole slice and of the last, shorter one: both settled before the first launch
+    Route whole, last;
+    const int64_t n_whole = n / slice, n_last = n % slice;
+    GEO_REQUIRE(n_whole == 0 || metric_route(dc, opt, slice, &ws_bytes, &whole),
+                "geo_decoder_metric_tensor: no column pass for a slice of %lld latents in %zu bytes", (long long)slice, ws_bytes);
+    GEO_REQUIRE(n_last == 0 || metric_route(dc, opt, n_last, &ws_bytes, &last),
+                "geo_decoder_metric_tensor: no column pass for a slice of %lld latents in %zu bytes", (long long)n_last, ws_bytes);
+
+    for (int64_t base = 0; base < n; base += slice) {
+        const int64_t ns = n - base < slice ? n - base : slice;
+        const MetricOut so = {out.G + (size_t)base * d * d, out.eig ? out.eig + (size_t)base * d : nullptr,
+                              out.logvol ? out.logvol + base : nullptr, out.rank ? out.rank + base : nullptr};
+        if (const int rc = run_jvp(dc, ns == slice ? whole : last, z + (size_t)base * d, ns, nullptr, nullptr, nullptr, nullptr, 1,
+                                   nullptr, ws, ws_bytes, stream, &so))
+            return rc;
+    }
+    return GEO_OK;
 }
 
 }  // namespace
@@ -2795,4 +3007,24 @@ extern "C" int geo_decoder_jvp_pairs(const geo_decoder_desc *dec, const float *z
     const geo::Options opt = geo::options();
     return decoder_jvp(dec, opt, false, nullptr, 0, nullptr, nullptr, z_start, z_end, n_edges, n_edges, batch_size, len_out, ws,
                        ws_bytes, stream);
+}
+
+extern "C" size_t geo_metric_tensor_workspace_bytes(const geo_decoder_desc *dec, int64_t n) {
+    const geo::Options opt = geo::options();
+    Route probe;
+    if (!metric_covers(dec, opt, &probe)) return 0;
+    return metric_slice_bytes(dec, opt, n < 1 ? 1 : (n < METRIC_MAX_SLICE ? n : METRIC_MAX_SLICE));
+}
+
+extern "C" size_t geo_metric_tensor_min_workspace_bytes(const geo_decoder_desc *dec) {
+    const geo::Options opt = geo::options();
+    Route probe;
+    if (!metric_covers(dec, opt, &probe)) return 0;
+    return metric_slice_bytes(dec, opt, METRIC_MIN_SLICE);
+}
+
+extern "C" int geo_decoder_metric_tensor(const geo_decoder_desc *dec, const float *z, int64_t n, double *G_out, double *eig_out,
+                                         double *logvol_out, int32_t *rank_out, void *ws, size_t ws_bytes, void *stream) {
+    const MetricOut out = {G_out, eig_out, logvol_out, rank_out};
+    return decoder_metric_tensor(dec, z, n, out, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }

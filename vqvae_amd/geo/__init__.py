@@ -3,15 +3,18 @@
 k-medoids analysis (fit_kmedoids_path, an extension), the matrix-free k-medoids refinement (fit_kmedoids_voronoi_graph,
 cell_medoid_update_device, an extension) and the Riemannian graph experiments of the reference's
 experiments/geo scripts (vqvae_amd.geo.experiments), and the bridging of a kNN graph's components (bridge_components_device,
-nearest_foreign_device, connect_components, an extension)."""
+nearest_foreign_device, connect_components, an extension), and the pull-back metric tensor per latent (pullback_metric,
+pullback_metric_device, native_metric_covers, an extension)."""
 from .knn_graph_optimized import (bridge_components_device, build_knn_graph, connect_components, kneighbors, knn_query_device,
                                   nearest_foreign_device)
 from .geo_shortest_paths import dijkstra_multi_source
 from .kmeans_optimized import cell_medoid_update_device, fit_kmedoids_path, fit_kmedoids_voronoi_graph
 from .experiments import (mean_shortest_path, mean_shortest_path_device, pick_sources_from_lcc, reweight_edges_symmetric_device,
                           riemann_graph_effects, riemann_sanity, stratified_edge_sample)
+from .riemannian_metric import PullbackMetric, native_metric_covers, pullback_metric, pullback_metric_device
 
 __all__ = ["bridge_components_device", "build_knn_graph", "cell_medoid_update_device", "connect_components", "dijkstra_multi_source", "fit_kmedoids_path", "fit_kmedoids_voronoi_graph",
            "kneighbors", "knn_query_device", "mean_shortest_path",
+           "PullbackMetric", "native_metric_covers", "pullback_metric", "pullback_metric_device",
            "mean_shortest_path_device", "nearest_foreign_device", "pick_sources_from_lcc", "reweight_edges_symmetric_device", "riemann_graph_effects", "riemann_sanity",
            "stratified_edge_sample"]

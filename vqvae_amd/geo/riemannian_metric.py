@@ -12,11 +12,13 @@ enter there.  Any other nn.Module (e.g. the Linear test decoder of the reference
 vanilla decoder with GroupNorm or train-mode BatchNorm, or a SpatialDecoder variant outside spatial_decoder.hip_kernels_cover)
 has no kernel: it is differentiated by autograd on the decoder's own device.
 """
+from dataclasses import dataclass
+
 import torch
 
 from .. import _lib
 from .._device import device, ptr, stream_ptr, workspace
-from .._export import capped_workspace
+from .._export import _fixed_statistics, capped_workspace
 from ..spatial_decoder import DecoderExport, hip_kernels_cover, looks_like_spatial_decoder
 from ..vanilla_decoder import VanillaDecoderExport, vanilla_kernels_cover
 
@@ -162,3 +164,171 @@ def edge_lengths_riemannian(decoder, z_start: torch.Tensor, z_end: torch.Tensor,
     if not pieces:
         return torch.empty(0, dtype=torch.float32, device=dec_dev)
     return torch.cat(pieces).to(torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------- the metric tensor itself
+# G(z) = J(z)^T J(z) per latent, its eigenvalues, the volume element sqrt(det G) (as logvol = 0.5 log det G) and the numerical
+# rank.  Covered decoders run geo_decoder_metric_tensor (csrc/jvp.hip: the column pass of the per-latent
+# Jacobian route, jacobian_gram_kernel, metric_spectrum_kernel); every other decoder, and the CPU, takes the generic route:
+# torch.func.jacfwd of sigmoid(decoder(.)) in float32, the Gram matrix and torch.linalg.eigvalsh in fp64.  Both routes apply
+# the same rank and logvol rules.  Float32 columns determine G's entries and its large eigenvalues; where G is nearly singular
+# (16 outputs from 16 latent dimensions: cond(G) up to 1e9) they do not determine the smallest eigenvalues or logvol.
+_GENERIC_BATCH = 256            # latents per jacfwd call on the generic route
+_GRAM_LOOP_MAX_OUTPUTS = 256    # up to this many outputs the generic Gram is accumulated output by output, ascending
+
+
+@dataclass
+class PullbackMetric:
+    """G fp64 [n, d, d] (or [N, H, W, d, d] for a latent grid); eig fp64 [..., d] ascending, logvol fp64 [...] = 0.5 log det G
+    (-inf unless every eigenvalue is > 0), rank int32 [...] -- None with spectrum=False; route "native" or "autograd"."""
+    G: object
+    eig: object
+    logvol: object
+    rank: object
+    route: str
+
+
+def native_metric_covers(decoder) -> bool:
+    """Whether geo_decoder_metric_tensor computes this decoder's metric tensor (else: the generic autograd route).  Exactly:
+    looks_like_spatial_decoder(decoder) and hip_kernels_cover(decoder), and
+      - fixed statistics: both norm layers nn.Identity, or nn.BatchNorm2d in eval mode with running statistics, or
+        nn.GroupNorm (32 groups per layer);
+      - latent_dim <= 16;
+      - dec_channels[1] in {32, 64, 128} and dec_channels[2] == 64, any dec_channels[0];
+      - 16, 32 or 192 outputs on the decoder's 1x1 latent: (out_channels, size) = (1, 28), (2, 28) or (3, 32).
+    Not covered: train-mode BatchNorm (a sample's Jacobian depends on its batch; pullback_metric* raise ValueError for it on
+    either route), latent_dim > 16, other widths or output sizes, the vanilla decoder and any other module."""
+    if not (isinstance(decoder, torch.nn.Module) and looks_like_spatial_decoder(decoder) and hip_kernels_cover(decoder)):
+        return False
+    seq = decoder.deconv_layers
+    fixed = all(isinstance(l, torch.nn.GroupNorm) or _fixed_statistics(l) for l in (seq[1], seq[4]))
+    s_out = 8 if seq[6].padding[0] == 1 else 4
+    tiles = (seq[6].out_channels * s_out * s_out + 31) // 32
+    return (fixed and decoder.conv_in.in_channels <= 16 and seq[0].out_channels in (32, 64, 128) and seq[3].out_channels == 64
+            and tiles in (1, 6))
+
+
+def _has_train_batchnorm(decoder) -> bool:
+    return any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and (m.training or m.running_mean is None)
+               for m in decoder.modules())
+
+
+def metric_spectrum_fields(G: torch.Tensor, eig: torch.Tensor, p_out: int):
+    """(logvol, rank) of ascending eigenvalues `eig` [n, d] of G [n, d, d], by the rules of metric_spectrum_kernel:
+    rank = #{i: sqrt(eig_i) > max(p_out, d) * FLT_EPSILON * sqrt(eig_max)}; logvol = 0.5 * sum log eig_i if all > 0, else -inf."""
+    d = eig.shape[-1]
+    pos = eig.clamp_min(0.0)
+    tol = float(max(p_out, d)) * float(torch.finfo(torch.float32).eps) * pos[:, -1:].sqrt()
+    rank = ((eig > 0) & (pos.sqrt() > tol)).sum(1).to(torch.int32)
+    all_pos = (eig > 0).all(1)
+    logs = torch.log(torch.where(eig > 0, eig, torch.ones_like(eig)))
+    logvol = torch.zeros(eig.shape[0], dtype=torch.float64, device=eig.device)
+    for i in range(d):                                   # ascending, like the kernel
+        logvol = logvol + logs[:, i]
+    logvol = torch.where(all_pos, 0.5 * logvol, torch.full_like(logvol, float("-inf")))
+    return logvol, rank
+
+
+def _generic_metric(decoder, z: torch.Tensor, spectrum: bool):
+    """The generic route on the decoder's own device: (G, eig, logvol, rank) for z [n, d]."""
+    dec_dev = next(decoder.parameters()).device
+    first = next(decoder.children())
+    flat_input = hasattr(first, "in_features")
+
+    def image(latent):                                   # one latent [d] -> its image, flattened
+        x = latent.view(1, -1) if flat_input else latent.view(1, -1, 1, 1)
+        return torch.sigmoid(decoder(x)).reshape(-1)
+
+    z = z.detach().to(dec_dev, torch.float32)
+    n, d = z.shape
+    G = torch.empty(n, d, d, dtype=torch.float64, device=dec_dev)
+    p_out = 0
+    for lo in range(0, n, _GENERIC_BATCH):
+        with torch.no_grad():
+            J = torch.func.vmap(torch.func.jacfwd(image))(z[lo:lo + _GENERIC_BATCH]).double()      # [b, p_out, d]
+        p_out = J.shape[1]
+        if p_out <= _GRAM_LOOP_MAX_OUTPUTS:
+            g = torch.zeros(J.shape[0], d, d, dtype=torch.float64, device=dec_dev)
+            for o in range(p_out):
+                g += J[:, o, :, None] * J[:, o, None, :]
+        else:                                            # (many outputs: one matrix product, the upper triangle mirrored)
+            g = torch.bmm(J.transpose(1, 2), J)
+            g = torch.triu(g) + torch.triu(g, 1).transpose(1, 2)
+        G[lo:lo + _GENERIC_BATCH] = g
+    if not spectrum:
+        return G, None, None, None
+    eig = torch.linalg.eigvalsh(G) if n else torch.empty(0, d, dtype=torch.float64, device=dec_dev)
+    logvol, rank = metric_spectrum_fields(G, eig, p_out)
+    return G, eig, logvol, rank
+
+
+def _native_metric(export: DecoderExport, z: torch.Tensor, spectrum: bool, max_workspace_bytes):
+    lib = _lib.load()
+    dev = z.device
+    n, d = z.shape
+    G = torch.empty(n, d, d, dtype=torch.float64, device=dev)
+    eig = torch.empty(n, d, dtype=torch.float64, device=dev) if spectrum else None
+    logvol = torch.empty(n, dtype=torch.float64, device=dev) if spectrum else None
+    rank = torch.empty(n, dtype=torch.int32, device=dev) if spectrum else None
+    if n == 0:
+        return G, eig, logvol, rank
+    with torch.cuda.device(dev):
+        ws = capped_workspace(lib.geo_metric_tensor_workspace_bytes(export.desc, n), max_workspace_bytes, dev,
+                              "geo_metric_tensor_workspace_bytes: decoder")
+        _lib.check(lib.geo_decoder_metric_tensor(export.desc, ptr(z), n, ptr(G), ptr(eig), ptr(logvol), ptr(rank), ptr(ws),
+                                                 ws.numel(), stream_ptr()), "geo_decoder_metric_tensor")
+    return G, eig, logvol, rank
+
+
+def pullback_metric_device(decoder_or_export, z: torch.Tensor, *, spectrum: bool = True,
+                           max_workspace_bytes=None) -> PullbackMetric:
+    """The pull-back metric tensor G = J^T J of every latent, J = d sigmoid(decoder(z)) / dz on a 1x1 latent, with (spectrum)
+    its eigenvalues, logvol = 0.5 log det G and numerical rank.  z: [n, d], or a latent grid [N, d, H, W], which is flattened
+    in build_codebook's (n, h, w) row order and gives fields shaped [N, H, W, ...].  The tensors live on z's device.
+    A decoder with native_metric_covers and z on a GPU run geo_decoder_metric_tensor (a DecoderExport always does;
+    `max_workspace_bytes` caps its workspace, not below geo_metric_tensor_min_workspace_bytes, and changes no bit); anything
+    else takes the generic autograd route on the decoder's device.  Train-mode BatchNorm raises ValueError on both routes: a
+    sample's Jacobian there depends on the batch it is in."""
+    grid = None
+    if z.ndim == 4:
+        N, d, H, W = z.shape
+        grid = (N, H, W)
+        z = z.permute(0, 2, 3, 1).reshape(-1, d)
+    if z.ndim != 2:
+        raise ValueError(f"z must be [n, d] or [N, d, H, W], got {tuple(z.shape)}")
+    out_dev = z.device
+    if isinstance(decoder_or_export, DecoderExport):
+        if decoder_or_export.desc.norm == 1 and decoder_or_export.desc.bn_train:
+            raise ValueError("pull-back metric tensor of a train-mode BatchNorm decoder: a sample's Jacobian depends on its "
+                             "batch; put the decoder in eval()")
+        fields = _native_metric(decoder_or_export, z.detach().to(torch.float32).contiguous(), spectrum, max_workspace_bytes)
+        route = "native"
+    else:
+        decoder = decoder_or_export
+        if _has_train_batchnorm(decoder):
+            raise ValueError("pull-back metric tensor of a train-mode BatchNorm decoder: a sample's Jacobian depends on its "
+                             "batch; put the decoder in eval()")
+        if native_metric_covers(decoder) and out_dev.type == "cuda":
+            if z.shape[1] != decoder.conv_in.in_channels:
+                raise ValueError(f"z has {z.shape[1]} latent dimensions, the decoder {decoder.conv_in.in_channels}")
+            fields = _native_metric(DecoderExport(decoder, out_dev), z.detach().to(torch.float32).contiguous(), spectrum,
+                                    max_workspace_bytes)
+            route = "native"
+        else:
+            fields = tuple(None if t is None else t.to(out_dev) for t in _generic_metric(decoder, z, spectrum))
+            route = "autograd"
+    if grid is not None:
+        fields = tuple(None if t is None else t.reshape(*grid, *t.shape[1:]) for t in fields)
+    return PullbackMetric(*fields, route=route)
+
+
+def pullback_metric(decoder, z) -> PullbackMetric:
+    """pullback_metric_device on host arrays: z a numpy array ([n, d] or [N, d, H, W]), the fields numpy arrays.  A covered decoder
+    runs natively (on its own GPU, or on this process's when it lives on the CPU and there is one); any other on its own device."""
+    dec_dev = next(decoder.parameters()).device
+    dev = dec_dev
+    if native_metric_covers(decoder) and dec_dev.type != "cuda" and torch.cuda.is_available():
+        dev = device()
+    res = pullback_metric_device(decoder, torch.as_tensor(z, dtype=torch.float32).to(dev))
+    return PullbackMetric(*(None if t is None else t.cpu().numpy() for t in (res.G, res.eig, res.logvol, res.rank)),
+                          route=res.route)
