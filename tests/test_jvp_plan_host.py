@@ -162,8 +162,8 @@ def test_options_select_the_other_live_kernels(lib):
     ("c1_48", b"dec_channels[1]=48 not in {32,64,128}"),
 ])
 def test_refused_decoders_report_the_run_s_verdict(lib, decoder, message):
-    """`px32_1ch_group` is a decoder that spatial_decoder.hip_kernels_cover() calls covered and the library refuses (GroupNorm
-    with a 64-output head has no matrix-core ConvT3): pinned as it is."""
+    """`px32_1ch_group`: GroupNorm with a 64-output head has no matrix-core ConvT3.  spatial_decoder.hip_kernels_cover()
+    refuses it as the library does (test_jvp_envelope_host.py sweeps the predicate against geo_jvp_plan)."""
     for graph in (False, True):
         assert plan(lib, decoder, "dense", graph) == E_ARG
         assert message in lib.geo_last_error()

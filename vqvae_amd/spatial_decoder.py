@@ -89,14 +89,19 @@ def looks_like_spatial_decoder(m: nn.Module) -> bool:
 def hip_kernels_cover(m: nn.Module) -> bool:
     """Whether csrc/jvp.hip implements this SpatialDecoder-shaped module (else the caller differentiates it
     with autograd): dec_channels[1] in {32,64,128}, dec_channels[2] a multiple of 16 dividing 128,
-    latent_dim <= 64, LDS budget of the output stage; GroupNorm with 32 groups per layer and
-    dec_channels[2] == 64 (the reference's default decoder 256-128-64)."""
+    latent_dim <= 64, LDS budget of the output stage; GroupNorm with 32 groups per layer,
+    dec_channels[2] == 64 (the reference's default decoder 256-128-64) and a head of 16, 32 or 192 outputs on the
+    1x1 latent -- (out_channels * s_out * s_out + 31) // 32 in {1, 6}, s_out = 4 at 28 px and 8 at 32 px: GroupNorm has
+    no VALU ConvT3.  The library's make_route (csrc/jvp.hip) decides the same way: for every module this function
+    answers what geo_jvp_plan >= 0 answers (tests/test_jvp_envelope_host.py sweeps both)."""
     seq = m.deconv_layers
     d, c1, c2, co = m.conv_in.in_channels, seq[0].out_channels, seq[3].out_channels, seq[6].out_channels
-    if isinstance(seq[1], nn.GroupNorm):
-        if seq[1].num_groups != 32 or seq[4].num_groups != 32 or c2 != 64:
-            return False
     s_out = 8 if seq[6].padding[0] == 1 else 4
+    if isinstance(seq[1], nn.GroupNorm):
+        if seq[1].num_groups != 32 or seq[4].num_groups != 32 or c2 != 64 or c1 % 16 != 0:
+            return False
+        if (co * s_out * s_out + 31) // 32 not in (1, 6):
+            return False
     back_lds = (2 * 8 * 16 * (c2 + 4) + 16 * co * (c2 + 4) + 8 * co * s_out * s_out) * 4
     return (d <= 64 and c1 in (32, 64, 128) and c2 % 16 == 0 and 128 % c2 == 0 and back_lds <= 160 * 1024
             and all(getattr(l, "bias", None) is not None for l in (m.conv_in, seq[0], seq[3], seq[6])))
