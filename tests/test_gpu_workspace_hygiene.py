@@ -208,6 +208,101 @@ def test_bridge_components(monkeypatch):
     assert connected_components_device(DeviceCSR(1500, out["indptr"], out["indices"], out["data"]))[0] == 1
 
 
+def test_csr_insert(monkeypatch):
+    """geo_csr_insert_count / _fill on their own: 7 undirected edges into a 300-node graph."""
+    from vqvae_amd.geo.knn_graph_optimized import csr_insert_device
+    W = _knn_graph("gauss", 300, 8, 41, 6)
+    WA, perm = _relabel(W, 6)
+
+    def edges(seed, Wg):
+        r = np.random.RandomState(seed)
+        src = r.choice(300, 7, replace=False).astype(np.int32)
+        dst = ((src + 1 + r.randint(0, 298, 7)) % 300).astype(np.int32)              # never a self edge
+        src[6], dst[6] = int(Wg.indices[Wg.indptr[5]]), 5                             # one pair the graph already stores
+        return _device_csr(Wg), _t(src), _t(dst), _t(r.rand(7).astype(np.float32) + np.float32(0.5))
+
+    def call(inp):
+        return _csr_out(csr_insert_device(*inp)), "insert"
+
+    out = _four_runs(monkeypatch, call, edges(2, WA), edges(1, W), "insert")
+    assert W.nnz < out["indices"].numel() <= W.nnz + 12
+
+
+@pytest.mark.parametrize("resident_nodes_max,cells", [(None, (5, 0)), (1, (0, 5))], ids=["resident", "slices"])
+def test_cell_costs(resident_nodes_max, cells, monkeypatch):
+    """geo_cell_costs on 600 nodes in 5 cells: every cell's rows in LDS, and (resident_nodes_max = 1) every cell in a slice of
+    the workspace."""
+    from vqvae_amd.geo.kmeans_optimized import cell_medoid_update_device
+    z = latents(600, 8, 43)
+    W = _knn_graph("gauss", 600, 8, 43, 6)
+    med = np.random.RandomState(3).choice(600, 5, replace=False).astype(np.int32)
+    assign = ((z[:, None, :] - z[med][None]) ** 2).sum(-1).argmin(1).astype(np.int32)
+    assert np.bincount(assign, minlength=5).min() > 1
+    WA, perm = _relabel(W, 7)
+    assignA = np.empty_like(assign)
+    assignA[perm] = assign
+
+    def call(inp):
+        info = {}
+        new, cost = cell_medoid_update_device(inp[0], inp[1], inp[2], resident_nodes_max=resident_nodes_max, info=info)
+        return {"medoids": new, "cost": cost}, (info["resident_cells"], info["workspace_cells"])
+
+    out = _four_runs(monkeypatch, call, (_device_csr(WA), _t(assignA), _t(perm[med].astype(np.int32))),
+                     (_device_csr(W), _t(assign), _t(med)), cells)
+    assert out["cost"].shape == (600,) and len(set(out["medoids"].tolist())) == 5
+
+
+def test_nearest_foreign(monkeypatch):
+    from vqvae_amd.geo.knn_graph_optimized import nearest_foreign_device
+
+    def inputs(seed):
+        r = np.random.RandomState(seed)
+        return (_t(latents(500, 5, seed)), _t(r.randint(0, 3, 500).astype(np.int32)),
+                _t(r.choice(500, 60, replace=False).astype(np.int32)))
+
+    def call(inp):
+        nbr, key = nearest_foreign_device(*inp)
+        return {"nbr": nbr, "key": key}, "foreign"
+
+    z, labels, rows = inputs(1)
+    out = _four_runs(monkeypatch, call, inputs(2), (z, labels, rows), "foreign")
+    nbr = out["nbr"].long()
+    assert out["nbr"].shape == (60,) and bool((labels[nbr] != labels[rows.long()]).all()) and bool(torch.isfinite(out["key"]).all())
+
+
+def test_knn_thresholds(monkeypatch):
+    """geo_knn_thresholds has no wrapper and no query of its own: twice geo_knn_workspace_bytes, as include/geo_hip.h says."""
+    from vqvae_amd import _device, _lib
+    lib = _lib.load()
+    n, d, kq, stride = 500, 5, 5, 8
+
+    def call(z):
+        tau = torch.full((n,), -7.0, dtype=torch.float64, device=z.device)
+        nbytes = 2 * lib.geo_knn_workspace_bytes(n, d)
+        with torch.cuda.device(z.device):
+            ws = _device.workspace(nbytes, z.device)
+            _lib.check(lib.geo_knn_thresholds(_device.ptr(z), n, d, kq, 0, 0, n, stride, _device.ptr(tau), _device.ptr(ws), nbytes,
+                                              _device.stream_ptr()), "geo_knn_thresholds")
+        return {"tau": tau}, "thresholds"
+
+    out = _four_runs(monkeypatch, call, _t(latents(n, d, 2)), _t(latents(n, d, 1)), "thresholds")
+    assert bool((out["tau"] >= 0).all()) and bool(torch.isfinite(out["tau"]).all())
+
+
+@pytest.mark.parametrize("n,d,m,kq,path", [(500, 5, 200, 10, EXACT), (16384, 64, 200, 10, BF16)], ids=["exact", "filter_bf16"])
+def test_knn_query(n, d, m, kq, path, monkeypatch):
+    """geo_knn_query: without the filter, and at the smallest corpus where the filter applies (d = 64)."""
+    from vqvae_amd import _lib
+    from vqvae_amd.geo.knn_graph_optimized import knn_query_device
+
+    def call(inp):
+        idx, d2 = knn_query_device(inp[0], inp[1], kq)
+        return {"idx": idx, "d2": d2}, _lib.load().geo_knn_last_path()
+
+    out = _four_runs(monkeypatch, call, (_t(latents(n, d, 2)), _t(latents(m, d, 4))), (_t(latents(n, d, 1)), _t(latents(m, d, 3))), path)
+    assert out["idx"].shape == (m, kq) and bool((out["d2"][:, 1:] >= out["d2"][:, :-1]).all())
+
+
 # --------------------------------------------------------------------------------------------- shortest paths and seeding
 SSSP_DEFAULTS = {"sssp_sb": -1, "sssp_push": 1, "sssp_delta": 8, "sssp_u32": 1, "sssp_group": 1, "sssp_push_blocks": 64,
                  "sssp_order": 0}

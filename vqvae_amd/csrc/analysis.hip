@@ -356,6 +356,15 @@ GramPlan gram_plan(int64_t n, int K) {
 }
 int64_t stat_slices(int64_t n) { return (n + SLICE - 1) / SLICE; }
 
+// The layouts of geo_feature_colstats and geo_feature_gram; geo_feature_workspace_bytes answers the larger plus its reserve.
+struct StatsWs { float *pmax; double *psum; };
+StatsWs carve_stats(geo::Arena &ar, int64_t n, int32_t K) {
+    const size_t count = (size_t)stat_slices(n) * K;
+    return {ar.take<float>(count), ar.take<double>(count)};
+}
+double *carve_gram(geo::Arena &ar, const GramPlan &g, int32_t K) { return ar.take<double>((size_t)g.slices * K * K); }
+constexpr size_t FEATURE_RESERVE = 256;
+
 bool feature_shape_ok(const float *D, int64_t ld, int32_t K, int64_t n) {
     return D && K >= 1 && K <= MAX_K && n >= 1 && n <= INT32_MAX && ld >= n;
 }
@@ -397,10 +406,8 @@ extern "C" int geo_cluster_label_scores(const int32_t *assign, const int32_t *la
 
 extern "C" size_t geo_feature_workspace_bytes(int64_t n, int32_t K) {
     if (K < 1 || K > MAX_K || n < 1 || n > INT32_MAX) return 0;
-    const size_t S = (size_t)stat_slices(n);
-    const size_t stats = geo::align_up(S * K * sizeof(float)) + geo::align_up(S * K * sizeof(double));
-    const size_t gram = geo::align_up((size_t)gram_plan(n, K).slices * K * K * sizeof(double));
-    return (stats > gram ? stats : gram) + 256;
+    const size_t stats = geo::measure(carve_stats, n, K), gram = geo::measure(carve_gram, gram_plan(n, K), K);
+    return (stats > gram ? stats : gram) + FEATURE_RESERVE;
 }
 
 extern "C" int geo_feature_colstats(const float *D, int64_t ld, int32_t K, int64_t n, float *colmax_out, float *fill_out,
@@ -410,10 +417,9 @@ extern "C" int geo_feature_colstats(const float *D, int64_t ld, int32_t K, int64
     GEO_REQUIRE(colmax_out && fill_out && mean_out && ws, "geo_feature_colstats: null pointer");
     const int S = (int)stat_slices(n);
     geo::Arena ar(ws, ws_bytes);
-    float *pmax = ar.take<float>((size_t)S * K);
-    double *psum = ar.take<double>((size_t)S * K);
-    if (!pmax || !psum) {
-        geo::set_error("geo_feature_colstats: workspace %zu too small", ws_bytes);
+    const auto [pmax, psum] = carve_stats(ar, n, K);
+    if (!ar.ok()) {
+        geo::set_error("geo_feature_colstats: workspace %zu too small (%zu needed)", ws_bytes, ar.off);
         return GEO_E_WORKSPACE;
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -435,9 +441,9 @@ extern "C" int geo_feature_gram(const float *D, int64_t ld, int32_t K, int64_t n
     GEO_REQUIRE(fill && mean && gram_out && ws, "geo_feature_gram: null pointer");
     const GramPlan g = gram_plan(n, K);
     geo::Arena ar(ws, ws_bytes);
-    double *partial = ar.take<double>((size_t)g.slices * K * K);
-    if (!partial) {
-        geo::set_error("geo_feature_gram: workspace %zu too small", ws_bytes);
+    double *partial = carve_gram(ar, g, K);
+    if (!ar.ok()) {
+        geo::set_error("geo_feature_gram: workspace %zu too small (%zu needed)", ws_bytes, ar.off);
         return GEO_E_WORKSPACE;
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_);

@@ -255,12 +255,18 @@ size_t slice_bytes(int32_t max_cell) {
     return geo::align_up((size_t)nodes * CELL_S * sizeof(double));
 }
 
-// Everything but the slices; the carve in geo_cell_costs takes the same items in the same order.
-size_t fixed_bytes(int32_t n, int64_t nnz, int32_t K) {
+// Everything but the slices: measured by the queries, carved by geo_cell_costs.
+struct CellWs { int32_t *hdr, *pos, *rowstart, *cnt, *cell_sorted, *unit_start; double *stage; int2 *cut; };
+CellWs carve_fixed(geo::Arena &ar, int32_t n, int64_t nnz, int32_t K) {
     const size_t N = n < 1 ? 1 : (size_t)n, E = nnz < 1 ? 1 : (size_t)nnz, C = K < 1 ? 1 : (size_t)K;
-    return geo::align_up(H_WORDS * sizeof(int32_t)) + 3 * geo::align_up(N * sizeof(int32_t)) + geo::align_up(C * sizeof(int32_t)) +
-           geo::align_up((C + 1) * sizeof(int32_t)) + geo::align_up(N * sizeof(double)) + geo::align_up(E * sizeof(int2));
+    CellWs o;
+    ar.take(o.hdr, H_WORDS); ar.take(o.pos, N); ar.take(o.rowstart, N); ar.take(o.cnt, N);
+    ar.take(o.cell_sorted, C); ar.take(o.unit_start, C + 1);
+    ar.take(o.stage, N);
+    ar.take(o.cut, E);
+    return o;
 }
+size_t fixed_bytes(int32_t n, int64_t nnz, int32_t K) { return geo::measure(carve_fixed, n, nnz, K); }
 
 }  // namespace
 
@@ -285,19 +291,15 @@ extern "C" int geo_cell_costs(const int32_t *indptr, const int32_t *indices, con
                 "geo_cell_costs: bad n=%d nnz=%lld K=%d power=%d resident_nodes_max=%d", n, (long long)nnz, K, power, resident_nodes_max);
     status_out[0] = status_out[1] = status_out[2] = status_out[3] = 0;
     const int32_t resident = resident_nodes_max == 0 || resident_nodes_max > CELL_LDS_NODES ? CELL_LDS_NODES : resident_nodes_max;
-    if (ws_bytes < fixed_bytes(n, nnz, K) + slice_bytes(0)) {
-        geo::set_error("geo_cell_costs: workspace of %zu bytes is below the minimum of %zu", ws_bytes, fixed_bytes(n, nnz, K) + slice_bytes(0));
-        return GEO_E_WORKSPACE;
-    }
     geo::Arena ar(ws, ws_bytes);
-    int32_t *hdr = ar.take<int32_t>(H_WORDS), *pos = ar.take<int32_t>(n), *rowstart = ar.take<int32_t>(n), *cnt = ar.take<int32_t>(n);
-    int32_t *cell_sorted = ar.take<int32_t>(K), *unit_start = ar.take<int32_t>((size_t)K + 1);
-    double *stage = ar.take<double>(n);
-    int2 *cut = ar.take<int2>(nnz < 1 ? 1 : (size_t)nnz);
-    if (!hdr || !pos || !rowstart || !cnt || !cell_sorted || !unit_start || !stage || !cut) {
-        geo::set_error("geo_cell_costs: workspace too small");
+    const CellWs w = carve_fixed(ar, n, nnz, K);
+    if (ws_bytes < ar.off + slice_bytes(0)) {
+        geo::set_error("geo_cell_costs: workspace of %zu bytes is below the minimum of %zu", ws_bytes, ar.off + slice_bytes(0));
         return GEO_E_WORKSPACE;
     }
+    int32_t *hdr = w.hdr, *pos = w.pos, *rowstart = w.rowstart, *cnt = w.cnt, *cell_sorted = w.cell_sorted, *unit_start = w.unit_start;
+    double *stage = w.stage;
+    int2 *cut = w.cut;
     GEO_HIP_CHECK(hipMemsetAsync(hdr, 0, H_WORDS * sizeof(int32_t), stream));
     GEO_HIP_CHECK(hipMemsetAsync(pos, 0xff, (size_t)n * sizeof(int32_t), stream));
     cell_plan_kernel<<<(unsigned)((K + 255) / 256), 256, 0, stream>>>(offsets, K, n, resident, cell_sorted, unit_start, hdr);

@@ -136,7 +136,7 @@ static int scan_rec(const int32_t *in, int32_t *out, int64_t n, Arena &ar, hipSt
     const int64_t t = tiles_of(n > 0 ? n : 1);
     int32_t *sums = ar.take<int32_t>((size_t)t + 1);
     int32_t *offs = ar.take<int32_t>((size_t)t + 1);
-    if (!sums || !offs) {
+    if (!ar.ok()) {
         set_error("exclusive_scan: workspace too small");
         return GEO_E_WORKSPACE;
     }

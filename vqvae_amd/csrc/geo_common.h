@@ -47,20 +47,40 @@ Options &options();
 
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// Bump allocator over the caller's workspace.
+// Bump allocator.  Over a caller's workspace it carves; default-constructed it measures: take() returns nullptr and only adds
+// up sizes.  take() always advances `off`, past the end too (returning nullptr there): after a layout function ran, `off` is the
+// bytes it needs and ok() whether it fitted.  One layout function per workspace, run by its query and its call.
 struct Arena {
-    char *base;
-    size_t size, off;
-    Arena(void *p, size_t n) : base(static_cast<char *>(p)), size(n), off(0) {}
+    char *base = nullptr;
+    size_t size = SIZE_MAX, off = 0;
+    bool measuring = true;
+    Arena() {}
+    Arena(void *p, size_t n) : base(static_cast<char *>(p)), size(n), measuring(false) {}
+    bool ok() const { return measuring || (base && off <= size); }      // a carving arena over a null workspace never fits
     template <typename T>
     T *take(size_t count) {
-        size_t bytes = align_up(count * sizeof(T));
-        if (off + bytes > size) return nullptr;
-        T *r = reinterpret_cast<T *>(base + off);
-        off += bytes;
-        return r;
+        const size_t at = off;
+        off += align_up(count * sizeof(T));
+        return base && off <= size ? reinterpret_cast<T *>(base + at) : nullptr;
     }
+    template <typename T>
+    void take(T *&p, size_t count) { p = take<T>(count); }
+    size_t mark() const { return off; }            // an optional group: m = mark(), take it, rewind(m) if !ok()
+    void rewind(size_t m) { off = m; }
 };
+// The bytes of a layout function lay(Arena &, args...): what its *_workspace_bytes query answers, plus the query's named reserve.
+template <typename F, typename... A>
+size_t measure(F lay, A... args) { Arena ar; lay(ar, args...); return ar.off; }
+
+// The ABI's rule (geo_hip.h): a workspace smaller than the size query that belongs to the call is refused before any launch.
+// `ar` is the arena the call's layout was just carved from: the query measures that layout, so the carve fits once the size does.
+#define GEO_REQUIRE_WORKSPACE(name, ar, need)                                                        \
+    do {                                                                                             \
+        if ((ar).size < (need) || !(ar).ok()) {                                                      \
+            geo::set_error(name ": workspace %zu too small (%zu needed)", (ar).size, (size_t)(need)); \
+            return GEO_E_WORKSPACE;                                                                  \
+        }                                                                                            \
+    } while (0)
 
 // ---- passes over a caller's workspace.  An entry point that keeps per-item buffers of 4-byte elements in the workspace cuts its
 // n items into passes of at most `cap`: the largest pass whose buffers fit, found by shrinking from min(n, cap).  The
@@ -90,12 +110,10 @@ static inline int plan_passes(const char *who, const size_t *per_item, int nb, i
         return GEO_E_WORKSPACE;
     }
     Arena ar(ws, ws_bytes);
-    for (int b = 0; b < nb; ++b) {
-        bufs[b] = ar.take<float>((size_t)pb * per_item[b]);
-        if (!bufs[b]) {
-            set_error("%s: workspace too small", who);
-            return GEO_E_WORKSPACE;
-        }
+    for (int b = 0; b < nb; ++b) ar.take(bufs[b], (size_t)pb * per_item[b]);
+    if (!ar.ok()) {
+        set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, ar.off);
+        return GEO_E_WORKSPACE;
     }
     *items = pb;
     return GEO_OK;

@@ -149,26 +149,18 @@ __global__ __launch_bounds__(256) void sym_sort_kernel(int32_t n, int32_t k, con
     }
 }
 
-struct SymWs {
-    int32_t *cnt_in, *off_in, *cursor, *in_src, *row_cnt, *tmp_col;
-    float *in_w, *tmp_val;
-    void *scan_tmp;
-    size_t scan_bytes;
-};
+struct SymWs { int32_t *cnt_in, *off_in, *cursor, *in_src, *row_cnt, *tmp_col; float *in_w, *tmp_val; char *scan_tmp; size_t scan_bytes; };
 
-void carve_sym(void *ws, size_t ws_bytes, int32_t n, int32_t k, SymWs *o) {
-    geo::Arena ar(ws, ws_bytes);
-    const size_t nk = (size_t)n * k;
-    o->cnt_in = ar.take<int32_t>((size_t)n + 1);
-    o->off_in = ar.take<int32_t>((size_t)n + 1);
-    o->cursor = ar.take<int32_t>((size_t)n + 1);
-    o->row_cnt = ar.take<int32_t>((size_t)n + 1);
-    o->in_src = ar.take<int32_t>(nk + 1);
-    o->in_w = ar.take<float>(nk + 1);
-    o->tmp_col = ar.take<int32_t>(2 * nk + 1);
-    o->tmp_val = ar.take<float>(2 * nk + 1);
-    o->scan_bytes = geo::scan_tmp_bytes((int64_t)n + 1);
-    o->scan_tmp = ar.take<char>(o->scan_bytes);
+// geo_symmetrize_count / _fill's layout: carved from the caller's workspace, measured by geo_symmetrize_workspace_bytes.
+SymWs carve_sym(geo::Arena &ar, int32_t n, int32_t k) {
+    const size_t n1 = (size_t)n + 1, nk = (size_t)n * k;
+    SymWs o;
+    ar.take(o.cnt_in, n1); ar.take(o.off_in, n1); ar.take(o.cursor, n1); ar.take(o.row_cnt, n1);
+    ar.take(o.in_src, nk + 1); ar.take(o.in_w, nk + 1);
+    ar.take(o.tmp_col, 2 * nk + 1); ar.take(o.tmp_val, 2 * nk + 1);
+    o.scan_bytes = geo::scan_tmp_bytes((int64_t)n + 1);
+    ar.take(o.scan_tmp, o.scan_bytes);
+    return o;
 }
 
 // ------------------------------------------------------------------------------------ upper edges
@@ -409,24 +401,50 @@ __global__ __launch_bounds__(256) void insert_fill_kernel(const int32_t *__restr
 
 unsigned rows_grid(int32_t n) { return (unsigned)((n + WPB - 1) / WPB); }
 
-// The ABI's rule (geo_hip.h): a workspace smaller than the size query that belongs to the call is refused before any launch.
-// The queries cover the carves below with slack, so a carve cannot fail once this has passed.
-#define GEO_REQUIRE_WORKSPACE(name, ws_bytes, need)                                                  \
-    do {                                                                                             \
-        if ((ws_bytes) < (need)) {                                                                   \
-            geo::set_error(name ": workspace %zu too small (%zu needed)", (size_t)(ws_bytes), (size_t)(need)); \
-            return GEO_E_WORKSPACE;                                                                  \
-        }                                                                                            \
-    } while (0)
+// The layouts of the other entry points, each measured by its query.  geo_upper_edges_count has no query of its own: it shares
+// geo_connected_components' and counts into `label`.
+struct CcWs { int32_t *label, *is_root, *rank, *changed; char *scan_tmp; size_t scan_bytes; };
+CcWs carve_cc(geo::Arena &ar, int32_t n) {
+    const size_t n1 = (size_t)n + 1;
+    CcWs o;
+    ar.take(o.label, n1); ar.take(o.is_root, n1); ar.take(o.rank, n1); ar.take(o.changed, 64);
+    o.scan_bytes = geo::scan_tmp_bytes((int64_t)n + 1);
+    ar.take(o.scan_tmp, o.scan_bytes);
+    return o;
+}
+
+struct CompactWs { int32_t *flag, *pos, *row_cnt; char *scan_tmp; size_t scan_bytes; };
+CompactWs carve_compact(geo::Arena &ar, int32_t n) {
+    const size_t n1 = (size_t)n + 1;
+    CompactWs o;
+    ar.take(o.flag, n1); ar.take(o.pos, n1); ar.take(o.row_cnt, n1);
+    o.scan_bytes = geo::scan_tmp_bytes((int64_t)n + 1);
+    ar.take(o.scan_tmp, o.scan_bytes);
+    return o;
+}
+
+struct InsertWs { int32_t *add_row, *add_col, *add_keep, *add_pre, *row_cnt; float *add_w; char *scan_tmp; size_t scan_bytes; };
+InsertWs carve_insert(geo::Arena &ar, int32_t n, int64_t E) {
+    const size_t A = (size_t)(2 * E + 1);
+    InsertWs o;
+    ar.take(o.add_row, A); ar.take(o.add_col, A); ar.take(o.add_w, A); ar.take(o.add_keep, A); ar.take(o.add_pre, A);
+    ar.take(o.row_cnt, (size_t)n + 1);
+    o.scan_bytes = geo::scan_tmp_bytes((int64_t)n + 1);
+    ar.take(o.scan_tmp, o.scan_bytes);
+    return o;
+}
+
+struct AddEntry { int32_t row, col; float w; };
+
+// What each query answers beyond its measured layout (CC: 4096 less the `changed` block, which it used to leave to the slack).
+constexpr size_t SYM_RESERVE = 4096, CC_RESERVE = 3840, COMPACT_RESERVE = 4096, INSERT_RESERVE = 4096;
 
 }  // namespace
 
 // ============================================================================================ ABI
 extern "C" size_t geo_symmetrize_workspace_bytes(int32_t n, int32_t k) {
     if (n <= 0 || k <= 0) return 1024;
-    const size_t nk = (size_t)n * k;
-    return 4 * geo::align_up(((size_t)n + 1) * 4) + 2 * geo::align_up((nk + 1) * 4) +
-           2 * geo::align_up((2 * nk + 1) * 4) + geo::align_up(geo::scan_tmp_bytes((int64_t)n + 1)) + 4096;
+    return geo::measure(carve_sym, n, k) + SYM_RESERVE;
 }
 
 extern "C" int geo_symmetrize_count(const int32_t *nbr_idx, const float *nbr_w, int32_t n, int32_t k, int32_t mode,
@@ -435,9 +453,9 @@ extern "C" int geo_symmetrize_count(const int32_t *nbr_idx, const float *nbr_w, 
     GEO_REQUIRE(nbr_idx && indptr_out && nnz_out && ws, "geo_symmetrize_count: null pointer");
     GEO_REQUIRE(n > 0 && k > 0 && (int64_t)n * k < ((int64_t)1 << 30), "geo_symmetrize_count: bad n=%d k=%d", n, k);
     GEO_REQUIRE(mode == 0 || mode == 1, "geo_symmetrize_count: mode must be 0 (union) or 1 (mutual)");
-    GEO_REQUIRE_WORKSPACE("geo_symmetrize_count", ws_bytes, geo_symmetrize_workspace_bytes(n, k));
-    SymWs w;
-    carve_sym(ws, ws_bytes, n, k, &w);
+    geo::Arena ar(ws, ws_bytes);
+    const SymWs w = carve_sym(ar, n, k);
+    GEO_REQUIRE_WORKSPACE("geo_symmetrize_count", ar, geo_symmetrize_workspace_bytes(n, k));
     const int64_t total = (int64_t)n * k;
     GEO_HIP_CHECK(hipMemsetAsync(w.cnt_in, 0, ((size_t)n + 1) * 4, s));
     GEO_HIP_CHECK(hipMemsetAsync(w.cursor, 0, ((size_t)n + 1) * 4, s));
@@ -460,9 +478,9 @@ extern "C" int geo_symmetrize_fill(const int32_t *nbr_idx, const float *nbr_w, i
     GEO_REQUIRE(nbr_idx && indptr && indices_out && data_out && ws, "geo_symmetrize_fill: null pointer");
     GEO_REQUIRE(n > 0 && k > 0 && (int64_t)n * k < ((int64_t)1 << 30), "geo_symmetrize_fill: bad n=%d k=%d", n, k);
     GEO_REQUIRE(mode == 0 || mode == 1, "geo_symmetrize_fill: mode must be 0 (union) or 1 (mutual)");
-    GEO_REQUIRE_WORKSPACE("geo_symmetrize_fill", ws_bytes, geo_symmetrize_workspace_bytes(n, k));
-    SymWs w;
-    carve_sym(ws, ws_bytes, n, k, &w);
+    geo::Arena ar(ws, ws_bytes);
+    const SymWs w = carve_sym(ar, n, k);
+    GEO_REQUIRE_WORKSPACE("geo_symmetrize_fill", ar, geo_symmetrize_workspace_bytes(n, k));
     // The workspace still holds what geo_symmetrize_count left: off_in and the rows' kept primaries at r k + off_in[r]
     // (tmp_col / tmp_val).  cnt_in and cursor are free: segment counts and their offsets.
     seg_count_kernel<<<geo::grid_for(n, 256, 1024), 256, 0, s>>>(indptr, n, w.cnt_in);
@@ -479,14 +497,13 @@ extern "C" int geo_upper_edges_count(const int32_t *indptr, const int32_t *indic
                                      int64_t *n_edges_out, void *ws, size_t ws_bytes, void *stream_) {
     hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(indptr && indices && upper_ptr_out && n_edges_out && ws && n > 0, "geo_upper_edges_count: bad argument");
-    GEO_REQUIRE_WORKSPACE("geo_upper_edges_count", ws_bytes, geo_cc_workspace_bytes(n));
     geo::Arena ar(ws, ws_bytes);
-    int32_t *cnt = ar.take<int32_t>((size_t)n + 1);
-    const size_t sb = geo::scan_tmp_bytes((int64_t)n + 1);
-    void *st = ar.take<char>(sb);
+    const CcWs w = carve_cc(ar, n);
+    GEO_REQUIRE_WORKSPACE("geo_upper_edges_count", ar, geo_cc_workspace_bytes(n));
+    int32_t *cnt = w.label;
     upper_count_kernel<<<geo::grid_for(n, 256), 256, 0, s>>>(indptr, indices, n, cnt);
     GEO_LAUNCH_CHECK();
-    return geo::exclusive_scan_i32(cnt, upper_ptr_out, n, st, sb, n_edges_out, s);
+    return geo::exclusive_scan_i32(cnt, upper_ptr_out, n, w.scan_tmp, w.scan_bytes, n_edges_out, s);
 }
 
 extern "C" int geo_upper_edges_fill(const int32_t *indptr, const int32_t *indices, int32_t n, const int32_t *upper_ptr,
@@ -510,7 +527,7 @@ extern "C" int geo_gather_edge_weights(const float *len, const int32_t *entry_ed
 
 extern "C" size_t geo_cc_workspace_bytes(int32_t n) {
     if (n <= 0) return 1024;
-    return 3 * geo::align_up(((size_t)n + 1) * 4) + geo::align_up(geo::scan_tmp_bytes((int64_t)n + 1)) + 4096;
+    return geo::measure(carve_cc, n) + CC_RESERVE;
 }
 
 extern "C" int geo_connected_components(const int32_t *indptr, const int32_t *indices, int32_t n, int32_t *labels_out,
@@ -518,14 +535,10 @@ extern "C" int geo_connected_components(const int32_t *indptr, const int32_t *in
     hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(indptr && indices && labels_out && n_components_out && ws && n > 0,
                 "geo_connected_components: bad argument");
-    GEO_REQUIRE_WORKSPACE("geo_connected_components", ws_bytes, geo_cc_workspace_bytes(n));
     geo::Arena ar(ws, ws_bytes);
-    int32_t *label = ar.take<int32_t>((size_t)n + 1);
-    int32_t *is_root = ar.take<int32_t>((size_t)n + 1);
-    int32_t *rank = ar.take<int32_t>((size_t)n + 1);
-    int32_t *changed = ar.take<int32_t>(64);
-    const size_t sb = geo::scan_tmp_bytes((int64_t)n + 1);
-    void *st = ar.take<char>(sb);
+    const CcWs w = carve_cc(ar, n);
+    GEO_REQUIRE_WORKSPACE("geo_connected_components", ar, geo_cc_workspace_bytes(n));
+    int32_t *label = w.label, *is_root = w.is_root, *rank = w.rank, *changed = w.changed;
     const int g = geo::grid_for(n, 256, 2048);
     const int gh = geo::grid_for(n, 16, 2048);
     cc_init_kernel<<<g, 256, 0, s>>>(label, n);
@@ -548,7 +561,7 @@ extern "C" int geo_connected_components(const int32_t *indptr, const int32_t *in
     cc_roots_kernel<<<g, 256, 0, s>>>(label, n, is_root);
     GEO_LAUNCH_CHECK();
     int64_t ncomp = 0;
-    int rc = geo::exclusive_scan_i32(is_root, rank, n, st, sb, &ncomp, s);
+    int rc = geo::exclusive_scan_i32(is_root, rank, n, w.scan_tmp, w.scan_bytes, &ncomp, s);
     if (rc) return rc;
     cc_number_kernel<<<g, 256, 0, s>>>(label, rank, n, labels_out);
     GEO_LAUNCH_CHECK();
@@ -559,7 +572,7 @@ extern "C" int geo_connected_components(const int32_t *indptr, const int32_t *in
 
 extern "C" size_t geo_csr_compact_workspace_bytes(int32_t n) {
     if (n <= 0) return 1024;
-    return 3 * geo::align_up(((size_t)n + 1) * 4) + geo::align_up(geo::scan_tmp_bytes((int64_t)n + 1)) + 4096;
+    return geo::measure(carve_compact, n) + COMPACT_RESERVE;
 }
 
 extern "C" int geo_csr_compact_count(const int32_t *indptr, const int32_t *indices, const float *data, int32_t n,
@@ -569,18 +582,15 @@ extern "C" int geo_csr_compact_count(const int32_t *indptr, const int32_t *indic
     hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(indptr && indices && new_index_out && indptr_out && n_out && nnz_out && ws && n > 0,
                 "geo_csr_compact_count: bad argument");
-    GEO_REQUIRE_WORKSPACE("geo_csr_compact_count", ws_bytes, geo_csr_compact_workspace_bytes(n));
     geo::Arena ar(ws, ws_bytes);
-    int32_t *flag = ar.take<int32_t>((size_t)n + 1);
-    int32_t *pos = ar.take<int32_t>((size_t)n + 1);
-    int32_t *row_cnt = ar.take<int32_t>((size_t)n + 1);
-    const size_t sb = geo::scan_tmp_bytes((int64_t)n + 1);
-    void *st = ar.take<char>(sb);
+    const CompactWs w = carve_compact(ar, n);
+    GEO_REQUIRE_WORKSPACE("geo_csr_compact_count", ar, geo_csr_compact_workspace_bytes(n));
+    int32_t *flag = w.flag, *pos = w.pos, *row_cnt = w.row_cnt;
     const int g = geo::grid_for(n, 256, 2048);
     keep_flags_kernel<<<g, 256, 0, s>>>(keep_node, n, flag);
     GEO_LAUNCH_CHECK();
     int64_t n_new = 0;
-    int rc = geo::exclusive_scan_i32(flag, pos, n, st, sb, &n_new, s);
+    int rc = geo::exclusive_scan_i32(flag, pos, n, w.scan_tmp, w.scan_bytes, &n_new, s);
     if (rc) return rc;
     new_index_kernel<<<g, 256, 0, s>>>(flag, pos, n, new_index_out);
     GEO_LAUNCH_CHECK();
@@ -593,7 +603,7 @@ extern "C" int geo_csr_compact_count(const int32_t *indptr, const int32_t *indic
     GEO_HIP_CHECK(hipMemsetAsync(row_cnt, 0, ((size_t)n + 1) * 4, s));
     compact_count_kernel<<<rows_grid(n), 256, 0, s>>>(indptr, indices, data, n, new_index_out, drop_zero, row_cnt);
     GEO_LAUNCH_CHECK();
-    return geo::exclusive_scan_i32(row_cnt, indptr_out, n_new, st, sb, nnz_out, s);
+    return geo::exclusive_scan_i32(row_cnt, indptr_out, n_new, w.scan_tmp, w.scan_bytes, nnz_out, s);
 }
 
 extern "C" int geo_csr_compact_fill(const int32_t *indptr, const int32_t *indices, const float *data, int32_t n,
@@ -610,35 +620,8 @@ extern "C" int geo_csr_compact_fill(const int32_t *indptr, const int32_t *indice
 
 extern "C" size_t geo_csr_insert_workspace_bytes(int32_t n, int64_t E) {
     if (n <= 0 || E < 0) return 1024;
-    return 5 * geo::align_up((size_t)(2 * E + 1) * 4) + geo::align_up(((size_t)n + 1) * 4) +
-           geo::align_up(geo::scan_tmp_bytes((int64_t)n + 1)) + 4096;
+    return geo::measure(carve_insert, n, E) + INSERT_RESERVE;
 }
-
-namespace {
-
-struct InsertWs {
-    int32_t *add_row, *add_col, *add_keep, *add_pre, *row_cnt;
-    float *add_w;
-    void *scan_tmp;
-    size_t scan_bytes;
-};
-
-void carve_insert(void *ws, size_t ws_bytes, int32_t n, int64_t E, InsertWs *o) {
-    geo::Arena ar(ws, ws_bytes);
-    const size_t A = (size_t)(2 * E + 1);
-    o->add_row = ar.take<int32_t>(A);
-    o->add_col = ar.take<int32_t>(A);
-    o->add_w = ar.take<float>(A);
-    o->add_keep = ar.take<int32_t>(A);
-    o->add_pre = ar.take<int32_t>(A);
-    o->row_cnt = ar.take<int32_t>((size_t)n + 1);
-    o->scan_bytes = geo::scan_tmp_bytes((int64_t)n + 1);
-    o->scan_tmp = ar.take<char>(o->scan_bytes);
-}
-
-struct AddEntry { int32_t row, col; float w; };
-
-}  // namespace
 
 extern "C" int geo_csr_insert_count(const int32_t *indptr, const int32_t *indices, int32_t n, const int32_t *src,
                                     const int32_t *dst, const float *w, int64_t E, int32_t *indptr_out, int64_t *nnz_out,
@@ -646,7 +629,9 @@ extern "C" int geo_csr_insert_count(const int32_t *indptr, const int32_t *indice
     hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(indptr && indices && src && dst && w && indptr_out && nnz_out && ws && n > 0, "geo_csr_insert_count: bad argument");
     GEO_REQUIRE(E >= 0 && E < ((int64_t)1 << 28), "geo_csr_insert_count: E=%lld out of range", (long long)E);
-    GEO_REQUIRE_WORKSPACE("geo_csr_insert_count", ws_bytes, geo_csr_insert_workspace_bytes(n, E));
+    geo::Arena ar(ws, ws_bytes);
+    const InsertWs o = carve_insert(ar, n, E);
+    GEO_REQUIRE_WORKSPACE("geo_csr_insert_count", ar, geo_csr_insert_workspace_bytes(n, E));
     // the edges are few: read them back, refuse a bad one before anything is launched, order both directions by (row, col)
     std::vector<int32_t> hs((size_t)E), hd((size_t)E);
     std::vector<float> hw((size_t)E);
@@ -677,8 +662,6 @@ extern "C" int geo_csr_insert_count(const int32_t *indptr, const int32_t *indice
         if (a > 0 && add[a].row == add[a - 1].row && add[a].col == add[a - 1].col) continue;
         hrow[u] = add[a].row; hcol[u] = add[a].col; hww[u] = add[a].w; ++u;
     }
-    InsertWs o;
-    carve_insert(ws, ws_bytes, n, E, &o);
     if (A > 0) {
         GEO_HIP_CHECK(hipMemcpyAsync(o.add_row, hrow.data(), A * 4, hipMemcpyHostToDevice, s));
         GEO_HIP_CHECK(hipMemcpyAsync(o.add_col, hcol.data(), A * 4, hipMemcpyHostToDevice, s));
@@ -696,9 +679,9 @@ extern "C" int geo_csr_insert_fill(const int32_t *indptr, const int32_t *indices
     hipStream_t s = static_cast<hipStream_t>(stream_);
     GEO_REQUIRE(indptr && indices && indptr_new && indices_out && data_out && ws && n > 0, "geo_csr_insert_fill: bad argument");
     GEO_REQUIRE(E >= 0 && E < ((int64_t)1 << 28), "geo_csr_insert_fill: E=%lld out of range", (long long)E);
-    GEO_REQUIRE_WORKSPACE("geo_csr_insert_fill", ws_bytes, geo_csr_insert_workspace_bytes(n, E));
-    InsertWs o;
-    carve_insert(ws, ws_bytes, n, E, &o);
+    geo::Arena ar(ws, ws_bytes);
+    const InsertWs o = carve_insert(ar, n, E);
+    GEO_REQUIRE_WORKSPACE("geo_csr_insert_fill", ar, geo_csr_insert_workspace_bytes(n, E));
     insert_fill_kernel<<<rows_grid(n), 256, 0, s>>>(indptr, indices, data, n, o.add_row, o.add_col, o.add_w, o.add_keep, o.add_pre,
                                                     (int32_t)(2 * E), indptr_new, indices_out, data_out);
     GEO_LAUNCH_CHECK();

@@ -1186,30 +1186,43 @@ struct KnnQuery {
 
 struct KnnLists { double *u; int32_t *cnt, *list, *overflow; };      // per query row of a range: [rows], [rows], [rows][FILTER_CAP]
 
+// ---- the workspace layouts, each run by its *_workspace_bytes query on a measuring arena and by its entry point on the caller's
+// memory.  The queries size the filter's arrays for the densest subset, the one of the longest lists:
+constexpr int KQ_DENSEST = 64;
+static_assert(filter_stride(KQ_DENSEST) == FILTER_STRIDE_MIN, "the queries measure the filter corpus at the smallest stride");
+
+// the padded float32 corpus, its fp64 copy and the squared norms (knn_prep_kernel)
+struct PlainCorpus { float *zp32; double *zq64, *nrm; };
+PlainCorpus carve_plain_corpus(geo::Arena &ar, const KnnPlan &p, int64_t n) {
+    return {ar.take<float>((size_t)n * p.dp), ar.take<double>((size_t)n * p.dp), ar.take<double>((size_t)n)};
+}
+
 // the filter's corpus-side arrays out of the arena, in geo_knn_topk's order (its u / cnt / list lie between nrm_s and overflow)
-bool carve_filter_corpus(geo::Arena &ar, const KnnPlan &p, int64_t n, int kq, KnnCorpus &c, KnnLists &lists, int64_t list_rows) {
+void carve_filter_corpus(geo::Arena &ar, const KnnPlan &p, int64_t n, int kq, KnnCorpus &c, KnnLists &lists, int64_t list_rows) {
     c.S = filter_stride(kq);
     c.m = (n + c.S - 1) / c.S;
-    c.zs32 = ar.take<float>((size_t)c.m * p.dp);
-    c.nrm_s = ar.take<double>((size_t)c.m);
+    ar.take(c.zs32, (size_t)c.m * p.dp);
+    ar.take(c.nrm_s, (size_t)c.m);
     if (list_rows > 0) {                                  // (geo_knn_query keeps them per slice, behind the corpus)
-        lists.u = ar.take<double>((size_t)list_rows);
-        lists.cnt = ar.take<int32_t>((size_t)list_rows);
-        lists.list = ar.take<int32_t>((size_t)list_rows * FILTER_CAP);
+        ar.take(lists.u, (size_t)list_rows);
+        ar.take(lists.cnt, (size_t)list_rows);
+        ar.take(lists.list, (size_t)list_rows * FILTER_CAP);
     }
-    lists.overflow = ar.take<int32_t>(16);
+    ar.take(lists.overflow, 16);
     c.dpb = p.dp < 16 ? 16 : p.dp;
     c.bf16_scan = geo::options().knn_filter != 2;         // 2: the float32 matrix-core scan (comparison runs)
     c.n_pad = (n + 255) / 256 * 256;                      // the scan reads whole tiles
     c.m_pad = (c.m + 255) / 256 * 256;
-    c.zb = ar.take<unsigned short>((size_t)c.n_pad * 2 * c.dpb);
-    c.negn = ar.take<float>((size_t)c.n_pad);
-    const size_t m0w = ((size_t)c.m + c.S - 1) / c.S;
-    c.zs0 = ar.take<float>(m0w * p.dp);
-    c.nrm_s0 = ar.take<double>(m0w);
-    c.zb_s = ar.take<unsigned short>((size_t)c.m_pad * 2 * c.dpb);
-    c.negn_s = ar.take<float>((size_t)c.m_pad);
-    if (!c.zs0 || !c.nrm_s0 || !c.zb_s || !c.negn_s) c.zs0 = nullptr;   // (a caller with a smaller workspace: one level)
+    ar.take(c.zb, (size_t)c.n_pad * 2 * c.dpb);
+    ar.take(c.negn, (size_t)c.n_pad);
+    c.m0 = (c.m + c.S - 1) / c.S;
+    // the second level's arrays, an optional group: a caller with a smaller workspace gets one level
+    const size_t one_level = ar.mark();
+    ar.take(c.zs0, (size_t)c.m0 * p.dp);
+    ar.take(c.nrm_s0, (size_t)c.m0);
+    ar.take(c.zb_s, (size_t)c.m_pad * 2 * c.dpb);
+    ar.take(c.negn_s, (size_t)c.m_pad);
+    if (!ar.ok()) { ar.rewind(one_level); c.zs0 = nullptr; c.nrm_s0 = nullptr; c.zb_s = nullptr; c.negn_s = nullptr; }
     // a d-term float32 dot product errs by < (d + 2) 2^-24 |x||y|, |x||y| <= (|x|^2 + |y|^2) / 2, and the float32
     // test adds a few more roundings of the same size: 16x margin
     // (the bf16 scan keeps 16 bits of every coordinate: its products err by < 2^-16 (|x|^2 + |y|^2) on top, 4x margin)
@@ -1218,9 +1231,7 @@ bool carve_filter_corpus(geo::Arena &ar, const KnnPlan &p, int64_t n, int kq, Kn
     // Two levels instead: thresholds from every S-th row of every S-th row (knn_bound_kernel), with them the SAME filter +
     // refinement over the every-S-th-row subset gives the exact kq-th distance to that subset -- at least as tight as the
     // threshold of the one-level scheme; the same candidate counts at both levels.
-    c.m0 = (c.m + c.S - 1) / c.S;
     c.two_level = c.bf16_scan && c.zs0 && n >= TWO_LEVEL_MIN && c.m0 >= kq;
-    return c.zs32 && c.nrm_s && lists.overflow && c.zb && c.negn && (list_rows <= 0 || (lists.u && lists.cnt && lists.list));
 }
 
 // the corpus-side launches of the filter paths: the threshold subset(s) and the bf16 parts
@@ -1357,42 +1368,35 @@ int query_per_item(const KnnPlan &p, bool filter, size_t *per_item) {
 constexpr int64_t QUERY_MIN_SLICE = 128, QUERY_PREP_CHUNK = 65536;
 
 // the corpus side of geo_knn_query's workspace: what geo_knn_topk keeps without its fp64 copy and per-row buffers, a
-// QUERY_PREP_CHUNK-row fp64 scratch for knn_prep_kernel instead, the padded float32 corpus last
-size_t query_corpus_bytes(int64_t n, const KnnPlan &p) {
-    const size_t chunk = (size_t)(n < QUERY_PREP_CHUNK ? n : QUERY_PREP_CHUNK);
-    size_t b = geo::align_up((size_t)n * sizeof(double)) + geo::align_up(chunk * p.dp * sizeof(double));
-    if (filter_applies(n, p.dp)) {
-        const size_t m = ((size_t)n + FILTER_STRIDE_MIN - 1) / FILTER_STRIDE_MIN;     // the densest subset (longest lists)
-        const size_t dpb = p.dp < 16 ? 16 : p.dp;
-        const size_t n_pad = ((size_t)n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;
-        const size_t m0 = (m + FILTER_STRIDE_MIN - 1) / FILTER_STRIDE_MIN;
-        b += geo::align_up(m * p.dp * sizeof(float)) + geo::align_up(m * sizeof(double)) + 256 +
-             geo::align_up(n_pad * 2 * dpb * sizeof(unsigned short)) + geo::align_up(n_pad * sizeof(float)) +
-             geo::align_up(m0 * p.dp * sizeof(float)) + geo::align_up(m0 * sizeof(double)) +
-             geo::align_up(m_pad * 2 * dpb * sizeof(unsigned short)) + geo::align_up(m_pad * sizeof(float));
-    }
-    return b + geo::align_up((size_t)n * p.dp * sizeof(float));
+// QUERY_PREP_CHUNK-row fp64 scratch for knn_prep_kernel instead (the corpus' fp64 rows are not read), the padded float32
+// corpus last: it ends where the slices' buffers begin
+struct QueryCorpus { double *nrm, *z64_scratch; float *zp_block; int64_t chunk; };
+QueryCorpus carve_query_corpus(geo::Arena &ar, const KnnPlan &p, int64_t n, bool filter, int kq, KnnCorpus *c, KnnLists *lists) {
+    QueryCorpus o;
+    o.chunk = n < QUERY_PREP_CHUNK ? n : QUERY_PREP_CHUNK;
+    ar.take(o.nrm, (size_t)n);
+    ar.take(o.z64_scratch, (size_t)o.chunk * p.dp);
+    if (filter) carve_filter_corpus(ar, p, n, kq, *c, *lists, 0);
+    ar.take(o.zp_block, (size_t)n * p.dp);
+    return o;
 }
+
+// what the geo_knn, geo_nearest_foreign and geo_bridge_components queries answer beyond their measured layouts
+constexpr size_t KNN_RESERVE = 1024, FOREIGN_RESERVE = 1024, BRIDGE_RESERVE = 1024;
 
 }  // namespace
 
 extern "C" size_t geo_knn_workspace_bytes(int64_t n, int32_t d) {
     if (n <= 0 || d <= 0) return 1024;
     const KnnPlan p = plan_for(d);
-    size_t b = geo::align_up((size_t)n * p.dp * sizeof(float)) + geo::align_up((size_t)n * p.dp * sizeof(double)) +
-               geo::align_up((size_t)n * sizeof(double)) + 1024;
+    geo::Arena ar;
+    carve_plain_corpus(ar, p, n);
     if (filter_applies(n, p.dp)) {
-        const size_t m = ((size_t)n + FILTER_STRIDE_MIN - 1) / FILTER_STRIDE_MIN;     // the densest subset (longest lists)
-        const size_t dpb = p.dp < 16 ? 16 : p.dp;
-        const size_t n_pad = ((size_t)n + 255) / 256 * 256, m_pad = (m + 255) / 256 * 256;   // the scan reads whole tiles
-        b += geo::align_up(m * p.dp * sizeof(float)) + geo::align_up(m * sizeof(double)) + geo::align_up((size_t)n * 8) +
-             geo::align_up((size_t)n * 4) + geo::align_up((size_t)n * FILTER_CAP * 4) + 256 +
-             geo::align_up(n_pad * 2 * dpb * sizeof(unsigned short)) + geo::align_up(n_pad * sizeof(float));
-        const size_t m0 = (m + FILTER_STRIDE_MIN - 1) / FILTER_STRIDE_MIN;
-        b += geo::align_up(m0 * p.dp * sizeof(float)) + geo::align_up(m0 * sizeof(double)) +
-             geo::align_up(m_pad * 2 * dpb * sizeof(unsigned short)) + geo::align_up(m_pad * sizeof(float));   // two-level thresholds
+        KnnCorpus c = {};
+        KnnLists lists = {};
+        carve_filter_corpus(ar, p, n, KQ_DENSEST, c, lists, n);
     }
-    return b;
+    return ar.off + KNN_RESERVE;
 }
 
 extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neighbors, int32_t form, int64_t row0,
@@ -1408,30 +1412,25 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
     GEO_REQUIRE(0 <= row0 && row0 <= row1 && row1 <= n, "geo_knn_topk: bad row range");
     if (row0 == row1) return GEO_OK;
     const KnnPlan p = plan_for(d);
-    geo::Arena ar(ws, ws_bytes);
-    float *zp32 = ar.take<float>((size_t)n * p.dp);
-    double *zq64 = ar.take<double>((size_t)n * p.dp);
-    double *nrm = ar.take<double>((size_t)n);
-    if (!zp32 || !zq64 || !nrm) {
-        geo::set_error("geo_knn_topk: workspace %zu too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
-    knn_prep_kernel<<<geo::grid_for(n, 256, 4096), 256, 0, stream>>>(z, n, d, p.dp, zp32, zq64, nrm);
-    GEO_LAUNCH_CHECK();
-    KnnCorpus c = {};
-    c.zp32 = zp32; c.nrm = nrm; c.n = n;
-    KnnLists lists = {};
     const int S = filter_stride(n_neighbors);
     const bool filter = n_neighbors <= 64 && filter_applies(n, p.dp) && (n + S - 1) / S >= n_neighbors;
+    geo::Arena ar(ws, ws_bytes);
+    const PlainCorpus pc = carve_plain_corpus(ar, p, n);
+    KnnCorpus c = {};
+    KnnLists lists = {};
+    if (filter) carve_filter_corpus(ar, p, n, n_neighbors, c, lists, n);
+    if (!ar.ok()) {
+        geo::set_error("geo_knn_topk: workspace %zu too small (%zu needed)", ws_bytes, ar.off);
+        return GEO_E_WORKSPACE;
+    }
+    c.zp32 = pc.zp32; c.nrm = pc.nrm; c.n = n;
+    knn_prep_kernel<<<geo::grid_for(n, 256, 4096), 256, 0, stream>>>(z, n, d, p.dp, pc.zp32, pc.zq64, pc.nrm);
+    GEO_LAUNCH_CHECK();
     if (filter) {
-        if (!carve_filter_corpus(ar, p, n, n_neighbors, c, lists, n)) {
-            geo::set_error("geo_knn_topk: workspace %zu too small", ws_bytes);
-            return GEO_E_WORKSPACE;
-        }
         const int rc = prepare_filter_corpus(p, c, stream);
         if (rc) return rc;
     }
-    const KnnQuery q = {zq64, nrm, c.zb, row0, row1, row0};     // the corpus' own rows
+    const KnnQuery q = {pc.zq64, pc.nrm, c.zb, row0, row1, row0};     // the corpus' own rows
     int32_t path = 0;
     const int rc = search_rows(p, form != 0, n_neighbors, c, q, filter ? &lists : nullptr, idx_out, d2_out, stream, &path);
     g_last_path = path;
@@ -1439,19 +1438,19 @@ extern "C" int geo_knn_topk(const float *z, int64_t n, int32_t d, int32_t n_neig
 }
 
 extern "C" size_t geo_knn_query_min_workspace_bytes(int64_t n, int32_t d) {
-    if (n <= 0 || d <= 0) return 1024;
-    const KnnPlan p = plan_for(d);
-    size_t per_item[QUERY_BUFS];
-    const int nb = query_per_item(p, filter_applies(n, p.dp), per_item);
-    return query_corpus_bytes(n, p) + geo::pass_bytes(per_item, nb, QUERY_MIN_SLICE);
+    return geo_knn_query_workspace_bytes(n, 0, d);        // one slice of QUERY_MIN_SLICE rows
 }
 
 extern "C" size_t geo_knn_query_workspace_bytes(int64_t n, int64_t m, int32_t d) {
     if (n <= 0 || d <= 0) return 1024;
     const KnnPlan p = plan_for(d);
     size_t per_item[QUERY_BUFS];
-    const int nb = query_per_item(p, filter_applies(n, p.dp), per_item);
-    return query_corpus_bytes(n, p) + geo::pass_bytes(per_item, nb, m > QUERY_MIN_SLICE ? m : QUERY_MIN_SLICE);
+    const bool filter = filter_applies(n, p.dp);
+    const int nb = query_per_item(p, filter, per_item);
+    KnnCorpus c = {};
+    KnnLists lists = {};
+    return geo::measure(carve_query_corpus, p, n, filter, KQ_DENSEST, &c, &lists) +
+           geo::pass_bytes(per_item, nb, m > QUERY_MIN_SLICE ? m : QUERY_MIN_SLICE);
 }
 
 extern "C" int geo_knn_query(const float *z, int64_t n, const float *q, int64_t m, int32_t d, int32_t n_neighbors, int32_t form,
@@ -1473,25 +1472,22 @@ extern "C" int geo_knn_query(const float *z, int64_t n, const float *q, int64_t 
     }
     // corpus side, prepared once for all slices
     geo::Arena ar(ws, ws_bytes);
-    const int64_t chunk = n < QUERY_PREP_CHUNK ? n : QUERY_PREP_CHUNK;
-    double *nrm = ar.take<double>((size_t)n);
-    double *z64_scratch = ar.take<double>((size_t)chunk * p.dp);          // knn_prep_kernel's fp64 rows: the corpus' are not read
     KnnCorpus c = {};
     c.n = n;
     const int S = filter_stride(n_neighbors);
     const bool filter_ws = filter_applies(n, p.dp);                       // what the workspace was sized for
     const bool filter = n_neighbors <= 64 && filter_ws && (n + S - 1) / S >= n_neighbors;
     KnnLists lists = {};
-    bool ok = nrm && z64_scratch;
-    if (ok && filter) ok = carve_filter_corpus(ar, p, n, n_neighbors, c, lists, 0);
-    // the padded float32 corpus ends where the slices' buffers begin: the float32 scan reads its queries from this array
-    const size_t zp_bytes = (size_t)n * p.dp * sizeof(float);
-    char *zp_block = ok ? reinterpret_cast<char *>(ar.take<float>((size_t)n * p.dp)) : nullptr;
-    if (!zp_block) {
-        geo::set_error("geo_knn_query: workspace %zu too small", ws_bytes);
+    const QueryCorpus qc = carve_query_corpus(ar, p, n, filter, n_neighbors, &c, &lists);
+    if (!ar.ok()) {
+        geo::set_error("geo_knn_query: workspace %zu too small (%zu needed)", ws_bytes, ar.off);
         return GEO_E_WORKSPACE;
     }
-    float *zp32 = reinterpret_cast<float *>(zp_block + (geo::align_up(zp_bytes) - zp_bytes));   // (a multiple of 32 bytes: dp >= 8)
+    const int64_t chunk = qc.chunk;
+    double *nrm = qc.nrm, *z64_scratch = qc.z64_scratch;
+    // the float32 scan reads its queries from the corpus array, so that ends flush with its block
+    const size_t zp_bytes = (size_t)n * p.dp * sizeof(float);
+    float *zp32 = qc.zp_block + (geo::align_up(zp_bytes) - zp_bytes) / sizeof(float);   // (a multiple of 32 bytes: dp >= 8)
     c.zp32 = zp32; c.nrm = nrm;
     // query side: slices of the rows that fit what is left
     size_t per_item[QUERY_BUFS];
@@ -1566,15 +1562,15 @@ extern "C" int geo_knn_thresholds(const float *z, int64_t n, int32_t d, int32_t 
     if (row0 == row1) return GEO_OK;
     const KnnPlan p = plan_for(d);
     geo::Arena ar(ws, ws_bytes);
-    float *zp32 = ar.take<float>((size_t)n * p.dp);
-    double *zq64 = ar.take<double>((size_t)n * p.dp);
-    double *nrm = ar.take<double>((size_t)n);
-    float *zs32 = ar.take<float>((size_t)m * p.dp);
+    const PlainCorpus pc = carve_plain_corpus(ar, p, n);
+    float *zs32 = ar.take<float>((size_t)m * p.dp);             // the subset: every stride-th row
     double *nrm_s = ar.take<double>((size_t)m);
-    if (!zp32 || !zq64 || !nrm || !zs32 || !nrm_s) {
-        geo::set_error("geo_knn_thresholds: workspace %zu too small", ws_bytes);
+    if (!ar.ok()) {
+        geo::set_error("geo_knn_thresholds: workspace %zu too small (%zu needed)", ws_bytes, ar.off);
         return GEO_E_WORKSPACE;
     }
+    float *zp32 = pc.zp32;
+    double *zq64 = pc.zq64, *nrm = pc.nrm;
     knn_prep_kernel<<<geo::grid_for(n, 256, 4096), 256, 0, stream>>>(z, n, d, p.dp, zp32, zq64, nrm);
     GEO_LAUNCH_CHECK();
     knn_subset_kernel<<<geo::grid_for(m * p.dp, 256, 4096), 256, 0, stream>>>(zp32, nrm, n, p.dp, stride, m, zs32, nrm_s);
@@ -1614,9 +1610,20 @@ int launch_nearest_foreign(const KnnPlan &p, bool ex, const float *zp32, const d
     return launch_nearest_foreign_d<32>(ex, zp32, zq64, nrm, labels, rows, m, n, p.nch, nbr, key, s);
 }
 
-size_t foreign_corpus_bytes(int64_t n, const KnnPlan &p) {
-    return geo::align_up((size_t)n * p.dp * sizeof(float)) + geo::align_up((size_t)n * p.dp * sizeof(double)) +
-           geo::align_up((size_t)n * sizeof(double));
+// geo_bridge_components' layout: the corpus and the Boruvka rounds' buffers
+struct BridgeWs { PlainCorpus pc; int32_t *cur, *flag, *pos, *rows, *nbr, *sizes, *map; double *key; char *sel, *scan_tmp; size_t scan_bytes; };
+BridgeWs carve_bridge(geo::Arena &ar, const KnnPlan &p, int64_t n, int32_t C) {
+    const size_t n1 = (size_t)n + 1;
+    BridgeWs o;
+    o.pc = carve_plain_corpus(ar, p, n);
+    ar.take(o.cur, n1); ar.take(o.flag, n1); ar.take(o.pos, n1); ar.take(o.rows, n1); ar.take(o.nbr, n1);
+    ar.take(o.key, (size_t)n);
+    ar.take(o.sel, (size_t)C * 20 + 64);         // what a round reads back, in one block: minkey u64 [C], minedge u64 [C], other i32 [C]
+    ar.take(o.sizes, (size_t)C + 16);            // sizes [C], then the bad-label flag
+    ar.take(o.map, (size_t)C + 16);
+    o.scan_bytes = geo::scan_tmp_bytes(n + 1);
+    ar.take(o.scan_tmp, o.scan_bytes);
+    return o;
 }
 
 struct BridgeEdge {
@@ -1638,7 +1645,7 @@ int32_t uf_find(int32_t *par, int32_t a) {
 
 extern "C" size_t geo_nearest_foreign_workspace_bytes(int64_t n, int32_t d) {
     if (n <= 0 || d <= 0) return 1024;
-    return foreign_corpus_bytes(n, plan_for(d)) + 1024;
+    return geo::measure(carve_plain_corpus, plan_for(d), n) + FOREIGN_RESERVE;
 }
 
 extern "C" int geo_nearest_foreign(const float *z, int64_t n, int32_t d, int32_t form, const int32_t *labels, const int32_t *rows,
@@ -1649,26 +1656,18 @@ extern "C" int geo_nearest_foreign(const float *z, int64_t n, int32_t d, int32_t
     GEO_REQUIRE(m >= 0 && m < (int64_t)1 << 31, "geo_nearest_foreign: m=%lld out of range", (long long)m);
     GEO_REQUIRE(d > 0 && d <= 128, "geo_nearest_foreign: d=%d not in [1,128]", d);
     if (m == 0) return GEO_OK;
-    const size_t need = geo_nearest_foreign_workspace_bytes(n, d);
-    if (ws_bytes < need) {
-        geo::set_error("geo_nearest_foreign: workspace of %zu bytes is below the %zu needed", ws_bytes, need);
-        return GEO_E_WORKSPACE;
-    }
     const KnnPlan p = plan_for(d);
     geo::Arena ar(ws, ws_bytes);
-    float *zp32 = ar.take<float>((size_t)n * p.dp);
-    double *zq64 = ar.take<double>((size_t)n * p.dp);
-    double *nrm = ar.take<double>((size_t)n);
-    knn_prep_kernel<<<geo::grid_for(n, 256, 4096), 256, 0, stream>>>(z, n, d, p.dp, zp32, zq64, nrm);
+    const PlainCorpus pc = carve_plain_corpus(ar, p, n);
+    GEO_REQUIRE_WORKSPACE("geo_nearest_foreign", ar, geo_nearest_foreign_workspace_bytes(n, d));
+    knn_prep_kernel<<<geo::grid_for(n, 256, 4096), 256, 0, stream>>>(z, n, d, p.dp, pc.zp32, pc.zq64, pc.nrm);
     GEO_LAUNCH_CHECK();
-    return launch_nearest_foreign(p, form != 0, zp32, zq64, nrm, labels, rows, m, n, nbr_out, key_out, stream);
+    return launch_nearest_foreign(p, form != 0, pc.zp32, pc.zq64, pc.nrm, labels, rows, m, n, nbr_out, key_out, stream);
 }
 
 extern "C" size_t geo_bridge_components_workspace_bytes(int64_t n, int32_t d, int32_t C) {
     if (n <= 0 || d <= 0 || C <= 0) return 1024;
-    const size_t c = (size_t)C;
-    return foreign_corpus_bytes(n, plan_for(d)) + 5 * geo::align_up(((size_t)n + 1) * 4) + geo::align_up((size_t)n * 8) +
-           geo::align_up(c * 20 + 64) + 2 * geo::align_up(c * 4 + 64) + geo::align_up(geo::scan_tmp_bytes(n + 1)) + 1024;
+    return geo::measure(carve_bridge, plan_for(d), n, C) + BRIDGE_RESERVE;
 }
 
 extern "C" int geo_bridge_components(const float *z, int64_t n, int32_t d, int32_t form, const int32_t *labels, int32_t C,
@@ -1679,32 +1678,16 @@ extern "C" int geo_bridge_components(const float *z, int64_t n, int32_t d, int32
     GEO_REQUIRE(n > 0 && n < (int64_t)1 << 31, "geo_bridge_components: n=%lld out of range", (long long)n);
     GEO_REQUIRE(d > 0 && d <= 128, "geo_bridge_components: d=%d not in [1,128]", d);
     GEO_REQUIRE(C >= 1 && C <= n, "geo_bridge_components: C=%d not in [1, n]", C);
-    const size_t need = geo_bridge_components_workspace_bytes(n, d, C);
-    if (ws_bytes < need) {
-        geo::set_error("geo_bridge_components: workspace of %zu bytes is below the %zu needed", ws_bytes, need);
-        return GEO_E_WORKSPACE;
-    }
     const KnnPlan p = plan_for(d);
     geo::Arena ar(ws, ws_bytes);
-    float *zp32 = ar.take<float>((size_t)n * p.dp);
-    double *zq64 = ar.take<double>((size_t)n * p.dp);
-    double *nrm = ar.take<double>((size_t)n);
-    int32_t *cur = ar.take<int32_t>((size_t)n + 1);
-    int32_t *flag = ar.take<int32_t>((size_t)n + 1);
-    int32_t *pos = ar.take<int32_t>((size_t)n + 1);
-    int32_t *rows = ar.take<int32_t>((size_t)n + 1);
-    int32_t *nbr = ar.take<int32_t>((size_t)n + 1);
-    double *key = ar.take<double>((size_t)n);
-    // what a round reads back, in one block: minkey u64 [C], minedge u64 [C], other i32 [C]
-    char *sel = ar.take<char>((size_t)C * 20 + 64);
-    int32_t *sizes = ar.take<int32_t>((size_t)C + 16);         // sizes [C], then the bad-label flag
-    int32_t *map = ar.take<int32_t>((size_t)C + 16);
-    const size_t sb = geo::scan_tmp_bytes(n + 1);
-    void *st = ar.take<char>(sb);
-    if (!zp32 || !zq64 || !nrm || !cur || !flag || !pos || !rows || !nbr || !key || !sel || !sizes || !map || !st) {
-        geo::set_error("geo_bridge_components: workspace %zu too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
+    const BridgeWs w = carve_bridge(ar, p, n, C);
+    GEO_REQUIRE_WORKSPACE("geo_bridge_components", ar, geo_bridge_components_workspace_bytes(n, d, C));
+    float *zp32 = w.pc.zp32;
+    double *zq64 = w.pc.zq64, *nrm = w.pc.nrm, *key = w.key;
+    int32_t *cur = w.cur, *flag = w.flag, *pos = w.pos, *rows = w.rows, *nbr = w.nbr, *sizes = w.sizes, *map = w.map;
+    char *sel = w.sel;
+    void *st = w.scan_tmp;
+    const size_t sb = w.scan_bytes;
     // the plan: labels in range, component sizes
     const int gn = geo::grid_for(n, 256, 4096);
     GEO_HIP_CHECK(hipMemsetAsync(sizes, 0, ((size_t)C + 1) * 4, stream));

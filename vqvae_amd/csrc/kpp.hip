@@ -1342,28 +1342,18 @@ size_t plan_ints_bound(int32_t n) {
     return 6 * leaves + 64 + 2 * CPLAN_INTS + (size_t)n / NP_BUFSIZE + 1;      // + the per-buffer plans and tickets
 }
 
-bool carve(void *ws, size_t ws_bytes, int32_t n, KppWs *o) {
-    geo::Arena ar(ws, ws_bytes);
-    o->ctl = ar.take<KppCtl>(4);
-    o->state = ar.take<KppState>(4);
-    o->u_dev = ar.take<double>((size_t)n);
-    o->d = ar.take<double>((size_t)n);
-    o->cdf = ar.take<double>((size_t)n);
-    const size_t tiles = ((size_t)n + SCAN_TILE - 1) / SCAN_TILE;
-    o->tile_sum = ar.take<double>(tiles + 1);
-    o->tile_off = ar.take<double>(tiles + 1);
-    o->mark = ar.take<int32_t>((size_t)n);
-    o->front[0] = ar.take<int32_t>((size_t)n);
-    o->front[1] = ar.take<int32_t>((size_t)n);
-    o->probs = ar.take<float>((size_t)n);
-    o->part_max = ar.take<float>(FINISH_GRID);
-    o->part_inf = ar.take<int32_t>(FINISH_GRID);
-    o->plan_ints = plan_ints_bound(n);
-    o->plan_blob = ar.take<int32_t>(o->plan_ints);
-    o->plan_val = ar.take<float>(o->plan_ints);
-    o->tail_leaf = ar.take<uint16_t>(NP_BUFSIZE);
-    o->progress = ar.take<int32_t>(4);
-    return o->progress != nullptr;
+// geo_kpp_chain's layout: carved from the caller's workspace, measured by geo_kpp_workspace_bytes.
+void carve(geo::Arena &ar, int32_t n, KppWs &o) {
+    const size_t N = (size_t)n, tiles = (N + SCAN_TILE - 1) / SCAN_TILE;
+    ar.take(o.ctl, 4); ar.take(o.state, 4);
+    ar.take(o.u_dev, N); ar.take(o.d, N); ar.take(o.cdf, N);
+    ar.take(o.tile_sum, tiles + 1); ar.take(o.tile_off, tiles + 1);
+    ar.take(o.mark, N); ar.take(o.front[0], N); ar.take(o.front[1], N); ar.take(o.probs, N);
+    ar.take(o.part_max, FINISH_GRID); ar.take(o.part_inf, FINISH_GRID);
+    o.plan_ints = plan_ints_bound(n);
+    ar.take(o.plan_blob, o.plan_ints); ar.take(o.plan_val, o.plan_ints);
+    ar.take(o.tail_leaf, NP_BUFSIZE);
+    ar.take(o.progress, 4);
 }
 
 enum class ChainMode { Budgeted, Step, Resident };
@@ -1594,14 +1584,17 @@ int run_resident(ChainCtx &c, int32_t it0, int32_t it1, int32_t *status_out) {
     return GEO_OK;
 }
 
+constexpr size_t KPP_RESERVE = 3840;     // what the query answers beyond the measured layout (4096 less `progress`)
+
 }  // namespace
 
 extern "C" size_t geo_kpp_workspace_bytes(int32_t n) {
     if (n <= 0) return 4096;
-    const size_t tiles = ((size_t)n + SCAN_TILE - 1) / SCAN_TILE;
-    return geo::align_up(4 * sizeof(KppCtl)) + geo::align_up(4 * sizeof(KppState)) + 3 * geo::align_up((size_t)n * 8) + 2 * geo::align_up((tiles + 1) * 8) +
-           5 * geo::align_up((size_t)n * 4) + 2 * geo::align_up(FINISH_GRID * 4) +
-           2 * geo::align_up(plan_ints_bound(n) * 4) + geo::align_up(NP_BUFSIZE * 2) + 4096;
+    geo::Arena ar;
+    KppWs w;
+    carve(ar, n, w);
+    ar.take<int32_t>((size_t)n);        // a fifth n-int array that the answer has always counted and no kernel uses
+    return ar.off + KPP_RESERVE;
 }
 
 extern "C" int32_t geo_kpp_resident_max_nodes(void) { return PG_MAX_NODES; }
@@ -1629,8 +1622,10 @@ extern "C" int geo_kpp_chain(const int32_t *indptr, const int32_t *indices, cons
     c.s = static_cast<hipStream_t>(stream_);
     c.indptr = indptr; c.indices = indices; c.weights = weights; c.n = n; c.n_centers_total = n_centers_total;
     c.centers = centers; c.argmin = argmin; c.is_center = is_center; c.dmin = dmin; c.u_host = u_host;
-    if (!carve(ws, ws_bytes, n, &c.w)) {
-        geo::set_error("geo_kpp_chain: workspace %zu too small", ws_bytes);
+    geo::Arena ar(ws, ws_bytes);
+    carve(ar, n, c.w);
+    if (!ar.ok()) {
+        geo::set_error("geo_kpp_chain: workspace %zu too small (%zu needed)", ws_bytes, ar.off);
         return GEO_E_WORKSPACE;
     }
     const KppWs &w = c.w;

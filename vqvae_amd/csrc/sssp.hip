@@ -1138,23 +1138,11 @@ struct MultiBufs {
     double *wsum;
 };
 
-// Over a workspace it hands out the buffers, over none (base == nullptr) it only adds up their sizes.
-struct Carver {
-    char *base;
-    size_t off = 0;
-    template <typename T>
-    void take(T *&p, size_t count) {
-        p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += geo::align_up(count * sizeof(T));
-    }
-};
-
 // slots of a solve: whole batches of `sb` sources, and (for the 32-source fixed-point layout of the same buffers) of 32
 size_t padded_slots(int32_t nb, int32_t sb) { return ((size_t)nb * sb + 31) / 32 * 32; }
 
-// The one description of the layout: the buffers of plan `p` carved from `ws` (or only measured); returns their bytes.
-size_t lay_out(const MultiPlan &p, int32_t n, int64_t nnz, bool with_pred, void *ws, MultiBufs &b) {
-    Carver c{static_cast<char *>(ws)};
+// The one description of the layout: the buffers of plan `p` carved from (or only measured on) `c`; returns their bytes.
+size_t lay_out(const MultiPlan &p, int32_t n, int64_t nnz, bool with_pred, geo::Arena &c, MultiBufs &b) {
     b = MultiBufs{};
     const size_t slots = padded_slots(p.nb, p.sb), nb = (size_t)p.nb, cs = (size_t)p.cs;
     c.take(b.dist, slots * n);
@@ -1201,15 +1189,22 @@ size_t lay_out(const MultiPlan &p, int32_t n, int64_t nnz, bool with_pred, void 
     return c.off;
 }
 
+// geo_sssp_single_update's layout
+struct SingleBufs { double *d; int32_t *flags; };
+SingleBufs lay_out_single(geo::Arena &c, int32_t n) { return {c.take<double>((size_t)n), c.take<int32_t>(4)}; }
+
 }  // namespace
 
 // Covers every plan the options can select after the query: both batch widths (chunked where 16 per batch is), predecessors wanted.
 extern "C" size_t geo_sssp_workspace_bytes(int32_t n, int64_t nnz, int32_t n_sources) {
     if (n < 0 || n_sources < 0 || nnz < 0) return 0;
     const int32_t nn = n > 0 ? n : 1, ss = n_sources > 0 ? n_sources : 1;
-    size_t bytes = geo::align_up((size_t)nn * sizeof(double)) + 256;          // geo_sssp_single_update: d[n], 4 flags
+    size_t bytes = geo::measure(lay_out_single, nn);
     MultiBufs b;
-    for (int sb : {16, 64}) bytes = std::max(bytes, lay_out(make_plan(nn, ss, sb), nn, nnz, true, nullptr, b));
+    for (int sb : {16, 64}) {
+        geo::Arena multi;
+        bytes = std::max(bytes, lay_out(make_plan(nn, ss, sb), nn, nnz, true, multi, b));
+    }
     return bytes;
 }
 
@@ -1238,12 +1233,12 @@ struct MultiCall {
 
 // Plan `c.plan`'s buffers from the caller's workspace.
 int carve(MultiCall &c, void *ws, size_t ws_bytes) {
-    const size_t need = lay_out(c.plan, c.n, c.nnz, c.P_out != nullptr, nullptr, c.buf);
-    if (ws_bytes < need) {
+    geo::Arena ar(ws, ws_bytes);
+    const size_t need = lay_out(c.plan, c.n, c.nnz, c.P_out != nullptr, ar, c.buf);
+    if (!ar.ok()) {
         geo::set_error("geo_sssp_multi: workspace %zu < %zu", ws_bytes, need);
         return GEO_E_WORKSPACE;
     }
-    lay_out(c.plan, c.n, c.nnz, c.P_out != nullptr, ws, c.buf);
     return GEO_OK;
 }
 
@@ -2068,11 +2063,25 @@ __global__ __launch_bounds__(64) void voronoi_resolve_kernel(const float *__rest
     }
 }
 
+namespace {
+// geo_sssp_nearest_source's layout; the suspects' rows are solved by sssp_multi_impl in a workspace of its own inside this one.
+struct NearestBufs { VPair *key; uint32_t *wunits, *scratch; float *Dsus; char *multi_ws; size_t multi_bytes; };
+NearestBufs lay_out_nearest(geo::Arena &c, int32_t n, int64_t nnz) {
+    NearestBufs b;
+    c.take(b.key, (size_t)n);
+    c.take(b.wunits, (size_t)nnz);                 // (no edges: no bytes, and no kernel touches it)
+    c.take(b.scratch, 128);
+    c.take(b.Dsus, (size_t)NEAREST_MAX_SUSPECTS * n);
+    b.multi_bytes = geo_sssp_workspace_bytes(n, nnz, NEAREST_MAX_SUSPECTS);
+    c.take(b.multi_ws, b.multi_bytes);
+    return b;
+}
+constexpr size_t NEAREST_RESERVE = 3840;     // what the query answers beyond the measured layout
+}  // namespace
+
 extern "C" size_t geo_sssp_nearest_workspace_bytes(int32_t n, int64_t nnz) {
     if (n <= 0 || nnz < 0) return 1024;
-    return geo::align_up((size_t)n * sizeof(VPair)) + geo::align_up((size_t)nnz * 4) + 4096 +
-           geo::align_up((size_t)NEAREST_MAX_SUSPECTS * n * sizeof(float)) +
-           geo_sssp_workspace_bytes(n, nnz, NEAREST_MAX_SUSPECTS) + 256;
+    return geo::measure(lay_out_nearest, n, nnz) + NEAREST_RESERVE;
 }
 
 extern "C" int geo_sssp_nearest_source(const int32_t *indptr, const int32_t *indices, const float *weights, int32_t n,
@@ -2088,16 +2097,14 @@ extern "C" int geo_sssp_nearest_source(const int32_t *indptr, const int32_t *ind
     status_out[3] = 0;                                         // why declined: 1 weights, 2 distance limit, 3 too many suspects, 4 K
     if (n_sources >= (1 << V_LABEL_BITS) - 1) { status_out[3] = 4; return GEO_OK; }
     geo::Arena ar(ws, ws_bytes);
-    VPair *key = ar.take<VPair>((size_t)n);
-    uint32_t *wunits = ar.take<uint32_t>((size_t)(nnz > 0 ? nnz : 1));
-    uint32_t *scratch = ar.take<uint32_t>(128);
-    float *Dsus = ar.take<float>((size_t)NEAREST_MAX_SUSPECTS * n);
-    const size_t multi_bytes_needed = geo_sssp_workspace_bytes(n, nnz, NEAREST_MAX_SUSPECTS);
-    char *multi_ws = ar.take<char>(multi_bytes_needed);
-    if (!key || !wunits || !scratch || !Dsus || !multi_ws) {
-        geo::set_error("geo_sssp_nearest_source: workspace %zu too small", ws_bytes);
+    const NearestBufs nb = lay_out_nearest(ar, n, nnz);
+    if (!ar.ok()) {
+        geo::set_error("geo_sssp_nearest_source: workspace %zu too small (%zu needed)", ws_bytes, ar.off);
         return GEO_E_WORKSPACE;
     }
+    VPair *key = nb.key;
+    uint32_t *wunits = nb.wunits, *scratch = nb.scratch;
+    float *Dsus = nb.Dsus;
     int shift = 0;
     if (weights && nnz > 0) {
         const uint32_t init[4] = {0xffffffffu, 0u, 0u, 0xffffffffu};
@@ -2159,7 +2166,7 @@ extern "C" int geo_sssp_nearest_source(const int32_t *indptr, const int32_t *ind
     if (hinfo[1] > 0 && argmin_out) {
         // d(suspect, .) rows: same weights, same exact sums, same float32 cast as the K x N matrix's column entries
         if (int rc = sssp_multi_impl(indptr, indices, weights, n, nnz, suspects, hinfo[1], Dsus, nullptr, nullptr, nullptr,
-                                     multi_ws, multi_bytes_needed, nullptr, stream_, 0))
+                                     nb.multi_ws, nb.multi_bytes, nullptr, stream_, 0))
             return rc;
         voronoi_resolve_kernel<<<(unsigned)hinfo[1], 64, 0, stream>>>(Dsus, n, suspects, sources, n_sources, dmin_out, argmin_out);
         GEO_LAUNCH_CHECK();
@@ -2189,9 +2196,8 @@ extern "C" int geo_sssp_single_update(const int32_t *indptr, const int32_t *indi
     GEO_REQUIRE(n > 0 && source >= 0 && source < n, "geo_sssp_single_update: bad n=%d source=%d", n, source);
     GEO_REQUIRE(indptr && indices && ws, "geo_sssp_single_update: null pointer");
     geo::Arena ar(ws, ws_bytes);
-    double *d = ar.take<double>((size_t)n);
-    int32_t *flags = ar.take<int32_t>(4);
-    if (!d || !flags) {
+    const auto [d, flags] = lay_out_single(ar, n);
+    if (!ar.ok()) {
         geo::set_error("geo_sssp_single_update: workspace too small");
         return GEO_E_WORKSPACE;
     }
