@@ -1,5 +1,9 @@
-"""Every kernel that takes its scratch from vqvae_amd._device.workspace(), run at EXACTLY the size its *_workspace_bytes query
-answers, between guard bands, on scratch that holds zeros, ones or the leftovers of another problem (tests/ws_guard.py).
+"""The geometry side's kernels that take their scratch from vqvae_amd._device.workspace() -- graph build, clustering, shortest
+paths, the spatial pull-back, the feature moments -- run at EXACTLY the size their *_workspace_bytes query answers, between
+guard bands, on scratch that holds zeros, ones or the leftovers of another problem (tests/ws_guard.py).  The model side (image
+encode and decode, LPIPS, the vanilla pull-back, the metric tensor, and the entry points that allocate their scratch per call:
+k-means, the quantizer, the ELBO, the prior's decode) is in tests/test_gpu_workspace_hygiene_models.py; between them the two
+reach every module of the package that hands a kernel scratch.
 
 Production hands the library a grow-only buffer that is at least 256 bytes (after a JVP stage: gigabytes) larger than asked
 for and holds what the last kernel left there, so a query that under-reports, an index a little past the last carve and a read

@@ -3,7 +3,8 @@
 vqvae_amd._device.workspace() hands every kernel one grow-only buffer of at least `nbytes + 256` bytes that holds whatever
 the previous kernel left in it.  GuardedWorkspace.workspace() is a drop-in that hands out EXACTLY `nbytes`, between two guard
 bands, with a payload the test chooses -- so a query that under-reports, an index a little past the last carve and a read of
-scratch the call never wrote can all fail a test.
+scratch the call never wrote can all fail a test.  Four modules allocate per call instead (SEAMS: one exact-size torch.empty
+behind a module-level `_workspace`); install() replaces those too, so their wrappers get the same guarded, pre-filled bytes.
 
 Payload patterns (all chosen so that no stray read can become an out-of-range address):
   "zeros"   every byte 0
@@ -20,6 +21,10 @@ import torch
 GUARD = 65536
 GUARD_BYTE = 0xC3
 FILLS = ("zeros", "ones32", "stale")
+# Modules that take their scratch from the caching allocator, one exact-size torch.empty per call, through a module-level
+# `_workspace`: (nbytes, dev) everywhere but in cluster, whose `_workspace(dev, n, d, K, S, L)` asks the size query itself.
+CLUSTER_SEAM = "vqvae_amd.cluster"
+SEAMS = (CLUSTER_SEAM, "vqvae_amd.vae", "vqvae_amd.prior.sampling", "vqvae_amd.baseline.model")
 
 
 class GuardedWorkspace:
@@ -76,10 +81,18 @@ class GuardedWorkspace:
                         f"workspace of {nbytes} bytes: {name} guard damaged, first at payload offset {lo + first} "
                         f"({int(bad.numel())} bytes changed, byte there 0x{int(band[first]):02x})")
 
+    def _cluster_workspace(self, dev, n, d, K, S=1, L=1) -> torch.Tensor:
+        """Drop-in for vqvae_amd.cluster._workspace, which sizes its scratch itself: the same query, the same refusal."""
+        from vqvae_amd import _lib
+        nbytes = _lib.load().geo_kmeans_workspace_bytes(n, d, K, S, L)
+        if nbytes == 0:
+            raise _lib.GeoHipError(f"geo_kmeans_workspace_bytes rejected n={n} d={d} K={K} starts={S} trials={L}")
+        return self.workspace(nbytes, dev)
+
     def install(self, monkeypatch) -> set:
-        """Replace `workspace` in vqvae_amd._device and in every loaded vqvae_amd.* module that imported it by name.
-        Returns the names of the patched modules."""
-        for name in ("vqvae_amd.geo", "vqvae_amd._export", "vqvae_amd.geo.analysis"):
+        """Replace `workspace` in vqvae_amd._device and in every loaded vqvae_amd.* module that imported it by name, and the
+        `_workspace` of the SEAMS modules, which allocate their scratch per call.  Returns the names of the patched modules."""
+        for name in ("vqvae_amd.geo", "vqvae_amd._export", "vqvae_amd.geo.analysis") + SEAMS:
             importlib.import_module(name)
         from vqvae_amd import _device
         original = _device.workspace
@@ -93,6 +106,12 @@ class GuardedWorkspace:
                 monkeypatch.setattr(mod, "workspace", self.workspace)
                 patched.add(name)
         assert "vqvae_amd._device" in patched
+        for name in SEAMS:
+            mod = sys.modules[name]
+            seam = vars(mod)["_workspace"]            # a KeyError here: the module lost its seam
+            assert callable(seam), (name, seam)
+            monkeypatch.setattr(mod, "_workspace", self._cluster_workspace if name == CLUSTER_SEAM else self.workspace)
+            patched.add(name)
         return patched
 
 

@@ -64,6 +64,11 @@ def _ptr(t: torch.Tensor) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _workspace(nbytes: int, dev) -> torch.Tensor:
+    """The quantizer's scratch: one exact-size allocation per call from the stream-ordered caching allocator (no device sync)."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
 class _VQFunction(torch.autograd.Function):
     """HIP forward (labels, z_q, z_q_st, idx, loss, stats and, in training, the EMA update in place) and backward."""
 
@@ -84,7 +89,7 @@ class _VQFunction(torch.autograd.Function):
         nbytes = L.geo_vq_workspace_bytes(n, C, K)
         if nbytes == 0:
             raise _lib.GeoHipError(f"geo_vq_workspace_bytes rejected n={n} C={C} K={K} (C <= 128, K <= 4096)")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _workspace(nbytes, dev)
         z_q = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
         z_q_st = torch.empty_like(z_q)
         idx = torch.empty(B, H, W, dtype=torch.int64, device=dev)

@@ -81,6 +81,11 @@ def _desc(model: Transformer):
     return d, blocks
 
 
+def _workspace(nbytes: int, dev) -> torch.Tensor:
+    """The decode's scratch: one exact-size allocation per call from the stream-ordered caching allocator (no device sync)."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
 def sample_native(model: Transformer, x: torch.Tensor, steps: int, temperature: float, top_k: Optional[int],
                   y: Optional[torch.Tensor], uniforms: Optional[torch.Tensor], return_logits: bool = False):
     """The HIP decode (csrc/prior_sample.hip).  Returns tokens int64 [B, T0 + steps] (and, with return_logits, the logits of
@@ -112,7 +117,7 @@ def sample_native(model: Transformer, x: torch.Tensor, steps: int, temperature: 
     L = _lib.load()
     desc, _blocks = _desc(model)
     nbytes = L.geo_prior_sample_workspace_bytes(ctypes.byref(desc), B, max(T0 + steps - 1, 1))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # stream-ordered caching allocator: no device sync
+    ws = _workspace(nbytes, dev)
     with torch.cuda.device(dev):
         _lib.check(L.geo_prior_sample(ctypes.byref(desc), ptr(x), T0, steps, ptr(y), ptr(uniforms) if steps else None,
                                       float(temperature), int(top_k or 0), ptr(tokens), ptr(logits), B, ptr(ws), nbytes,

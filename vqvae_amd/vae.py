@@ -109,6 +109,11 @@ def _ptr(t: torch.Tensor) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _workspace(nbytes: int, dev) -> torch.Tensor:
+    """The ELBO's scratch: one exact-size allocation per call from the stream-ordered caching allocator (no device sync)."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
 class _ElboFunction(torch.autograd.Function):
     """out f64 [4] = total, recon, kl, regulated kl (geo_vae_elbo_forward); only out[0] carries a gradient."""
 
@@ -129,7 +134,7 @@ class _ElboFunction(torch.autograd.Function):
         if nbytes == 0:
             raise _lib.GeoHipError(f"geo_vae_elbo_workspace_bytes rejected B={B} P={P} d={d}")
         dev = l.device
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _workspace(nbytes, dev)
         out = torch.empty(4, dtype=torch.float64, device=dev)
         has_fb = free_bits is not None
         args = (B, P, d, int(recon_mode), int(has_fb), float(free_bits) if has_fb else 0.0, float(beta), float(target),
