@@ -6,6 +6,13 @@
 // _argkmin.pyx.tp:492-502, used for d > 15) or directly as sum (x-y)^2 (kd-tree path, d <= 15);
 // both are fma chains over the dimensions in ascending order, ties are ordered by index.
 //
+// THE KEY is stated once, in f32x4_to_f64 / key_chain / key_close below: the candidate's float32 coordinates converted to fp64,
+// the chain over the zero-padded dimensions a chunk at a time, the expansion form closed by (n_a + (-2 acc)) + n_b and clamped
+// at 0, the direct form its chain.  Every search kernel of this file (knn_kernel, knn_bound_kernel, knn_refine_kernel,
+// nearest_foreign_kernel) forms its keys with these three and differs only in its schedule around them; a new one does the same.
+// (One exception, with its reason where it stands: nearest_foreign_kernel writes the closing out around its branch on the order of
+// the two norms.)
+//
 // Mapping: one wave owns Q query rows; every lane owns ONE candidate row per step (64 candidates
 // per step, coordinates converted f32->f64 once and reused for the Q queries).  Query coordinates
 // are wave-uniform and stream through the scalar cache (fp64 copy in the workspace), so the
@@ -18,6 +25,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -30,6 +38,39 @@ __device__ __forceinline__ double readlane_f64(double x, int lane) {
     const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), lane);
     const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+// Four float32 coordinates of a candidate row (one 16-byte load, issued by the caller on its own schedule) as fp64.  A row chunk
+// is DCH / 4 of these, looped over in the caller: a chunk-wide helper with the loop inside is unrolled on its own before it is
+// inlined, and the kernels then allocate differently (knn_bound_kernel<16, 8, 2, true> 108 -> 114 VGPRs, knn_kernel<8, 4, false, 1>
+// 54 -> 101 with SGPRs spilled to lanes); this way they compile to the instructions they had with the conversion written out.
+__device__ __forceinline__ void f32x4_to_f64(const float4 &f, double *c) {
+    c[0] = (double)f.x; c[1] = (double)f.y; c[2] = (double)f.z; c[3] = (double)f.w;
+}
+
+// the chain over DCH consecutive dimensions: qv = the query's fp64 coordinates there (a wave-uniform address in every caller)
+template <int DCH, bool EXPANSION>
+__device__ __forceinline__ double key_chain(const double *qv, const double (&cj)[DCH], double acc) {
+#pragma unroll
+    for (int k = 0; k < DCH; ++k) {
+        if (EXPANSION) {
+            acc = fma(qv[k], cj[k], acc);
+        } else {
+            const double t = qv[k] - cj[k];
+            acc = fma(t, t, acc);
+        }
+    }
+    return acc;
+}
+
+// the finished chain -> the key.  Expansion form: the two squared norms in the caller's order (sklearn adds the query's first;
+// the sum is not symmetric in them), clamped at 0 -- a norm of +inf added last stays +inf.  Direct form: the chain itself.
+template <bool EXPANSION>
+__device__ __forceinline__ double key_close(double acc, double n_first, double n_last) {
+    if (!EXPANSION) return acc;
+    double d2 = (n_first + (-2.0 * acc)) + n_last;
+    if (!(d2 > 0.0)) d2 = 0.0;
+    return d2;
 }
 
 // zp32 [n][dp] f32 zero padded, zq64 [n][dp] f64 zero padded, nrm [n] fp64 fma-chain squared norms
@@ -83,37 +124,20 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ zp32
             double cj[DCH];
             const float4 *src = reinterpret_cast<const float4 *>(zp32 + jc * dp + ch * DCH);
 #pragma unroll
-            for (int v = 0; v < DCH / 4; ++v) {
-                const float4 f = src[v];
-                cj[4 * v] = (double)f.x; cj[4 * v + 1] = (double)f.y;
-                cj[4 * v + 2] = (double)f.z; cj[4 * v + 3] = (double)f.w;
-            }
+            for (int v = 0; v < DCH / 4; ++v) f32x4_to_f64(src[v], cj + 4 * v);
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
                 int64_t qr = q0 + q;
                 if (qr >= row1) qr = row1 - 1;
-                const double *__restrict__ qv = zq64 + qr * dp + ch * DCH;     // wave-uniform address
-#pragma unroll
-                for (int k = 0; k < DCH; ++k) {
-                    if (EXPANSION) {
-                        acc[q] = fma(qv[k], cj[k], acc[q]);
-                    } else {
-                        const double t = qv[k] - cj[k];
-                        acc[q] = fma(t, t, acc[q]);
-                    }
-                }
+                acc[q] = key_chain<DCH, EXPANSION>(zq64 + qr * dp + ch * DCH, cj, acc[q]);
             }
         }
         const double nj = EXPANSION ? nrm[jc] : 0.0;
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            double d2 = acc[q];
-            if (EXPANSION) {
-                int64_t qr = q0 + q;
-                if (qr >= row1) qr = row1 - 1;
-                d2 = (nrm_q[qr] + (-2.0 * d2)) + nj;
-                if (!(d2 > 0.0)) d2 = 0.0;
-            }
+            int64_t qr = q0 + q;
+            if (qr >= row1) qr = row1 - 1;
+            const double d2 = key_close<EXPANSION>(acc[q], EXPANSION ? nrm_q[qr] : 0.0, nj);
             unsigned long long hits = __ballot(valid && d2 < tau[q]);
             while (hits) {
                 const int src_lane = __builtin_ctzll(hits);
@@ -165,7 +189,7 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ zp32
 // 2. knn_scan_kernel: approximate squared distances of ALL pairs on the matrix cores (v_mfma_f32_32x32x2_f32, expansion
 //    form with the fp64 norms); pair (i, j) is kept when  approx <= tau[i] + eps * (|x_i|^2 + |x_j|^2),  eps far above
 //    the rounding of a d-term float32 dot product -- every true neighbour is kept, plus ~S * kq others.
-// 3. knn_refine_kernel: the kept candidates are re-evaluated with the same fp64 fma chains as knn_kernel and ranked
+// 3. knn_refine_kernel: the kept candidates are re-evaluated with the fp64 key and ranked
 //    by (distance, index): the result is the one knn_kernel gives.  A query whose list overflows FILTER_CAP (heavily
 //    duplicated points) is reported and the caller falls back to knn_kernel.
 constexpr int FILTER_STRIDE = 8, FILTER_STRIDE_MIN = 4, FILTER_CAP = 1024;
@@ -191,14 +215,84 @@ __global__ __launch_bounds__(256) void knn_subset_kernel(const float *__restrict
     }
 }
 
-// u[i] = tau[i] - |x_i|^2 (1 - eps): the scan keeps (i, j) when  |x_j|^2 (1 - eps) - 2 x_i.x_j <= u[i]
-// (two-level path only: tau from the kq-th entry of the refined subset lists; knn_bound_kernel writes u itself)
+// ---- what the scans compare, stated once: pair (i, j) is kept when  |x_j|^2 (1 - eps) - 2 x_i.x_j <= u[i]  with
+// u[i] = tau[i] - |x_i|^2 (1 - eps).  In float32 u is rounded UP and the norm column DOWN, so rounding only ever keeps more.
+__device__ __forceinline__ double scan_threshold(double tau, double nq, double eps) { return tau + eps * nq - nq; }
+
+__device__ __forceinline__ float f32_round_up(double x) {
+    float r = (float)x;
+    if ((double)r < x) r = nextafterf(r, 3.4e38f);
+    return r;
+}
+
+__device__ __forceinline__ float f32_round_down(double x) {
+    float r = (float)x;
+    if ((double)r > x) r = nextafterf(r, -3.4e38f);
+    return r;
+}
+
+// |x_j|^2 (1 - eps) of the norm column
+__device__ __forceinline__ float scan_norm(double nrm, double eps) { return f32_round_down(nrm * (1.0 - eps)); }
+
+// the corpus tiles [lo, hi) of SCAN_CT candidates that slice `split` of `splits` scans (empty when lo >= hi)
+struct TileRange { int64_t lo, hi; };
+__device__ __forceinline__ TileRange split_tiles(int64_t n, int scan_ct, int splits, int split) {
+    const int64_t all_tiles = (n + scan_ct - 1) / scan_ct, per_split = (all_tiles + splits - 1) / splits;
+    const int64_t lo = per_split * split;
+    return {lo, lo + per_split < all_tiles ? lo + per_split : all_tiles};
+}
+
+// ---- the kept-pair queue of the scans.  Kept pairs go to a per-wave LDS queue first (the returning global atomic that reserves
+// a list slot costs microseconds, too much inside the MFMA stream; the queue is flushed at tile ends).  A lane holds the pairs it
+// keeps as set bits of one word (each scan packs its own); lanes take their set bits one per round and get queue positions from
+// the round's ballot: no LDS atomics, a handful of branches per tile with something to keep.
+constexpr int EQ_CAP = 128;
+struct KeptQueue {
+    unsigned long long *eb;            // this wave's EQ_CAP entries in LDS: (local query row << 32) | candidate
+    int32_t *cnt, *list;               // [rows], [rows][FILTER_CAP]
+    int qn;                            // pairs queued by this wave (wave-uniform)
+
+    __device__ __forceinline__ void to_list(int32_t row, int32_t cand) const {
+        const int32_t slot = atomicAdd(&cnt[row], 1);
+        if (slot < FILTER_CAP) list[(int64_t)row * FILTER_CAP + slot] = cand;
+    }
+    __device__ __forceinline__ void flush(int lane) {           // wave-uniform call
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        const int m = qn < EQ_CAP ? qn : EQ_CAP;
+        for (int i = lane; i < m; i += 64) {
+            const unsigned long long e = eb[i];
+            to_list((int32_t)(e >> 32), (int32_t)(e & 0xffffffffu));
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        qn = 0;
+    }
+    // pair_of(b) = the (row, candidate) of this lane's bit b
+    template <class PairOf>
+    __device__ __forceinline__ void take(unsigned bits, PairOf pair_of) {
+        for (;;) {
+            const unsigned long long hit = __ballot(bits != 0);
+            if (!hit) break;
+            if (bits != 0) {
+                const int b = __builtin_ctz(bits);
+                bits &= bits - 1;
+                const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hit >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hit, 0u));
+                const int2 rc = pair_of(b);
+                if (pos < EQ_CAP) eb[pos] = ((unsigned long long)(unsigned)rc.x << 32) | (unsigned)rc.y;
+                else to_list(rc.x, rc.y);                     // queue full (masses of duplicates): straight to the list
+            }
+            qn += __builtin_popcountll(hit);
+        }
+    }
+};
+
+// the two-level path's thresholds: tau from the kq-th entry of the refined subset lists (knn_bound_kernel writes u itself)
 __global__ __launch_bounds__(256) void knn_tau_kernel(const double *__restrict__ d2_sub, const double *__restrict__ nrm,
                                                      int64_t row0, int64_t rows, int kq, double eps,
                                                      double *__restrict__ u, int32_t *__restrict__ cnt) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {
-        const double nq = nrm[row0 + i];
-        u[i] = d2_sub[i * kq + (kq - 1)] + eps * nq - nq;
+        u[i] = scan_threshold(d2_sub[i * kq + (kq - 1)], nrm[row0 + i], eps);
         cnt[i] = 0;
     }
 }
@@ -214,8 +308,8 @@ __global__ __launch_bounds__(256) void knn_tau_kernel(const double *__restrict__
 // candidates than the exact one at (kq, S) = (21, 16), 5 % at (40, 8), 14 % at (64, 4) (20 000 normal rows, d = 16); one
 // minimum per lane loses 20 % - 5x.  Lists longer than 24 keep THREE per lane (192 values, 0.6 % and 2 % more candidates).
 //
-// One workgroup owns Q queries; its four waves take the subset's 64-row steps round robin (same key chains as knn_kernel and
-// knn_refine_kernel: query coordinates wave-uniform through the scalar cache, the next step's row in flight under the fmas),
+// One workgroup owns Q queries; its four waves take the subset's 64-row steps round robin (query coordinates wave-uniform
+// through the scalar cache, the next step's row in flight under the fmas),
 // leave their minima in LDS, and each wave then merges and selects for Q / 4 of the queries.  30 000 waves of 15 steps at
 // 60 000 queries x 3 750 rows where knn_kernel<.., 16> had 3 750 of 59, and a rank's share of the rows still fills the chip.
 constexpr int BOUND_Q = 8;
@@ -298,10 +392,7 @@ __global__ __launch_bounds__(256) void knn_bound_kernel(const float *__restrict_
     while (s < steps) {
         double cj[DCH];
 #pragma unroll
-        for (int v = 0; v < DCH / 4; ++v) {
-            cj[4 * v] = (double)f[v].x; cj[4 * v + 1] = (double)f[v].y;
-            cj[4 * v + 2] = (double)f[v].z; cj[4 * v + 3] = (double)f[v].w;
-        }
+        for (int v = 0; v < DCH / 4; ++v) f32x4_to_f64(f[v], cj + 4 * v);
         if (ch == 0) {
             nj = nj_next;
 #pragma unroll
@@ -315,27 +406,11 @@ __global__ __launch_bounds__(256) void knn_bound_kernel(const float *__restrict_
         for (int q = 0; q < Q; ++q) {
             int64_t qr = q0 + q;
             if (qr >= row1) qr = row1 - 1;
-            const double *__restrict__ qv = zq64 + qr * dp + ch * DCH;         // wave-uniform address
-#pragma unroll
-            for (int k = 0; k < DCH; ++k) {
-                if (EXPANSION) {
-                    acc[q] = fma(qv[k], cj[k], acc[q]);
-                } else {
-                    const double t = qv[k] - cj[k];
-                    acc[q] = fma(t, t, acc[q]);
-                }
-            }
+            acc[q] = key_chain<DCH, EXPANSION>(zq64 + qr * dp + ch * DCH, cj, acc[q]);
         }
         if (ch == nch - 1) {
 #pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                double d2 = acc[q];
-                if (EXPANSION) {
-                    d2 = (nq[q] + (-2.0 * d2)) + nj;
-                    if (!(d2 > 0.0)) d2 = 0.0;
-                }
-                keep_smallest<NM>(mn[q], d2);
-            }
+            for (int q = 0; q < Q; ++q) keep_smallest<NM>(mn[q], key_close<EXPANSION>(acc[q], nq[q], nj));
         }
         s = s_n;
         ch = ch_n;
@@ -360,8 +435,7 @@ __global__ __launch_bounds__(256) void knn_bound_kernel(const float *__restrict_
         const double tau = kth_of_wave<NM>(a, kq);
         if (lane == 0) {
             if (u) {
-                const double nq = nrm_q[qr];
-                u[qr - row0] = tau + eps * nq - nq;
+                u[qr - row0] = scan_threshold(tau, nrm_q[qr], eps);
                 cnt[qr - row0] = 0;
             }
             if (tau_out) tau_out[qr - row0] = tau;
@@ -390,17 +464,11 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(const float *__restrict__
         const int64_t q = live ? qbase + r : rows - 1;
 #pragma unroll
         for (int i = 0; i < KI - 1; ++i) a[i] = -2.0f * zp32[(row0 + q) * DP + 2 * i + h];
-        float ur = -3.0e38f;                                   // padded queries keep nothing
-        if (live) {
-            const double ud = u[q];
-            ur = (float)ud;
-            if ((double)ur < ud) ur = nextafterf(ur, 3.4e38f);
-        }
+        const float ur = live ? f32_round_up(u[q]) : -3.0e38f;  // padded queries keep nothing
         a[KI - 1] = h == 0 ? 1.0f : -ur;
     }
-    const int64_t all_tiles = (n + SCAN_CT - 1) / SCAN_CT, per_split = (all_tiles + splits - 1) / splits;
-    const int64_t tile_lo = per_split * split;
-    const int64_t n_tiles = tile_lo + per_split < all_tiles ? tile_lo + per_split : all_tiles;
+    const TileRange tiles = split_tiles(n, SCAN_CT, splits, split);
+    const int64_t tile_lo = tiles.lo, n_tiles = tiles.hi;
     if (tile_lo >= n_tiles) return;
     // staging in two halves: the global loads of the next tile are issued before the MFMAs of the current one and
     // written to the other LDS buffer after them
@@ -418,12 +486,7 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(const float *__restrict__
         }
         if (threadIdx.x < SCAN_CT) {
             const int64_t jj = c0 + threadIdx.x;
-            nval = 3.0e38f;                                    // beyond the corpus: never kept
-            if (jj < n) {
-                const double nd = nrm[jj] * (1.0 - eps);
-                nval = (float)nd;
-                if ((double)nval > nd) nval = nextafterf(nval, -3.4e38f);
-            }
+            nval = jj < n ? scan_norm(nrm[jj], eps) : 3.0e38f;  // beyond the corpus: never kept
         }
     };
     auto put = [&](int buf) {
@@ -437,27 +500,11 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(const float *__restrict__
             Bs[buf][threadIdx.x >> 5][KI - 1][32 + (threadIdx.x & 31)] = 1.0f;
         }
     };
-    constexpr int EQ_CAP = 128;
     __shared__ unsigned long long eb[4][EQ_CAP];
-    int qn = 0;                                                // pairs queued by this wave (wave-uniform)
-    auto flush = [&]() {                                       // wave-uniform call
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        const int m = qn < EQ_CAP ? qn : EQ_CAP;
-        for (int i = lane; i < m; i += 64) {
-            const unsigned long long e = eb[wave][i];
-            const int64_t row = (int64_t)(e >> 32);
-            const int32_t slot = atomicAdd(&cnt[row], 1);
-            if (slot < FILTER_CAP) list[row * FILTER_CAP + slot] = (int32_t)(e & 0xffffffffu);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        qn = 0;
-    };
-    // Kept pairs go to a per-wave LDS queue first (the returning global atomic that reserves a list slot costs
-    // microseconds, too much inside the MFMA stream; the queue is flushed at tile ends).  The signs of a lane's 32
-    // accumulator entries (two column tiles) are packed into one word; lanes then take their set bits one per round and
-    // get queue positions from the round's ballot: no LDS atomics, a handful of branches per 2 048 pairs.
+    KeptQueue kept = {eb[wave], cnt, list, 0};
+    // The signs of a lane's 32 accumulator entries (two column tiles) are packed into one word for the queue: a handful of
+    // branches per 2 048 pairs.
+    const int32_t rowb = (int32_t)qbase + 4 * h;               // local row of accumulator entry q: rowb + (q & 3) + 8 (q >> 2)
     auto keep_pairs = [&](const f32x16v &acc0, const f32x16v &acc1, int64_t cand0) {
         unsigned any = 0;
 #pragma unroll
@@ -469,25 +516,10 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(const float *__restrict__
             bits |= (__float_as_uint(acc0[q]) >> 31) << q;
             bits |= (__float_as_uint(acc1[q]) >> 31) << (16 + q);
         }
-        for (;;) {
-            const unsigned long long hit = __ballot(bits != 0);
-            if (!hit) break;
-            if (bits != 0) {
-                const int b = __builtin_ctz(bits);
-                bits &= bits - 1;
-                const int q = b & 15;
-                const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hit >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hit, 0u));
-                const int64_t row = qbase + (q & 3) + 8 * (q >> 2) + 4 * h;
-                const int32_t cand = (int32_t)(cand0 + (b >> 4) * 32 + r);
-                if (pos < EQ_CAP) {
-                    eb[wave][pos] = ((unsigned long long)row << 32) | (unsigned)cand;
-                } else {                                       // queue full (masses of duplicates): straight to the list
-                    const int32_t slot = atomicAdd(&cnt[row], 1);
-                    if (slot < FILTER_CAP) list[row * FILTER_CAP + slot] = cand;
-                }
-            }
-            qn += __builtin_popcountll(hit);
-        }
+        kept.take(bits, [&](int b) {
+            const int q = b & 15;
+            return make_int2(rowb + (q & 3) + 8 * (q >> 2), (int32_t)(cand0 + (b >> 4) * 32 + r));
+        });
     };
     fetch(tile_lo);
     put((int)(tile_lo & 1));
@@ -507,11 +539,11 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(const float *__restrict__
             }
             keep_pairs(acc0, acc1, tile * SCAN_CT + t * 32);       // a negative entry = a pair to keep
         }
-        if (qn >= EQ_CAP / 2) flush();
+        if (kept.qn >= EQ_CAP / 2) kept.flush(lane);
         if (tile + 1 < n_tiles) put(buf ^ 1);
         __syncthreads();
     }
-    flush();
+    kept.flush(lane);
 }
 
 // ---- the same filter on the bf16 matrix cores ---------------------------------------------------------------------------
@@ -544,13 +576,7 @@ __global__ __launch_bounds__(256) void knn_split_kernel(const float *__restrict_
         zb[(r * 2 + 1) * dpb + c] = bf16_rne(rest);
         if (c == 0) {
             // -|x_j|^2 (1 - eps), the magnitude rounded DOWN to float32 (the scan keeps a pair when acc < this)
-            float nval = 3.0e38f;
-            if (r < n) {
-                const double nd = nrm[r] * (1.0 - eps);
-                nval = (float)nd;
-                if ((double)nval > nd) nval = nextafterf(nval, -3.4e38f);
-            }
-            negn[r] = -nval;
+            negn[r] = -(r < n ? scan_norm(nrm[r], eps) : 3.0e38f);
         }
     }
 }
@@ -596,21 +622,15 @@ __global__ __launch_bounds__(256) void knn_scan_bf16_kernel(const unsigned short
 #pragma unroll
         for (int qq = 0; qq < 16; ++qq) {
             const int64_t row = qbase + (qq & 3) + 8 * (qq >> 2) + 4 * h;
-            float ur = -3.0e38f;                               // padded queries keep nothing
-            if (row < rows) {
-                const double ud = u[row];
-                ur = (float)ud;
-                if ((double)ur < ud) ur = nextafterf(ur, 3.4e38f);
-            }
+            const float ur = row < rows ? f32_round_up(u[row]) : -3.0e38f;   // padded queries keep nothing
             uq[qq] = -ur;                                      // the accumulator starts at -u (the MFMA's C operand)
         }
     }
     f32x16v negu;
 #pragma unroll
     for (int qq = 0; qq < 16; ++qq) negu[qq] = uq[qq];
-    const int64_t all_tiles = (n + SCAN_CT - 1) / SCAN_CT, per_split = (all_tiles + splits - 1) / splits;
-    const int64_t tile_lo = per_split * split;
-    const int64_t n_tiles = tile_lo + per_split < all_tiles ? tile_lo + per_split : all_tiles;
+    const TileRange tiles = split_tiles(n, SCAN_CT, splits, split);
+    const int64_t tile_lo = tiles.lo, n_tiles = tiles.hi;
     if (tile_lo >= n_tiles) return;
     // staging: a tile's candidates are one contiguous run of SCAN_CT x 4 DPB bytes in zb (rows padded to whole tiles by
     // knn_split_kernel, so no index is clamped): piece k * 256 + tid of 16 bytes per thread and k, from a wave-uniform base
@@ -637,29 +657,11 @@ __global__ __launch_bounds__(256) void knn_scan_bf16_kernel(const unsigned short
         }
         if (threadIdx.x < SCAN_CT) Nf[buf][threadIdx.x] = nval;
     };
-    constexpr int EQ_CAP = 128;
     __shared__ unsigned long long eb[4][EQ_CAP];
-    int qn = 0;                                                // pairs queued by this wave (wave-uniform)
-    auto flush = [&]() {                                       // wave-uniform call
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        const int m = qn < EQ_CAP ? qn : EQ_CAP;
-        for (int i = lane; i < m; i += 64) {
-            const unsigned long long e = eb[wave][i];
-            const int64_t row = (int64_t)(e >> 32);
-            const int32_t slot = atomicAdd(&cnt[row], 1);
-            if (slot < FILTER_CAP) list[row * FILTER_CAP + slot] = (int32_t)(e & 0xffffffffu);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        qn = 0;
-    };
-    // Kept pairs go to a per-wave LDS queue first (the returning global atomic that reserves a list slot costs
-    // microseconds, too much inside the MFMA stream; the queue is flushed at tile ends).  One 32 x 32 tile at a time: the lane's
-    // minimum against -n_j decides wave-wide whether anything is kept (8 v_min3 + a compare; ~70 % of the tiles end here).
-    // Otherwise the signs of acc - (-n_j) of a lane's 16 entries are packed into one word (the sign of a float32 difference is
-    // the sign of the exact difference, denormals included); lanes then take their set bits one per round and get queue
-    // positions from the round's ballot: no LDS atomics, a handful of branches per tile with something to keep.
+    KeptQueue kept = {eb[wave], cnt, list, 0};
+    // One 32 x 32 tile at a time: the lane's minimum against -n_j decides wave-wide whether anything is kept (8 v_min3 + a
+    // compare; ~70 % of the tiles end here).  Otherwise the signs of acc - (-n_j) of a lane's 16 entries are packed into one word
+    // for the queue (the sign of a float32 difference is the sign of the exact difference, denormals included).
     const int32_t rowb = (int32_t)qbase + 4 * h;               // local row of accumulator entry q: rowb + (q & 3) + 8 (q >> 2)
     auto keep_tile = [&](const f32x16v &acc, float negn, int32_t cand) {
         // (the two halves of the lane's entries separately: a tile that keeps something builds the sign word of one half only)
@@ -685,24 +687,10 @@ __global__ __launch_bounds__(256) void knn_scan_bf16_kernel(const unsigned short
             for (int q = 8; q < 16; ++q) w = __builtin_amdgcn_alignbit(w, __float_as_uint(acc[q] - negn), 31);
             bits |= w;
         }
-        for (;;) {
-            const unsigned long long hit = __ballot(bits != 0);
-            if (!hit) break;
-            if (bits != 0) {
-                const int b = __builtin_ctz(bits);
-                bits &= bits - 1;
-                const int q = 15 - b;
-                const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hit >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hit, 0u));
-                const int32_t row = rowb + (q & 3) + 8 * (q >> 2);
-                if (pos < EQ_CAP) {
-                    eb[wave][pos] = ((unsigned long long)(unsigned)row << 32) | (unsigned)cand;
-                } else {                                       // queue full (masses of duplicates): straight to the list
-                    const int32_t slot = atomicAdd(&cnt[row], 1);
-                    if (slot < FILTER_CAP) list[(int64_t)row * FILTER_CAP + slot] = cand;
-                }
-            }
-            qn += __builtin_popcountll(hit);
-        }
+        kept.take(bits, [&](int b) {
+            const int q = 15 - b;
+            return make_int2(rowb + (q & 3) + 8 * (q >> 2), cand);
+        });
     };
     fetch(tile_lo);
     put((int)(tile_lo & 1));
@@ -746,14 +734,14 @@ __global__ __launch_bounds__(256) void knn_scan_bf16_kernel(const unsigned short
             if (t > 0) keep_tile(accs[cur ^ 1], negn_prev, cand_t0 + (t - 1) * 32);   // an entry below -n_j = a pair to keep
         }
         keep_tile(accs[(NT - 1) & 1], negns[(NT - 1) & 1], cand_t0 + (NT - 1) * 32);
-        if (qn >= EQ_CAP / 2) flush();
+        if (kept.qn >= EQ_CAP / 2) kept.flush(lane);
         if (tile + 1 < n_tiles) put(buf ^ 1);
         __syncthreads();
     }
-    flush();
+    kept.flush(lane);
 }
 
-// one wave per query: exact fp64 distances of its kept candidates (same fma chains as knn_kernel) into LDS, then the
+// one wave per query: the keys of its kept candidates into LDS, then the
 // kq smallest in (distance, index) order -- the lists are a few hundred entries, unordered
 template <int DCH, bool EXPANSION>
 __global__ __launch_bounds__(256) void knn_refine_kernel(const float *__restrict__ zp32, const double *__restrict__ zq64,
@@ -797,30 +785,19 @@ __global__ __launch_bounds__(256) void knn_refine_kernel(const float *__restrict
 #pragma unroll
                 for (int v = 0; v < DCH / 4; ++v) f[u][v] = src[v];
             }
-            const double *__restrict__ qv = zq64 + qr * dp + ch * DCH;     // wave-uniform address
 #pragma unroll
-            for (int u = 0; u < U; ++u)
+            for (int u = 0; u < U; ++u) {
 #pragma unroll
                 for (int v = 0; v < DCH / 4; ++v) {
-                    const double c4[4] = {(double)f[u][v].x, (double)f[u][v].y, (double)f[u][v].z, (double)f[u][v].w};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        if (EXPANSION) {
-                            acc[u] = fma(qv[4 * v + k], c4[k], acc[u]);
-                        } else {
-                            const double t = qv[4 * v + k] - c4[k];
-                            acc[u] = fma(t, t, acc[u]);
-                        }
-                    }
+                    double c4[4];
+                    f32x4_to_f64(f[u][v], c4);
+                    acc[u] = key_chain<4, EXPANSION>(zq64 + qr * dp + ch * DCH + 4 * v, c4, acc[u]);
                 }
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            double d2 = acc[u];
-            if (EXPANSION) {
-                d2 = (nrm_q[qr] + (-2.0 * d2)) + nrm[j[u]];
-                if (!(d2 > 0.0)) d2 = 0.0;
-            }
+            const double d2 = key_close<EXPANSION>(acc[u], EXPANSION ? nrm_q[qr] : 0.0, EXPANSION ? nrm[j[u]] : 0.0);
             if (valid[u]) sv[wave][c0 + u * 64 + lane] = d2;
         }
     }
@@ -978,33 +955,23 @@ __global__ __launch_bounds__(256) void nearest_foreign_kernel(const float *__res
             double cj[DCH];
             const float4 *src = reinterpret_cast<const float4 *>(zp32 + jc * dp + ch * DCH);
 #pragma unroll
-            for (int v = 0; v < DCH / 4; ++v) {
-                const float4 f = src[v];
-                cj[4 * v] = (double)f.x; cj[4 * v + 1] = (double)f.y;
-                cj[4 * v + 2] = (double)f.z; cj[4 * v + 3] = (double)f.w;
-            }
+            for (int v = 0; v < DCH / 4; ++v) f32x4_to_f64(src[v], cj + 4 * v);
 #pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                const double *__restrict__ qv = zq64 + (int64_t)qrow[q] * dp + ch * DCH;     // wave-uniform address
-#pragma unroll
-                for (int k = 0; k < DCH; ++k) {
-                    if (EXPANSION) {
-                        acc[q] = fma(qv[k], cj[k], acc[q]);
-                    } else {
-                        const double t = qv[k] - cj[k];
-                        acc[q] = fma(t, t, acc[q]);
-                    }
-                }
-            }
+            for (int q = 0; q < Q; ++q)
+                acc[q] = key_chain<DCH, EXPANSION>(zq64 + (int64_t)qrow[q] * dp + ch * DCH, cj, acc[q]);
         }
         const double nj = out ? inf64() : nrm_j;
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             double d2 = acc[q];
             if (EXPANSION) {
-                const double t = -2.0 * d2;
                 const uint32_t qr = (uint32_t)qrow[q];
                 const double nq = nrm[qrow[q]];
+                // key_close written out, the one copy: -2 acc before and the clamp after the wave-uniform branch on the order of
+                // the norms.  With key_close in each arm the arms each multiply and clamp (<16, 4, true> 1 272 -> 1 316
+                // instructions, the first round's scan at 60 000 x 16 mutual k = 10 1.108 -> 1.140 ms); with the norms picked
+                // in the arms and one key_close after them the compiler selects per lane in every step (<8, 8, true> 69 -> 82 VGPRs)
+                const double t = -2.0 * d2;
                 if (c0 > qr) d2 = (nq + t) + nj;                               // the query is the lower row of every pair
                 else if (c0 + 63 < qr) d2 = (nj + t) + nq;                     // ... the higher row of every pair
                 else d2 = j < qr ? (nj + t) + nq : (nq + t) + nj;
@@ -1108,42 +1075,22 @@ KnnPlan plan_for(int d) {
     return p;
 }
 
-template <int DCH, int Q, int LR = 1>
-int launch_knn(bool expansion, const float *zp32, const double *zq64, const double *nrm, const double *nrm_q, int64_t n,
-               int nch, int kq, int64_t row0, int64_t row1, int32_t *idx_out, double *d2_out, hipStream_t s) {
-    const int64_t rows = row1 - row0;
-    const int64_t waves = (rows + Q - 1) / Q;
-    const unsigned grid = (unsigned)((waves + KNN_WAVES - 1) / KNN_WAVES);
-    if (expansion)
-        knn_kernel<DCH, Q, true, LR><<<grid, 256, 0, s>>>(zp32, zq64, nrm, nrm_q, n, nch, kq, row0, row1, idx_out, d2_out);
-    else
-        knn_kernel<DCH, Q, false, LR><<<grid, 256, 0, s>>>(zp32, zq64, nrm, nrm_q, n, nch, kq, row0, row1, idx_out, d2_out);
-    GEO_LAUNCH_CHECK();
-    return GEO_OK;
-}
+// ---- one dispatch of the search kernels' template instances ----------------------------------------------------------------
+// The run-time (p.dch, expansion) as compile-time constants: f(int_c<DCH>, std::bool_constant<EXPANSION>).  Every launch of a
+// search kernel goes through here; what else a kernel is instantiated on (queries per wave, list registers, minima per lane) its
+// launcher passes the same way, so a generic lambda instantiates the combinations its launcher's routes reach and no others.
+template <int V>
+using int_c = std::integral_constant<int, V>;
 
-// lists longer than one wave (64 < kq <= 256): 2 or 4 list registers per lane, 4 queries per wave
-template <int DCH>
-int launch_knn_wide(bool expansion, const float *zp32, const double *zq64, const double *nrm, const double *nrm_q, int64_t n,
-                    int nch, int kq, int64_t row0, int64_t row1, int32_t *idx_out, double *d2_out, hipStream_t s) {
-    if (kq <= 128) return launch_knn<DCH, 4, 2>(expansion, zp32, zq64, nrm, nrm_q, n, nch, kq, row0, row1, idx_out, d2_out, s);
-    return launch_knn<DCH, 4, 4>(expansion, zp32, zq64, nrm, nrm_q, n, nch, kq, row0, row1, idx_out, d2_out, s);
-}
-
-int launch_knn_bound(const KnnPlan &p, bool expansion, const float *zs32, const double *zq64, const double *nrm_s,
-                     const double *nrm_q, int64_t m, int kq, int64_t row0, int64_t row1, double eps, double *u, int32_t *cnt,
-                     double *tau_out, hipStream_t s) {
-    const unsigned grid = (unsigned)((row1 - row0 + BOUND_Q - 1) / BOUND_Q);
-#define GEO_BOUND(DCHV, NMV, EXV) \
-    knn_bound_kernel<DCHV, BOUND_Q, NMV, EXV><<<grid, 256, 0, s>>>(zs32, zq64, nrm_s, nrm_q, m, p.nch, kq, row0, row1, eps, u, cnt, tau_out)
-#define GEO_BOUND_NM(DCHV, EXV) do { if (bound_minima(kq) == 2) GEO_BOUND(DCHV, 2, EXV); else GEO_BOUND(DCHV, 3, EXV); } while (0)
-    if (p.dch == 8) { if (expansion) GEO_BOUND_NM(8, true); else GEO_BOUND_NM(8, false); }
-    else if (p.dch == 16) { if (expansion) GEO_BOUND_NM(16, true); else GEO_BOUND_NM(16, false); }
-    else { if (expansion) GEO_BOUND_NM(32, true); else GEO_BOUND_NM(32, false); }
-#undef GEO_BOUND_NM
-#undef GEO_BOUND
-    GEO_LAUNCH_CHECK();
-    return GEO_OK;
+template <class F>
+void with_key_form(const KnnPlan &p, bool expansion, F &&f) {
+    auto with_form = [&](auto dch) {
+        if (expansion) f(dch, std::true_type{});
+        else f(dch, std::false_type{});
+    };
+    if (p.dch == 8) with_form(int_c<8>{});
+    else if (p.dch == 16) with_form(int_c<16>{});
+    else with_form(int_c<32>{});
 }
 
 // the path the calling thread's last geo_knn_topk took (GEO_KNN_PATH_* of include/geo_hip.h), for tests and profiles
@@ -1160,6 +1107,10 @@ bool filter_applies(int64_t n, int dp) {
 // geo_knn_topk (queries = rows of the corpus) and geo_knn_query (queries of their own) differ in where the query side of the
 // kernels points, nothing else: the corpus side is prepared once (KnnCorpus), a range of query rows is described by KnnQuery
 // and searched by search_rows, which picks the path from n, dp, kq and the knn_filter option alone.
+
+// the corpus side of one pass: the rows a kernel searches (zb / negn: their bf16 parts and norm column, where a scan reads them)
+struct KnnSide { const float *z32; const double *nrm; const unsigned short *zb; const float *negn; int64_t rows; };
+
 struct KnnCorpus {
     const float *zp32;                 // [n][dp] zero padded
     const double *nrm;                 // [n]
@@ -1173,6 +1124,9 @@ struct KnnCorpus {
     unsigned short *zb; float *negn;   // [n_pad][2][dpb], [n_pad]
     float *zs0; double *nrm_s0;        // [m0][dp], [m0]                 (two levels)
     unsigned short *zb_s; float *negn_s;
+    KnnSide all() const { return {zp32, nrm, zb, negn, n}; }
+    KnnSide subset() const { return {zs32, nrm_s, zb_s, negn_s, m}; }
+    KnnSide subset0() const { return {zs0, nrm_s0, nullptr, nullptr, m0}; }
 };
 
 // query rows [row0, row1) of the arrays below; outputs and the per-query buffers are indexed from row0
@@ -1253,105 +1207,151 @@ int prepare_filter_corpus(const KnnPlan &p, const KnnCorpus &c, hipStream_t stre
     return GEO_OK;
 }
 
+// ---- the launches of a search: each takes the corpus side it runs against and the query range ---------------------------------
+// The exact scan.  Lists longer than one wave (64 < kq <= 256) take 2 or 4 list registers per lane at 4 queries per wave; of the
+// one-register lists, fewer queries per wave keep the chip busy on small inputs.
+int launch_knn_exact(const KnnPlan &p, bool ex, int kq, const KnnSide &c, const KnnQuery &q, int32_t *idx_out, double *d2_out,
+                     hipStream_t s) {
+    auto launch = [&](auto q_c, auto lr_c) {
+        constexpr int Q = decltype(q_c)::value, LR = decltype(lr_c)::value;
+        const int64_t waves = (q.row1 - q.row0 + Q - 1) / Q;
+        const unsigned grid = (unsigned)((waves + KNN_WAVES - 1) / KNN_WAVES);
+        with_key_form(p, ex, [&](auto dch, auto form) {
+            knn_kernel<decltype(dch)::value, Q, decltype(form)::value, LR><<<grid, 256, 0, s>>>(
+                c.z32, q.zq64, c.nrm, q.nrm_q, c.rows, p.nch, kq, q.row0, q.row1, idx_out, d2_out);
+        });
+    };
+    if (kq > 128) launch(int_c<4>{}, int_c<4>{});
+    else if (kq > 64) launch(int_c<4>{}, int_c<2>{});
+    else if (q.row1 - q.row0 < 16384) launch(int_c<4>{}, int_c<1>{});
+    else launch(int_c<16>{}, int_c<1>{});
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// thresholds bounded over the rows of `sub`: u / cnt for a scan, tau_out for geo_knn_thresholds (either may be null)
+int launch_knn_bound(const KnnPlan &p, bool ex, int kq, const KnnSide &sub, const KnnQuery &q, double eps, double *u, int32_t *cnt,
+                     double *tau_out, hipStream_t s) {
+    const unsigned grid = (unsigned)((q.row1 - q.row0 + BOUND_Q - 1) / BOUND_Q);
+    auto launch = [&](auto nm_c) {
+        with_key_form(p, ex, [&](auto dch, auto form) {
+            knn_bound_kernel<decltype(dch)::value, BOUND_Q, decltype(nm_c)::value, decltype(form)::value><<<grid, 256, 0, s>>>(
+                sub.z32, q.zq64, sub.nrm, q.nrm_q, sub.rows, p.nch, kq, q.row0, q.row1, eps, u, cnt, tau_out);
+        });
+    };
+    if (bound_minima(kq) == 2) launch(int_c<2>{});
+    else launch(int_c<3>{});
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// corpus slices per 128-query block of a scan: enough workgroups, tiles to spare
+int scan_splits(int64_t rows, int64_t corpus) {
+    const int64_t qb = (rows + 127) / 128;
+    int64_t sp = 16384 / qb;
+    if (sp > 64) sp = 64;
+    if (sp > (corpus + 255) / 256) sp = (corpus + 255) / 256;
+    return (int)(sp > 1 ? sp : 1);
+}
+
+int launch_scan_bf16(int dpb, const KnnSide &c, const KnnQuery &q, const KnnLists &l, hipStream_t s) {
+    const int64_t rows = q.row1 - q.row0;
+    const int splits = scan_splits(rows, c.rows);
+    const unsigned grid = (unsigned)((rows + 127) / 128) * (unsigned)splits;
+    auto launch = [&](auto dpb_c, auto ct_c) {
+        knn_scan_bf16_kernel<decltype(dpb_c)::value, decltype(ct_c)::value><<<grid, 256, 0, s>>>(
+            c.zb, q.zbq, c.negn, l.u, c.rows, q.row0, rows, splits, l.cnt, l.list);
+    };
+    if (dpb == 16) launch(int_c<16>{}, int_c<256>{});
+    else if (dpb == 32) launch(int_c<32>{}, int_c<256>{});
+    else launch(int_c<64>{}, int_c<128>{});
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// (reads its queries from the corpus array, from row q.f32_row0)
+int launch_scan_f32(int dp, const KnnSide &c, const KnnQuery &q, double eps, const KnnLists &l, hipStream_t s) {
+    const int64_t rows = q.row1 - q.row0;
+    const int splits = scan_splits(rows, c.rows);
+    const unsigned grid = (unsigned)((rows + 127) / 128) * (unsigned)splits;
+    auto launch = [&](auto dp_c, auto ct_c) {
+        knn_scan_kernel<decltype(dp_c)::value, decltype(ct_c)::value><<<grid, 256, 0, s>>>(
+            c.z32, c.nrm, l.u, c.rows, q.f32_row0, rows, eps, splits, l.cnt, l.list);
+    };
+    if (dp == 8) launch(int_c<8>{}, int_c<256>{});
+    else if (dp == 16) launch(int_c<16>{}, int_c<256>{});
+    else if (dp == 32) launch(int_c<32>{}, int_c<256>{});
+    else launch(int_c<64>{}, int_c<128>{});
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+int launch_knn_refine(const KnnPlan &p, bool ex, int kq, const KnnSide &c, const KnnQuery &q, const KnnLists &l, int32_t *idx_out,
+                      double *d2_out, hipStream_t s) {
+    const int64_t rows = q.row1 - q.row0;
+    const unsigned grid = (unsigned)((rows + KNN_WAVES - 1) / KNN_WAVES);
+    with_key_form(p, ex, [&](auto dch, auto form) {
+        knn_refine_kernel<decltype(dch)::value, decltype(form)::value><<<grid, 256, 0, s>>>(
+            c.z32, q.zq64, c.nrm, q.nrm_q, p.nch, kq, q.row0, rows, l.cnt, l.list, idx_out, d2_out, l.overflow);
+    });
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// One pass of the filter over the rows of `side`: thresholds -> scan -> refinement -> the overflow word read back (the pass' one
+// stream synchronisation).  The thresholds are a bound over the rows of `thr`, or, with thr null, the kq-th entries that the pass
+// before left in d2_out.  *overflowed: some query kept more than FILTER_CAP candidates (masses of near-duplicates), the lists
+// are not valid.  The caller has cleared the overflow word.
+int filter_pass(const KnnPlan &p, bool ex, int kq, const KnnCorpus &c, const KnnSide *thr, const KnnSide &side, const KnnQuery &q,
+                const KnnLists &l, int32_t *idx_out, double *d2_out, hipStream_t stream, bool *overflowed) {
+    int rc;
+    if (thr) {
+        rc = launch_knn_bound(p, ex, kq, *thr, q, c.eps, l.u, l.cnt, nullptr, stream);
+        if (rc) return rc;
+    } else {
+        const int64_t rows = q.row1 - q.row0;
+        knn_tau_kernel<<<geo::grid_for(rows, 256, 4096), 256, 0, stream>>>(d2_out, q.nrm_q, q.row0, rows, kq, c.eps, l.u, l.cnt);
+        GEO_LAUNCH_CHECK();
+    }
+    rc = c.bf16_scan ? launch_scan_bf16(c.dpb, side, q, l, stream) : launch_scan_f32(p.dp, side, q, c.eps, l, stream);
+    if (rc) return rc;
+    rc = launch_knn_refine(p, ex, kq, side, q, l, idx_out, d2_out, stream);
+    if (rc) return rc;
+    int32_t h_over = 0;
+    GEO_HIP_CHECK(hipMemcpyAsync(&h_over, l.overflow, 4, hipMemcpyDeviceToHost, stream));
+    GEO_HIP_CHECK(hipStreamSynchronize(stream));
+    *overflowed = h_over != 0;
+    return GEO_OK;
+}
+
 // The kq nearest corpus rows of the query rows q, into idx_out / d2_out [row1 - row0][kq]; *path = the GEO_KNN_PATH_* taken.
 // l = the range's candidate buffers when the filter applies (corpus prepared by prepare_filter_corpus), else null.
 int search_rows(const KnnPlan &p, bool ex, int kq, const KnnCorpus &c, const KnnQuery &q, const KnnLists *l, int32_t *idx_out,
                 double *d2_out, hipStream_t stream, int32_t *path) {
-    const int64_t row0 = q.row0, row1 = q.row1, rows = row1 - row0, n = c.n;
     if (kq > 64) {                                // no float32 filter here: its candidate lists are sized for kq <= 64
         *path = GEO_KNN_PATH_EXACT_WIDE;
-        if (p.dch == 8) return launch_knn_wide<8>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
-        if (p.dch == 16) return launch_knn_wide<16>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
-        return launch_knn_wide<32>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
+        return launch_knn_exact(p, ex, kq, c.all(), q, idx_out, d2_out, stream);
     }
     if (l) {
-        const int dpb = c.dpb;
-        const double eps = c.eps;
-        double *u = l->u;
-        int32_t *cnt = l->cnt, *list = l->list, *overflow = l->overflow;
-        GEO_HIP_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
-        const unsigned rgrid = (unsigned)((rows + KNN_WAVES - 1) / KNN_WAVES);
-        auto splits_for = [&](int64_t corpus) {                // corpus slices per 128-query block: enough workgroups, tiles to spare
-            const int64_t qb = (rows + 127) / 128;
-            int64_t sp = 16384 / qb;
-            if (sp > 64) sp = 64;
-            if (sp > (corpus + 255) / 256) sp = (corpus + 255) / 256;
-            return (int)(sp > 1 ? sp : 1);
-        };
-#define GEO_REFINE(DCHV, EXV, ZC, NRMC) \
-    knn_refine_kernel<DCHV, EXV><<<rgrid, 256, 0, stream>>>(ZC, q.zq64, NRMC, q.nrm_q, p.nch, kq, row0, rows, cnt, list, \
-                                                          idx_out, d2_out, overflow)
-#define GEO_REFINE_ANY(ZC, NRMC)                                                                                   \
-    do {                                                                                                           \
-        if (p.dch == 8) { if (ex) GEO_REFINE(8, true, ZC, NRMC); else GEO_REFINE(8, false, ZC, NRMC); }              \
-        else if (p.dch == 16) { if (ex) GEO_REFINE(16, true, ZC, NRMC); else GEO_REFINE(16, false, ZC, NRMC); }      \
-        else { if (ex) GEO_REFINE(32, true, ZC, NRMC); else GEO_REFINE(32, false, ZC, NRMC); }                       \
-    } while (0)
-        int rc = 0;
-        bool tau_done = false;
-        if (c.two_level) {
-            rc = launch_knn_bound(p, ex, c.zs0, q.zq64, c.nrm_s0, q.nrm_q, c.m0, kq, row0, row1, eps, u, cnt, nullptr, stream);
+        const KnnSide subset0 = c.subset0(), subset = c.subset(), all = c.all();
+        GEO_HIP_CHECK(hipMemsetAsync(l->overflow, 0, 4, stream));
+        bool over = false, tau_done = false;
+        if (c.two_level) {                        // the kq smallest exact distances to the subset -> d2_out
+            const int rc = filter_pass(p, ex, kq, c, &subset0, subset, q, *l, idx_out, d2_out, stream, &over);
             if (rc) return rc;
-            const int sp1 = splits_for(c.m);
-            const unsigned g1 = (unsigned)((rows + 127) / 128) * (unsigned)sp1;
-            if (dpb == 16) knn_scan_bf16_kernel<16, 256><<<g1, 256, 0, stream>>>(c.zb_s, q.zbq, c.negn_s, u, c.m, row0, rows, sp1, cnt, list);
-            else if (dpb == 32) knn_scan_bf16_kernel<32, 256><<<g1, 256, 0, stream>>>(c.zb_s, q.zbq, c.negn_s, u, c.m, row0, rows, sp1, cnt, list);
-            else knn_scan_bf16_kernel<64, 128><<<g1, 256, 0, stream>>>(c.zb_s, q.zbq, c.negn_s, u, c.m, row0, rows, sp1, cnt, list);
-            GEO_LAUNCH_CHECK();
-            GEO_REFINE_ANY(c.zs32, c.nrm_s);                   // kq smallest exact distances to the subset -> d2_out
-            GEO_LAUNCH_CHECK();
-            int32_t h_over0 = 0;
-            GEO_HIP_CHECK(hipMemcpyAsync(&h_over0, overflow, 4, hipMemcpyDeviceToHost, stream));
-            GEO_HIP_CHECK(hipStreamSynchronize(stream));
-            tau_done = h_over0 == 0;
-            if (tau_done) *path = GEO_KNN_PATH_TWO_LEVEL;
-            if (!tau_done) GEO_HIP_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
+            tau_done = !over;
+            if (over) GEO_HIP_CHECK(hipMemsetAsync(l->overflow, 0, 4, stream));
         }
-        if (tau_done) {                                        // the subset's exact kq-th distances, left in d2_out by the refinement
-            knn_tau_kernel<<<geo::grid_for(rows, 256, 4096), 256, 0, stream>>>(d2_out, q.nrm_q, row0, rows, kq, eps, u, cnt);
-            GEO_LAUNCH_CHECK();
-        } else {
-            *path = c.bf16_scan ? GEO_KNN_PATH_FILTER_BF16 : GEO_KNN_PATH_FILTER_F32;
-            rc = launch_knn_bound(p, ex, c.zs32, q.zq64, c.nrm_s, q.nrm_q, c.m, kq, row0, row1, eps, u, cnt, nullptr, stream);
-            if (rc) return rc;
-        }
-        const int splits = splits_for(n);
-        const unsigned sgrid = (unsigned)((rows + 127) / 128) * (unsigned)splits;
-        if (c.bf16_scan) {
-            if (dpb == 16) knn_scan_bf16_kernel<16, 256><<<sgrid, 256, 0, stream>>>(c.zb, q.zbq, c.negn, u, n, row0, rows, splits, cnt, list);
-            else if (dpb == 32) knn_scan_bf16_kernel<32, 256><<<sgrid, 256, 0, stream>>>(c.zb, q.zbq, c.negn, u, n, row0, rows, splits, cnt, list);
-            else knn_scan_bf16_kernel<64, 128><<<sgrid, 256, 0, stream>>>(c.zb, q.zbq, c.negn, u, n, row0, rows, splits, cnt, list);
-        } else
-        if (p.dp == 8) knn_scan_kernel<8, 256><<<sgrid, 256, 0, stream>>>(c.zp32, c.nrm, u, n, q.f32_row0, rows, eps, splits, cnt, list);
-        else if (p.dp == 16) knn_scan_kernel<16, 256><<<sgrid, 256, 0, stream>>>(c.zp32, c.nrm, u, n, q.f32_row0, rows, eps, splits, cnt, list);
-        else if (p.dp == 32) knn_scan_kernel<32, 256><<<sgrid, 256, 0, stream>>>(c.zp32, c.nrm, u, n, q.f32_row0, rows, eps, splits, cnt, list);
-        else knn_scan_kernel<64, 128><<<sgrid, 256, 0, stream>>>(c.zp32, c.nrm, u, n, q.f32_row0, rows, eps, splits, cnt, list);
-        GEO_LAUNCH_CHECK();
-        GEO_REFINE_ANY(c.zp32, c.nrm);
-#undef GEO_REFINE_ANY
-#undef GEO_REFINE
-        GEO_LAUNCH_CHECK();
-        int32_t h_over = 0;
-        GEO_HIP_CHECK(hipMemcpyAsync(&h_over, overflow, 4, hipMemcpyDeviceToHost, stream));
-        GEO_HIP_CHECK(hipStreamSynchronize(stream));
-        if (h_over == 0) return GEO_OK;
-        // some query kept more than FILTER_CAP candidates (masses of near-duplicates): exact scan for everything
+        *path = tau_done ? GEO_KNN_PATH_TWO_LEVEL : c.bf16_scan ? GEO_KNN_PATH_FILTER_BF16 : GEO_KNN_PATH_FILTER_F32;
+        const int rc = filter_pass(p, ex, kq, c, tau_done ? nullptr : &subset, all, q, *l, idx_out, d2_out, stream, &over);
+        if (rc) return rc;
+        if (!over) return GEO_OK;
+        // some query kept more than FILTER_CAP candidates: exact scan for everything
         *path |= GEO_KNN_PATH_OVERFLOW;
     } else {
         *path = GEO_KNN_PATH_EXACT;
     }
-    const bool small = rows < 16384;              // fewer queries per wave keeps the chip busy on small inputs
-    int rc;
-    if (p.dch == 8)
-        rc = small ? launch_knn<8, 4>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream)
-                   : launch_knn<8, 16>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
-    else if (p.dch == 16)
-        rc = small ? launch_knn<16, 4>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream)
-                   : launch_knn<16, 16>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
-    else
-        rc = small ? launch_knn<32, 4>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream)
-                   : launch_knn<32, 16>(ex, c.zp32, q.zq64, c.nrm, q.nrm_q, n, p.nch, kq, row0, row1, idx_out, d2_out, stream);
-    return rc;
+    return launch_knn_exact(p, ex, kq, c.all(), q, idx_out, d2_out, stream);
 }
 
 // what one query row of a slice keeps in geo_knn_query's workspace, in 4-byte elements (geo::plan_passes): the padded
@@ -1575,7 +1575,9 @@ extern "C" int geo_knn_thresholds(const float *z, int64_t n, int32_t d, int32_t 
     GEO_LAUNCH_CHECK();
     knn_subset_kernel<<<geo::grid_for(m * p.dp, 256, 4096), 256, 0, stream>>>(zp32, nrm, n, p.dp, stride, m, zs32, nrm_s);
     GEO_LAUNCH_CHECK();
-    return launch_knn_bound(p, form != 0, zs32, zq64, nrm_s, nrm, m, n_neighbors, row0, row1, 0.0, nullptr, nullptr, tau_out, stream);
+    const KnnSide sub = {zs32, nrm_s, nullptr, nullptr, m};
+    const KnnQuery q = {zq64, nrm, nullptr, row0, row1, row0};
+    return launch_knn_bound(p, form != 0, n_neighbors, sub, q, 0.0, nullptr, nullptr, tau_out, stream);
 }
 
 // ---- nearest foreign node / component bridges -----------------------------------------------------------------------------------
@@ -1585,29 +1587,22 @@ namespace {
 // Not knn_kernel's 16: the gathered rows cost an address pair, a row number and a label in SGPRs per query, and at 16 the
 // scalar registers spill -- measured on 74 679 / 217 456 queries of 960 000 x 16 / 800 000 x 32 latents, in 10^12 fp64 FMA/s:
 // Q = 4: 6.9 / 6.8, Q = 8: 10.9 / 9.7, Q = 16: 9.1 / 6.7 (knn_kernel's exact scan of as many rows: 11.4 / 13.3).
-template <int DCH>
-int launch_nearest_foreign_d(bool ex, const float *zp32, const double *zq64, const double *nrm, const int32_t *labels,
-                             const int32_t *rows, int64_t m, int64_t n, int nch, int32_t *nbr, double *key, hipStream_t s) {
-    const int Q = m <= 2048 ? 1 : (m < 16384 ? 4 : 8);
-    const int64_t waves = (m + Q - 1) / Q;
-    const unsigned grid = (unsigned)((waves + KNN_WAVES - 1) / KNN_WAVES);
-#define GEO_NF(QV)                                                                                                          \
-    do {                                                                                                                    \
-        if (ex) nearest_foreign_kernel<DCH, QV, true><<<grid, 256, 0, s>>>(zp32, zq64, nrm, labels, rows, m, n, nch, nbr, key); \
-        else nearest_foreign_kernel<DCH, QV, false><<<grid, 256, 0, s>>>(zp32, zq64, nrm, labels, rows, m, n, nch, nbr, key);   \
-    } while (0)
-    if (Q == 1) GEO_NF(1); else if (Q == 4) GEO_NF(4); else GEO_NF(8);
-#undef GEO_NF
+int launch_nearest_foreign(const KnnPlan &p, bool ex, const PlainCorpus &c, int64_t n, const int32_t *labels, const int32_t *rows,
+                           int64_t m, int32_t *nbr, double *key, hipStream_t s) {
+    auto launch = [&](auto q_c) {
+        constexpr int Q = decltype(q_c)::value;
+        const int64_t waves = (m + Q - 1) / Q;
+        const unsigned grid = (unsigned)((waves + KNN_WAVES - 1) / KNN_WAVES);
+        with_key_form(p, ex, [&](auto dch, auto form) {
+            nearest_foreign_kernel<decltype(dch)::value, Q, decltype(form)::value><<<grid, 256, 0, s>>>(
+                c.zp32, c.zq64, c.nrm, labels, rows, m, n, p.nch, nbr, key);
+        });
+    };
+    if (m <= 2048) launch(int_c<1>{});
+    else if (m < 16384) launch(int_c<4>{});
+    else launch(int_c<8>{});
     GEO_LAUNCH_CHECK();
     return GEO_OK;
-}
-
-int launch_nearest_foreign(const KnnPlan &p, bool ex, const float *zp32, const double *zq64, const double *nrm,
-                           const int32_t *labels, const int32_t *rows, int64_t m, int64_t n, int32_t *nbr, double *key,
-                           hipStream_t s) {
-    if (p.dch == 8) return launch_nearest_foreign_d<8>(ex, zp32, zq64, nrm, labels, rows, m, n, p.nch, nbr, key, s);
-    if (p.dch == 16) return launch_nearest_foreign_d<16>(ex, zp32, zq64, nrm, labels, rows, m, n, p.nch, nbr, key, s);
-    return launch_nearest_foreign_d<32>(ex, zp32, zq64, nrm, labels, rows, m, n, p.nch, nbr, key, s);
 }
 
 // geo_bridge_components' layout: the corpus and the Boruvka rounds' buffers
@@ -1662,7 +1657,7 @@ extern "C" int geo_nearest_foreign(const float *z, int64_t n, int32_t d, int32_t
     GEO_REQUIRE_WORKSPACE("geo_nearest_foreign", ar, geo_nearest_foreign_workspace_bytes(n, d));
     knn_prep_kernel<<<geo::grid_for(n, 256, 4096), 256, 0, stream>>>(z, n, d, p.dp, pc.zp32, pc.zq64, pc.nrm);
     GEO_LAUNCH_CHECK();
-    return launch_nearest_foreign(p, form != 0, pc.zp32, pc.zq64, pc.nrm, labels, rows, m, n, nbr_out, key_out, stream);
+    return launch_nearest_foreign(p, form != 0, pc, n, labels, rows, m, nbr_out, key_out, stream);
 }
 
 extern "C" size_t geo_bridge_components_workspace_bytes(int64_t n, int32_t d, int32_t C) {
@@ -1723,7 +1718,7 @@ extern "C" int geo_bridge_components(const float *z, int64_t n, int32_t d, int32
         if (int rc = geo::exclusive_scan_i32(flag, pos, n, st, sb, nullptr, stream)) return rc;
         bridge_rows_kernel<<<gn, 256, 0, stream>>>(flag, pos, n, rows);
         GEO_LAUNCH_CHECK();
-        if (int rc = launch_nearest_foreign(p, form != 0, zp32, zq64, nrm, cur, rows, m, n, nbr, key, stream)) return rc;
+        if (int rc = launch_nearest_foreign(p, form != 0, w.pc, n, cur, rows, m, nbr, key, stream)) return rc;
         unsigned long long *minkey = reinterpret_cast<unsigned long long *>(sel), *minedge = minkey + cc;
         int32_t *other = reinterpret_cast<int32_t *>(minedge + cc);
         GEO_HIP_CHECK(hipMemsetAsync(sel, 0xff, (size_t)cc * 20, stream));
