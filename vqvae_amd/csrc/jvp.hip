@@ -2275,24 +2275,89 @@ bool chunks_match_mid_geom(const ChunkTable &tab, int *bad_chunk) {
     return true;
 }
 
+// ---- the workspace.  Three groups of buffers, each described once by a layout function over a geo::Arena: the sizes make_route
+// compares are measurements of these functions, and run_jvp carves the caller's memory with the same three.
+struct Buffers {
+    float *M01, *b01, *B2p, *W3p, *pre1, *tpre1, *pre2, *tpre2, *norms;
+    unsigned short *B3, *W3b;
+    double *part1, *part2; NormConst *k1, *k2;                // partial sums and norm constants of layers 1, 2
+    float2 *stats;                                              // batch statistics on their way into the running ones
+    int32_t *slot_valid;
+    float4 *gs1, *gs2;                                          // GroupNorm
+    float *pre2_node, *sg_node;                                 // per_node
+    int32_t *row_map, *rep, *n_compact;                         // dedup
+    float *sg_compact;                                          // dedup
+    int32_t *psrc, *pdst; float *jac;                           // node_jacobian: pseudo-edge lists, columns
+    ChunkTable tab;
+};
+
+struct Tiling { size_t slots, tiles, groups; };                 // of one pass: padded sample positions, tiles of TS, chunk sides
+
+constexpr int64_t MAX_SLOTS_PER_PASS = 1 << 20;      // bounds the activation workspace (~12.5 GB; the C2 graph takes two passes)
+constexpr size_t JVP_PASS_RESERVE = 4096;            // what Plan::bytes holds beyond the measured layout of a pass
+
+size_t round_up_to_tile(int64_t n) { return n > 0 ? ((size_t)n + TS - 1) / TS * TS : 0; }
+size_t part1_count(const Shape &s, const Tiling &t) { return t.tiles * s.n1 * 4; }      // layer 1's partial sums, [tile][n1][4]
+
+// the buffers of a pass of chunks: packed weights, activations, partial sums, norm constants and statistics
+void lay_out_pass(geo::Arena &ar, Buffers *b, const Shape &s, const Tiling &t, bool group_norm) {
+    ar.take(b->M01, (size_t)s.d * s.n1); ar.take(b->b01, (size_t)s.n1);
+    ar.take(b->B2p, (size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC);
+    ar.take(b->B3, (size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC * 3);                       // bf16 x 3
+    ar.take(b->W3p, (size_t)16 * s.co * s.c2);
+    ar.take(b->W3b, (size_t)16 * s.c2 * 192 * 3);                                          // bf16 x 3
+    ar.take(b->pre1, t.slots * s.n1); ar.take(b->tpre1, t.slots * s.n1);
+    ar.take(b->pre2, t.slots * s.n2); ar.take(b->tpre2, t.slots * s.n2);
+    ar.take(b->part1, part1_count(s, t)); ar.take(b->part2, t.tiles * s.n2 * 4);
+    ar.take(b->k1, (t.groups + 1) * s.c1); ar.take(b->k2, (t.groups + 1) * s.c2);
+    ar.take(b->norms, t.slots);
+    ar.take(b->stats, (t.groups + 1) * (size_t)(s.c1 > s.c2 ? s.c1 : s.c2));
+    ar.take(b->slot_valid, t.slots);
+    if (group_norm) { ar.take(b->gs1, t.slots * 32); ar.take(b->gs2, t.slots * 32); }
+}
+
+// the per-node primal buffers: pre2 of every latent and the sigmoid of every output
+void lay_out_nodes(geo::Arena &ar, Buffers *b, const Shape &s, int64_t n_nodes) {
+    const size_t node_slots = round_up_to_tile(n_nodes);
+    ar.take(b->pre2_node, node_slots * s.n2);
+    ar.take(b->sg_node, node_slots * (size_t)((s.p_out + 31) / 32) * 32);
+}
+
+// node_jacobian: the pseudo-edge lists and the Jacobian's columns, jac_np padded outputs each
+void lay_out_jacobian(geo::Arena &ar, Buffers *b, const Shape &s, int64_t n_nodes, int64_t n_pseudo, size_t jac_np) {
+    ar.take(b->psrc, (size_t)n_pseudo); ar.take(b->pdst, (size_t)n_pseudo);
+    ar.take(b->jac, (size_t)n_nodes * s.d * jac_np);
+}
+
+// What the dedup route keeps inside buffers of the pass that are dead by then.  The run maps (row_map and rep per slot, n_compact
+// per group) live in part1, dead after finalize_batch_kernel; on the front_once route start_runs_kernel runs before the front, so
+// there they sit behind the front's partial sums, [tile][c1][4] at the head of part1.  The compact rows' output sigmoids live in
+// pre1, dead after ConvT2.  make_route asks whether these fit, run_jvp takes the pointers.
+struct StartRuns {
+    size_t slots, n1, part1_bytes, front_bytes, maps_bytes;
+    StartRuns(const Shape &s, const Tiling &t)
+        : slots(t.slots), n1((size_t)s.n1), part1_bytes(part1_count(s, t) * sizeof(double)), front_bytes(t.tiles * s.c1 * 4 * sizeof(double)),
+          maps_bytes((2 * t.slots + t.groups) * sizeof(int32_t)) {}
+    size_t maps_at(bool front_once) const { return front_once ? front_bytes : 0; }
+    bool maps_fit(bool front_once) const { return maps_at(front_once) + maps_bytes <= part1_bytes; }
+    bool sigmoids_fit(size_t padded_outputs) const { return padded_outputs <= n1; }      // a row of pre1 holds a row's sigmoids
+    void place(Buffers *b, bool front_once) const {
+        b->row_map = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(b->part1) + maps_at(front_once));
+        b->rep = b->row_map + slots; b->n_compact = b->rep + slots;
+        b->sg_compact = b->pre1;
+    }
+};
+
 struct Plan {
     Shape sh;
     int batch, tiles_per_group, slots_per_group;
     int64_t chunks_per_pass;
-    size_t bytes;
+    size_t bytes;                                               // lay_out_pass measured, plus JVP_PASS_RESERVE
     size_t pass_slots() const { return (size_t)chunks_per_pass * 2 * slots_per_group; }
+    Tiling tiling() const { return {pass_slots(), pass_slots() / TS, (size_t)chunks_per_pass * 2}; }
 };
 
-constexpr int64_t MAX_SLOTS_PER_PASS = 1 << 20;      // bounds the activation workspace (~12.5 GB; the C2 graph takes two passes)
-
-size_t round_up_to_tile(int64_t n) { return n > 0 ? ((size_t)n + TS - 1) / TS * TS : 0; }
-
-// bytes of the per-node primal buffers (pre2 of every latent + the sigmoid of every output)
-size_t node_bytes(const Shape &s, int64_t n_nodes) {
-    if (n_nodes <= 0) return 0;
-    const size_t np = (size_t)((s.p_out + 31) / 32) * 32;
-    return geo::align_up(round_up_to_tile(n_nodes) * s.n2 * 4) + geo::align_up(round_up_to_tile(n_nodes) * np * 4);
-}
+size_t node_bytes(const Shape &s, int64_t n_nodes) { Buffers b; return geo::measure(lay_out_nodes, &b, s, n_nodes); }
 
 bool make_plan(const geo_decoder_desc *dc, int64_t n_edges, int batch, Plan *p) {
     if (!make_shape(dc, &p->sh)) return false;
@@ -2304,21 +2369,8 @@ bool make_plan(const geo_decoder_desc *dc, int64_t n_edges, int batch, Plan *p) 
     if (cpp < 1) cpp = 1;
     if (cpp > chunks) cpp = chunks > 0 ? chunks : 1;
     p->chunks_per_pass = cpp;
-    const Shape &s = p->sh;
-    const size_t slots = p->pass_slots(), tiles = slots / TS, groups = (size_t)cpp * 2;
-    size_t b = 0;
-    b += geo::align_up((size_t)s.d * s.n1 * 4) + geo::align_up((size_t)s.n1 * 4);          // M01, b01
-    b += geo::align_up((size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC * 4);                   // B2p
-    b += geo::align_up((size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC * 2 * 3);               // B3 (bf16 x 3)
-    b += geo::align_up((size_t)16 * s.co * s.c2 * 4);                                       // W3p
-    b += geo::align_up((size_t)16 * s.c2 * 192 * 3 * 2);                                    // W3b (bf16 x 3)
-    b += 2 * geo::align_up(slots * s.n1 * 4) + 2 * geo::align_up(slots * s.n2 * 4);         // pre1,tpre1,pre2,tpre2
-    b += geo::align_up(tiles * s.n1 * 4 * 8) + geo::align_up(tiles * s.n2 * 4 * 8);         // partial sums
-    b += geo::align_up((groups + 1) * s.c1 * sizeof(NormConst)) + geo::align_up((groups + 1) * s.c2 * sizeof(NormConst));
-    b += geo::align_up((groups + 1) * (size_t)(s.c1 > s.c2 ? s.c1 : s.c2) * sizeof(float2));      // batch statistics
-    b += geo::align_up(slots * 4) * 2;                                                      // norms, slot_valid
-    if (dc->norm == 2) b += 2 * geo::align_up(slots * 32 * sizeof(float4));                 // GroupNorm statistics
-    p->bytes = b + 4096;
+    Buffers b;
+    p->bytes = geo::measure(lay_out_pass, &b, p->sh, p->tiling(), dc->norm == 2) + JVP_PASS_RESERVE;
     return true;
 }
 
@@ -2409,7 +2461,8 @@ bool make_route(const geo_decoder_desc *dc, const geo::Options &o, bool graph_ed
         (o.jvp_node_jacobian != 1 || 4 * build_edges >= 3 * n_nodes * s.d) && n_pseudo < (int64_t)1 << 31 &&
         make_plan(dc, n_pseudo, batch, &jpl) && node_slots <= jpl.pass_slots()) {
         r->jac_np = (size_t)r->back_nt * 32;
-        r->jac_extra_bytes = 2 * geo::align_up((size_t)n_pseudo * 4) + geo::align_up((size_t)n_nodes * s.d * r->jac_np * 4);
+        Buffers b;
+        r->jac_extra_bytes = geo::measure(lay_out_jacobian, &b, s, n_nodes, n_pseudo, r->jac_np);
         jac_bytes = r->jac_extra_bytes + jpl.bytes + node_bytes(s, n_nodes);
     }
     r->bytes = jac_bytes > per_edge_end_bytes ? jac_bytes : per_edge_end_bytes;
@@ -2423,15 +2476,14 @@ bool make_route(const geo_decoder_desc *dc, const geo::Options &o, bool graph_ed
     const size_t run_ws = ws - (r->node_jacobian ? r->jac_extra_bytes : 0);
     r->per_node = per_node_kernels && node_slots && node_slots <= r->pl.pass_slots() &&
                   run_ws >= r->pl.bytes + node_bytes(s, n_nodes);
-    const size_t slots = r->pl.pass_slots(), tiles = slots / TS, groups = (size_t)r->pl.chunks_per_pass * 2;
-    r->dedup = r->batch_stats && graph_edges && mid_pipe && back_mfma && o.jvp_start_dedup != 0 &&
-               (2 * slots + groups) * 4 <= tiles * s.n1 * 4 * 8 && (size_t)r->back_nt * 32 <= (size_t)s.n1;
+    const StartRuns runs(s, r->pl.tiling());
+    r->dedup = r->batch_stats && graph_edges && mid_pipe && back_mfma && o.jvp_start_dedup != 0 && runs.maps_fit(false) &&
+               runs.sigmoids_fit((size_t)r->back_nt * 32);
     // (dedup implies c1 = 128, the width front_edge_kernel is compiled for, and the maps fit behind the front's partial sums:
     // 4 KB of the 16 KB a tile has in part1, the maps take 260 B; mid_start_kernel addresses a group's rows through one buffer
     // descriptor with 32-bit offsets: all spelled out)
     r->front_once = r->dedup && r->front == GEO_JVP_FRONT_VALU && o.jvp_front_once != 0 && s.n1 == FRONT_EDGE_N1 &&
-                    tiles * s.c1 * 4 * 8 + (2 * slots + groups) * 4 <= tiles * s.n1 * 4 * 8 &&
-                    (size_t)base.slots_per_group * s.n1 * 4 < ((size_t)1 << 31);
+                    runs.maps_fit(true) && (size_t)base.slots_per_group * s.n1 * 4 < ((size_t)1 << 31);
 
     r->mid = r->per_node ? GEO_JVP_MID_ALL_TANGENT
            : mid_pipe    ? (r->dedup ? GEO_JVP_MID_PIPE_DEDUP : GEO_JVP_MID_PIPE)
@@ -2470,19 +2522,6 @@ int encode_route(const Route &r) {
 }
 
 // ---------------------------------------------------------------------------------- host side: launchers
-struct Buffers {
-    float *M01, *b01, *B2p, *W3p, *pre1, *tpre1, *pre2, *tpre2, *norms;
-    unsigned short *B3, *W3b;
-    double *part1, *part2; NormConst *k1, *k2;                // partial sums and norm constants of layers 1, 2
-    float2 *stats;                                              // batch statistics on their way into the running ones
-    int32_t *slot_valid;
-    float4 *gs1, *gs2;                                          // GroupNorm
-    float *pre2_node, *sg_node;                                 // per_node
-    int32_t *row_map, *rep, *n_compact;                         // dedup
-    float *sg_compact, *jac;                                    // dedup; node_jacobian
-    ChunkTable tab;
-};
-
 // One launch sequence front -> ConvT2 -> ConvT3: a pass of chunks over the edges, or the per-node primal pass over the latents
 // (one group: every latent on the "start" side).
 struct Pass {
@@ -2708,43 +2747,18 @@ int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t 
     const Plan &pl = r.pl;
     const Shape &s = pl.sh;
     const int batch = pl.batch;
-    const size_t slots = pl.pass_slots(), tiles = slots / TS, groups = (size_t)pl.chunks_per_pass * 2;
+    const Tiling t = pl.tiling();
 
-    // ---- carve the workspace
+    // ---- carve the workspace: the groups in the order make_route subtracts them (Jacobian columns, pass, per-node rows)
     geo::Arena ar(ws, ws_bytes);
     Buffers b = {};
-    int32_t *psrc = nullptr, *pdst = nullptr;
-    if (r.node_jacobian) {
-        psrc = ar.take<int32_t>((size_t)r.run_edges);
-        pdst = ar.take<int32_t>((size_t)r.run_edges);
-        b.jac = ar.take<float>((size_t)n_nodes * s.d * r.jac_np);
-        GEO_REQUIRE(b.jac != nullptr, "geo_decoder_jvp_edges: workspace carve failed");
-    }
-    b.M01 = ar.take<float>((size_t)s.d * s.n1);
-    b.b01 = ar.take<float>((size_t)s.n1);
-    b.B2p = ar.take<float>((size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC);
-    b.B3 = ar.take<unsigned short>((size_t)s.n_chunks * MAX_BLOCKS * s.c1 * NC * 3);
-    b.W3p = ar.take<float>((size_t)16 * s.co * s.c2);
-    b.W3b = ar.take<unsigned short>((size_t)16 * s.c2 * 192 * 3);
-    b.pre1 = ar.take<float>(slots * s.n1); b.tpre1 = ar.take<float>(slots * s.n1);
-    b.pre2 = ar.take<float>(slots * s.n2); b.tpre2 = ar.take<float>(slots * s.n2);
-    b.part1 = ar.take<double>(tiles * s.n1 * 4); b.part2 = ar.take<double>(tiles * s.n2 * 4);
-    b.k1 = ar.take<NormConst>((groups + 1) * s.c1); b.k2 = ar.take<NormConst>((groups + 1) * s.c2);
-    b.norms = ar.take<float>(slots);
-    b.stats = ar.take<float2>((groups + 1) * (size_t)(s.c1 > s.c2 ? s.c1 : s.c2));
-    b.slot_valid = ar.take<int32_t>(slots);
-    if (r.group_norm) { b.gs1 = ar.take<float4>(slots * 32); b.gs2 = ar.take<float4>(slots * 32); }
+    if (r.node_jacobian) lay_out_jacobian(ar, &b, s, n_nodes, r.run_edges, r.jac_np);
+    lay_out_pass(ar, &b, s, t, r.group_norm);
+    if (r.per_node) lay_out_nodes(ar, &b, s, n_nodes);
+    // (unreachable: make_route took each route only where the measurements of these same functions fit in ws_bytes)
+    GEO_REQUIRE(ar.ok(), "geo_decoder_jvp: workspace carve failed");
+    if (r.dedup) StartRuns(s, t).place(&b, r.front_once);
     const size_t node_slots = round_up_to_tile(n_nodes);
-    if (r.per_node) {
-        b.pre2_node = ar.take<float>(node_slots * s.n2);
-        b.sg_node = ar.take<float>(node_slots * (size_t)((s.p_out + 31) / 32) * 32);
-    }
-    GEO_REQUIRE(b.slot_valid && (!r.group_norm || b.gs2) && (!r.per_node || b.sg_node), "geo_decoder_jvp: workspace carve failed");
-    if (r.dedup) {
-        // (front_once: the maps exist before the front writes its partial sums, [tile][c1][4], to the head of part1)
-        b.row_map = reinterpret_cast<int32_t *>(b.part1 + (r.front_once ? tiles * s.c1 * 4 : 0)); b.rep = b.row_map + slots; b.n_compact = b.rep + slots;
-        b.sg_compact = b.pre1;
-    }
 
     // ---- pack the weights, fixed norm constants
     make_chunks(s, &b.tab);
@@ -2786,7 +2800,7 @@ int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t 
 
     // ---- passes over the edges (node_jacobian: over the pseudo-edges, unit tangents, columns to b.jac instead of lengths)
     if (r.node_jacobian) {
-        pair_edges_kernel<<<geo::grid_for(r.run_edges, 256), 256, 0, stream>>>(n_nodes, s.d, r.run_edges, psrc, pdst);
+        pair_edges_kernel<<<geo::grid_for(r.run_edges, 256), 256, 0, stream>>>(n_nodes, s.d, r.run_edges, b.psrc, b.pdst);
         GEO_LAUNCH_CHECK();
     }
     const int64_t total_chunks = (r.run_edges + batch - 1) / batch;
@@ -2796,7 +2810,7 @@ int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t 
         ep.mid = r.mid; ep.back = r.back;
         ep.tiles = nch * 2 * pl.tiles_per_group; ep.tiles_per_group = pl.tiles_per_group;
         ep.e_base = c0 * batch; ep.n_edges = r.run_edges; ep.batch = batch; ep.stat = r.batch_stats ? 1 : 0;
-        ep.z = z; ep.src = r.node_jacobian ? psrc : src; ep.dst = r.node_jacobian ? pdst : dst;
+        ep.z = z; ep.src = r.node_jacobian ? b.psrc : src; ep.dst = r.node_jacobian ? b.pdst : dst;
         ep.z_start = z_start; ep.z_end = z_end;
         ep.unit_d = r.node_jacobian ? s.d : 0;
         ep.mid_pre2 = b.pre2; ep.back_pre2 = r.per_node ? b.pre2_node : b.pre2;

@@ -641,7 +641,6 @@ int ns_for(int d) {
 }
 
 struct Plan {
-    size_t bytes = 0;
     // assignment / Lloyd
     float *Ap, *cnp, *C0, *C1;
     double *keys, *sums, *shift2, *scal;
@@ -653,38 +652,43 @@ struct Plan {
     int32_t *cand;
 };
 
-Plan plan(int64_t n, int d, int K, int S, int L, void *ws) {
-    Plan p;
+// What the k-means calls and the vector quantizer both keep, as two sub-layouts: the centre packing and the status of the
+// assignment, and the counting sort with the per-cluster sums.
+void lay_out_assign(geo::Arena &ar, Plan *p, int d, int K) {
     const int ns = ns_for(d), ntiles = (K + 31) / 32;
+    ar.take(p->Ap, (size_t)ntiles * ns * 64);
+    ar.take(p->cnp, (size_t)ntiles * 32);
+    ar.take(p->st, 1);
+}
+
+void lay_out_sort(geo::Arena &ar, Plan *p, int64_t n, int d, int K) {
     const int64_t nchunk = (n + CHUNK - 1) / CHUNK;
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char * {
-        char *r = ws ? static_cast<char *>(ws) + off : nullptr;
-        off += geo::align_up(bytes);
-        return r;
-    };
-    p.Ap = (float *)take((size_t)ntiles * ns * 64 * 4);
-    p.cnp = (float *)take((size_t)ntiles * 32 * 4);
-    p.C0 = (float *)take((size_t)K * d * 4);
-    p.C1 = (float *)take((size_t)K * d * 4);
-    p.keys = (double *)take((size_t)n * 8);
-    p.sums = (double *)take((size_t)K * d * 8);
-    p.shift2 = (double *)take((size_t)K * 8);
-    p.scal = (double *)take(64);
-    p.chunk_hist = (int32_t *)take((size_t)nchunk * K * 4);
-    p.counts = (int32_t *)take((size_t)K * 4);
-    p.offs = (int32_t *)take((size_t)(K + 1) * 4);
-    p.order = (int32_t *)take((size_t)n * 4);
-    p.st = (Status *)take(sizeof(Status));
-    p.closest = (float *)take((size_t)S * n * 4);
-    p.pot = (float *)take((size_t)S * 4);
-    p.P = (double *)take((size_t)S * n * 8);
-    p.segT = (double *)take((size_t)S * nchunk * 8);
-    p.segMax = (double *)take((size_t)S * nchunk * 8);
-    p.partial = (double *)take((size_t)S * L * nchunk * 8);
-    p.u = (double *)take((size_t)S * (K > 1 ? K - 1 : 1) * L * 8);
-    p.cand = (int32_t *)take((size_t)S * L * 4);
-    p.bytes = off;
+    ar.take(p->chunk_hist, (size_t)nchunk * K);
+    ar.take(p->counts, (size_t)K);
+    ar.take(p->offs, (size_t)(K + 1));
+    ar.take(p->order, (size_t)n);
+    ar.take(p->sums, (size_t)K * d);
+}
+
+// The one workspace of geo_kmeans_assign / _pp / _lloyd (S starts, L trials): measured by geo_kmeans_workspace_bytes.
+Plan lay_out(geo::Arena &ar, int64_t n, int d, int K, int S, int L) {
+    Plan p;
+    const int64_t nchunk = (n + CHUNK - 1) / CHUNK;
+    lay_out_assign(ar, &p, d, K);
+    ar.take(p.C0, (size_t)K * d);
+    ar.take(p.C1, (size_t)K * d);
+    ar.take(p.keys, (size_t)n);
+    ar.take(p.shift2, (size_t)K);
+    ar.take(p.scal, 8);
+    lay_out_sort(ar, &p, n, d, K);
+    ar.take(p.closest, (size_t)S * n);
+    ar.take(p.pot, (size_t)S);
+    ar.take(p.P, (size_t)S * n);
+    ar.take(p.segT, (size_t)S * nchunk);
+    ar.take(p.segMax, (size_t)S * nchunk);
+    ar.take(p.partial, (size_t)S * L * nchunk);
+    ar.take(p.u, (size_t)S * (K > 1 ? K - 1 : 1) * L);
+    ar.take(p.cand, (size_t)S * L);
     return p;
 }
 
@@ -727,7 +731,7 @@ int launch_assign(const float *X, int64_t n, int d, const float *C, int K, const
 
 extern "C" size_t geo_kmeans_workspace_bytes(int64_t n, int32_t d, int32_t K, int32_t n_starts, int32_t n_trials) {
     if (n < 1 || n >= ((int64_t)1 << 31) - CHUNK || d < 1 || d > MAX_D || K < 1 || K > MAX_K || n_starts < 1 || n_trials < 1 || n_trials > MAX_TRIALS) return 0;
-    return plan(n, d, K, n_starts, n_trials, nullptr).bytes;
+    return geo::measure(lay_out, n, d, K, n_starts, n_trials);
 }
 
 extern "C" int geo_kmeans_assign(const float *X, int64_t n, int32_t d, const float *C, int32_t K, int32_t *labels_out,
@@ -735,11 +739,9 @@ extern "C" int geo_kmeans_assign(const float *X, int64_t n, int32_t d, const flo
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (int e = check_common("geo_kmeans_assign", X, n, d, K, ws, false)) return e;
     GEO_REQUIRE(C && labels_out, "geo_kmeans_assign: null C or labels_out");
-    const Plan p = plan(n, d, K, 1, 1, ws);
-    if (ws_bytes < plan(n, d, K, 1, 1, nullptr).bytes) {
-        geo::set_error("geo_kmeans_assign: workspace %zu bytes too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
+    geo::Arena ar(ws, ws_bytes);
+    const Plan p = lay_out(ar, n, d, K, 1, 1);
+    GEO_REQUIRE_WORKSPACE("geo_kmeans_assign", ar, ar.off);
     GEO_HIP_CHECK(hipMemsetAsync(p.st, 0, sizeof(Status), stream));
     if (int e = launch_pack(C, K, d, p, false, stream)) return e;
     if (int e = launch_assign(X, n, d, C, K, p, labels_out, keys_out, 0, 0, stream)) return e;
@@ -763,11 +765,9 @@ extern "C" int geo_kmeans_pp(const float *X, int64_t n, int32_t d, int32_t K, in
     const int S = n_starts, L = n_trials;
     for (int s = 0; s < S; ++s)
         GEO_REQUIRE(first_host[s] >= 0 && first_host[s] < n, "geo_kmeans_pp: first[%d]=%d", s, first_host[s]);
-    const Plan p = plan(n, d, K, S, L, ws);
-    if (ws_bytes < plan(n, d, K, S, L, nullptr).bytes) {
-        geo::set_error("geo_kmeans_pp: workspace %zu bytes too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
+    geo::Arena ar(ws, ws_bytes);
+    const Plan p = lay_out(ar, n, d, K, S, L);
+    GEO_REQUIRE_WORKSPACE("geo_kmeans_pp", ar, ar.off);
     std::vector<int32_t> first((size_t)S * K, 0);
     for (int s = 0; s < S; ++s) first[(size_t)s * K] = first_host[s];
     GEO_HIP_CHECK(hipMemcpyAsync(indices_out, first.data(), first.size() * 4, hipMemcpyHostToDevice, stream));
@@ -805,11 +805,9 @@ extern "C" int geo_kmeans_lloyd(const float *X, int64_t n, int32_t d, int32_t K,
     GEO_REQUIRE(init && centers_out && labels_out && inertia_out && n_iter_out, "geo_kmeans_lloyd: null argument");
     GEO_REQUIRE(n_starts >= 1 && max_iter >= 1 && tol >= 0.0, "geo_kmeans_lloyd: n_starts=%d max_iter=%d tol=%g", n_starts,
                 max_iter, tol);
-    const Plan p = plan(n, d, K, 1, 1, ws);
-    if (ws_bytes < plan(n, d, K, 1, 1, nullptr).bytes) {
-        geo::set_error("geo_kmeans_lloyd: workspace %zu bytes too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
+    geo::Arena ar(ws, ws_bytes);
+    const Plan p = lay_out(ar, n, d, K, 1, 1);
+    GEO_REQUIRE_WORKSPACE("geo_kmeans_lloyd", ar, ar.off);
     const int64_t nchunk = (n + CHUNK - 1) / CHUNK;
     const size_t Kd = (size_t)K * d;
     int64_t fallback_total = 0;
@@ -1075,35 +1073,18 @@ struct VqPlan {
     float *rows, *norm;
     int32_t *labels;
     double *partial, *seg;
-    size_t bytes;
 };
 
-// Only what the quantizer's launches touch: the centre packing and status of the assignment, the counting sort and the sums.
-VqPlan vq_plan(int64_t n, int d, int K, void *ws) {
+// Of k-means only what the quantizer's launches touch (lay_out_assign, lay_out_sort), then its own buffers.
+VqPlan vq_lay_out(geo::Arena &ar, int64_t n, int d, int K) {
     VqPlan v{};
-    Plan &p = v.km;
-    const int ns = ns_for(d), ntiles = (K + 31) / 32;
-    const int64_t nchunk = (n + CHUNK - 1) / CHUNK;
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char * {
-        char *r = ws ? static_cast<char *>(ws) + off : nullptr;
-        off += geo::align_up(bytes);
-        return r;
-    };
-    p.Ap = (float *)take((size_t)ntiles * ns * 64 * 4);
-    p.cnp = (float *)take((size_t)ntiles * 32 * 4);
-    p.st = (Status *)take(sizeof(Status));
-    p.chunk_hist = (int32_t *)take((size_t)nchunk * K * 4);
-    p.counts = (int32_t *)take((size_t)K * 4);
-    p.offs = (int32_t *)take((size_t)(K + 1) * 4);
-    p.order = (int32_t *)take((size_t)n * 4);
-    p.sums = (double *)take((size_t)K * d * 8);
-    v.rows = (float *)take((size_t)n * d * 4);
-    v.labels = (int32_t *)take((size_t)n * 4);
-    v.partial = (double *)take((size_t)VQ_OUT_BLOCKS * 2 * 8);
-    v.norm = (float *)take((size_t)K * 4);
-    v.seg = (double *)take((size_t)n * d * 8);
-    v.bytes = off;
+    lay_out_assign(ar, &v.km, d, K);
+    lay_out_sort(ar, &v.km, n, d, K);
+    ar.take(v.rows, (size_t)n * d);
+    ar.take(v.labels, (size_t)n);
+    ar.take(v.partial, (size_t)VQ_OUT_BLOCKS * 2);
+    ar.take(v.norm, (size_t)K);
+    ar.take(v.seg, (size_t)n * d);
     return v;
 }
 
@@ -1118,7 +1099,7 @@ int vq_check(const char *who, int64_t B, int C, int64_t HW, int K) {
 
 extern "C" size_t geo_vq_workspace_bytes(int64_t n, int32_t d, int32_t K) {
     if (n < 1 || n >= ((int64_t)1 << 31) - CHUNK || d < 1 || d > MAX_D || K < 1 || K > MAX_K) return 0;
-    return vq_plan(n, d, K, nullptr).bytes;
+    return geo::measure(vq_lay_out, n, d, K);
 }
 
 extern "C" int geo_vq_forward(const void *z_e, int32_t half, int32_t B, int32_t C, int32_t HW, float *embed, float *cluster_size,
@@ -1131,11 +1112,9 @@ extern "C" int geo_vq_forward(const void *z_e, int32_t half, int32_t B, int32_t 
     GEO_REQUIRE(!training || (cluster_size && embed_avg), "geo_vq_forward: training needs cluster_size and embed_avg");
     GEO_REQUIRE(ws && ((uintptr_t)ws) % 256 == 0, "geo_vq_forward: workspace null or not 256-byte aligned");
     const int64_t n = (int64_t)B * HW, total = n * C;
-    const VqPlan v = vq_plan(n, C, K, ws);
-    if (ws_bytes < vq_plan(n, C, K, nullptr).bytes) {
-        geo::set_error("geo_vq_forward: workspace %zu bytes too small", ws_bytes);
-        return GEO_E_WORKSPACE;
-    }
+    geo::Arena ar(ws, ws_bytes);
+    const VqPlan v = vq_lay_out(ar, n, C, K);
+    GEO_REQUIRE_WORKSPACE("geo_vq_forward", ar, ar.off);
     const Plan &p = v.km;
     GEO_HIP_CHECK(hipMemsetAsync(p.st, 0, sizeof(Status), stream));
     const int ptiles = (HW + 31) / 32;

@@ -364,27 +364,18 @@ __global__ __launch_bounds__(256) void ps_draw_kernel(DrawArgs a, int V) {
     if (a.build_next) embed_row(a.e, b, tok, a.t + 1, a.x);
 }
 
-struct Plan {
-    float *kv, *x, *q, *att, *hid, *logits;
-    size_t bytes;
-};
+struct Plan { float *kv, *x, *q, *att, *hid, *logits; };
 
-Plan plan(const geo_prior_desc *d, int B, int S, void *ws) {
+// geo_prior_sample's workspace for B rows and S cached positions: measured by geo_prior_sample_workspace_bytes.
+Plan lay_out(geo::Arena &ar, const geo_prior_desc *d, int B, int S) {
     const size_t C = d->embed_dim;
-    size_t off = 0;
-    Plan p{};
-    auto take = [&](size_t n) {
-        float *r = ws ? reinterpret_cast<float *>(static_cast<char *>(ws) + off) : nullptr;
-        off += geo::align_up(n * sizeof(float));
-        return r;
-    };
-    p.kv = take((size_t)d->n_layers * 2 * B * S * C);
-    p.x = take((size_t)B * C);
-    p.q = take((size_t)B * C);
-    p.att = take((size_t)B * C);
-    p.hid = take((size_t)B * 4 * C);
-    p.logits = take((size_t)B * d->num_tokens);
-    p.bytes = off;
+    Plan p;
+    ar.take(p.kv, (size_t)d->n_layers * 2 * B * S * C);
+    ar.take(p.x, (size_t)B * C);
+    ar.take(p.q, (size_t)B * C);
+    ar.take(p.att, (size_t)B * C);
+    ar.take(p.hid, (size_t)B * 4 * C);
+    ar.take(p.logits, (size_t)B * d->num_tokens);
     return p;
 }
 
@@ -420,7 +411,7 @@ int check_desc(const geo_prior_desc *d, const char *fn) {
 
 extern "C" size_t geo_prior_sample_workspace_bytes(const geo_prior_desc *d, int32_t B, int32_t n_positions) {
     if (!d || B < 1 || n_positions < 1) return 0;
-    return plan(d, B, n_positions, nullptr).bytes;
+    return geo::measure(lay_out, d, B, n_positions);
 }
 
 extern "C" int geo_prior_sample(const geo_prior_desc *d, const int64_t *prompt, int32_t T0, int32_t steps, const int64_t *y,
@@ -439,12 +430,10 @@ extern "C" int geo_prior_sample(const geo_prior_desc *d, const int64_t *prompt, 
     const int T_total = T0 + steps, rounds = T_total - 1;
     const int C = d->embed_dim, H = d->n_head, V = d->num_tokens, hd = C / H;
     const int S = rounds > 0 ? rounds : 1;
-    const Plan p = plan(d, B, S, ws);
     GEO_REQUIRE(ws && ((uintptr_t)ws) % 256 == 0, "geo_prior_sample: workspace null or not 256-byte aligned");
-    if (ws_bytes < p.bytes) {
-        geo::set_error("geo_prior_sample: workspace %zu bytes < %zu", ws_bytes, p.bytes);
-        return GEO_E_WORKSPACE;
-    }
+    geo::Arena ar(ws, ws_bytes);
+    const Plan p = lay_out(ar, d, B, S);
+    GEO_REQUIRE_WORKSPACE("geo_prior_sample", ar, ar.off);
     const float *A = d->arena;
     EmbArgs e{A + d->token_emb, A + d->pos_emb, y ? A + d->class_emb : nullptr, y, V, C, d->num_classes};
     ps_init_kernel<<<B, 256, 0, stream>>>(e, prompt, T0, T_total, tokens_out, p.x);

@@ -60,11 +60,16 @@ bool make_shape(const geo_vanilla_decoder_desc *dc, Shape *s) {
 }
 
 // Workspace: per point slot the two masks and sigmoid'; per pass of EB edges the front's and the mid's outputs of 2 EB items.
-size_t layout_bytes(const Shape &s, int64_t slots, int64_t eb) {
-    using geo::align_up;
-    return align_up((size_t)slots * (s.n1 / 32) * 4) + align_up((size_t)slots * (s.n2 / 32) * 4) +
-           align_up((size_t)slots * s.nout * 4) + align_up((size_t)2 * eb * s.n1 * 4) + align_up((size_t)2 * eb * s.n2 * 4);
+// One layout: the queries and run()'s shrink loop measure it, run() carves with it.
+struct Workspace { uint32_t *mask1, *mask2; float *sigp, *buf1, *buf2; };
+Workspace lay_out(geo::Arena &ar, const Shape &s, int64_t slots, int64_t eb) {
+    Workspace w;
+    ar.take(w.mask1, (size_t)slots * (s.n1 / 32)); ar.take(w.mask2, (size_t)slots * (s.n2 / 32));
+    ar.take(w.sigp, (size_t)slots * s.nout);
+    ar.take(w.buf1, (size_t)2 * eb * s.n1); ar.take(w.buf2, (size_t)2 * eb * s.n2);
+    return w;
 }
+size_t layout_bytes(const Shape &s, int64_t slots, int64_t eb) { return geo::measure(lay_out, s, slots, eb); }
 
 // Where the latents of a pass come from.  List A holds the start points, list B the end points: entry i of a list is row
 // (index ? index[base + i] : base + i) of its array.  The points of a point pass are A[0 .. nA) followed by B[0 ..).
@@ -369,22 +374,18 @@ int run(const geo_vanilla_decoder_desc *dc, const Shape &sh, const float *zA, co
     }
     const int64_t slots = resident ? n_resident : 2 * eb;
     geo::Arena ar(ws, ws_bytes);
-    uint32_t *mask1 = ar.take<uint32_t>((size_t)slots * (sh.n1 / 32));
-    uint32_t *mask2 = ar.take<uint32_t>((size_t)slots * (sh.n2 / 32));
-    float *sigp = ar.take<float>((size_t)slots * sh.nout);
-    float *buf1 = ar.take<float>((size_t)2 * eb * sh.n1);
-    float *buf2 = ar.take<float>((size_t)2 * eb * sh.n2);
-    if (!mask1 || !mask2 || !sigp || !buf1 || !buf2) {
+    const Workspace w = lay_out(ar, sh, slots, eb);
+    if (!ar.ok()) {                                             // (unreachable: the shrink loop measured this layout)
         geo::set_error("%s: workspace too small", who);
         return GEO_E_WORKSPACE;
     }
     auto point_pass = [&](const Ends &e, int64_t count, int64_t slot0) -> int {
         const dim3 grid((unsigned)((count + FRONT_ROWS - 1) / FRONT_ROWS), FRONT_SPLIT);
-        vj_front_kernel<false><<<grid, 256, 0, st>>>(e, (int)count, sh.d, sh.dp, sh.n1, dc->At, dc->c, buf1, mask1, slot0);
+        vj_front_kernel<false><<<grid, 256, 0, st>>>(e, (int)count, sh.d, sh.dp, sh.n1, dc->At, dc->c, w.buf1, w.mask1, slot0);
         GEO_LAUNCH_CHECK();
-        int rc = run_mid<false>(sh, dc, buf1, buf2, mask1, mask2, e, 0, slot0, count, st);
+        int rc = run_mid<false>(sh, dc, w.buf1, w.buf2, w.mask1, w.mask2, e, 0, slot0, count, st);
         if (rc != GEO_OK) return rc;
-        return run_back<false>(sh, dc, buf2, sigp, e, 0, slot0, count, nullptr, st);
+        return run_back<false>(sh, dc, w.buf2, w.sigp, e, 0, slot0, count, nullptr, st);
     };
     if (resident)
         for (int64_t p0 = 0; p0 < n_resident; p0 += 2 * eb) {
@@ -401,11 +402,11 @@ int run(const geo_vanilla_decoder_desc *dc, const Shape &sh, const float *zA, co
             if (rc != GEO_OK) return rc;
         }
         const dim3 grid((unsigned)((ne + FRONT_ROWS - 1) / FRONT_ROWS), FRONT_SPLIT);
-        vj_front_kernel<true><<<grid, 256, 0, st>>>(e, (int)ne, sh.d, sh.dp, sh.n1, dc->At, dc->c, buf1, nullptr, 0);
+        vj_front_kernel<true><<<grid, 256, 0, st>>>(e, (int)ne, sh.d, sh.dp, sh.n1, dc->At, dc->c, w.buf1, nullptr, 0);
         GEO_LAUNCH_CHECK();
-        int rc = run_mid<true>(sh, dc, buf1, buf2, mask1, mask2, e, resident, 0, 2 * ne, st);
+        int rc = run_mid<true>(sh, dc, w.buf1, w.buf2, w.mask1, w.mask2, e, resident, 0, 2 * ne, st);
         if (rc != GEO_OK) return rc;
-        rc = run_back<true>(sh, dc, buf2, sigp, e, resident, 0, ne, len_out + e0, st);
+        rc = run_back<true>(sh, dc, w.buf2, w.sigp, e, resident, 0, ne, len_out + e0, st);
         if (rc != GEO_OK) return rc;
     }
     return GEO_OK;
