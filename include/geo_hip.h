@@ -825,6 +825,40 @@ int geo_path_stats(const float *D, int64_t ld, int32_t n_rows, int64_t n, double
 int geo_csr_set_symmetric(const int32_t *indptr, const int32_t *indices, float *data, int32_t n, const int32_t *src,
                           const int32_t *dst, const float *val, int64_t m, int32_t *n_missing_out, void *stream);
 
+/* ---- Geodesic paths and points along them (an extension) ----
+ * The walk inputs: P i32, S rows of leading dimension ld >= n (geo_sssp_multi's P_out, or a strided view of it), sources i32 [S]
+ * (the solve's), and M pairs rows i32 [M] (a row of P) / targets i32 [M] (a node).  Pair m starts at targets[m] and follows
+ * P[rows[m]][.] until sources[rows[m]].
+ * geo_sssp_paths_count: hops_out i32 [M] = the number of edges (0 when the target is the source), status_out i32 [M] =
+ *   0 source reached | 1 unreachable: a node other than the source whose predecessor is the sentinel -9999, at the target or
+ *   in mid-walk | 2 malformed: max_hops edges walked without reaching the source, a predecessor outside [0, n), or a row /
+ *   target / source that is no index.  hops_out = -1 for status 1 and 2.  Status 2 is a real outcome on graphs with
+ *   zero-weight edges (or weights below one ulp of the distance): two nodes at equal distance can name each other.
+ *   0 <= max_hops <= n - 1.  Every predecessor is checked before it is used: nothing outside P's S x ld block is read.
+ * geo_sssp_paths_fill: offsets i64 [M + 1] = the exclusive prefix sum of hops + 1 over the status-0 pairs (0 slots for the
+ *   others), T = offsets[M].  For a status-0 pair, nodes_out i32 [T] holds on [offsets[m], offsets[m + 1]) the path's nodes
+ *   source -> target and cum_out f64 [T] its running length: cum[0] = 0, cum[i] = cum[i - 1] + (double)w_i, one rounding per
+ *   hop, w_i = the minimum weight among the entries of row node[i] of the pull CSR (indptr / indices / weights, the graph the
+ *   solve ran on; weights == NULL = unit weights) whose index is node[i - 1] (+inf when there is none).  That is the solver's
+ *   accumulation order: (float)cum[hops] == D[row][target] bit for bit.
+ * geo_polyline_resample: z f32 [n][d]; frames_out f32 [M][F][d], F >= 2, receives F points per path at equal arc length:
+ *   frame 0 = z[node[0]] and frame F - 1 = z[node[hops]] exactly; frame f between them sits at s = cum[hops] * f / (F - 1)
+ *   (fp64, the product first), in segment i = the largest i <= hops - 1 with cum[i] <= s, at u = (s - cum[i]) / (cum[i + 1] -
+ *   cum[i]) (0 when the denominator is 0), and is a + u * (b - a) of the two node latents in fp64 without contraction,
+ *   rounded once to f32.  A path of 0 hops repeats its latent; a pair with an empty slice leaves its F d outputs untouched.
+ *   The straight chord of two nodes is the polyline nodes = [a, b], cum = [0, 1].
+ * Limits: n, S >= 1, 0 <= M < 2^31, M F < 2^32; GEO_E_ARG outside and for a null pointer, before any launch; M == 0 returns
+ * GEO_OK without a launch.  No workspace, no atomics: outputs are bit-identical across runs and streams.  Asynchronous. */
+int geo_sssp_paths_count(const int32_t *P, int64_t ld, int32_t S, const int32_t *sources, const int32_t *rows,
+                         const int32_t *targets, int64_t M, int32_t n, int32_t max_hops, int32_t *hops_out, int32_t *status_out,
+                         void *stream);
+int geo_sssp_paths_fill(const int32_t *P, int64_t ld, int32_t S, const int32_t *sources, const int32_t *rows,
+                        const int32_t *targets, int64_t M, int32_t n, const int32_t *indptr, const int32_t *indices,
+                        const float *weights, const int64_t *offsets, int64_t T, int32_t *nodes_out, double *cum_out,
+                        void *stream);
+int geo_polyline_resample(const float *z, int64_t n, int32_t d, const int32_t *nodes, const int64_t *offsets, const double *cum,
+                          int64_t M, int32_t F, float *frames_out, void *stream);
+
 /* ---- EMA vector quantizer (the reference's baseline VQ-VAE, VectorQuantizerEMA) ----
  * z_e [B][C][HW] (NCHW, contiguous) f32 (half = 0) or f16 (half = 1), 1 <= C <= 128, 1 <= K <= 4096, any n = B HW >= 1 (K > n
  * allowed).  Rows are z_e's positions (b, h, w) in that order, upcast to f32.  idx_out i64 [n] = geo_kmeans_assign's labels

@@ -147,6 +147,9 @@ _SIGNATURES = {
     "geo_feature_gram": (ctypes.c_int, [c_p, i64, i32, i64, c_p, c_p, c_p, c_p, sz, c_p]),
     "geo_feature_project": (ctypes.c_int, [c_p, i64, i32, i64, c_p, c_p, c_p, i32, c_p, c_p]),
     "geo_path_stats": (ctypes.c_int, [c_p, i64, i32, i64, c_p, c_p, c_p, c_p, c_p]),
+    "geo_sssp_paths_count": (ctypes.c_int, [c_p, i64, i32, c_p, c_p, c_p, i64, i32, i32, c_p, c_p, c_p]),
+    "geo_sssp_paths_fill": (ctypes.c_int, [c_p, i64, i32, c_p, c_p, c_p, i64, i32, c_p, c_p, c_p, c_p, i64, c_p, c_p, c_p]),
+    "geo_polyline_resample": (ctypes.c_int, [c_p, i64, i32, c_p, c_p, c_p, i64, i32, c_p, c_p]),
     "geo_csr_set_symmetric": (ctypes.c_int, [c_p, c_p, c_p, i32, c_p, c_p, c_p, i64, c_p, c_p]),
     "geo_vq_workspace_bytes": (sz, [i64, i32, i32]),
     "geo_vq_forward": (ctypes.c_int, [c_p, i32, i32, i32, i32, c_p, c_p, c_p, i32, i32, ctypes.c_double, ctypes.c_double,

@@ -4,10 +4,14 @@ k-medoids analysis (fit_kmedoids_path, an extension), the matrix-free k-medoids 
 cell_medoid_update_device, an extension) and the Riemannian graph experiments of the reference's
 experiments/geo scripts (vqvae_amd.geo.experiments), and the bridging of a kNN graph's components (bridge_components_device,
 nearest_foreign_device, connect_components, an extension), and the pull-back metric tensor per latent (pullback_metric,
-pullback_metric_device, native_metric_covers, an extension)."""
+pullback_metric_device, native_metric_covers, an extension), and geodesic paths and interpolation along them (geodesic_paths,
+geodesic_paths_device, paths_from_predecessors_device, resample_paths_device, chord_frames_device, geodesic_interpolation,
+interpolate_images_spatial, an extension)."""
 from .knn_graph_optimized import (bridge_components_device, build_knn_graph, connect_components, kneighbors, knn_query_device,
                                   nearest_foreign_device)
-from .geo_shortest_paths import dijkstra_multi_source
+from .geo_shortest_paths import (GeodesicPaths, chord_frames_device, dijkstra_multi_source, geodesic_paths, geodesic_paths_device,
+                                 paths_from_predecessors_device, resample_paths_device)
+from .interpolation import geodesic_interpolation, interpolate_images_spatial
 from .kmeans_optimized import cell_medoid_update_device, fit_kmedoids_path, fit_kmedoids_voronoi_graph
 from .experiments import (mean_shortest_path, mean_shortest_path_device, pick_sources_from_lcc, reweight_edges_symmetric_device,
                           riemann_graph_effects, riemann_sanity, stratified_edge_sample)
@@ -17,4 +21,6 @@ __all__ = ["bridge_components_device", "build_knn_graph", "cell_medoid_update_de
            "kneighbors", "knn_query_device", "mean_shortest_path",
            "PullbackMetric", "native_metric_covers", "pullback_metric", "pullback_metric_device",
            "mean_shortest_path_device", "nearest_foreign_device", "pick_sources_from_lcc", "reweight_edges_symmetric_device", "riemann_graph_effects", "riemann_sanity",
-           "stratified_edge_sample"]
+           "stratified_edge_sample",
+           "GeodesicPaths", "chord_frames_device", "geodesic_paths", "geodesic_paths_device", "paths_from_predecessors_device",
+           "resample_paths_device", "geodesic_interpolation", "interpolate_images_spatial"]

@@ -1,7 +1,9 @@
 """Geodesic shortest paths on the MI355X -- same API as the reference's
 src/geo/geo_shortest_paths.py (ensure_valid_graph :13, dijkstra_multi_source :24,
 dijkstra_single_source :53, distances_between :66), with scipy's Dijkstra replaced by the fp64
-label-correcting kernels of csrc/sssp.hip (geo_sssp_multi).  Host objects in, host objects out."""
+label-correcting kernels of csrc/sssp.hip (geo_sssp_multi).  Host objects in, host objects out.
+An extension below: the paths themselves (geodesic_paths, geodesic_paths_device, csrc/paths.hip)."""
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
@@ -9,7 +11,7 @@ import torch
 from scipy import sparse
 
 from .. import _lib
-from .._device import DeviceCSR, device, ptr, stream_ptr, workspace
+from .._device import DeviceCSR, device, ptr, ptr_or_stand_in, stream_ptr, workspace
 
 
 def ensure_valid_graph(W: sparse.spmatrix) -> sparse.spmatrix:
@@ -146,6 +148,193 @@ def distances_between(W: sparse.spmatrix, sources, targets, directed: bool = Fal
     D = dijkstra_multi_source(W, sources, directed=directed, unweighted=unweighted,
                               return_predecessors=False, dtype=dtype)
     return D[:, targets]
+
+
+# ------------------------------------------------------------------------------------- geodesic paths
+@dataclass
+class GeodesicPaths:
+    """M paths, device-resident, as csrc/paths.hip leaves them: pair m owns the slice [offsets[m], offsets[m + 1]) of `nodes`
+    (source -> target) and `cum` (the running fp64 length, the solver's accumulation order); the slice is empty unless
+    status[m] == 0.  status: 0 source reached, 1 target unreachable, 2 malformed predecessors (hops = -1 for both)."""
+    nodes: torch.Tensor        # i32 [T]
+    offsets: torch.Tensor      # i64 [M + 1]
+    cum: torch.Tensor          # f64 [T]
+    hops: torch.Tensor         # i32 [M]
+    status: torch.Tensor       # i32 [M]
+
+    def __len__(self) -> int:
+        return int(self.hops.numel())
+
+    def path(self, m: int):
+        """(nodes np.int32, cum np.float64) of pair m on the host; empty arrays unless status[m] == 0."""
+        lo, hi = (int(x) for x in self.offsets[m:m + 2].tolist())
+        return self.nodes[lo:hi].cpu().numpy(), self.cum[lo:hi].cpu().numpy()
+
+    def to_lists(self):
+        """(list of M np.int32 node arrays, list of M np.float64 cum arrays): one copy of each array to the host."""
+        nodes, cum, off = self.nodes.cpu().numpy(), self.cum.cpu().numpy(), self.offsets.cpu().numpy()
+        return ([nodes[off[m]:off[m + 1]] for m in range(len(self))], [cum[off[m]:off[m + 1]] for m in range(len(self))])
+
+
+def _i32(x, dev) -> torch.Tensor:
+    return torch.as_tensor(x, device=dev).to(torch.int32).contiguous().view(-1)
+
+
+def paths_from_predecessors_device(G: DeviceCSR, P: torch.Tensor, sources: torch.Tensor, rows: torch.Tensor,
+                                   targets: torch.Tensor, *, unweighted: bool = False,
+                                   max_hops: Optional[int] = None) -> GeodesicPaths:
+    """The paths the predecessor rows `P` (i32 [S, n], sssp_multi_device(want_P=True) on `G`; a view with a row stride >= n
+    is taken as it is) hold for the M pairs (rows[m], targets[m]): row rows[m] of P was solved from sources[rows[m]].
+    count -> cumsum -> fill on the current stream; one synchronisation (the total number of path nodes sizes the outputs)."""
+    lib = _lib.load()
+    dev = G.indptr.device
+    n = G.n
+    if P.dtype != torch.int32 or P.dim() != 2 or P.shape[1] != n or P.stride(1) != 1 or (P.shape[0] > 1 and P.stride(0) < n):
+        raise ValueError(f"P must be int32 [S, {n}] with unit column stride and a row stride >= n, got {P.dtype} "
+                         f"{tuple(P.shape)} strides {tuple(P.stride())}")
+    S, ld = int(P.shape[0]), int(P.stride(0)) if P.shape[0] > 1 else n
+    sources, rows, targets = _i32(sources, dev), _i32(rows, dev), _i32(targets, dev)
+    M = int(rows.numel())
+    if int(sources.numel()) != S or int(targets.numel()) != M:
+        raise ValueError(f"{int(sources.numel())} sources for {S} rows of P, {int(targets.numel())} targets for {M} rows")
+    max_hops = n - 1 if max_hops is None else int(max_hops)
+    if not 0 <= max_hops <= n - 1:
+        raise ValueError(f"max_hops = {max_hops} outside [0, n - 1 = {n - 1}]")
+    hops = torch.empty(M, dtype=torch.int32, device=dev)
+    status = torch.empty(M, dtype=torch.int32, device=dev)
+    offsets = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+    if M == 0:
+        return GeodesicPaths(torch.empty(0, dtype=torch.int32, device=dev), offsets,
+                             torch.empty(0, dtype=torch.float64, device=dev), hops, status)
+    weights = None if unweighted else G.data
+    with torch.cuda.device(dev):
+        _lib.check(lib.geo_sssp_paths_count(ptr(P), ld, S, ptr(sources), ptr(rows), ptr(targets), M, n, max_hops, ptr(hops),
+                                            ptr(status), stream_ptr()), "geo_sssp_paths_count")
+        torch.cumsum((hops + 1).to(torch.int64), 0, out=offsets[1:])          # hops = -1 wherever status != 0: no slot
+        T = int(offsets[-1].item())
+        nodes = torch.empty(T, dtype=torch.int32, device=dev)
+        cum = torch.empty(T, dtype=torch.float64, device=dev)
+        _lib.check(lib.geo_sssp_paths_fill(ptr(P), ld, S, ptr(sources), ptr(rows), ptr(targets), M, n, ptr(G.indptr),
+                                           ptr_or_stand_in(G.indices), ptr(weights), ptr(offsets), T, ptr_or_stand_in(nodes),
+                                           ptr_or_stand_in(cum), stream_ptr()), "geo_sssp_paths_fill")
+    return GeodesicPaths(nodes, offsets, cum, hops, status)
+
+
+def geodesic_paths_device(G: DeviceCSR, src_nodes, dst_nodes, *, unweighted: bool = False,
+                          max_block_bytes: int = 4 << 30) -> Tuple[GeodesicPaths, torch.Tensor]:
+    """Geodesics between the M node pairs (src_nodes[m], dst_nodes[m]) of G: (GeodesicPaths, dist f32 [M]) in the caller's
+    pair order, dist[m] = D[row of src][dst] of sssp_multi_device.  The pairs are grouped by unique source; the sources are
+    solved in blocks whose D and P rows (8 n bytes per source) fit `max_block_bytes` -- at least one source per block."""
+    dev = G.indptr.device
+    n = G.n
+    src, dst = _i32(src_nodes, dev), _i32(dst_nodes, dev)
+    M = int(src.numel())
+    if int(dst.numel()) != M:
+        raise ValueError(f"{M} sources for {int(dst.numel())} targets")
+    if M and (int(torch.minimum(src.min(), dst.min())) < 0 or int(torch.maximum(src.max(), dst.max())) >= n):
+        raise ValueError(f"indices out of range 0...{n}")
+    dist = torch.empty(M, dtype=torch.float32, device=dev)
+    hops = torch.empty(M, dtype=torch.int32, device=dev)
+    status = torch.empty(M, dtype=torch.int32, device=dev)
+    offsets = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+    if M == 0:
+        return GeodesicPaths(torch.empty(0, dtype=torch.int32, device=dev), offsets,
+                             torch.empty(0, dtype=torch.float64, device=dev), hops, status), dist
+    uniq, row_of = torch.unique(src, return_inverse=True)                     # sorted sources; row_of[m] = its row
+    per_block = max(1, int(max_block_bytes) // (8 * n))
+    order = torch.argsort(row_of, stable=True)                                # pairs by source row, the caller's order within
+    row_sorted = row_of[order]
+    parts = []
+    for s0 in range(0, int(uniq.numel()), per_block):
+        s1 = min(int(uniq.numel()), s0 + per_block)
+        sel = order[(row_sorted >= s0) & (row_sorted < s1)]
+        D, P, _, _, _ = sssp_multi_device(G, uniq[s0:s1].contiguous(), unweighted=unweighted, want_D=True, want_P=True)
+        rows = (row_of[sel] - s0).to(torch.int32)
+        part = paths_from_predecessors_device(G, P, uniq[s0:s1], rows, dst[sel], unweighted=unweighted)
+        dist[sel] = D[rows.long(), dst[sel].long()]
+        hops[sel], status[sel] = part.hops, part.status
+        parts.append((sel, part))
+    torch.cumsum((hops + 1).to(torch.int64), 0, out=offsets[1:])
+    T = int(offsets[-1].item())
+    nodes = torch.empty(T, dtype=torch.int32, device=dev)
+    cum = torch.empty(T, dtype=torch.float64, device=dev)
+    for sel, part in parts:                                                   # each block's slices to their place in pair order
+        length = part.offsets[1:] - part.offsets[:-1]
+        if int(part.nodes.numel()) == 0:
+            continue
+        pair = torch.repeat_interleave(torch.arange(sel.numel(), device=dev), length)
+        at = offsets[sel][pair] + (torch.arange(part.nodes.numel(), device=dev) - part.offsets[:-1][pair])
+        nodes[at], cum[at] = part.nodes, part.cum
+    return GeodesicPaths(nodes, offsets, cum, hops, status), dist
+
+
+def _check_frames(n_frames: int) -> int:
+    if int(n_frames) < 2:
+        raise ValueError(f"n_frames = {n_frames}: a curve needs its two ends (n_frames >= 2)")
+    return int(n_frames)
+
+
+def _resample(z: torch.Tensor, nodes, offsets, cum, M: int, F: int) -> torch.Tensor:
+    lib = _lib.load()
+    if z.dtype != torch.float32 or z.dim() != 2 or not z.is_contiguous():
+        raise ValueError(f"z must be a contiguous float32 [n, d] tensor, got {z.dtype} {tuple(z.shape)}")
+    frames = torch.full((M, F, z.shape[1]), float("nan"), dtype=torch.float32, device=z.device)
+    with torch.cuda.device(z.device):
+        _lib.check(lib.geo_polyline_resample(ptr(z), z.shape[0], z.shape[1], ptr_or_stand_in(nodes), ptr(offsets),
+                                             ptr_or_stand_in(cum), M, F, ptr_or_stand_in(frames), stream_ptr()),
+                   "geo_polyline_resample")
+    return frames
+
+
+def resample_paths_device(z: torch.Tensor, paths: GeodesicPaths, n_frames: int) -> torch.Tensor:
+    """n_frames points at equal arc length along each path's polyline through the latents z f32 [n, d]: f32 [M, F, d], the
+    first the source's latent and the last the target's, bit for bit.  NaN for a pair without a path (status != 0)."""
+    F = _check_frames(n_frames)
+    return _resample(z, paths.nodes, paths.offsets, paths.cum, len(paths), F)
+
+
+def chord_frames_device(z: torch.Tensor, src_nodes, dst_nodes, n_frames: int) -> torch.Tensor:
+    """n_frames equally spaced points on the straight line from z[src_nodes[m]] to z[dst_nodes[m]]: f32 [M, F, d], through the
+    kernel of resample_paths_device as the two-node polyline nodes = [a, b], cum = [0, 1]."""
+    F = _check_frames(n_frames)
+    src, dst = _i32(src_nodes, z.device), _i32(dst_nodes, z.device)
+    M = int(src.numel())
+    if int(dst.numel()) != M:
+        raise ValueError(f"{M} sources for {int(dst.numel())} targets")
+    if M and (int(torch.minimum(src.min(), dst.min())) < 0 or int(torch.maximum(src.max(), dst.max())) >= z.shape[0]):
+        raise ValueError(f"indices out of range 0...{z.shape[0]}")
+    nodes = torch.stack([src, dst], dim=1).contiguous().view(-1)
+    offsets = torch.arange(M + 1, dtype=torch.int64, device=z.device) * 2
+    cum = torch.tensor([0.0, 1.0], dtype=torch.float64, device=z.device).repeat(M)
+    return _resample(z, nodes, offsets, cum, M, F)
+
+
+def geodesic_paths(W: sparse.spmatrix, sources, targets, directed: bool = False, unweighted: bool = False):
+    """Geodesics between the pairs (sources[m], targets[m]) of W: (list of np.int32 node arrays source -> target, np.float32
+    distances).  Validation, index normalisation and exception classes of dijkstra_multi_source.  An unreachable pair gives
+    an empty array and inf.  Raises ValueError when the solve's predecessors do not lead back to a source: on a graph with
+    zero-weight edges (or weights below one ulp of the distances) two nodes at the same distance can name each other."""
+    if len(sources) == 0 or len(targets) == 0:
+        raise ValueError("sources and targets must be non-empty.")
+    if len(sources) != len(targets):
+        raise ValueError(f"{len(sources)} sources for {len(targets)} targets: one target per source")
+    W = ensure_valid_graph(W)
+    n = W.shape[0]
+    src, dst = _normalise_sources(sources, n), _normalise_sources(targets, n)
+    if n == 0:
+        raise ValueError("graph has no nodes")
+    dev = device()
+    G = DeviceCSR.from_scipy(_pull_structure(W, directed), dev, with_data=not unweighted)
+    paths, dist = geodesic_paths_device(G, src.astype(np.int32), dst.astype(np.int32), unweighted=unweighted)
+    status = paths.status.cpu().numpy()
+    bad = np.flatnonzero(status == 2)
+    if bad.size:
+        m = int(bad[0])
+        raise ValueError(f"pair {m} ({int(src[m])} -> {int(dst[m])}): the predecessors of the solve do not lead back to the "
+                         f"source ({bad.size} such pair(s)).  With zero-weight edges, or weights below one ulp of the "
+                         "distances, two nodes at equal distance can name each other as predecessor; drop or merge such "
+                         "edges (build_codebook does)")
+    return paths.to_lists()[0], dist.cpu().numpy().astype(np.float32, copy=False)
 
 
 def all_pairs_geodesic_device(G: DeviceCSR, block: int = 512, max_bytes: int = 200 << 30) -> torch.Tensor:

@@ -1,0 +1,112 @@
+"""Interpolation along geodesics of a pull-back weighted latent graph, next to the straight line (an extension: the reference's
+demos stop at colouring nodes by geodesic distance).
+
+geodesic_interpolation: node pairs -> the geodesic's polyline resampled at equal arc length (csrc/paths.hip), the chord, and
+the pull-back length of both curves (edge_lengths_riemannian over consecutive frames).
+interpolate_images_spatial: image pairs of the spatial pipeline -> 16 node pairs each, one per grid position, assembled into
+latent grids, decoded (decode_images), with the image-space length of both routes (geo_image_pair_moments).
+"""
+from typing import Dict, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .._device import DeviceCSR
+from .geo_shortest_paths import _check_frames, chord_frames_device, geodesic_paths_device, resample_paths_device
+from .riemannian_metric import edge_lengths_riemannian
+
+
+def curve_lengths(decoder, frames: torch.Tensor, batch_size: int = 512) -> torch.Tensor:
+    """Pull-back length of M polylines frames f32 [M, F, d]: f32 [M], the sum over the F - 1 segments, in segment order, of
+    edge_lengths_riemannian(decoder, frames[:, f], frames[:, f + 1])."""
+    total = torch.zeros(frames.shape[0], dtype=torch.float32, device=frames.device)
+    for f in range(frames.shape[1] - 1):
+        seg = edge_lengths_riemannian(decoder, frames[:, f].contiguous(), frames[:, f + 1].contiguous(), batch_size)
+        total = total + seg.to(frames.device)
+    return total
+
+
+def geodesic_interpolation(z: torch.Tensor, G: DeviceCSR, decoder, src_nodes, dst_nodes, n_frames: int, *,
+                           batch_size: int = 512) -> Dict[str, torch.Tensor]:
+    """Curves between the M node pairs of the graph G over the latents z f32 [n, d] (device).  Returns frames_geo, frames_lin
+    f32 [M, F, d]; graph_dist f32 [M] (the solver's distance); hops, status i32 [M] (GeodesicPaths); curve_len_geo,
+    curve_len_lin f32 [M] (curve_lengths).  A pair without a path (status != 0) gets the chord as frames_geo.  Call with the
+    decoder in eval mode: a train-mode BatchNorm would move its statistics and make a segment depend on its batch."""
+    F = _check_frames(n_frames)
+    paths, dist = geodesic_paths_device(G, src_nodes, dst_nodes)
+    frames_lin = chord_frames_device(z, src_nodes, dst_nodes, F)
+    frames_geo = resample_paths_device(z, paths, F)
+    frames_geo = torch.where((paths.status != 0).view(-1, 1, 1), frames_lin, frames_geo)
+    return {"frames_geo": frames_geo, "frames_lin": frames_lin, "graph_dist": dist, "hops": paths.hops, "status": paths.status,
+            "curve_len_geo": curve_lengths(decoder, frames_geo, batch_size),
+            "curve_len_lin": curve_lengths(decoder, frames_lin, batch_size)}
+
+
+def image_curve_lengths(images: torch.Tensor) -> torch.Tensor:
+    """images f32 [M, F, C, S, S] -> f64 [M]: the sum over f, in order, of sqrt(squared error) between frames f and f + 1, the
+    squared error being geo_image_pair_moments' sixth moment."""
+    from ..eval.metrics import image_pair_moments
+    M, F = images.shape[:2]
+    flat = images.reshape(M, F, -1)
+    total = torch.zeros(M, dtype=torch.float64, device=images.device)
+    for f in range(F - 1):
+        total = total + torch.sqrt(image_pair_moments(flat[:, f].contiguous(), flat[:, f + 1].contiguous())[:, 5])
+    return total
+
+
+def interpolate_images_spatial(z_grids: torch.Tensor, lcc_index, G: DeviceCSR, decoder, image_pairs: Sequence[Tuple[int, int]],
+                               n_frames: int, dataset: str, apply_sigmoid: bool, *, batch_size: int = 512) -> Dict:
+    """Image pairs of the spatial pipeline.  z_grids f32 [N, d, 4, 4] (any h x w grid); lcc_index: the flat positions
+    img * h * w + y * w + x that are nodes of G, ascending -- np.flatnonzero(codes.reshape(-1) >= 0) of a build_codebook
+    output: a position's node is its rank in that list.  Pair (i, j) is h * w node pairs, position p of image i to position p
+    of image j; a position with an end outside the graph, or without a path, takes the chord and is listed in
+    fallback_positions (per pair, the sorted positions p).  Returns frames_geo, frames_lin f32 [M, F, d, h, w]; images_geo,
+    images_lin f32 [M, F, C, S, S] (decode_images of those grids); graph_dist f32 [M, h w] (NaN outside the graph, inf
+    without a path), hops, status i32 [M, h w] (-1 and 3 for a position outside the graph); curve_len_geo, curve_len_lin f32
+    [M] (pull-back lengths summed over the positions in position order); image_len_geo, image_len_lin f64 [M]."""
+    from ..decode import decode_images
+    F = _check_frames(n_frames)
+    dev = G.indptr.device
+    N, d, h, w = z_grids.shape
+    hw = h * w
+    pairs = np.asarray(image_pairs, dtype=np.int64).reshape(-1, 2)
+    M = pairs.shape[0]
+    if M == 0:
+        raise ValueError("image_pairs must be a non-empty sequence of (i, j)")
+    if pairs.min() < 0 or pairs.max() >= N:
+        raise ValueError(f"image indices out of range 0...{N}")
+    lcc_index = np.asarray(lcc_index, dtype=np.int64).reshape(-1)
+    if lcc_index.size != G.n or (lcc_index.size and (lcc_index.min() < 0 or lcc_index.max() >= N * hw
+                                                      or (np.diff(lcc_index) <= 0).any())):
+        raise ValueError(f"lcc_index must list the {G.n} nodes of the graph as ascending flat positions below {N * hw}")
+    node_of = np.full(N * hw, -1, dtype=np.int64)
+    node_of[lcc_index] = np.arange(lcc_index.size)
+    flat = z_grids.to(dev, torch.float32).permute(0, 2, 3, 1).reshape(N * hw, d).contiguous()
+    pos = np.arange(hw)
+    a = (pairs[:, :1] * hw + pos).reshape(-1)                                # flat positions of the M hw node pairs
+    b = (pairs[:, 1:] * hw + pos).reshape(-1)
+    frames_lin = chord_frames_device(flat, a, b, F)                           # over all positions: a chord needs no graph
+    in_graph = (node_of[a] >= 0) & (node_of[b] >= 0)
+    sel = np.flatnonzero(in_graph)
+    frames_geo = frames_lin.clone()
+    graph_dist = torch.full((M * hw,), float("nan"), dtype=torch.float32, device=dev)
+    hops = torch.full((M * hw,), -1, dtype=torch.int32, device=dev)
+    status = torch.full((M * hw,), 3, dtype=torch.int32, device=dev)
+    if sel.size:
+        sel_t = torch.from_numpy(sel).to(dev)
+        z_lcc = flat[torch.from_numpy(lcc_index).to(dev)].contiguous()
+        paths, dist = geodesic_paths_device(G, node_of[a[sel]], node_of[b[sel]])
+        geo = resample_paths_device(z_lcc, paths, F)
+        frames_geo[sel_t] = torch.where((paths.status != 0).view(-1, 1, 1), frames_lin[sel_t], geo)
+        graph_dist[sel_t], hops[sel_t], status[sel_t] = dist, paths.hops, paths.status
+    st = status.view(M, hw).cpu().numpy()
+    out = {"frames_geo": None, "frames_lin": None, "graph_dist": graph_dist.view(M, hw), "hops": hops.view(M, hw),
+           "status": status.view(M, hw), "fallback_positions": [np.flatnonzero(st[m] != 0).astype(np.int32) for m in range(M)]}
+    for name, fr in (("geo", frames_geo), ("lin", frames_lin)):
+        out[f"curve_len_{name}"] = curve_lengths(decoder, fr, batch_size).view(M, hw).sum(dim=1)
+        grids = fr.view(M, h, w, F, d).permute(0, 3, 4, 1, 2).contiguous()   # [M, F, d, h, w]
+        images = decode_images(decoder, grids.view(M * F, d, h, w), dataset=dataset, apply_sigmoid=apply_sigmoid)
+        out[f"frames_{name}"] = grids
+        out[f"images_{name}"] = images.view(M, F, *images.shape[1:])
+        out[f"image_len_{name}"] = image_curve_lengths(out[f"images_{name}"])
+    return out

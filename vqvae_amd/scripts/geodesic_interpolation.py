@@ -1,0 +1,136 @@
+"""Interpolate between training images along the geodesics of a built codebook's graph, next to the straight line.
+
+    python -m vqvae_amd.scripts.geodesic_interpolation --codebook_dir DIR --out_dir OUT
+        (--pairs i:j [i:j ...] | --num_pairs N [--seed S]) [--frames 9] [--dataset other] [--batch_size 512]
+        [--train_latents_path PATH]
+
+DIR is an output of vqvae_amd.scripts.build_codebook (spatial pipeline): codebook.pt's "config" names the checkpoint, the
+training latents and the decoder's arguments, exactly as vqvae_amd.training.assign_codes_val_geodesic reads them.  A pair i:j
+is two images of the training latents; each of their grid positions is one node pair of knn_graph_geodesic.npz
+(geo.interpolation.interpolate_images_spatial).  The decoder runs in eval() mode.  An extension: the reference's demos
+(visualizations/interactive_knn_viz.py, demos/interactive_exploration.py) colour nodes by geodesic distance and stop there.
+
+Writes to OUT:
+  interpolation.png   two rows of `frames` images per pair: the chord on top, the geodesic below (the grid of codebook_sampling)
+  interpolation.npz   pairs i64 [M, 2]; frames_lin, frames_geo f32 [M, F, d, h, w]; images_lin, images_geo f32 [M, F, C, S, S];
+                      graph_dist f32, hops, status i32 [M, h w]; curve_len_lin, curve_len_geo f32 [M]; image_len_lin,
+                      image_len_geo f64 [M]; fallback_pair, fallback_position i32 [n_fallback] (the positions that took the chord)
+  interpolation.json  per pair: graph_dist (summed over the positions with a path), the four lengths, ratio_curve and
+                      ratio_image (geodesic / chord), fallback_positions; and the totals over the pairs
+
+Whether the geodesic is the shorter curve under the decoder's metric is a property of the trained model; the JSON reports
+the ratio and the script asserts nothing about it.
+"""
+import argparse
+import json
+from pathlib import Path
+
+import numpy as np
+import torch
+
+
+def parse_pairs(tokens, n_images: int) -> np.ndarray:
+    """["3:17", ...] -> i64 [M, 2]; ValueError for a token that is not i:j or an image outside [0, n_images)."""
+    pairs = []
+    for tok in tokens:
+        parts = tok.split(":")
+        if len(parts) != 2 or not all(p.strip().lstrip("-").isdigit() for p in parts):
+            raise ValueError(f"--pairs: '{tok}' is not of the form i:j")
+        i, j = int(parts[0]), int(parts[1])
+        if not (0 <= i < n_images and 0 <= j < n_images):
+            raise ValueError(f"--pairs: '{tok}' names an image outside 0...{n_images}")
+        pairs.append((i, j))
+    return np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+
+
+def draw_pairs(n_images: int, num_pairs: int, seed: int) -> np.ndarray:
+    """num_pairs pairs of distinct images, RandomState(seed).choice without replacement per pair."""
+    if n_images < 2 or num_pairs < 1:
+        raise ValueError(f"--num_pairs {num_pairs} of {n_images} images: at least one pair of two images is needed")
+    rng = np.random.RandomState(seed)
+    return np.stack([rng.choice(n_images, size=2, replace=False) for _ in range(num_pairs)]).astype(np.int64)
+
+
+def _ratio(a: float, b: float):
+    return a / b if b > 0 else None
+
+
+def main(args) -> dict:
+    from .._device import DeviceCSR, device
+    from ..geo.interpolation import interpolate_images_spatial
+    from ..spatial_decoder import load_decoder_from_checkpoint
+    from ..training.assign_codes_val_geodesic import lcc_rows, load_build
+    from .generate_samples import save_image
+    cb_dir, out_dir = Path(args.codebook_dir), Path(args.out_dir)
+    if (args.pairs is None) == (args.num_pairs is None):
+        raise ValueError("give either --pairs i:j ... or --num_pairs N")
+    codebook, W, _ = load_build(cb_dir, args.train_latents_path)       # checks that the artefacts belong together
+    cfg = codebook["config"]
+    z = torch.load(args.train_latents_path or cfg["latents_path"], map_location="cpu").float()
+    if z.dim() != 4:
+        raise ValueError(f"the build's latents are {tuple(z.shape)}: this script interpolates latent grids [N, d, h, w]")
+    pairs = parse_pairs(args.pairs, z.shape[0]) if args.pairs is not None else draw_pairs(z.shape[0], args.num_pairs, args.seed)
+    dev = device()
+    decoder = load_decoder_from_checkpoint(
+        cfg["vae_ckpt_path"], in_channels=cfg["in_channels"], dec_channels=cfg["dec_channels"], latent_dim=cfg["latent_dim"],
+        output_image_size=cfg["output_image_size"], norm_type=cfg["norm_type"], device=dev).eval()
+    apply_sigmoid = str(cfg.get("recon_loss", "mse")).lower() == "bce" or bool(cfg.get("mse_use_sigmoid", False))
+    out = interpolate_images_spatial(z, lcc_rows(np.load(cb_dir / "codes.npy")), DeviceCSR.from_scipy(W, dev), decoder,
+                                     pairs, args.frames, args.dataset, apply_sigmoid, batch_size=args.batch_size)
+
+    M, F = pairs.shape[0], int(args.frames)
+    host = {k: out[k].cpu().numpy() for k in ("frames_lin", "frames_geo", "images_lin", "images_geo", "graph_dist", "hops",
+                                               "status", "curve_len_lin", "curve_len_geo", "image_len_lin", "image_len_geo")}
+    fallback = out["fallback_positions"]
+    per_pair = []
+    for m in range(M):
+        d = host["graph_dist"][m]
+        with_path = host["status"][m] == 0
+        rec = {"pair": [int(pairs[m, 0]), int(pairs[m, 1])],
+               "graph_dist": float(d[with_path].astype(np.float64).sum()),
+               "fallback_positions": [int(p) for p in fallback[m]]}
+        for k in ("curve_len_lin", "curve_len_geo", "image_len_lin", "image_len_geo"):
+            rec[k] = float(host[k][m])
+        rec["ratio_curve"] = _ratio(rec["curve_len_geo"], rec["curve_len_lin"])
+        rec["ratio_image"] = _ratio(rec["image_len_geo"], rec["image_len_lin"])
+        per_pair.append(rec)
+    totals = {k: float(sum(r[k] for r in per_pair))
+              for k in ("graph_dist", "curve_len_lin", "curve_len_geo", "image_len_lin", "image_len_geo")}
+    totals["ratio_curve"] = _ratio(totals["curve_len_geo"], totals["curve_len_lin"])
+    totals["ratio_image"] = _ratio(totals["image_len_geo"], totals["image_len_lin"])
+    totals["fallback_positions"] = int(sum(len(p) for p in fallback))
+    summary = {"codebook_dir": str(cb_dir), "frames": F, "dataset": args.dataset, "apply_sigmoid": apply_sigmoid,
+               "pairs": per_pair, "totals": totals}
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rows = torch.stack([out["images_lin"], out["images_geo"]], dim=1)    # [M, 2, F, C, S, S]: chord above geodesic, per pair
+    save_image(rows.reshape(M * 2 * F, *rows.shape[3:]).cpu(), str(out_dir / "interpolation.png"), nrow=F)
+    np.savez(out_dir / "interpolation.npz", pairs=pairs,
+             fallback_pair=np.concatenate([np.full(len(p), m, dtype=np.int32) for m, p in enumerate(fallback)]),
+             fallback_position=np.concatenate([np.asarray(p, dtype=np.int32) for p in fallback]), **host)
+    with open(out_dir / "interpolation.json", "w") as f:
+        json.dump(summary, f, indent=2)
+    t = totals
+    print(f"{M} pair(s), {F} frames: pull-back length geodesic {t['curve_len_geo']:.4f} / chord {t['curve_len_lin']:.4f}; "
+          f"image-space length geodesic {t['image_len_geo']:.4f} / chord {t['image_len_lin']:.4f}; "
+          f"{t['fallback_positions']} position(s) took the chord")
+    print(f"Saved artifacts to: {out_dir}")
+    return out
+
+
+def make_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Geodesic and straight-line interpolation between training images of a built codebook.")
+    p.add_argument("--codebook_dir", type=str, required=True)
+    p.add_argument("--out_dir", type=str, required=True)
+    p.add_argument("--pairs", type=str, nargs="+", default=None, help="image pairs i:j")
+    p.add_argument("--num_pairs", type=int, default=None, help="draw this many random pairs instead of --pairs")
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--frames", type=int, default=9)
+    p.add_argument("--dataset", type=str, default="other", help="CIFAR10: un-normalise RGB images decoded without a sigmoid")
+    p.add_argument("--batch_size", type=int, default=512)
+    p.add_argument("--train_latents_path", type=str, default=None)
+    return p
+
+
+if __name__ == "__main__":
+    main(make_parser().parse_args())
