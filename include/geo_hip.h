@@ -498,6 +498,38 @@ size_t geo_metric_tensor_min_workspace_bytes(const geo_decoder_desc *dec);
 int geo_decoder_metric_tensor(const geo_decoder_desc *dec, const float *z, int64_t n, double *G_out, double *eig_out,
                               double *logvol_out, int32_t *rank_out, void *ws, size_t ws_bytes, void *stream);
 
+/* Curves under the pull-back metric: the discrete energy of C curves of F frames each, and its monotone relaxation with the ends
+ * fixed.  x is f32 [C][F][d], 2 <= F <= 64.  Same decoder, same J and same output sigmoids g as
+ * geo_decoder_metric_tensor: the per-node primal pass and the column pass over the C * F latents; coverage and refusals as there.
+ * Evaluate(x), a function of the curve's own F rows, every sum one fp64 accumulator over ascending indices, nothing contracted:
+ *   seg_sq[f]  = sum_o ((double)g[f+1][o] - (double)g[f][o])^2, f = 0 .. F-2;      E = sum_f seg_sq[f]
+ *   grad[f][k] = 2 * sum_o (double)J[f][k][o] * (((double)g[f][o] - g[f-1][o]) - ((double)g[f+1][o] - g[f][o])), interior f;
+ *                grad[0] = grad[F-1] = 0 exactly
+ *   tr[f]      = sum_k (sum_o (double)J[f][k][o]^2)
+ * and E = NaN for a curve with a NaN or an inf among its F * d coordinates, whatever the passes made of it.
+ * geo_curve_energy: energy_out f64 [C]; seg_sq_out f64 [C][F-1], grad_out f64 [C][F][d], g_out f32 [C][F][p_out] and jac_out
+ * f32 [C][F][d][p_out] (unpadded) may each be null.
+ * geo_curve_relax: x_inout is relaxed in place, n_iters trial steps per curve, each curve on its own and decided on the device.
+ * The call evaluates x (energy0_out, may be null).  step_inout f64 [C]: a step < 0 becomes 1 / (8 * max over interior f of tr[f]),
+ * 0 where that maximum is 0 (also with n_iters == 0).  Each iteration: y[f] = (float)((double)x[f] - step * grad[f]) for interior f,
+ * the ends copied; Evaluate(y); if E_y < E (a NaN on either side is a rejection) then x, E, grad <- y's, step *= 2 and
+ * accepted += 1, else step /= 4.  energy_out f64 [C] and accepted_out i32 [C] are required, seg_sq_out f64 [C][F-1] may be null.
+ * E can only fall; n iterations of one call leave the bits n calls of one iteration leave.  F == 2 or n_iters == 0 evaluates only.
+ * GEO_E_ARG before any launch, the reason in geo_last_error: a decoder geo_decoder_metric_tensor does not cover (train-mode
+ * BatchNorm included; both queries answer 0 for it), F outside [2, 64], n_iters < 0, C < 0, a null required pointer, a workspace
+ * below geo_curve_min_workspace_bytes (one curve's).  C == 0 returns GEO_OK without a launch.
+ * Slices are whole curves, sized from ws_bytes (at most 2^18 latents, which is what the query sizes for more); the packed weights
+ * are written once per slice, not once per iteration.  A curve's outputs are a function of its own rows: the same bits for any
+ * C, position, slice length, stream and earlier workspace contents; a NaN or inf stays in its curve, which comes back unchanged
+ * with accepted == 0.  No atomics. */
+size_t geo_curve_workspace_bytes(const geo_decoder_desc *dec, int64_t C, int32_t F);
+size_t geo_curve_min_workspace_bytes(const geo_decoder_desc *dec, int32_t F);
+int geo_curve_energy(const geo_decoder_desc *dec, const float *x, int64_t C, int32_t F, double *energy_out, double *seg_sq_out,
+                     double *grad_out, float *g_out, float *jac_out, void *ws, size_t ws_bytes, void *stream);
+int geo_curve_relax(const geo_decoder_desc *dec, float *x_inout, int64_t C, int32_t F, int32_t n_iters, double *step_inout,
+                    double *energy0_out, double *energy_out, double *seg_sq_out, int32_t *accepted_out, void *ws, size_t ws_bytes,
+                    void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * K-quad weights and the chain order, shared by the native pull-back, decode, encode and LPIPS below.
  * A convolution weight read as a matrix [K][N] (K = input channels of one tap, N = output channels) is packed

@@ -119,6 +119,10 @@ _SIGNATURES = {
     "geo_metric_tensor_workspace_bytes": (sz, [ctypes.POINTER(DecoderDesc), i64]),
     "geo_metric_tensor_min_workspace_bytes": (sz, [ctypes.POINTER(DecoderDesc)]),
     "geo_decoder_metric_tensor": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, i64, c_p, c_p, c_p, c_p, c_p, sz, c_p]),
+    "geo_curve_workspace_bytes": (sz, [ctypes.POINTER(DecoderDesc), i64, i32]),
+    "geo_curve_min_workspace_bytes": (sz, [ctypes.POINTER(DecoderDesc), i32]),
+    "geo_curve_energy": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, sz, c_p]),
+    "geo_curve_relax": (ctypes.c_int, [ctypes.POINTER(DecoderDesc), c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, sz, c_p]),
     "geo_vanilla_jvp_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64]),
     "geo_vanilla_jvp_edges_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64, i64]),
     "geo_vanilla_jvp_pairs": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),

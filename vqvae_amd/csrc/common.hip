@@ -32,6 +32,7 @@ const OptionName kOptionNames[] = {
     {"jvp_start_dedup", "GEO_JVP_START_DEDUP", &Options::jvp_start_dedup},
     {"jvp_front_once", "GEO_JVP_FRONT_ONCE", &Options::jvp_front_once},
     {"jvp_head_stream", "GEO_JVP_HEAD_STREAM", &Options::jvp_head_stream},
+    {"curve_repack", "GEO_CURVE_REPACK", &Options::curve_repack},
 };
 Options from_environment() {
     Options o;

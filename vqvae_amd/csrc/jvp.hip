@@ -35,6 +35,9 @@
 //   node_jacobian: the per_node kernels over unit tangents, then jacobian_lengths_kernel.
 //   geo_decoder_metric_tensor: the same column pass over slices of latents, then jacobian_gram_kernel (G = J^T J per latent, fp64)
 //                              and metric_spectrum_kernel (eigenvalues, rank, 0.5 log det G) -- DESIGN.md section 24.
+//   geo_curve_energy / geo_curve_relax: the per-node primal pass and the column pass over slices of whole curves, then
+//                              curve_reduce_kernel (energy, gradient, trace per curve, fp64) and curve_step_kernel (the accept /
+//                              reject decision and the next trial, per curve on the device) -- DESIGN.md section 26.
 #include "geo_common.h"
 
 #include <cfloat>
@@ -2223,6 +2226,161 @@ __global__ __launch_bounds__(SPEC_THREADS) void metric_spectrum_kernel(const dou
     if (logvol_out) logvol_out[node] = positive ? 0.5 * logdet : -(double)INFINITY;
 }
 
+// ---------------------------------------------------------------------------------- curve energy and relaxation
+// geo_curve_energy / geo_curve_relax: a curve is F consecutive latents of a slice, so the per-node primal
+// pass leaves its output sigmoids g[f] in sg_node and the column pass its Jacobians J[f] in jac, rows c * F + f.
+// curve_reduce_kernel, one workgroup per curve at a time, g staged in LDS ([F][p_out + 1]: the odd row length keeps threads of
+// different frames on different banks), every sum one fp64 accumulator over o ascending, nothing contracted:
+//   seg_sq[f] = sum_o ((double)g[f+1][o] - (double)g[f][o])^2                                  one thread per segment
+//   grad[f][k] = 2 * sum_o (double)J[f][k][o] * r[o],  r[o] = (g[f][o] - g[f-1][o]) - (g[f+1][o] - g[f][o]) in fp64; 0 at the ends
+//   row[f][k]  = sum_o (double)J[f][k][o]^2 (exact products)                                   one thread per (f, k) for both
+//   E = sum_f seg_sq[f], tr[f] = sum_k row[f][k], ascending, one thread each
+// A curve with a NaN or an inf among its F * d coordinates has E = NaN, whatever the passes made of it (their ReLU is a maximum,
+// which drops a NaN): every comparison with that E is false, so geo_curve_relax never moves such a curve.
+// A thread reads its own column of J from global memory (768 contiguous bytes at most); the padding o >= p_out is never read.
+constexpr int CURVE_MAX_F = 64, CURVE_THREADS = 256;
+__global__ __launch_bounds__(CURVE_THREADS) void curve_reduce_kernel(const float *__restrict__ sg_node, int sg_ld,
+                                                                    const float *__restrict__ jac_node,
+                                                                    const float *__restrict__ x, int64_t n_curves, int F,
+                                                                    int d, int p_out, int np, double *__restrict__ energy,
+                                                                    double *__restrict__ seg_sq, double *__restrict__ grad,
+                                                                    double *__restrict__ tr) {
+#pragma clang fp contract(off)      // plain operators below: the pragma governs them
+    extern __shared__ float curve_g[];
+    __shared__ double seg_s[CURVE_MAX_F];
+    __shared__ double row_s[CURVE_MAX_F * GRAM_MAX_D];
+    __shared__ int not_finite;
+    const int ld = p_out + 1;
+    for (int64_t c = blockIdx.x; c < n_curves; c += gridDim.x) {
+        __syncthreads();                                       // (the last curve's sums are read)
+        if (threadIdx.x == 0) not_finite = 0;
+        const float *g = sg_node + (size_t)c * F * sg_ld;
+        for (int i = threadIdx.x; i < F * p_out; i += CURVE_THREADS) {
+            const int f = i / p_out, o = i - f * p_out;
+            curve_g[f * ld + o] = g[(size_t)f * sg_ld + o];
+        }
+        __syncthreads();
+        for (int f = threadIdx.x; f < F - 1; f += CURVE_THREADS) {
+            const float *g0 = curve_g + f * ld, *g1 = g0 + ld;
+            double s = 0.0;
+            for (int o = 0; o < p_out; ++o) {
+                const double dg = (double)g1[o] - (double)g0[o];
+                s += dg * dg;
+            }
+            seg_s[f] = s;
+            if (seg_sq) seg_sq[(size_t)c * (F - 1) + f] = s;
+        }
+        for (int i = threadIdx.x; i < F * d; i += CURVE_THREADS) {
+            const int f = i / d, k = i - f * d;
+            const float *J = jac_node + (((size_t)c * F + f) * d + k) * np;
+            const bool interior = f > 0 && f < F - 1;
+            const float *gm = curve_g + (interior ? f - 1 : f) * ld, *g0 = curve_g + f * ld,
+                        *gp = curve_g + (interior ? f + 1 : f) * ld;
+            double s = 0.0, sq = 0.0;
+            for (int o = 0; o < p_out; ++o) {
+                const double j = (double)J[o];
+                const double r = ((double)g0[o] - (double)gm[o]) - ((double)gp[o] - (double)g0[o]);
+                s += j * r;
+                sq += j * j;
+            }
+            row_s[i] = sq;
+            if ((__float_as_uint(x[(size_t)c * F * d + i]) & 0x7f800000u) == 0x7f800000u) not_finite = 1;      // (all writers: 1)
+            if (grad) grad[(size_t)c * F * d + i] = interior ? 2.0 * s : 0.0;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double e = 0.0;
+            for (int f = 0; f < F - 1; ++f) e += seg_s[f];
+            energy[c] = not_finite ? (double)NAN : e;
+        }
+        if (tr)
+            for (int f = threadIdx.x; f < F; f += CURVE_THREADS) {
+                double t = 0.0;
+                for (int k = 0; k < d; ++k) t += row_s[f * d + k];
+                tr[(size_t)c * F + f] = t;
+            }
+    }
+}
+
+// g_out [n][p_out] and jac_out [n][d][p_out] of a slice, without the padding of sg_node's and jac's rows (either may be null)
+__global__ __launch_bounds__(256) void curve_export_kernel(const float *__restrict__ sg_node, int sg_ld,
+                                                          const float *__restrict__ jac_node, int64_t n_nodes, int d, int p_out,
+                                                          int np, float *__restrict__ g_out, float *__restrict__ jac_out) {
+    const int64_t rows = n_nodes * d, stride = (int64_t)gridDim.x * 256;
+    if (g_out)
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_nodes * p_out; i += stride)
+            g_out[i] = sg_node[(size_t)(i / p_out) * sg_ld + i % p_out];
+    if (jac_out)
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < rows * p_out; i += stride)
+            jac_out[i] = jac_node[(size_t)(i / p_out) * np + i % p_out];
+}
+
+// The state of a slice's relaxation, in the workspace: the trial y, and E / seg_sq / grad of the curve (cur) and of what was just
+// evaluated (ev).  tr is read once, for a step the caller left to the call.
+struct CurveState {
+    float *y;
+    double *e_ev, *e_cur, *seg_ev, *seg_cur, *grad_ev, *grad_cur, *tr;
+};
+
+// curve_step_kernel, one workgroup per curve: the decision about what was just evaluated, then the next trial.
+//   first  x itself was evaluated: it becomes the state; energy0 = E; a step < 0 becomes 1 / (8 * max over interior f of tr[f]),
+//          0 where that maximum is 0 (the maximum ignores a NaN, and 1 / inf is 0: such a curve never moves)
+//   else   y was evaluated: E_y < E (false for a NaN on either side) accepts -- x, E, seg_sq, grad <- those of y, step *= 2,
+//          accepted += 1 -- anything else rejects, step /= 4
+//   last   no further trial: energy_out and seg_sq_out (may be null) take the state
+//   else   y[f] = (float)((double)x[f] - step * grad[f]) for interior f, uncontracted; the ends are copied
+// Every thread reads the decision's inputs before the barrier and the state is written after it.
+__global__ __launch_bounds__(CURVE_THREADS) void curve_step_kernel(CurveState st, float *__restrict__ x, int F, int d, int first,
+                                                                  int last, double *__restrict__ step, double *__restrict__ energy0,
+                                                                  double *__restrict__ energy_out, double *__restrict__ seg_sq_out,
+                                                                  int32_t *__restrict__ accepted) {
+#pragma clang fp contract(off)
+    const int64_t c = blockIdx.x;
+    const int fd = F * d, t = threadIdx.x;
+    const size_t at = (size_t)c * fd, seg_at = (size_t)c * (F - 1);
+    const double e_ev = st.e_ev[c], e_cur = first ? e_ev : st.e_cur[c];
+    double h = step[c];
+    const bool take = first || e_ev < e_cur;
+    if (first) {
+        if (h < 0.0) {
+            double m = 0.0;
+            for (int f = 1; f < F - 1; ++f) {
+                const double v = st.tr[(size_t)c * F + f];
+                if (v > m) m = v;
+            }
+            h = m > 0.0 ? 1.0 / (8.0 * m) : 0.0;
+        }
+    } else {
+        h = take ? 2.0 * h : h / 4.0;
+    }
+    __syncthreads();
+    if (take) {
+        for (int i = t; i < fd; i += CURVE_THREADS) {
+            st.grad_cur[at + i] = st.grad_ev[at + i];
+            if (!first) x[at + i] = st.y[at + i];
+        }
+        for (int f = t; f < F - 1; f += CURVE_THREADS) st.seg_cur[seg_at + f] = st.seg_ev[seg_at + f];
+    }
+    if (t == 0) {
+        if (take) st.e_cur[c] = e_ev;
+        step[c] = h;
+        if (first) { accepted[c] = 0; if (energy0) energy0[c] = e_ev; }
+        else if (take) accepted[c] += 1;
+        if (last) energy_out[c] = take ? e_ev : e_cur;
+    }
+    __syncthreads();                                            // (the state below is this workgroup's own writes)
+    if (last) {
+        if (seg_sq_out)
+            for (int f = t; f < F - 1; f += CURVE_THREADS) seg_sq_out[seg_at + f] = st.seg_cur[seg_at + f];
+        return;
+    }
+    for (int i = t; i < fd; i += CURVE_THREADS) {
+        const int f = i / d;
+        const float xv = x[at + i];
+        st.y[at + i] = f > 0 && f < F - 1 ? (float)((double)xv - h * st.grad_cur[at + i]) : xv;
+    }
+}
+
 // ---------------------------------------------------------------------------------- host side: shape, plan, route
 bool make_shape(const geo_decoder_desc *dc, Shape *s) {
     s->d = dc->latent_dim; s->c0 = dc->c0; s->c1 = dc->c1; s->c2 = dc->c2; s->co = dc->out_channels;
@@ -2739,28 +2897,30 @@ int launch_pass(const Route &r, const geo_decoder_desc *dc, const Pass &p, const
 // what geo_decoder_metric_tensor keeps of a slice of latents (eig / logvol / rank: all three null = no spectrum)
 struct MetricOut { double *G, *eig, *logvol; int32_t *rank; };
 
-// graph edges (z, src, dst) or explicit end points (z_start, z_end); `r` is make_route's answer for exactly this call.
-// metric (node_jacobian routes only): no edges are read and no lengths written; the columns are reduced to G and its spectrum.
-int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t n_nodes, const int32_t *src, const int32_t *dst,
-            const float *z_start, const float *z_end, int64_t n_edges, float *len_out, void *ws, size_t ws_bytes,
-            hipStream_t stream, const MetricOut *metric = nullptr) {
+// run_jvp is three steps, each a function of its own so that geo_curve_relax can carve and pack once and run the passes once per
+// iteration: jvp_carve, jvp_pack, jvp_passes -- the same launches in the same order as ever.
+int jvp_carve(const Route &r, int64_t n_nodes, void *ws, size_t ws_bytes, Buffers *bp) {
     const Plan &pl = r.pl;
     const Shape &s = pl.sh;
-    const int batch = pl.batch;
     const Tiling t = pl.tiling();
+    Buffers &b = *bp;
 
     // ---- carve the workspace: the groups in the order make_route subtracts them (Jacobian columns, pass, per-node rows)
     geo::Arena ar(ws, ws_bytes);
-    Buffers b = {};
+    b = Buffers{};
     if (r.node_jacobian) lay_out_jacobian(ar, &b, s, n_nodes, r.run_edges, r.jac_np);
     lay_out_pass(ar, &b, s, t, r.group_norm);
     if (r.per_node) lay_out_nodes(ar, &b, s, n_nodes);
     // (unreachable: make_route took each route only where the measurements of these same functions fit in ws_bytes)
     GEO_REQUIRE(ar.ok(), "geo_decoder_jvp: workspace carve failed");
     if (r.dedup) StartRuns(s, t).place(&b, r.front_once);
-    const size_t node_slots = round_up_to_tile(n_nodes);
+    return GEO_OK;
+}
 
-    // ---- pack the weights, fixed norm constants
+// the packed weights and the fixed norm constants: functions of the decoder alone, read by every pass and written by none
+int jvp_pack(const geo_decoder_desc *dc, const Route &r, Buffers *bp, hipStream_t stream) {
+    const Shape &s = r.pl.sh;
+    Buffers &b = *bp;
     make_chunks(s, &b.tab);
     int bad_chunk = 0;
     GEO_REQUIRE(!(s.n_chunks == 8 && s.opix_per_chunk == 2) || chunks_match_mid_geom(b.tab, &bad_chunk),
@@ -2787,6 +2947,16 @@ int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t 
         finalize_fixed_kernel<<<1, 256, 0, stream>>>(s.c2, dc->norm, dc->g2, dc->be2, dc->rm2, dc->rv2, dc->eps, b.k2);
         GEO_LAUNCH_CHECK();
     }
+    return GEO_OK;
+}
+
+int jvp_passes(const geo_decoder_desc *dc, const Route &r, const Buffers &b, const float *z, int64_t n_nodes, const int32_t *src,
+               const int32_t *dst, const float *z_start, const float *z_end, int64_t n_edges, float *len_out, hipStream_t stream,
+               const MetricOut *metric, bool columns_only = false) {
+    const Plan &pl = r.pl;
+    const Shape &s = pl.sh;
+    const int batch = pl.batch;
+    const size_t node_slots = round_up_to_tile(n_nodes);
 
     // ---- per-node primal pass: every latent once, its ConvT2 rows and output sigmoids kept
     if (r.per_node) {
@@ -2825,6 +2995,7 @@ int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t 
             GEO_LAUNCH_CHECK();
         }
     }
+    if (columns_only) return GEO_OK;                            // (geo_curve_*: the columns and sigmoids are the result)
     if (r.node_jacobian && metric) {                            // G = J^T J per latent, then its spectrum
         jacobian_gram_kernel<<<geo::grid_for(n_nodes, 1), 256, 0, stream>>>(b.jac, n_nodes, s.d, s.p_out, (int)r.jac_np, metric->G);
         GEO_LAUNCH_CHECK();
@@ -2840,6 +3011,17 @@ int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t 
         GEO_LAUNCH_CHECK();
     }
     return GEO_OK;
+}
+
+// graph edges (z, src, dst) or explicit end points (z_start, z_end); `r` is make_route's answer for exactly this call.
+// metric (node_jacobian routes only): no edges are read and no lengths written; the columns are reduced to G and its spectrum.
+int run_jvp(const geo_decoder_desc *dc, const Route &r, const float *z, int64_t n_nodes, const int32_t *src, const int32_t *dst,
+            const float *z_start, const float *z_end, int64_t n_edges, float *len_out, void *ws, size_t ws_bytes,
+            hipStream_t stream, const MetricOut *metric = nullptr) {
+    Buffers b;
+    if (const int rc = jvp_carve(r, n_nodes, ws, ws_bytes, &b)) return rc;
+    if (const int rc = jvp_pack(dc, r, &b, stream)) return rc;
+    return jvp_passes(dc, r, b, z, n_nodes, src, dst, z_start, z_end, n_edges, len_out, stream, metric);
 }
 
 // validation shared by the two entry points, then the route and the run
@@ -2936,6 +3118,173 @@ int decoder_metric_tensor(const geo_decoder_desc *dc, const float *z, int64_t n,
         if (const int rc = run_jvp(dc, ns == slice ? whole : last, z + (size_t)base * d, ns, nullptr, nullptr, nullptr, nullptr, 1,
                                    nullptr, ws, ws_bytes, stream, &so))
             return rc;
+    }
+    return GEO_OK;
+}
+
+// ---------------------------------------------------------------------------------- host side: curve energy and relaxation
+// geo_curve_energy / geo_curve_relax.  C curves of F frames are C * F latents, curve after curve; a slice is
+// whole curves, as many as fit in the workspace (at most METRIC_MAX_SLICE latents).  The workspace of a slice: the relaxation's
+// state (lay_out_curves), then what the column pass of geo_decoder_metric_tensor takes for the slice's latents.  A slice is
+// carved and its weights packed once; every evaluation after that is jvp_passes alone, then curve_reduce_kernel.
+void lay_out_curves(geo::Arena &ar, CurveState *st, int64_t n_curves, int F, int d) {
+    const size_t fd = (size_t)n_curves * F * d, segs = (size_t)n_curves * (F - 1);
+    ar.take(st->y, fd);
+    ar.take(st->e_ev, (size_t)n_curves); ar.take(st->e_cur, (size_t)n_curves);
+    ar.take(st->seg_ev, segs); ar.take(st->seg_cur, segs);
+    ar.take(st->grad_ev, fd); ar.take(st->grad_cur, fd);
+    ar.take(st->tr, (size_t)n_curves * F);
+}
+
+size_t curve_state_bytes(const geo_decoder_desc *dc, int64_t n_curves, int F) {
+    CurveState st;
+    return geo::measure(lay_out_curves, &st, n_curves, F, dc->latent_dim);
+}
+
+size_t curve_slice_bytes(const geo_decoder_desc *dc, const geo::Options &o, int64_t n_curves, int F) {
+    const size_t columns = metric_slice_bytes(dc, o, n_curves * F);
+    return columns ? curve_state_bytes(dc, n_curves, F) + columns : 0;
+}
+
+int64_t curve_slice_cap(int64_t C, int F) {
+    const int64_t cap = METRIC_MAX_SLICE / F;
+    return C < 1 ? 1 : (C < cap ? C : cap);
+}
+
+// one slice, carved and packed
+struct CurveSlice {
+    Route route;
+    CurveState st;
+    Buffers b;
+    int64_t n_curves;
+};
+
+// what both entry points check before anything else, in the issue's order: coverage (train-mode BatchNorm included), F
+int curve_check(const char *who, const geo_decoder_desc *dc, const geo::Options &opt, int64_t C, int F) {
+    Route probe;
+    if (!metric_covers(dc, opt, &probe)) {
+        geo::set_error("%s: no column pass (%s)", who, probe.error);
+        return GEO_E_ARG;
+    }
+    GEO_REQUIRE(F >= 2 && F <= CURVE_MAX_F, "%s: F %d not in [2,%d]", who, F, CURVE_MAX_F);
+    GEO_REQUIRE(C >= 0, "%s: C %lld < 0", who, (long long)C);
+    return GEO_OK;
+}
+
+// the curves per slice a workspace holds: everything (up to the cap) when it fits, else the largest count that does
+int curve_slice_length(const char *who, const geo_decoder_desc *dc, const geo::Options &opt, int64_t C, int F, size_t ws_bytes,
+                       int64_t *slice) {
+    const int64_t cap = curve_slice_cap(C, F);
+    const size_t cap_bytes = curve_slice_bytes(dc, opt, cap, F);
+    *slice = cap;
+    if (cap_bytes && ws_bytes >= cap_bytes) return GEO_OK;
+    const size_t min_bytes = curve_slice_bytes(dc, opt, 1, F);
+    GEO_REQUIRE(min_bytes && ws_bytes >= min_bytes, "%s: workspace of %zu bytes is below the minimum of %zu", who, ws_bytes, min_bytes);
+    int64_t lo = 1, hi = cap;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        const size_t bytes = curve_slice_bytes(dc, opt, mid, F);
+        if (bytes && bytes <= ws_bytes) lo = mid; else hi = mid - 1;
+    }
+    *slice = lo;
+    return GEO_OK;
+}
+
+// host arithmetic only: the route and the carve of a slice of n_curves in this workspace
+int curve_slice_plan(const char *who, const geo_decoder_desc *dc, const geo::Options &opt, int64_t n_curves, int F, void *ws,
+                     size_t ws_bytes, CurveSlice *sl) {
+    sl->n_curves = n_curves;
+    geo::Arena ar(ws, ws_bytes);
+    lay_out_curves(ar, &sl->st, n_curves, F, dc->latent_dim);
+    GEO_REQUIRE(ar.ok(), "%s: workspace of %zu bytes does not hold the state of %lld curves", who, ws_bytes, (long long)n_curves);
+    const size_t rest = ws_bytes - ar.off;
+    GEO_REQUIRE(metric_route(dc, opt, n_curves * F, &rest, &sl->route), "%s: no column pass for a slice of %lld latents in %zu bytes",
+                who, (long long)(n_curves * F), rest);
+    return jvp_carve(sl->route, n_curves * F, static_cast<char *>(ws) + ar.off, rest, &sl->b);
+}
+
+// Evaluate: the primal and column passes over the slice's latents z, reduced per curve (tr / seg_sq / grad may be null)
+int curve_evaluate(const geo_decoder_desc *dc, const CurveSlice &sl, const float *z, int F, double *energy, double *seg_sq,
+                   double *grad, double *tr, hipStream_t stream) {
+    const Shape &s = sl.route.pl.sh;
+    if (const int rc = jvp_passes(dc, sl.route, sl.b, z, sl.n_curves * F, nullptr, nullptr, nullptr, nullptr, 1, nullptr, stream,
+                                  nullptr, true))
+        return rc;
+    curve_reduce_kernel<<<geo::grid_for(sl.n_curves, 1), CURVE_THREADS, (size_t)F * (s.p_out + 1) * sizeof(float), stream>>>(
+        sl.b.sg_node, (int)sl.route.jac_np, sl.b.jac, z, sl.n_curves, F, s.d, s.p_out, (int)sl.route.jac_np, energy, seg_sq, grad, tr);
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+int curve_energy(const geo_decoder_desc *dc, const float *x, int64_t C, int F, double *energy_out, double *seg_sq_out,
+                 double *grad_out, float *g_out, float *jac_out, void *ws, size_t ws_bytes, hipStream_t stream) {
+    static const char who[] = "geo_curve_energy";
+    const geo::Options opt = geo::options();
+    if (const int rc = curve_check(who, dc, opt, C, F)) return rc;
+    if (C == 0) return GEO_OK;
+    GEO_REQUIRE(x && energy_out && ws, "%s: null pointer", who);
+    int64_t slice = 0;
+    if (const int rc = curve_slice_length(who, dc, opt, C, F, ws_bytes, &slice)) return rc;
+    CurveSlice whole, last;
+    const int64_t n_whole = C / slice, n_last = C % slice;
+    if (n_whole)
+        if (const int rc = curve_slice_plan(who, dc, opt, slice, F, ws, ws_bytes, &whole)) return rc;
+    if (n_last)
+        if (const int rc = curve_slice_plan(who, dc, opt, n_last, F, ws, ws_bytes, &last)) return rc;
+    const int d = dc->latent_dim;
+    for (int64_t base = 0; base < C; base += slice) {
+        CurveSlice &sl = C - base < slice ? last : whole;
+        const Shape &s = sl.route.pl.sh;
+        const size_t at = (size_t)base * F;                       // the slice's first latent
+        if (const int rc = jvp_pack(dc, sl.route, &sl.b, stream)) return rc;
+        if (const int rc = curve_evaluate(dc, sl, x + at * d, F, energy_out + base,
+                                          seg_sq_out ? seg_sq_out + (size_t)base * (F - 1) : nullptr,
+                                          grad_out ? grad_out + at * d : nullptr, nullptr, stream))
+            return rc;
+        if (g_out || jac_out) {
+            const int64_t n = sl.n_curves * F;
+            curve_export_kernel<<<geo::grid_for(n * d * s.p_out, 256), 256, 0, stream>>>(
+                sl.b.sg_node, (int)sl.route.jac_np, sl.b.jac, n, d, s.p_out, (int)sl.route.jac_np,
+                g_out ? g_out + at * s.p_out : nullptr, jac_out ? jac_out + at * d * s.p_out : nullptr);
+            GEO_LAUNCH_CHECK();
+        }
+    }
+    return GEO_OK;
+}
+
+int curve_relax(const geo_decoder_desc *dc, float *x, int64_t C, int F, int n_iters, double *step, double *energy0_out,
+                double *energy_out, double *seg_sq_out, int32_t *accepted_out, void *ws, size_t ws_bytes, hipStream_t stream) {
+    static const char who[] = "geo_curve_relax";
+    const geo::Options opt = geo::options();
+    if (const int rc = curve_check(who, dc, opt, C, F)) return rc;
+    GEO_REQUIRE(n_iters >= 0, "%s: n_iters %d < 0", who, n_iters);
+    if (C == 0) return GEO_OK;
+    GEO_REQUIRE(x && step && energy_out && accepted_out && ws, "%s: null pointer", who);
+    int64_t slice = 0;
+    if (const int rc = curve_slice_length(who, dc, opt, C, F, ws_bytes, &slice)) return rc;
+    CurveSlice whole, last;
+    const int64_t n_whole = C / slice, n_last = C % slice;
+    if (n_whole)
+        if (const int rc = curve_slice_plan(who, dc, opt, slice, F, ws, ws_bytes, &whole)) return rc;
+    if (n_last)
+        if (const int rc = curve_slice_plan(who, dc, opt, n_last, F, ws, ws_bytes, &last)) return rc;
+    const int d = dc->latent_dim;
+    const int iters = F == 2 ? 0 : n_iters;                       // no interior frame: nothing can move
+    for (int64_t base = 0; base < C; base += slice) {
+        CurveSlice &sl = C - base < slice ? last : whole;
+        const CurveState &st = sl.st;
+        float *xs = x + (size_t)base * F * d;
+        double *seg_s = seg_sq_out ? seg_sq_out + (size_t)base * (F - 1) : nullptr;
+        if (const int rc = jvp_pack(dc, sl.route, &sl.b, stream)) return rc;        // once per slice, not per iteration
+        for (int it = -1; it < iters; ++it) {                     // it = -1: the curve itself
+            if (it >= 0 && opt.curve_repack)                      // (measurement switch: what packing per iteration would cost)
+                if (const int rc = jvp_pack(dc, sl.route, &sl.b, stream)) return rc;
+            if (const int rc = curve_evaluate(dc, sl, it < 0 ? xs : st.y, F, st.e_ev, st.seg_ev, st.grad_ev, st.tr, stream)) return rc;
+            curve_step_kernel<<<(unsigned)sl.n_curves, CURVE_THREADS, 0, stream>>>(
+                st, xs, F, d, it < 0, it == iters - 1, step + base, energy0_out ? energy0_out + base : nullptr, energy_out + base,
+                seg_s, accepted_out + base);
+            GEO_LAUNCH_CHECK();
+        }
     }
     return GEO_OK;
 }
@@ -3041,4 +3390,31 @@ extern "C" int geo_decoder_metric_tensor(const geo_decoder_desc *dec, const floa
                                          double *logvol_out, int32_t *rank_out, void *ws, size_t ws_bytes, void *stream) {
     const MetricOut out = {G_out, eig_out, logvol_out, rank_out};
     return decoder_metric_tensor(dec, z, n, out, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t geo_curve_workspace_bytes(const geo_decoder_desc *dec, int64_t C, int32_t F) {
+    const geo::Options opt = geo::options();
+    Route probe;
+    if (!metric_covers(dec, opt, &probe) || F < 2 || F > CURVE_MAX_F) return 0;
+    return curve_slice_bytes(dec, opt, curve_slice_cap(C, F), F);
+}
+
+extern "C" size_t geo_curve_min_workspace_bytes(const geo_decoder_desc *dec, int32_t F) {
+    const geo::Options opt = geo::options();
+    Route probe;
+    if (!metric_covers(dec, opt, &probe) || F < 2 || F > CURVE_MAX_F) return 0;
+    return curve_slice_bytes(dec, opt, 1, F);
+}
+
+extern "C" int geo_curve_energy(const geo_decoder_desc *dec, const float *x, int64_t C, int32_t F, double *energy_out,
+                                double *seg_sq_out, double *grad_out, float *g_out, float *jac_out, void *ws, size_t ws_bytes,
+                                void *stream) {
+    return curve_energy(dec, x, C, F, energy_out, seg_sq_out, grad_out, g_out, jac_out, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int geo_curve_relax(const geo_decoder_desc *dec, float *x_inout, int64_t C, int32_t F, int32_t n_iters,
+                               double *step_inout, double *energy0_out, double *energy_out, double *seg_sq_out,
+                               int32_t *accepted_out, void *ws, size_t ws_bytes, void *stream) {
+    return curve_relax(dec, x_inout, C, F, n_iters, step_inout, energy0_out, energy_out, seg_sq_out, accepted_out, ws, ws_bytes,
+                       static_cast<hipStream_t>(stream));
 }

@@ -5,6 +5,8 @@ geodesic_interpolation: node pairs -> the geodesic's polyline resampled at equal
 the pull-back length of both curves (edge_lengths_riemannian over consecutive frames).
 interpolate_images_spatial: image pairs of the spatial pipeline -> 16 node pairs each, one per grid position, assembled into
 latent grids, decoded (decode_images), with the image-space length of both routes (geo_image_pair_moments).
+relax_iters > 0 (both): the geodesic's frames and the chord are each relaxed under the decoder's metric with the ends fixed
+(relax_curves_device) and the result with the lower energy is kept per pair: never worse than either start.
 """
 from typing import Dict, Sequence, Tuple
 
@@ -13,6 +15,7 @@ import torch
 
 from .._device import DeviceCSR
 from .geo_shortest_paths import _check_frames, chord_frames_device, geodesic_paths_device, resample_paths_device
+from .relaxation import relax_curves_device
 from .riemannian_metric import edge_lengths_riemannian
 
 
@@ -26,20 +29,39 @@ def curve_lengths(decoder, frames: torch.Tensor, batch_size: int = 512) -> torch
     return total
 
 
+def relax_best(decoder, frames_geo: torch.Tensor, frames_lin: torch.Tensor, relax_iters: int) -> Dict[str, torch.Tensor]:
+    """Relax both starts of M curves [M, F, d] for relax_iters iterations and keep, per curve, the result with the lower final
+    energy (a tie goes to the geodesic).  Returns frames_relaxed f32 [M, F, d]; relax_from i32 [M] (0 the chord, 1 the
+    geodesic); energy_geo, energy_lin f64 [M] (of the starts), energy_relaxed f64 [M] (<= both); accepted_geo, accepted_lin
+    i32 [M]."""
+    geo = relax_curves_device(decoder, frames_geo, relax_iters)
+    lin = relax_curves_device(decoder, frames_lin, relax_iters)
+    from_geo = geo.energy <= lin.energy
+    return {"frames_relaxed": torch.where(from_geo.view(-1, 1, 1), geo.frames, lin.frames),
+            "relax_from": from_geo.to(torch.int32), "energy_geo": geo.energy0, "energy_lin": lin.energy0,
+            "energy_relaxed": torch.where(from_geo, geo.energy, lin.energy), "accepted_geo": geo.accepted,
+            "accepted_lin": lin.accepted}
+
+
 def geodesic_interpolation(z: torch.Tensor, G: DeviceCSR, decoder, src_nodes, dst_nodes, n_frames: int, *,
-                           batch_size: int = 512) -> Dict[str, torch.Tensor]:
+                           batch_size: int = 512, relax_iters: int = 0) -> Dict[str, torch.Tensor]:
     """Curves between the M node pairs of the graph G over the latents z f32 [n, d] (device).  Returns frames_geo, frames_lin
     f32 [M, F, d]; graph_dist f32 [M] (the solver's distance); hops, status i32 [M] (GeodesicPaths); curve_len_geo,
     curve_len_lin f32 [M] (curve_lengths).  A pair without a path (status != 0) gets the chord as frames_geo.  Call with the
-    decoder in eval mode: a train-mode BatchNorm would move its statistics and make a segment depend on its batch."""
+    decoder in eval mode: a train-mode BatchNorm would move its statistics and make a segment depend on its batch.
+    relax_iters > 0 adds relax_best's fields and curve_len_relaxed f32 [M]; with 0 the result is what it always was."""
     F = _check_frames(n_frames)
     paths, dist = geodesic_paths_device(G, src_nodes, dst_nodes)
     frames_lin = chord_frames_device(z, src_nodes, dst_nodes, F)
     frames_geo = resample_paths_device(z, paths, F)
     frames_geo = torch.where((paths.status != 0).view(-1, 1, 1), frames_lin, frames_geo)
-    return {"frames_geo": frames_geo, "frames_lin": frames_lin, "graph_dist": dist, "hops": paths.hops, "status": paths.status,
-            "curve_len_geo": curve_lengths(decoder, frames_geo, batch_size),
-            "curve_len_lin": curve_lengths(decoder, frames_lin, batch_size)}
+    out = {"frames_geo": frames_geo, "frames_lin": frames_lin, "graph_dist": dist, "hops": paths.hops, "status": paths.status,
+           "curve_len_geo": curve_lengths(decoder, frames_geo, batch_size),
+           "curve_len_lin": curve_lengths(decoder, frames_lin, batch_size)}
+    if relax_iters > 0:
+        out.update(relax_best(decoder, frames_geo, frames_lin, int(relax_iters)))
+        out["curve_len_relaxed"] = curve_lengths(decoder, out["frames_relaxed"], batch_size)
+    return out
 
 
 def image_curve_lengths(images: torch.Tensor) -> torch.Tensor:
@@ -55,7 +77,8 @@ def image_curve_lengths(images: torch.Tensor) -> torch.Tensor:
 
 
 def interpolate_images_spatial(z_grids: torch.Tensor, lcc_index, G: DeviceCSR, decoder, image_pairs: Sequence[Tuple[int, int]],
-                               n_frames: int, dataset: str, apply_sigmoid: bool, *, batch_size: int = 512) -> Dict:
+                               n_frames: int, dataset: str, apply_sigmoid: bool, *, batch_size: int = 512,
+                               relax_iters: int = 0) -> Dict:
     """Image pairs of the spatial pipeline.  z_grids f32 [N, d, 4, 4] (any h x w grid); lcc_index: the flat positions
     img * h * w + y * w + x that are nodes of G, ascending -- np.flatnonzero(codes.reshape(-1) >= 0) of a build_codebook
     output: a position's node is its rank in that list.  Pair (i, j) is h * w node pairs, position p of image i to position p
@@ -63,7 +86,10 @@ def interpolate_images_spatial(z_grids: torch.Tensor, lcc_index, G: DeviceCSR, d
     fallback_positions (per pair, the sorted positions p).  Returns frames_geo, frames_lin f32 [M, F, d, h, w]; images_geo,
     images_lin f32 [M, F, C, S, S] (decode_images of those grids); graph_dist f32 [M, h w] (NaN outside the graph, inf
     without a path), hops, status i32 [M, h w] (-1 and 3 for a position outside the graph); curve_len_geo, curve_len_lin f32
-    [M] (pull-back lengths summed over the positions in position order); image_len_geo, image_len_lin f64 [M]."""
+    [M] (pull-back lengths summed over the positions in position order); image_len_geo, image_len_lin f64 [M].
+    relax_iters > 0 relaxes every position's two curves (relax_best) and adds frames_relaxed, images_relaxed, image_len_relaxed
+    and curve_len_relaxed like the other two routes', and relax_from, accepted_geo, accepted_lin i32 [M, h w], energy_geo,
+    energy_lin, energy_relaxed f64 [M, h w]; with 0 the result is what it always was."""
     from ..decode import decode_images
     F = _check_frames(n_frames)
     dev = G.indptr.device
@@ -102,7 +128,12 @@ def interpolate_images_spatial(z_grids: torch.Tensor, lcc_index, G: DeviceCSR, d
     st = status.view(M, hw).cpu().numpy()
     out = {"frames_geo": None, "frames_lin": None, "graph_dist": graph_dist.view(M, hw), "hops": hops.view(M, hw),
            "status": status.view(M, hw), "fallback_positions": [np.flatnonzero(st[m] != 0).astype(np.int32) for m in range(M)]}
-    for name, fr in (("geo", frames_geo), ("lin", frames_lin)):
+    routes = [("geo", frames_geo), ("lin", frames_lin)]
+    if relax_iters > 0:
+        best = relax_best(decoder, frames_geo, frames_lin, int(relax_iters))
+        routes.append(("relaxed", best.pop("frames_relaxed")))
+        out.update({k: v.view(M, hw) for k, v in best.items()})
+    for name, fr in routes:
         out[f"curve_len_{name}"] = curve_lengths(decoder, fr, batch_size).view(M, hw).sum(dim=1)
         grids = fr.view(M, h, w, F, d).permute(0, 3, 4, 1, 2).contiguous()   # [M, F, d, h, w]
         images = decode_images(decoder, grids.view(M * F, d, h, w), dataset=dataset, apply_sigmoid=apply_sigmoid)

@@ -2,7 +2,7 @@
 
     python -m vqvae_amd.scripts.geodesic_interpolation --codebook_dir DIR --out_dir OUT
         (--pairs i:j [i:j ...] | --num_pairs N [--seed S]) [--frames 9] [--dataset other] [--batch_size 512]
-        [--train_latents_path PATH]
+        [--train_latents_path PATH] [--relax_iters N]
 
 DIR is an output of vqvae_amd.scripts.build_codebook (spatial pipeline): codebook.pt's "config" names the checkpoint, the
 training latents and the decoder's arguments, exactly as vqvae_amd.training.assign_codes_val_geodesic reads them.  A pair i:j
@@ -17,6 +17,15 @@ Writes to OUT:
                       image_len_geo f64 [M]; fallback_pair, fallback_position i32 [n_fallback] (the positions that took the chord)
   interpolation.json  per pair: graph_dist (summed over the positions with a path), the four lengths, ratio_curve and
                       ratio_image (geodesic / chord), fallback_positions; and the totals over the pairs
+
+--relax_iters N (default 0: none of the following) relaxes, per grid position, the geodesic's frames and the chord under the
+decoder's metric with the ends fixed for N iterations each (geo.relaxation) and keeps the result with the lower curve energy:
+  interpolation.png   a third row per pair, the relaxed curve
+  interpolation.npz   also frames_relaxed, images_relaxed, curve_len_relaxed, image_len_relaxed; relax_from, accepted_geo,
+                      accepted_lin i32 [M, h w]; energy_geo, energy_lin, energy_relaxed f64 [M, h w]
+  interpolation.json  per pair also curve_len_relaxed, image_len_relaxed, energy_geo, energy_lin, energy_relaxed (summed over
+                      the positions), relax_from and the accepted counts per position; the totals of the lengths and energies
+The relaxed curve is never worse in energy than either start, by construction.
 
 Whether the geodesic is the shorter curve under the decoder's metric is a property of the trained model; the JSON reports
 the ratio and the script asserts nothing about it.
@@ -76,11 +85,17 @@ def main(args) -> dict:
         output_image_size=cfg["output_image_size"], norm_type=cfg["norm_type"], device=dev).eval()
     apply_sigmoid = str(cfg.get("recon_loss", "mse")).lower() == "bce" or bool(cfg.get("mse_use_sigmoid", False))
     out = interpolate_images_spatial(z, lcc_rows(np.load(cb_dir / "codes.npy")), DeviceCSR.from_scipy(W, dev), decoder,
-                                     pairs, args.frames, args.dataset, apply_sigmoid, batch_size=args.batch_size)
+                                     pairs, args.frames, args.dataset, apply_sigmoid, batch_size=args.batch_size,
+                                     relax_iters=args.relax_iters)
 
     M, F = pairs.shape[0], int(args.frames)
     host = {k: out[k].cpu().numpy() for k in ("frames_lin", "frames_geo", "images_lin", "images_geo", "graph_dist", "hops",
                                                "status", "curve_len_lin", "curve_len_geo", "image_len_lin", "image_len_geo")}
+    relaxed = args.relax_iters > 0
+    relax_sums = ("curve_len_relaxed", "image_len_relaxed", "energy_geo", "energy_lin", "energy_relaxed")
+    relax_lists = ("relax_from", "accepted_geo", "accepted_lin")
+    if relaxed:
+        host.update({k: out[k].cpu().numpy() for k in ("frames_relaxed", "images_relaxed") + relax_sums + relax_lists})
     fallback = out["fallback_positions"]
     per_pair = []
     for m in range(M):
@@ -93,18 +108,28 @@ def main(args) -> dict:
             rec[k] = float(host[k][m])
         rec["ratio_curve"] = _ratio(rec["curve_len_geo"], rec["curve_len_lin"])
         rec["ratio_image"] = _ratio(rec["image_len_geo"], rec["image_len_lin"])
+        if relaxed:
+            for k in relax_sums:
+                rec[k] = float(np.asarray(host[k][m], dtype=np.float64).sum())
+            for k in relax_lists:
+                rec[k] = [int(v) for v in host[k][m]]
         per_pair.append(rec)
     totals = {k: float(sum(r[k] for r in per_pair))
               for k in ("graph_dist", "curve_len_lin", "curve_len_geo", "image_len_lin", "image_len_geo")}
     totals["ratio_curve"] = _ratio(totals["curve_len_geo"], totals["curve_len_lin"])
     totals["ratio_image"] = _ratio(totals["image_len_geo"], totals["image_len_lin"])
     totals["fallback_positions"] = int(sum(len(p) for p in fallback))
+    if relaxed:
+        totals.update({k: float(sum(r[k] for r in per_pair)) for k in relax_sums})
     summary = {"codebook_dir": str(cb_dir), "frames": F, "dataset": args.dataset, "apply_sigmoid": apply_sigmoid,
                "pairs": per_pair, "totals": totals}
+    if relaxed:
+        summary["relax_iters"] = int(args.relax_iters)
 
     out_dir.mkdir(parents=True, exist_ok=True)
-    rows = torch.stack([out["images_lin"], out["images_geo"]], dim=1)    # [M, 2, F, C, S, S]: chord above geodesic, per pair
-    save_image(rows.reshape(M * 2 * F, *rows.shape[3:]).cpu(), str(out_dir / "interpolation.png"), nrow=F)
+    # [M, 2 or 3, F, C, S, S]: chord above geodesic (above the relaxed curve), per pair
+    rows = torch.stack([out["images_lin"], out["images_geo"]] + ([out["images_relaxed"]] if relaxed else []), dim=1)
+    save_image(rows.reshape(M * rows.shape[1] * F, *rows.shape[3:]).cpu(), str(out_dir / "interpolation.png"), nrow=F)
     np.savez(out_dir / "interpolation.npz", pairs=pairs,
              fallback_pair=np.concatenate([np.full(len(p), m, dtype=np.int32) for m, p in enumerate(fallback)]),
              fallback_position=np.concatenate([np.asarray(p, dtype=np.int32) for p in fallback]), **host)
@@ -114,6 +139,10 @@ def main(args) -> dict:
     print(f"{M} pair(s), {F} frames: pull-back length geodesic {t['curve_len_geo']:.4f} / chord {t['curve_len_lin']:.4f}; "
           f"image-space length geodesic {t['image_len_geo']:.4f} / chord {t['image_len_lin']:.4f}; "
           f"{t['fallback_positions']} position(s) took the chord")
+    if relaxed:
+        print(f"relaxed for {args.relax_iters} iteration(s): pull-back length {t['curve_len_relaxed']:.4f}, image-space length "
+              f"{t['image_len_relaxed']:.4f}; curve energy {t['energy_relaxed']:.6g} from geodesic {t['energy_geo']:.6g} / chord "
+              f"{t['energy_lin']:.6g}; {int(sum(sum(r['relax_from']) for r in per_pair))} position(s) kept the geodesic's result")
     print(f"Saved artifacts to: {out_dir}")
     return out
 
@@ -129,6 +158,8 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--dataset", type=str, default="other", help="CIFAR10: un-normalise RGB images decoded without a sigmoid")
     p.add_argument("--batch_size", type=int, default=512)
     p.add_argument("--train_latents_path", type=str, default=None)
+    p.add_argument("--relax_iters", type=int, default=0,
+                   help="relax geodesic and chord under the decoder's metric for this many iterations and add the better result")
     return p
 
 
