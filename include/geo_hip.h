@@ -561,6 +561,11 @@ typedef struct geo_vanilla_decoder_desc {
     const float *shift2;       /* [c2] */
     const float *w3p;          /* ConvT3 weight w3 [c2][C][4][4] as [parity][tap][C][c2], same parity / tap meaning */
     const float *b3;           /* [C] */
+    /* the transposed packs of geo_vanilla_vjp alone; every other entry point ignores them and accepts them null */
+    const float *w2t;          /* w2 as [tap 4 ky + kx][c2 / 4][c1][4]: element (tap, q, ci, r) = w2[ci][4 q + r][ky][kx] */
+    const float *w3t;          /* w3 as [tap 4 ky + kx][C][c2]: element (tap, c, ci) = w3[ci][c][ky][kx] */
+    const float *Atq;          /* At as [n1 / 4][dn][4], dn = d rounded up to a multiple of 32: element (q, k, r) = At[k][4 q + r],
+                                  0 for k >= d */
 } geo_vanilla_decoder_desc;
 
 /* Workspace of geo_vanilla_jvp_pairs for n_edges edges; 0 for a descriptor outside the coverage above (host arithmetic).
@@ -580,6 +585,46 @@ int geo_vanilla_jvp_pairs(const geo_vanilla_decoder_desc *dec, const float *z_st
 int geo_vanilla_jvp_edges(const geo_vanilla_decoder_desc *dec, const float *z, int64_t n_nodes, const int32_t *src,
                           const int32_t *dst, int64_t n_edges, int32_t batch_size, float *len_out, void *ws, size_t ws_bytes,
                           void *stream);
+
+/* Vector-Jacobian product of the same decoder: with g(z) = sigmoid(decoder(z)) flattened to
+ * nout = C S S values ([C][S][S]) and J = dg/dz,  out[i] = J(z_i)^T u_i,  z_i = z[index ? index[i] : i].
+ * z f32 [.][d], index NULL or i32 [n], u f32 [n][nout], out f64 [n][d]; the descriptor's w2t, w3t and Atq are required.
+ * The masks and sigmoid' come from the point pass of geo_vanilla_jvp_pairs; the three layers are walked backwards in f32 and
+ * the last product is summed in fp64, every value a fixed-order chain of its own item, no atomics: a row's bits do not depend
+ * on n, its position, index, the pass size, the stream or earlier workspace contents; u_i = 0 gives exactly 0.  The items are
+ * cut into passes that fit the workspace: any size from geo_vanilla_vjp_min_workspace_bytes(dec) upwards is legal (a smaller
+ * one: GEO_E_WORKSPACE).  The queries answer 0 for a descriptor outside the coverage and the call rejects it (GEO_E_ARG) before
+ * any launch.  n == 0 returns GEO_OK without a launch; n < 2^31.  Asynchronous on `stream`. */
+size_t geo_vanilla_vjp_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n);
+size_t geo_vanilla_vjp_min_workspace_bytes(const geo_vanilla_decoder_desc *dec);
+int geo_vanilla_vjp(const geo_vanilla_decoder_desc *dec, const float *z, const int32_t *index, int64_t n, const float *u, double *out,
+                    void *ws, size_t ws_bytes, void *stream);
+
+/* Curve energy and relaxation under the vanilla decoder: the definitions, the loop and the rules of
+ * geo_curve_energy / geo_curve_relax above (section 26), with g(z) = sigmoid(decoder(z)) [nout] and the gradient by
+ * geo_vanilla_vjp's passes instead of a Jacobian.  x f32 [C][F][d], 2 <= F <= 64:
+ *   seg_sq[f] = |g[f+1] - g[f]|^2 from the f32 outputs in fp64: thread t of 256 adds the squares of outputs t, t + 256, ... in
+ *               ascending order (one accumulator from 0, product and sum separate), then p[t] += p[t + s], s = 128, 64, .., 1
+ *   E = sum_f seg_sq[f] ascending;  NaN for a curve with a NaN or an inf among its coordinates
+ *   r[f] = (g[f] - g[f-1]) - (g[f+1] - g[f]) in fp64, rounded once to f32;  grad[f] = 2 J(x[f])^T r[f], 0 at the ends
+ *   trace[f] = sum_k |J(x[f]) e_k|^2, each square norm in f32 by the tangent kernels of geo_vanilla_jvp_pairs, summed over k
+ *              ascending in fp64
+ * energy f64 [C]; seg_sq f64 [C][F-1], grad f64 [C][F][d], g_out f32 [C][F][nout], trace_out f64 [C][F] may each be null.  The
+ * trace (d tangents per frame) is computed only where asked for: by trace_out, or in geo_vanilla_curve_relax for a slice that
+ * holds a curve with step_inout < 0, which then starts from 1 / (8 max interior trace).  Curves are cut into slices of whole
+ * curves that fit the workspace: any size from geo_vanilla_curve_min_workspace_bytes(dec, F) upwards is legal and no bit depends
+ * on it, nor on C, a curve's position, the stream or earlier workspace contents.  geo_vanilla_curve_relax reads step_inout once
+ * on the host before its first launch (it synchronises the stream there) and decides every iteration on the device; n iterations
+ * in one call are the bits of n calls of one iteration continued through step_inout.  Uncovered descriptor: queries 0, calls
+ * GEO_E_ARG before any launch. */
+size_t geo_vanilla_curve_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t C, int32_t F);
+size_t geo_vanilla_curve_min_workspace_bytes(const geo_vanilla_decoder_desc *dec, int32_t F);
+int geo_vanilla_curve_energy(const geo_vanilla_decoder_desc *dec, const float *x, int64_t C, int32_t F, double *energy_out,
+                             double *seg_sq_out, double *grad_out, float *g_out, double *trace_out, void *ws, size_t ws_bytes,
+                             void *stream);
+int geo_vanilla_curve_relax(const geo_vanilla_decoder_desc *dec, float *x_inout, int64_t C, int32_t F, int32_t n_iters,
+                            double *step_inout, double *energy0_out, double *energy_out, double *seg_sq_out, int32_t *accepted_out,
+                            void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Image decode: latents or codes -> the decoder's raw output (before any sigmoid), f32 NCHW

@@ -26,7 +26,7 @@ class DecoderDesc(ctypes.Structure):
 class VanillaDecoderDesc(ctypes.Structure):
     """geo_vanilla_decoder_desc of include/geo_hip.h."""
     _fields_ = ([(n, i32) for n in ("latent_dim", "c1", "c2", "out_channels", "out_size")]
-                + [(n, c_p) for n in ("At", "c", "w2p", "scale2", "shift2", "w3p", "b3")])
+                + [(n, c_p) for n in ("At", "c", "w2p", "scale2", "shift2", "w3p", "b3", "w2t", "w3t", "Atq")])
 
 
 class SpatialImageDecoderDesc(ctypes.Structure):
@@ -127,6 +127,14 @@ _SIGNATURES = {
     "geo_vanilla_jvp_edges_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64, i64]),
     "geo_vanilla_jvp_pairs": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
     "geo_vanilla_jvp_edges": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, i64, c_p, c_p, i64, i32, c_p, c_p, sz, c_p]),
+    "geo_vanilla_vjp_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64]),
+    "geo_vanilla_vjp_min_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc)]),
+    "geo_vanilla_vjp": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, c_p, c_p, c_p, sz, c_p]),
+    "geo_vanilla_curve_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64, i32]),
+    "geo_vanilla_curve_min_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i32]),
+    "geo_vanilla_curve_energy": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, sz, c_p]),
+    "geo_vanilla_curve_relax": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, sz,
+                                               c_p]),
     "geo_vanilla_decode_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64]),
     "geo_vanilla_decode": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, c_p, c_p, sz, c_p]),
     "geo_spatial_decode_workspace_bytes": (sz, [ctypes.POINTER(SpatialImageDecoderDesc), i64]),

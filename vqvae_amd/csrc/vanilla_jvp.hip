@@ -17,6 +17,8 @@
 //
 // The image decode at the end of this file (geo_vanilla_decode, geo_spatial_decode) runs the point pass's
 // front and mid without the masks and writes the logits instead of sigmoid'.
+// The vector-Jacobian product (geo_vanilla_vjp) and the curve energy and relaxation built on it (geo_vanilla_curve_energy,
+// geo_vanilla_curve_relax) run the point pass as it is and then the three layers backwards.
 //
 // ConvT2 (k4, s2, p1) is four implicit GEMMs, one per output-pixel parity: out[(2y+py, 2x+px)][co] = sum over the taps
 // (a, b) in {0,1}^2 and ci of in[(y+py-a, x+px-b)][ci] w2[ci][co][2a+1-py][2b+1-px]; M = (item, pixel) rows, K = 4 c1, N = c2, on
@@ -24,6 +26,9 @@
 // depend on the pass size, the position in a pass, the entry point, the run or the stream.  dz = 0 gives exactly 0.
 #include "geo_common.h"
 #include "mfma_conv.h"
+#include "curve_step.h"
+
+#include <vector>
 
 namespace {
 
@@ -260,10 +265,13 @@ __global__ __launch_bounds__(512) void vj_mid_kernel(const float *__restrict__ i
 // ---- back: ConvT3 (same parity form, w3p [parity][tap][C][c2]: uniform reads) of one item per workgroup, the input
 // ([pixel][c2]) in LDS.  Point pass: sigmoid' = e / (1 + e)^2, e = exp(-|logit|), to the slot.  Edge pass: both ends of one
 // edge in turn; squares summed per thread in position order, then a fixed tree over the wave and the four waves in order.
-template <int C2, int CO, bool TANGENT>
+// SQ (edge pass): len_out [2 E] takes each end's sum of squares instead of the edge's length.  G_OUT (point pass): g_out takes
+// the sigmoid itself beside sigmoid', from the same e: 1 / (1 + e) for a logit >= 0, else e / (1 + e).
+template <int C2, int CO, bool TANGENT, bool SQ = false, bool G_OUT = false>
 __global__ __launch_bounds__(256) void vj_back_kernel(const float *__restrict__ in, float *__restrict__ sigp, Ends s,
                                                       int resident, int64_t slot0, int s2, const float *__restrict__ w3p,
-                                                      const float *__restrict__ b3, float *__restrict__ len_out) {
+                                                      const float *__restrict__ b3, float *__restrict__ len_out,
+                                                      float *__restrict__ g_out) {
     constexpr int LD = C2 + 4;
     __shared__ __attribute__((aligned(16))) float lds[(MID_ROWS + 1) * LD];
     __shared__ float wsum[4];
@@ -313,6 +321,7 @@ __global__ __launch_bounds__(256) void vj_back_kernel(const float *__restrict__ 
                     } else {
                         const float e = expf(-fabsf(acc[c]));
                         sg[o] = e / ((1.f + e) * (1.f + e));
+                        if (G_OUT) g_out[(size_t)slot * nout + o] = acc[c] >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
                     }
                 }
             }
@@ -322,10 +331,11 @@ __global__ __launch_bounds__(256) void vj_back_kernel(const float *__restrict__ 
             for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off, 64);
             if ((tid & 63) == 0) wsum[tid >> 6] = ss;
             __syncthreads();
-            norm[side] = sqrtf(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+            if (SQ) { if (tid == 0) len_out[it] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]; }
+            else norm[side] = sqrtf(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
         }
     }
-    if (TANGENT && tid == 0) len_out[blockIdx.x] = 0.5f * (norm[0] + norm[1]);
+    if (TANGENT && !SQ && tid == 0) len_out[blockIdx.x] = 0.5f * (norm[0] + norm[1]);
 }
 
 template <int C1, int C2, bool TANGENT>
@@ -345,12 +355,13 @@ int run_mid(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *in
     return launch_mid<64, 32, TANGENT>(sh, dc, in, out, mask1, mask2, e, resident, slot0, n_items, st);
 }
 
-template <bool TANGENT>
+template <bool TANGENT, bool SQ = false, bool G_OUT = false>
 int run_back(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *in, float *sigp, const Ends &e, int resident,
-             int64_t slot0, int64_t blocks, float *len_out, hipStream_t st) {
+             int64_t slot0, int64_t blocks, float *len_out, hipStream_t st, float *g_out = nullptr) {
     const unsigned grid = (unsigned)blocks;
 #define VJ_BACK(C2_, CO_)                                                                                                     \
-    vj_back_kernel<C2_, CO_, TANGENT><<<grid, 256, 0, st>>>(in, sigp, e, resident, slot0, sh.s2, dc->w3p, dc->b3, len_out)
+    vj_back_kernel<C2_, CO_, TANGENT, SQ, G_OUT><<<grid, 256, 0, st>>>(in, sigp, e, resident, slot0, sh.s2, dc->w3p, dc->b3,     \
+                                                                        len_out, g_out)
     if (sh.c2 == 64 && sh.co == 1) VJ_BACK(64, 1);
     else if (sh.c2 == 64) VJ_BACK(64, 3);
     else if (sh.co == 1) VJ_BACK(32, 1);
@@ -358,6 +369,19 @@ int run_back(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *i
 #undef VJ_BACK
     GEO_LAUNCH_CHECK();
     return GEO_OK;
+}
+
+// The point pass over `count` latents of e's lists: masks and sigmoid' to slots slot0 .., the activations through w.buf1 / w.buf2;
+// g_out (may be null): the sigmoids [slot][nout] as well.
+int run_point_pass(const geo_vanilla_decoder_desc *dc, const Shape &sh, const Workspace &w, const Ends &e, int64_t count,
+                   int64_t slot0, hipStream_t st, float *g_out = nullptr) {
+    const dim3 grid((unsigned)((count + FRONT_ROWS - 1) / FRONT_ROWS), FRONT_SPLIT);
+    vj_front_kernel<false><<<grid, 256, 0, st>>>(e, (int)count, sh.d, sh.dp, sh.n1, dc->At, dc->c, w.buf1, w.mask1, slot0);
+    GEO_LAUNCH_CHECK();
+    int rc = run_mid<false>(sh, dc, w.buf1, w.buf2, w.mask1, w.mask2, e, 0, slot0, count, st);
+    if (rc != GEO_OK) return rc;
+    if (g_out) return run_back<false, false, true>(sh, dc, w.buf2, w.sigp, e, 0, slot0, count, nullptr, st, g_out);
+    return run_back<false>(sh, dc, w.buf2, w.sigp, e, 0, slot0, count, nullptr, st);
 }
 
 // n_resident > 0: the point pass runs once over the latents z[0 .. n_resident) and the edges index them (iA = src, iB = dst);
@@ -379,14 +403,7 @@ int run(const geo_vanilla_decoder_desc *dc, const Shape &sh, const float *zA, co
         geo::set_error("%s: workspace too small", who);
         return GEO_E_WORKSPACE;
     }
-    auto point_pass = [&](const Ends &e, int64_t count, int64_t slot0) -> int {
-        const dim3 grid((unsigned)((count + FRONT_ROWS - 1) / FRONT_ROWS), FRONT_SPLIT);
-        vj_front_kernel<false><<<grid, 256, 0, st>>>(e, (int)count, sh.d, sh.dp, sh.n1, dc->At, dc->c, w.buf1, w.mask1, slot0);
-        GEO_LAUNCH_CHECK();
-        int rc = run_mid<false>(sh, dc, w.buf1, w.buf2, w.mask1, w.mask2, e, 0, slot0, count, st);
-        if (rc != GEO_OK) return rc;
-        return run_back<false>(sh, dc, w.buf2, w.sigp, e, 0, slot0, count, nullptr, st);
-    };
+    auto point_pass = [&](const Ends &e, int64_t count, int64_t slot0) -> int { return run_point_pass(dc, sh, w, e, count, slot0, st); };
     if (resident)
         for (int64_t p0 = 0; p0 < n_resident; p0 += 2 * eb) {
             const int64_t cnt = n_resident - p0 < 2 * eb ? n_resident - p0 : 2 * eb;
@@ -593,7 +610,513 @@ bool make_spatial_shape(const geo_spatial_image_decoder_desc *dc, SpatialShape *
     return true;
 }
 
+// ================================ vector-Jacobian product ================================
+// out[i] = J(z_i)^T u_i, J = d sigmoid(decoder(z)) / dz: the point pass above for the two masks and sigmoid', then the three
+// layers backwards.  A transposed convolution's adjoint is the convolution with the same kernel: input pixel (iy, ix) collects
+// output pixels (2 iy - 1 + ky, 2 ix - 1 + kx), ky, kx = 0 .. 3, nothing outside the image.
+//
+//   vv_back_kernel    u3 = sigmoid' * u ([C][S][S]) -> u2 [s2 s2][c2] = mask2 * scale2 * conv(u3, w3)        VALU, K = 16 C
+//   vv_mid_kernel     u2 -> u1 [s1 s1][c1] = mask1 * conv(u2, w2)                                             MFMA, K = 16 c2
+//   vv_final_kernel   part[row y][i][k] = sum over the pixels of row y and the channels of At[k][n] u1[i][n]   MFMA, K = s1 c1
+//   vv_sum_kernel     out[i][k] = sum over y of part[y][i][k]                                                  fp64
+//
+// Fixed orders: u2 is one fmaf chain from 0 over (ky, kx, c) ascending; u1 is the K-quad chain over tap 4 ky + kx and the c2
+// channels; a pixel's share of out is the K-quad chain over its c1 channels in f32, the pixels of a row are added in fp64 in
+// ascending order, then the rows in ascending order.  No atomics; every value belongs to one item.
+constexpr int64_t VJP_ITEMS_PER_PASS = 1024;
+constexpr int VV_MID_ITEMS = 2;                 // items of one vv_mid workgroup: 2 x 256 input rows in LDS, 4 M tiles of outputs
+
+struct VjpWorkspace { Workspace pt; double *part; };
+VjpWorkspace lay_out_vjp(geo::Arena &ar, const Shape &s, int64_t pb) {
+    VjpWorkspace w;
+    ar.take(w.pt.mask1, (size_t)pb * (s.n1 / 32)); ar.take(w.pt.mask2, (size_t)pb * (s.n2 / 32));
+    ar.take(w.pt.sigp, (size_t)pb * s.nout);
+    ar.take(w.pt.buf1, (size_t)pb * s.n1); ar.take(w.pt.buf2, (size_t)pb * s.n2);
+    ar.take(w.part, (size_t)s.s1 * pb * ((s.d + 31) & ~31));
+    return w;
+}
+size_t vjp_layout_bytes(const Shape &s, int64_t pb) { return geo::measure(lay_out_vjp, s, pb); }
+
+// w3t: [tap 4 ky + kx][C][c2].  A thread owns one channel ci of c2 and keeps its 16 C weights in registers; u3 sits in LDS
+// with a border of one zero pixel, so no tap tests a bound.  One item per workgroup.
+template <int C2, int CO>
+__global__ __launch_bounds__(256) void vv_back_kernel(const float *__restrict__ u, const float *__restrict__ sigp,
+                                                      const uint32_t *__restrict__ mask2, float *__restrict__ out, int64_t row0,
+                                                      int s2, const float *__restrict__ w3t, const float *__restrict__ sc2) {
+    constexpr int NPG = 256 / C2, TN = C2 / 32;
+    __shared__ float us[CO * 34 * 34];
+    const int S = 2 * s2, SP = S + 2, P2 = s2 * s2, n2 = P2 * C2, nout = CO * S * S;
+    const int tid = threadIdx.x;
+    const int64_t it = blockIdx.x;
+    const float *ui = u + (size_t)(row0 + it) * nout, *sg = sigp + (size_t)it * nout;
+    for (int q = tid; q < CO * SP * SP; q += 256) {
+        const int c = q / (SP * SP), rem = q - c * SP * SP, py = rem / SP, px = rem - py * SP;
+        const bool in = py >= 1 && py <= S && px >= 1 && px <= S;
+        const int o = (c * S + py - 1) * S + px - 1;
+        us[q] = in ? sg[o] * ui[o] : 0.f;
+    }
+    const int ci = tid % C2, pg = tid / C2;
+    float w[16 * CO];
+#pragma unroll
+    for (int t = 0; t < 16 * CO; ++t) w[t] = w3t[(size_t)t * C2 + ci];
+    const float scale = sc2[ci];
+    __syncthreads();
+    for (int pix = pg; pix < P2; pix += NPG) {
+        const int y = pix / s2, x = pix - y * s2;
+        float acc = 0.f;
+#pragma unroll
+        for (int tap = 0; tap < 16; ++tap)
+#pragma unroll
+            for (int c = 0; c < CO; ++c)
+                acc = fmaf(us[(c * SP + 2 * y + (tap >> 2)) * SP + 2 * x + (tap & 3)], w[tap * CO + c], acc);
+        const uint32_t bits = mask2[(size_t)it * (n2 / 32) + (size_t)pix * TN + (ci >> 5)];
+        out[(size_t)it * n2 + (size_t)pix * C2 + ci] = (bits >> (ci & 31)) & 1u ? scale * acc : 0.f;
+    }
+}
+
+// w2t: [tap 4 ky + kx][c2 / 4][c1][4], element (tap, q, ci, r) = w2[ci][4 q + r][ky][kx].  M = (item, pixel of s1 x s1) rows, the
+// items' u2 ([pixel of s2 x s2][c2]) staged in mfma_conv.h's layout; 8 waves: wave = (N tile, M tiles sharing the B read).
+template <int C1, int C2>
+__global__ __launch_bounds__(512) void vv_mid_kernel(const float *__restrict__ in, float *__restrict__ out,
+                                                     const uint32_t *__restrict__ mask1, int64_t n_items, int s1,
+                                                     const float *__restrict__ w2t) {
+    constexpr int LD = C2 + 4, TN = C1 / 32, WPN = 8 / TN, MT = 4 / WPN, G = VV_MID_ITEMS;
+    __shared__ __attribute__((aligned(16))) float lds[(G * 256 + 1) * LD];
+    const int P = s1 * s1, s2 = 2 * s1, P2 = 4 * P, n1 = P * C1, n2 = P2 * C2;
+    const int rows = G * P, ZR = G * P2;
+    const int64_t item0 = (int64_t)blockIdx.x * G;
+    const int tid = threadIdx.x;
+    for (int g = 0; g < G; ++g)
+        if (item0 + g < n_items) mfma_conv::stage_rows<C2, 512>(lds + (size_t)g * P2 * LD, in + (size_t)(item0 + g) * n2, P2, tid);
+    mfma_conv::fill_zero_row<512>(lds, ZR, LD, tid);
+    __syncthreads();
+
+    const int lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int nt = wave % TN, m0 = wave / TN;
+    int rg[MT], ry[MT], rx[MT];
+    bool rv[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int r = (m0 + m * WPN) * 32 + j;
+        const int g = r < rows ? r / P : 0;
+        rv[m] = r < rows && item0 + g < n_items;
+        rg[m] = g;
+        const int pq = r < rows ? r - g * P : 0;
+        ry[m] = pq / s1;
+        rx[m] = pq - ry[m] * s1;
+    }
+    const int ci = nt * 32 + j;
+    mfma_conv::f32x16 acc[MT];
+    mfma_conv::clear(acc);
+    for (int tap = 0; tap < 16; ++tap) {
+        const int ky = tap >> 2, kx = tap & 3;
+        const float *ap[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+            ap[m] = mfma_conv::tap_row(lds, LD, ZR, rv[m], rg[m], 2 * ry[m] - 1 + ky, 2 * rx[m] - 1 + kx, s2, P2, h);
+        const float4 *wp = reinterpret_cast<const float4 *>(w2t) + ((size_t)tap * (C2 / 4) + h) * C1 + ci;
+        mfma_conv::k_chain<MT, 4>(acc, ap, wp, C2 / 8, C1);
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int r = mfma_conv::acc_row(q, h, (m0 + m * WPN) * 32);
+            const int g = r < rows ? r / P : 0;
+            const int64_t it = item0 + g;
+            if (r < rows && it < n_items) {
+                const int pix = r - g * P;
+                const uint32_t bits = mask1[(size_t)it * (n1 / 32) + (size_t)pix * TN + nt];
+                out[(size_t)it * n1 + (size_t)pix * C1 + ci] = (bits >> j) & 1u ? acc[m][q] : 0.f;
+            }
+        }
+    }
+}
+
+// Atq: [n1 / 4][dn][4], dn = d rounded up to a multiple of 32, element (q, k, r) = At[k][4 q + r], 0 for k >= d.  A workgroup is
+// 32 items x one pixel row of the s1 x s1 grid, a wave one tile of 32 latent dimensions; A straight from global memory (a lane
+// reads 16 consecutive bytes of its own item).  A row past `cnt` reads the last item's and is not written.
+__global__ __launch_bounds__(256) void vv_final_kernel(const float *__restrict__ u1, int cnt, int n1, int c1, int s1, int dn,
+                                                       const float *__restrict__ Atq, double *__restrict__ part) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int tile0 = blockIdx.x * 32, y = blockIdx.y;
+    const int row = tile0 + j < cnt ? tile0 + j : cnt - 1;
+    const int col = wave * 32 + j;
+    const float *ar = u1 + (size_t)row * n1 + 4 * h;
+    const float4 *bq = reinterpret_cast<const float4 *>(Atq) + (size_t)h * dn + col;
+    double sum[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sum[q] = 0.0;
+    for (int x = 0; x < s1; ++x) {
+        const int k0 = (y * s1 + x) * c1;
+        mfma_conv::f32x16 acc;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+        for (int cb = 0; cb < c1 / 8; ++cb) {
+            const float4 av = *reinterpret_cast<const float4 *>(ar + k0 + cb * 8);
+            const float4 bv = bq[(size_t)(k0 / 4 + 2 * cb) * dn];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) sum[q] += (double)acc[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int r = tile0 + mfma_conv::acc_row(q, h);
+        if (r < cnt) part[((size_t)y * cnt + r) * dn + col] = sum[q];
+    }
+}
+
+// F = 0: out = the sum.  F >= 2 (the items are curves of F frames): out = twice the sum at an interior frame, 0 at the ends.
+__global__ __launch_bounds__(256) void vv_sum_kernel(const double *__restrict__ part, int cnt, int d, int dn, int s1, int F,
+                                                     double *__restrict__ out) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= (int64_t)cnt * d) return;
+    const int i = (int)(q / d), k = (int)(q - (int64_t)i * d);
+    double s = 0.0;
+    for (int y = 0; y < s1; ++y) s += part[((size_t)y * cnt + i) * dn + k];
+    if (F) {
+        const int f = i % F;
+        s = f > 0 && f < F - 1 ? 2.0 * s : 0.0;
+    }
+    out[q] = s;
+}
+
+// u f32 [.][nout] rows row0 .. row0 + cnt of the call -> out f64 [cnt][d], with the masks and sigmoid' of slots 0 .. cnt - 1.
+int run_vjp_tail(const geo_vanilla_decoder_desc *dc, const Shape &sh, const VjpWorkspace &w, const float *u, int64_t row0,
+                 int64_t cnt, double *out, hipStream_t st, int F = 0) {
+#define VV_BACK(C2_, CO_)                                                                                                     \
+    vv_back_kernel<C2_, CO_><<<(unsigned)cnt, 256, 0, st>>>(u, w.pt.sigp, w.pt.mask2, w.pt.buf2, row0, sh.s2, dc->w3t, dc->scale2)
+    if (sh.c2 == 64 && sh.co == 1) VV_BACK(64, 1);
+    else if (sh.c2 == 64) VV_BACK(64, 3);
+    else if (sh.co == 1) VV_BACK(32, 1);
+    else VV_BACK(32, 3);
+#undef VV_BACK
+    GEO_LAUNCH_CHECK();
+    const unsigned mid_grid = (unsigned)((cnt + VV_MID_ITEMS - 1) / VV_MID_ITEMS);
+    if (sh.c1 == 128) vv_mid_kernel<128, 64><<<mid_grid, 512, 0, st>>>(w.pt.buf2, w.pt.buf1, w.pt.mask1, cnt, sh.s1, dc->w2t);
+    else vv_mid_kernel<64, 32><<<mid_grid, 512, 0, st>>>(w.pt.buf2, w.pt.buf1, w.pt.mask1, cnt, sh.s1, dc->w2t);
+    GEO_LAUNCH_CHECK();
+    const int dn = (sh.d + 31) & ~31;
+    const dim3 grid((unsigned)((cnt + 31) / 32), (unsigned)sh.s1);
+    vv_final_kernel<<<grid, 2 * dn, 0, st>>>(w.pt.buf1, (int)cnt, sh.n1, sh.c1, sh.s1, dn, dc->Atq, w.part);
+    GEO_LAUNCH_CHECK();
+    vv_sum_kernel<<<(unsigned)((cnt * sh.d + 255) / 256), 256, 0, st>>>(w.part, (int)cnt, sh.d, dn, sh.s1, F, out);
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// ================================ curve energy and relaxation ================================
+// geo_vanilla_curve_energy / geo_vanilla_curve_relax: section 26's definitions and loop (curve_step.h) over this decoder.  C curves
+// of F frames are C F latents, curve after curve; a slice is whole curves, as many as the workspace holds.  Evaluate(z):
+//   point pass with G_OUT          masks, sigmoid' and g [frame][nout]
+//   vc_residual_kernel             per frame: seg_sq[f] = |g[f+1] - g[f]|^2 and r[f] = (g[f] - g[f-1]) - (g[f+1] - g[f]) in fp64,
+//                                  r rounded once to f32 (0 at the ends)
+//   vc_energy_kernel               per curve: E = sum of seg_sq ascending; NaN for a curve with a NaN or an inf
+//   the VJP tail with F            grad[f] = 2 J(x[f])^T r[f], 0 at the ends
+// The order of a segment's sum depends on nout alone: thread t of 256 adds the squares of outputs t, t + 256, t + 512, ... in
+// ascending order into one fp64 accumulator (from 0, product and sum separate operations), then the 256 partial sums are folded
+// p[t] += p[t + s] for s = 128, 64, ..., 1.
+// The trace tr J^T J of a frame is the sum over k ascending, in fp64, of |J e_k|^2 in f32: unit tangent e_k enters the tangent
+// kernels as row k of At (what vj_front_kernel<true> makes of e_k, exactly), an "edge" is (pair of frames, k), its two ends the
+// two frames, and the back kernel with SQ writes each end's sum of squares.
+constexpr int64_t CURVE_SLICE_ITEMS = 4096;      // at most this many frames per slice
+constexpr int TRACE_EDGES = 512;                 // about this many (pair of frames, k) per trace pass
+
+struct CurveWorkspace {
+    CurveState st;
+    VjpWorkspace v;
+    float *g, *r, *sq;
+    int32_t *ia, *ib;
+    int64_t trace_pairs;        // pairs of frames per trace pass
+};
+
+int64_t trace_pairs_for(const Shape &s, int64_t n) {
+    const int64_t pairs = (n + 1) / 2, fit = TRACE_EDGES / s.d < 1 ? 1 : TRACE_EDGES / s.d;
+    return pairs < fit ? pairs : fit;
+}
+
+CurveWorkspace lay_out_curve_slice(geo::Arena &ar, const Shape &s, int64_t n_curves, int F) {
+    CurveWorkspace w;
+    const int64_t n = n_curves * F;
+    w.trace_pairs = trace_pairs_for(s, n);
+    const int64_t eb = w.trace_pairs * s.d;                   // the trace pass: eb tangent rows, 2 eb items
+    lay_out_curves(ar, &w.st, n_curves, F, s.d);
+    ar.take(w.v.pt.mask1, (size_t)n * (s.n1 / 32)); ar.take(w.v.pt.mask2, (size_t)n * (s.n2 / 32));
+    ar.take(w.v.pt.sigp, (size_t)n * s.nout);
+    ar.take(w.v.pt.buf1, (size_t)(n > eb ? n : eb) * s.n1); ar.take(w.v.pt.buf2, (size_t)(n > 2 * eb ? n : 2 * eb) * s.n2);
+    ar.take(w.v.part, (size_t)s.s1 * n * ((s.d + 31) & ~31));
+    ar.take(w.g, (size_t)n * s.nout); ar.take(w.r, (size_t)n * s.nout);
+    ar.take(w.sq, (size_t)2 * eb); ar.take(w.ia, (size_t)eb); ar.take(w.ib, (size_t)eb);
+    return w;
+}
+size_t curve_slice_bytes(const Shape &s, int64_t n_curves, int F) { return geo::measure(lay_out_curve_slice, s, n_curves, F); }
+
+int64_t curve_slice_cap(int64_t C, int F) {
+    const int64_t cap = CURVE_SLICE_ITEMS / F;
+    return C < 1 ? 1 : (C < cap ? C : cap);
+}
+
+// one workgroup per frame p = c F + f of the slice
+__global__ __launch_bounds__(256) void vc_residual_kernel(const float *__restrict__ g, int F, int nout, double *__restrict__ seg_sq,
+                                                          float *__restrict__ r) {
+#pragma clang fp contract(off)      // plain operators below: the pragma governs them
+    __shared__ double part_s[256];
+    const int64_t p = blockIdx.x, c = p / F;
+    const int f = (int)(p - c * F), tid = threadIdx.x;
+    const bool interior = f > 0 && f < F - 1;
+    const float *g0 = g + (size_t)p * nout, *gm = f > 0 ? g0 - nout : g0, *gp = f < F - 1 ? g0 + nout : g0;
+    float *rp = r + (size_t)p * nout;
+    double part = 0.0;
+    for (int o = tid; o < nout; o += 256) {
+        const double ahead = (double)gp[o] - (double)g0[o];
+        part += ahead * ahead;
+        rp[o] = interior ? (float)(((double)g0[o] - (double)gm[o]) - ahead) : 0.f;
+    }
+    part_s[tid] = part;
+    for (int s = 128; s >= 1; s >>= 1) {
+        __syncthreads();
+        if (tid < s) part_s[tid] += part_s[tid + s];
+    }
+    if (tid == 0 && f < F - 1) seg_sq[(size_t)c * (F - 1) + f] = part_s[0];
+}
+
+// one wave per curve
+__global__ __launch_bounds__(64) void vc_energy_kernel(const double *__restrict__ seg_sq, const float *__restrict__ x, int F, int d,
+                                                       double *__restrict__ energy) {
+#pragma clang fp contract(off)
+    const int64_t c = blockIdx.x;
+    bool bad = false;
+    for (int i = threadIdx.x; i < F * d; i += 64)
+        bad |= (__float_as_uint(x[(size_t)c * F * d + i]) & 0x7f800000u) == 0x7f800000u;
+    const bool any_bad = __ballot(bad) != 0ull;
+    if (threadIdx.x == 0) {
+        double e = 0.0;
+        for (int f = 0; f < F - 1; ++f) e += seg_sq[(size_t)c * (F - 1) + f];
+        energy[c] = any_bad ? (double)NAN : e;
+    }
+}
+
+// the tangent rows and slots of a trace pass: row l = (pair q, k) is At[k], its two ends frames p0 + 2 q and p0 + 2 q + 1 (the
+// last frame again where the slice ends on an odd count; that end's result is not read)
+__global__ __launch_bounds__(256) void vc_unit_kernel(const float *__restrict__ At, int d, int n1, int64_t p0, int64_t n,
+                                                      float *__restrict__ rows, int32_t *__restrict__ ia, int32_t *__restrict__ ib) {
+    const int64_t l = blockIdx.x, q = l / d;
+    const int k = (int)(l - q * d);
+    const float4 *src = reinterpret_cast<const float4 *>(At + (size_t)k * n1);
+    float4 *dst = reinterpret_cast<float4 *>(rows + (size_t)l * n1);
+    for (int i = threadIdx.x; i < n1 / 4; i += 256) dst[i] = src[i];
+    if (threadIdx.x == 0) {
+        const int64_t a = p0 + 2 * q, b = a + 1 < n ? a + 1 : n - 1;
+        ia[l] = (int32_t)a;
+        ib[l] = (int32_t)b;
+    }
+}
+
+// tr[p0 + j] = sum over k ascending of (double)sq[2 ((j / 2) d + k) + (j & 1)], one thread per frame of the pass
+__global__ __launch_bounds__(256) void vc_trace_kernel(const float *__restrict__ sq, int d, int64_t p0, int64_t frames,
+                                                       double *__restrict__ tr) {
+#pragma clang fp contract(off)
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= frames) return;
+    double t = 0.0;
+    for (int k = 0; k < d; ++k) t += (double)sq[2 * ((j >> 1) * d + k) + (j & 1)];
+    tr[p0 + j] = t;
+}
+
+// Evaluate(z) over a slice of n_curves: energy [n_curves], seg_sq [n_curves][F-1], grad [n_curves][F][d]; g (the slice's own
+// buffer or the caller's) [n][nout]; tr [n] or null (the masks and sigmoid' it reads are this evaluation's)
+int curve_evaluate(const geo_vanilla_decoder_desc *dc, const Shape &sh, const CurveWorkspace &w, const float *z, int64_t n_curves,
+                   int F, double *energy, double *seg_sq, double *grad, float *g, double *tr, hipStream_t st) {
+    const int64_t n = n_curves * F;
+    const Ends e{z, z, nullptr, nullptr, 0, (int)n};
+    int rc = run_point_pass(dc, sh, w.v.pt, e, n, 0, st, g);
+    if (rc != GEO_OK) return rc;
+    vc_residual_kernel<<<(unsigned)n, 256, 0, st>>>(g, F, sh.nout, seg_sq, w.r);
+    GEO_LAUNCH_CHECK();
+    vc_energy_kernel<<<(unsigned)n_curves, 64, 0, st>>>(seg_sq, z, F, sh.d, energy);
+    GEO_LAUNCH_CHECK();
+    if (tr) {
+        for (int64_t p0 = 0; p0 < n; p0 += 2 * w.trace_pairs) {
+            const int64_t frames = n - p0 < 2 * w.trace_pairs ? n - p0 : 2 * w.trace_pairs;
+            const int64_t ne = (frames + 1) / 2 * sh.d;
+            vc_unit_kernel<<<(unsigned)ne, 256, 0, st>>>(dc->At, sh.d, sh.n1, p0, n, w.v.pt.buf1, w.ia, w.ib);
+            GEO_LAUNCH_CHECK();
+            const Ends t{z, z, w.ia, w.ib, 0, (int)ne};
+            rc = run_mid<true>(sh, dc, w.v.pt.buf1, w.v.pt.buf2, w.v.pt.mask1, w.v.pt.mask2, t, 1, 0, 2 * ne, st);
+            if (rc != GEO_OK) return rc;
+            rc = run_back<true, true>(sh, dc, w.v.pt.buf2, w.v.pt.sigp, t, 1, 0, ne, w.sq, st);
+            if (rc != GEO_OK) return rc;
+            vc_trace_kernel<<<(unsigned)((frames + 255) / 256), 256, 0, st>>>(w.sq, sh.d, p0, frames, tr);
+            GEO_LAUNCH_CHECK();
+        }
+    }
+    return run_vjp_tail(dc, sh, w.v, w.r, 0, n, grad, st, F);
+}
+
+int curve_check(const char *who, const geo_vanilla_decoder_desc *dc, Shape *sh, int64_t C, int F) {
+    int rc = check_desc(dc, sh, who);
+    if (rc != GEO_OK) return rc;
+    GEO_REQUIRE(dc->w2t && dc->w3t && dc->Atq, "%s: null transposed pack in the descriptor", who);
+    GEO_REQUIRE(F >= 2 && F <= CURVE_MAX_F, "%s: F %d not in [2,%d]", who, F, CURVE_MAX_F);
+    GEO_REQUIRE(C >= 0, "%s: C %lld < 0", who, (long long)C);
+    return GEO_OK;
+}
+
+// the curves per slice a workspace holds: everything (up to the cap) when it fits, else the largest count that does
+int curve_slice_length(const char *who, const Shape &sh, int64_t C, int F, size_t ws_bytes, int64_t *slice) {
+    const int64_t cap = curve_slice_cap(C, F);
+    *slice = cap;
+    if (ws_bytes >= curve_slice_bytes(sh, cap, F)) return GEO_OK;
+    const size_t min_bytes = curve_slice_bytes(sh, 1, F);
+    if (ws_bytes < min_bytes) {
+        geo::set_error("%s: workspace of %zu bytes is below the minimum of %zu", who, ws_bytes, min_bytes);
+        return GEO_E_WORKSPACE;
+    }
+    int64_t lo = 1, hi = cap;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        if (curve_slice_bytes(sh, mid, F) <= ws_bytes) lo = mid; else hi = mid - 1;
+    }
+    *slice = lo;
+    return GEO_OK;
+}
+
+int curve_energy(const geo_vanilla_decoder_desc *dc, const float *x, int64_t C, int F, double *energy_out, double *seg_sq_out,
+                 double *grad_out, float *g_out, double *trace_out, void *ws, size_t ws_bytes, hipStream_t st) {
+    static const char who[] = "geo_vanilla_curve_energy";
+    Shape sh;
+    if (const int rc = curve_check(who, dc, &sh, C, F)) return rc;
+    if (C == 0) return GEO_OK;
+    GEO_REQUIRE(x && energy_out && ws, "%s: null pointer", who);
+    int64_t slice = 0;
+    if (const int rc = curve_slice_length(who, sh, C, F, ws_bytes, &slice)) return rc;
+    for (int64_t base = 0; base < C; base += slice) {
+        const int64_t nc = C - base < slice ? C - base : slice;
+        geo::Arena ar(ws, ws_bytes);
+        const CurveWorkspace w = lay_out_curve_slice(ar, sh, nc, F);
+        GEO_REQUIRE_WORKSPACE("geo_vanilla_curve_energy", ar, curve_slice_bytes(sh, nc, F));
+        const size_t at = (size_t)base * F;
+        if (const int rc = curve_evaluate(dc, sh, w, x + at * sh.d, nc, F, energy_out + base,
+                                          seg_sq_out ? seg_sq_out + (size_t)base * (F - 1) : w.st.seg_ev,
+                                          grad_out ? grad_out + at * sh.d : w.st.grad_ev, g_out ? g_out + at * sh.nout : w.g,
+                                          trace_out ? trace_out + at : nullptr, st))
+            return rc;
+    }
+    return GEO_OK;
+}
+
+int curve_relax(const geo_vanilla_decoder_desc *dc, float *x, int64_t C, int F, int n_iters, double *step, double *energy0_out,
+                double *energy_out, double *seg_sq_out, int32_t *accepted_out, void *ws, size_t ws_bytes, hipStream_t st) {
+    static const char who[] = "geo_vanilla_curve_relax";
+    Shape sh;
+    if (const int rc = curve_check(who, dc, &sh, C, F)) return rc;
+    GEO_REQUIRE(n_iters >= 0, "%s: n_iters %d < 0", who, n_iters);
+    if (C == 0) return GEO_OK;
+    GEO_REQUIRE(x && step && energy_out && accepted_out && ws, "%s: null pointer", who);
+    int64_t slice = 0;
+    if (const int rc = curve_slice_length(who, sh, C, F, ws_bytes, &slice)) return rc;
+    // the trace costs d tangents per frame: only for a slice with a curve whose step the caller left to the call (one copy of the
+    // steps to the host, before the first launch; nothing is read back per iteration)
+    std::vector<double> step_h((size_t)C);
+    GEO_HIP_CHECK(hipMemcpyAsync(step_h.data(), step, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost, st));
+    GEO_HIP_CHECK(hipStreamSynchronize(st));
+    const int iters = F == 2 ? 0 : n_iters;                       // no interior frame: nothing can move
+    for (int64_t base = 0; base < C; base += slice) {
+        const int64_t nc = C - base < slice ? C - base : slice;
+        geo::Arena ar(ws, ws_bytes);
+        const CurveWorkspace w = lay_out_curve_slice(ar, sh, nc, F);
+        GEO_REQUIRE_WORKSPACE("geo_vanilla_curve_relax", ar, curve_slice_bytes(sh, nc, F));
+        bool need_trace = false;
+        for (int64_t c = base; c < base + nc; ++c) need_trace |= step_h[(size_t)c] < 0.0;
+        const CurveState &cs = w.st;
+        float *xs = x + (size_t)base * F * sh.d;
+        double *seg_s = seg_sq_out ? seg_sq_out + (size_t)base * (F - 1) : nullptr;
+        for (int it = -1; it < iters; ++it) {                     // it = -1: the curve itself
+            if (const int rc = curve_evaluate(dc, sh, w, it < 0 ? xs : cs.y, nc, F, cs.e_ev, cs.seg_ev, cs.grad_ev, w.g,
+                                              it < 0 && need_trace ? cs.tr : nullptr, st))
+                return rc;
+            curve_step_kernel<<<(unsigned)nc, CURVE_THREADS, 0, st>>>(cs, xs, F, sh.d, it < 0, it == iters - 1, step + base,
+                                                                      energy0_out ? energy0_out + base : nullptr, energy_out + base,
+                                                                      seg_s, accepted_out + base);
+            GEO_LAUNCH_CHECK();
+        }
+    }
+    return GEO_OK;
+}
+
 }  // namespace
+
+extern "C" size_t geo_vanilla_curve_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t C, int32_t F) {
+    Shape sh;
+    if (!make_shape(dec, &sh) || C < 0 || F < 2 || F > CURVE_MAX_F) return 0;
+    return curve_slice_bytes(sh, curve_slice_cap(C, F), F);
+}
+
+extern "C" size_t geo_vanilla_curve_min_workspace_bytes(const geo_vanilla_decoder_desc *dec, int32_t F) {
+    Shape sh;
+    if (!make_shape(dec, &sh) || F < 2 || F > CURVE_MAX_F) return 0;
+    return curve_slice_bytes(sh, 1, F);
+}
+
+extern "C" int geo_vanilla_curve_energy(const geo_vanilla_decoder_desc *dec, const float *x, int64_t C, int32_t F, double *energy_out,
+                                        double *seg_sq_out, double *grad_out, float *g_out, double *trace_out, void *ws,
+                                        size_t ws_bytes, void *stream) {
+    return curve_energy(dec, x, C, F, energy_out, seg_sq_out, grad_out, g_out, trace_out, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int geo_vanilla_curve_relax(const geo_vanilla_decoder_desc *dec, float *x_inout, int64_t C, int32_t F, int32_t n_iters,
+                                       double *step_inout, double *energy0_out, double *energy_out, double *seg_sq_out,
+                                       int32_t *accepted_out, void *ws, size_t ws_bytes, void *stream) {
+    return curve_relax(dec, x_inout, C, F, n_iters, step_inout, energy0_out, energy_out, seg_sq_out, accepted_out, ws, ws_bytes,
+                       static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t geo_vanilla_vjp_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n) {
+    Shape sh;
+    if (!make_shape(dec, &sh) || n < 0) return 0;
+    return vjp_layout_bytes(sh, n < 1 ? 1 : (n < VJP_ITEMS_PER_PASS ? n : VJP_ITEMS_PER_PASS));
+}
+
+extern "C" size_t geo_vanilla_vjp_min_workspace_bytes(const geo_vanilla_decoder_desc *dec) {
+    Shape sh;
+    return make_shape(dec, &sh) ? vjp_layout_bytes(sh, 1) : 0;
+}
+
+extern "C" int geo_vanilla_vjp(const geo_vanilla_decoder_desc *dec, const float *z, const int32_t *index, int64_t n, const float *u,
+                               double *out, void *ws, size_t ws_bytes, void *stream) {
+    Shape sh;
+    int rc = check_desc(dec, &sh, "geo_vanilla_vjp");
+    if (rc != GEO_OK) return rc;
+    GEO_REQUIRE(dec->w2t && dec->w3t && dec->Atq, "geo_vanilla_vjp: null transposed pack in the descriptor");
+    GEO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "geo_vanilla_vjp: n %lld", (long long)n);
+    if (n == 0) return GEO_OK;
+    GEO_REQUIRE(z && u && out && ws, "geo_vanilla_vjp: null pointer");
+    int64_t pb = n < VJP_ITEMS_PER_PASS ? n : VJP_ITEMS_PER_PASS;
+    while (pb >= 1 && vjp_layout_bytes(sh, pb) > ws_bytes) pb = geo::shrink_pass(pb);
+    if (pb < 1) {
+        geo::set_error("geo_vanilla_vjp: workspace of %zu bytes is below the minimum of %zu", ws_bytes, vjp_layout_bytes(sh, 1));
+        return GEO_E_WORKSPACE;
+    }
+    geo::Arena ar(ws, ws_bytes);
+    const VjpWorkspace w = lay_out_vjp(ar, sh, pb);
+    GEO_REQUIRE_WORKSPACE("geo_vanilla_vjp", ar, vjp_layout_bytes(sh, pb));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (int64_t p0 = 0; p0 < n; p0 += pb) {
+        const int64_t cnt = n - p0 < pb ? n - p0 : pb;
+        const Ends e{z, z, index, nullptr, p0, (int)cnt};
+        rc = run_point_pass(dec, sh, w.pt, e, cnt, 0, st);
+        if (rc != GEO_OK) return rc;
+        rc = run_vjp_tail(dec, sh, w, u, p0, cnt, out + (size_t)p0 * sh.d, st);
+        if (rc != GEO_OK) return rc;
+    }
+    return GEO_OK;
+}
 
 extern "C" size_t geo_vanilla_jvp_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n_edges) {
     Shape sh;

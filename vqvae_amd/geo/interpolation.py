@@ -5,6 +5,7 @@ geodesic_interpolation: node pairs -> the geodesic's polyline resampled at equal
 the pull-back length of both curves (edge_lengths_riemannian over consecutive frames).
 interpolate_images_spatial: image pairs of the spatial pipeline -> 16 node pairs each, one per grid position, assembled into
 latent grids, decoded (decode_images), with the image-space length of both routes (geo_image_pair_moments).
+interpolate_images_vanilla: the same for a vanilla pipeline's vector latents, one node pair per image pair.
 relax_iters > 0 (both): the geodesic's frames and the chord are each relaxed under the decoder's metric with the ends fixed
 (relax_curves_device) and the result with the lower energy is kept per pair: never worse than either start.
 """
@@ -76,6 +77,83 @@ def image_curve_lengths(images: torch.Tensor) -> torch.Tensor:
     return total
 
 
+def _row_pair_curves(flat: torch.Tensor, lcc_index: np.ndarray, G: DeviceCSR, a: np.ndarray, b: np.ndarray, F: int):
+    """Curves between rows a[i] and b[i] of flat f32 [n, d] (device), of which the rows lcc_index (ascending) are the nodes of G:
+    (frames_geo, frames_lin f32 [P, F, d], graph_dist f32 [P], hops, status i32 [P]).  A pair with an end outside the graph
+    (graph_dist NaN, hops -1, status 3) or without a path takes the chord as frames_geo."""
+    dev = G.indptr.device
+    P = a.shape[0]
+    node_of = np.full(flat.shape[0], -1, dtype=np.int64)
+    node_of[lcc_index] = np.arange(lcc_index.size)
+    frames_lin = chord_frames_device(flat, a, b, F)                           # over all pairs: a chord needs no graph
+    in_graph = (node_of[a] >= 0) & (node_of[b] >= 0)
+    sel = np.flatnonzero(in_graph)
+    frames_geo = frames_lin.clone()
+    graph_dist = torch.full((P,), float("nan"), dtype=torch.float32, device=dev)
+    hops = torch.full((P,), -1, dtype=torch.int32, device=dev)
+    status = torch.full((P,), 3, dtype=torch.int32, device=dev)
+    if sel.size:
+        sel_t = torch.from_numpy(sel).to(dev)
+        z_lcc = flat[torch.from_numpy(lcc_index).to(dev)].contiguous()
+        paths, dist = geodesic_paths_device(G, node_of[a[sel]], node_of[b[sel]])
+        geo = resample_paths_device(z_lcc, paths, F)
+        frames_geo[sel_t] = torch.where((paths.status != 0).view(-1, 1, 1), frames_lin[sel_t], geo)
+        graph_dist[sel_t], hops[sel_t], status[sel_t] = dist, paths.hops, paths.status
+    return frames_geo, frames_lin, graph_dist, hops, status
+
+
+def _check_pairs(image_pairs, lcc_index, n_images: int, n_rows: int, G: DeviceCSR):
+    """(pairs i64 [M, 2], lcc_index i64) checked as both image interpolations document them."""
+    pairs = np.asarray(image_pairs, dtype=np.int64).reshape(-1, 2)
+    if pairs.shape[0] == 0:
+        raise ValueError("image_pairs must be a non-empty sequence of (i, j)")
+    if pairs.min() < 0 or pairs.max() >= n_images:
+        raise ValueError(f"image indices out of range 0...{n_images}")
+    lcc_index = np.asarray(lcc_index, dtype=np.int64).reshape(-1)
+    if lcc_index.size != G.n or (lcc_index.size and (lcc_index.min() < 0 or lcc_index.max() >= n_rows
+                                                      or (np.diff(lcc_index) <= 0).any())):
+        raise ValueError(f"lcc_index must list the {G.n} nodes of the graph as ascending flat positions below {n_rows}")
+    return pairs, lcc_index
+
+
+def interpolate_images_vanilla(z: torch.Tensor, lcc_index, G: DeviceCSR, decoder, image_pairs: Sequence[Tuple[int, int]],
+                               n_frames: int, dataset: str, apply_sigmoid: bool, *, batch_size: int = 512,
+                               relax_iters: int = 0) -> Dict:
+    """Image pairs of a vanilla (vector-latent) pipeline: z f32 [N, d], one latent and so one node pair per image pair.
+    lcc_index: the rows of z that are nodes of G, ascending -- np.flatnonzero(codes >= 0) of a build_riemannian_codebook_legacy
+    output.  The fields of interpolate_images_spatial without the position axis: frames_geo, frames_lin f32 [M, F, d];
+    images_geo, images_lin f32 [M, F, C, S, S] (decode_images); graph_dist f32 [M] (NaN outside the graph, inf without a path),
+    hops, status i32 [M] (-1 and 3 outside the graph); curve_len_*, f32 [M]; image_len_* f64 [M]; fallback_positions per pair
+    ([0] where the pair took the chord, else empty).  relax_iters > 0 adds frames_relaxed, images_relaxed, image_len_relaxed,
+    curve_len_relaxed, relax_from, accepted_geo, accepted_lin i32 [M], energy_geo, energy_lin, energy_relaxed f64 [M]
+    (relax_best: natively for a decoder native_vanilla_relax_covers admits)."""
+    from ..decode import decode_images
+    F = _check_frames(n_frames)
+    dev = G.indptr.device
+    if z.dim() != 2:
+        raise ValueError(f"z must be [N, d], got {tuple(z.shape)}")
+    N, d = z.shape
+    pairs, lcc_index = _check_pairs(image_pairs, lcc_index, N, N, G)
+    M = pairs.shape[0]
+    flat = z.to(dev, torch.float32).contiguous()
+    frames_geo, frames_lin, graph_dist, hops, status = _row_pair_curves(flat, lcc_index, G, pairs[:, 0], pairs[:, 1], F)
+    st = status.cpu().numpy()
+    out = {"graph_dist": graph_dist, "hops": hops, "status": status,
+           "fallback_positions": [np.flatnonzero(st[m:m + 1] != 0).astype(np.int32) for m in range(M)]}
+    routes = [("geo", frames_geo), ("lin", frames_lin)]
+    if relax_iters > 0:
+        best = relax_best(decoder, frames_geo, frames_lin, int(relax_iters))
+        routes.append(("relaxed", best.pop("frames_relaxed")))
+        out.update(best)
+    for name, fr in routes:
+        out[f"frames_{name}"] = fr
+        out[f"curve_len_{name}"] = curve_lengths(decoder, fr, batch_size)
+        images = decode_images(decoder, fr.reshape(M * F, d), dataset=dataset, apply_sigmoid=apply_sigmoid)
+        out[f"images_{name}"] = images.view(M, F, *images.shape[1:])
+        out[f"image_len_{name}"] = image_curve_lengths(out[f"images_{name}"])
+    return out
+
+
 def interpolate_images_spatial(z_grids: torch.Tensor, lcc_index, G: DeviceCSR, decoder, image_pairs: Sequence[Tuple[int, int]],
                                n_frames: int, dataset: str, apply_sigmoid: bool, *, batch_size: int = 512,
                                relax_iters: int = 0) -> Dict:
@@ -95,36 +173,13 @@ def interpolate_images_spatial(z_grids: torch.Tensor, lcc_index, G: DeviceCSR, d
     dev = G.indptr.device
     N, d, h, w = z_grids.shape
     hw = h * w
-    pairs = np.asarray(image_pairs, dtype=np.int64).reshape(-1, 2)
+    pairs, lcc_index = _check_pairs(image_pairs, lcc_index, N, N * hw, G)
     M = pairs.shape[0]
-    if M == 0:
-        raise ValueError("image_pairs must be a non-empty sequence of (i, j)")
-    if pairs.min() < 0 or pairs.max() >= N:
-        raise ValueError(f"image indices out of range 0...{N}")
-    lcc_index = np.asarray(lcc_index, dtype=np.int64).reshape(-1)
-    if lcc_index.size != G.n or (lcc_index.size and (lcc_index.min() < 0 or lcc_index.max() >= N * hw
-                                                      or (np.diff(lcc_index) <= 0).any())):
-        raise ValueError(f"lcc_index must list the {G.n} nodes of the graph as ascending flat positions below {N * hw}")
-    node_of = np.full(N * hw, -1, dtype=np.int64)
-    node_of[lcc_index] = np.arange(lcc_index.size)
     flat = z_grids.to(dev, torch.float32).permute(0, 2, 3, 1).reshape(N * hw, d).contiguous()
     pos = np.arange(hw)
     a = (pairs[:, :1] * hw + pos).reshape(-1)                                # flat positions of the M hw node pairs
     b = (pairs[:, 1:] * hw + pos).reshape(-1)
-    frames_lin = chord_frames_device(flat, a, b, F)                           # over all positions: a chord needs no graph
-    in_graph = (node_of[a] >= 0) & (node_of[b] >= 0)
-    sel = np.flatnonzero(in_graph)
-    frames_geo = frames_lin.clone()
-    graph_dist = torch.full((M * hw,), float("nan"), dtype=torch.float32, device=dev)
-    hops = torch.full((M * hw,), -1, dtype=torch.int32, device=dev)
-    status = torch.full((M * hw,), 3, dtype=torch.int32, device=dev)
-    if sel.size:
-        sel_t = torch.from_numpy(sel).to(dev)
-        z_lcc = flat[torch.from_numpy(lcc_index).to(dev)].contiguous()
-        paths, dist = geodesic_paths_device(G, node_of[a[sel]], node_of[b[sel]])
-        geo = resample_paths_device(z_lcc, paths, F)
-        frames_geo[sel_t] = torch.where((paths.status != 0).view(-1, 1, 1), frames_lin[sel_t], geo)
-        graph_dist[sel_t], hops[sel_t], status[sel_t] = dist, paths.hops, paths.status
+    frames_geo, frames_lin, graph_dist, hops, status = _row_pair_curves(flat, lcc_index, G, a, b, F)
     st = status.view(M, hw).cpu().numpy()
     out = {"frames_geo": None, "frames_lin": None, "graph_dist": graph_dist.view(M, hw), "hops": hops.view(M, hw),
            "status": status.view(M, hw), "fallback_positions": [np.flatnonzero(st[m] != 0).astype(np.int32) for m in range(M)]}

@@ -7,9 +7,12 @@ every sum one fp64 accumulator over ascending indices; a curve with a NaN or an 
 relax_curves_device takes n_iters trial steps y = x - step * grad per curve, keeps a trial only where its energy is lower
 (step *= 2, else step /= 4) and never moves the ends: E can only fall.
 
-Covered decoders (native_relax_covers) with frames on a GPU run geo_curve_energy / geo_curve_relax (csrc/jvp.hip); every other
-decoder, and the CPU, takes the torch route with the same rules: g from the float32 eval module, J by
-torch.autograd.functional.jacobian in float32, the reductions in fp64 by explicit ascending loops.
+Covered decoders (native_relax_covers) with frames on a GPU run geo_curve_energy / geo_curve_relax (csrc/jvp.hip); covered
+vanilla decoders (native_vanilla_relax_covers; g the flattened image) run geo_vanilla_curve_energy / geo_vanilla_curve_relax
+(csrc/vanilla_jvp.hip), whose gradient is one vector-Jacobian product per frame and whose sums over the
+outputs follow the fixed order written down there; every other decoder, and the CPU, takes the torch route with the same rules:
+g from the float32 eval module, J by torch.autograd.functional.jacobian in float32, the reductions in fp64 by explicit ascending
+loops.
 """
 from dataclasses import dataclass
 
@@ -19,6 +22,7 @@ from .. import _lib
 from .._device import ptr, stream_ptr
 from .._export import capped_workspace, eval_mode
 from ..spatial_decoder import DecoderExport
+from ..vanilla_decoder import VanillaDecoderExport, vanilla_kernels_cover
 from .riemannian_metric import _has_train_batchnorm, native_metric_covers
 
 MAX_FRAMES = 64
@@ -29,13 +33,15 @@ _BN_ERROR = ("curve energy under a train-mode BatchNorm decoder: a sample's Jaco
 @dataclass
 class CurveEnergy:
     """energy f64 [C]; seg_sq f64 [C, F-1]; grad f64 [C, F, d] (0 at the ends); outputs f32 [C, F, p_out] (the sigmoids g);
-    jac f32 [C, F, d, p_out] or None; route "native" or "torch"."""
+    jac f32 [C, F, d, p_out] or None; route "native" or "torch"; trace f64 [C, F] (tr J^T J per frame) where the call was asked
+    for it on the native vanilla route, else None."""
     energy: object
     seg_sq: object
     grad: object
     outputs: object
     jac: object
     route: str
+    trace: object = None
 
 
 @dataclass
@@ -56,6 +62,11 @@ def native_relax_covers(decoder) -> bool:
     return native_metric_covers(decoder)
 
 
+def native_vanilla_relax_covers(decoder) -> bool:
+    """Whether geo_vanilla_curve_energy / geo_vanilla_curve_relax take this decoder: exactly vanilla_kernels_cover."""
+    return vanilla_kernels_cover(decoder)
+
+
 def _check_frames(frames: torch.Tensor) -> torch.Tensor:
     if frames.ndim != 3:
         raise ValueError(f"frames must be [C, F, d], got {tuple(frames.shape)}")
@@ -64,8 +75,18 @@ def _check_frames(frames: torch.Tensor) -> torch.Tensor:
     return frames.detach().to(torch.float32).contiguous()
 
 
-def _route(decoder_or_export, frames: torch.Tensor):
-    """(export or None, decoder or None): the native route's export, or the module of the torch route."""
+def _route(decoder_or_export, frames: torch.Tensor, jacobian: bool = False):
+    """(export or None, decoder or None): the native route's export (a DecoderExport, or a VanillaDecoderExport, whose route
+    computes no Jacobian), or the module of the torch route."""
+    if isinstance(decoder_or_export, VanillaDecoderExport):
+        if jacobian:
+            raise ValueError("jacobian=True with a VanillaDecoderExport: the native vanilla route computes vector-Jacobian "
+                             "products, not the d x p_out Jacobian of a frame; pass the module for the torch route")
+        if frames.shape[2] != decoder_or_export.latent_dim:
+            raise ValueError(f"frames have {frames.shape[2]} latent dimensions, the decoder {decoder_or_export.latent_dim}")
+        if frames.device.type != "cuda":
+            raise ValueError("a VanillaDecoderExport runs the native route only: the frames must be on its GPU")
+        return decoder_or_export, None
     if isinstance(decoder_or_export, DecoderExport):
         if decoder_or_export.desc.norm == 1 and decoder_or_export.desc.bn_train:
             raise ValueError(_BN_ERROR)
@@ -77,6 +98,10 @@ def _route(decoder_or_export, frames: torch.Tensor):
         if frames.shape[2] != decoder.conv_in.in_channels:
             raise ValueError(f"frames have {frames.shape[2]} latent dimensions, the decoder {decoder.conv_in.in_channels}")
         return DecoderExport(decoder, frames.device), None
+    if native_vanilla_relax_covers(decoder) and frames.device.type == "cuda" and not jacobian:
+        if frames.shape[2] != decoder.fc.in_features:
+            raise ValueError(f"frames have {frames.shape[2]} latent dimensions, the decoder {decoder.fc.in_features}")
+        return VanillaDecoderExport(decoder, frames.device), None
     return None, decoder
 
 
@@ -177,15 +202,37 @@ def _torch_relax(decoder, x: torch.Tensor, n_iters: int, step: torch.Tensor):
 
 
 # ------------------------------------------------------------------------------------------------------------ public
-def curve_energy_device(decoder_or_export, frames: torch.Tensor, *, jacobian: bool = False,
-                        max_workspace_bytes=None) -> CurveEnergy:
-    """Evaluate C curves: frames f32 [C, F, d], 2 <= F <= 64.  The tensors live on frames' device.  `jacobian` also returns the
-    float32 Jacobians the sums were taken over; `max_workspace_bytes` caps the native route's workspace (not below
-    geo_curve_min_workspace_bytes) and changes no bit.  Train-mode BatchNorm raises ValueError on both routes."""
-    x = _check_frames(frames)
-    export, decoder = _route(decoder_or_export, x)
+def _vanilla_energy(export, x, trace, max_workspace_bytes) -> CurveEnergy:
+    lib = _lib.load()
     C, F, d = x.shape
     dev = x.device
+    energy = torch.empty(C, dtype=torch.float64, device=dev)
+    seg = torch.empty(C, F - 1, dtype=torch.float64, device=dev)
+    grad = torch.empty(C, F, d, dtype=torch.float64, device=dev)
+    g = torch.empty(C, F, export.n_out, dtype=torch.float32, device=dev)
+    tr = torch.empty(C, F, dtype=torch.float64, device=dev) if trace else None
+    if C:
+        with torch.cuda.device(dev):
+            ws = capped_workspace(lib.geo_vanilla_curve_workspace_bytes(export.desc, C, F), max_workspace_bytes, dev,
+                                  "geo_vanilla_curve_workspace_bytes: decoder")
+            _lib.check(lib.geo_vanilla_curve_energy(export.desc, ptr(x), C, F, ptr(energy), ptr(seg), ptr(grad), ptr(g), ptr(tr),
+                                                    ptr(ws), ws.numel(), stream_ptr()), "geo_vanilla_curve_energy")
+    return CurveEnergy(energy, seg, grad, g, None, "native", tr)
+
+
+def curve_energy_device(decoder_or_export, frames: torch.Tensor, *, jacobian: bool = False, trace: bool = False,
+                        max_workspace_bytes=None) -> CurveEnergy:
+    """Evaluate C curves: frames f32 [C, F, d], 2 <= F <= 64.  The tensors live on frames' device.  `jacobian` also returns the
+    float32 Jacobians the sums were taken over (a covered vanilla module then takes the torch route, a VanillaDecoderExport
+    raises ValueError: that route computes no Jacobian); `trace` asks the native vanilla route for tr J^T J per frame (other
+    routes leave it None); `max_workspace_bytes` caps the native route's workspace (not below geo_curve_min_workspace_bytes /
+    geo_vanilla_curve_min_workspace_bytes) and changes no bit.  Train-mode BatchNorm raises ValueError on both routes."""
+    x = _check_frames(frames)
+    export, decoder = _route(decoder_or_export, x, jacobian)
+    C, F, d = x.shape
+    dev = x.device
+    if isinstance(export, VanillaDecoderExport):
+        return _vanilla_energy(export, x, trace, max_workspace_bytes)
     if export is None:
         dec_dev = next(decoder.parameters()).device
         energy, seg, grad, _, g, jac = _torch_evaluate(decoder, x.to(dec_dev))
@@ -238,7 +285,14 @@ def relax_curves_device(decoder_or_export, frames: torch.Tensor, n_iters: int, *
     energy = torch.empty(C, dtype=torch.float64, device=dev)
     seg = torch.empty(C, F - 1, dtype=torch.float64, device=dev)
     accepted = torch.zeros(C, dtype=torch.int32, device=dev)
-    if C:
+    if C and isinstance(export, VanillaDecoderExport):
+        with torch.cuda.device(dev):
+            ws = capped_workspace(lib.geo_vanilla_curve_workspace_bytes(export.desc, C, F), max_workspace_bytes, dev,
+                                  "geo_vanilla_curve_workspace_bytes: decoder")
+            _lib.check(lib.geo_vanilla_curve_relax(export.desc, ptr(x), C, F, n_iters, ptr(step_t), ptr(energy0), ptr(energy),
+                                                   ptr(seg), ptr(accepted), ptr(ws), ws.numel(), stream_ptr()),
+                       "geo_vanilla_curve_relax")
+    elif C:
         with torch.cuda.device(dev):
             ws = capped_workspace(lib.geo_curve_workspace_bytes(export.desc, C, F), max_workspace_bytes, dev,
                                   "geo_curve_workspace_bytes: decoder")

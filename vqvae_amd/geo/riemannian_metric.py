@@ -98,6 +98,39 @@ def edge_lengths_vanilla_device(export: VanillaDecoderExport, z_start: torch.Ten
     return out
 
 
+def vanilla_vjp_device(export_or_decoder, z: torch.Tensor, u: torch.Tensor, *, index=None, max_workspace_bytes=None) -> torch.Tensor:
+    """out[i] = J(z_i)^T u_i in fp64 for a covered vanilla decoder (vanilla_kernels_cover) or its VanillaDecoderExport, with
+    g = sigmoid(decoder(.)) flattened to [C S S] and J = dg/dz: z f32 [., d] on a GPU, u f32 [n, C S S] (any trailing shape of
+    that many values), `index` None or int32 [n] choosing row i's latent z[index[i]].  Native only (geo_vanilla_vjp): an
+    uncovered decoder raises ValueError.  `max_workspace_bytes` caps the workspace (not below
+    geo_vanilla_vjp_min_workspace_bytes) and changes no bit."""
+    lib = _lib.load()
+    dev = z.device
+    export = export_or_decoder if isinstance(export_or_decoder, VanillaDecoderExport) else VanillaDecoderExport(export_or_decoder, dev)
+    n = int(z.shape[0] if index is None else index.numel())
+    if z.ndim != 2 or z.shape[1] != export.latent_dim:
+        raise ValueError(f"z must be [., {export.latent_dim}], got {tuple(z.shape)}")
+    if u.shape[0] != n or u.numel() != n * export.n_out:
+        raise ValueError(f"u must hold {n} rows of {export.n_out} values, got {tuple(u.shape)}")
+    if index is not None:
+        if index.dtype != torch.int32:
+            raise ValueError("index must be int32")
+        if n and not (0 <= int(index.min()) and int(index.max()) < z.shape[0]):
+            raise ValueError("index out of range")
+        index = index.to(dev).contiguous()
+    z = z.detach().to(torch.float32).contiguous()
+    u = u.detach().to(dev, torch.float32).contiguous()
+    out = torch.empty(n, export.latent_dim, dtype=torch.float64, device=dev)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        ws = capped_workspace(lib.geo_vanilla_vjp_workspace_bytes(export.desc, n), max_workspace_bytes, dev,
+                              "geo_vanilla_vjp_workspace_bytes: decoder")
+        _lib.check(lib.geo_vanilla_vjp(export.desc, ptr(z), ptr(index), n, ptr(u), ptr(out), ptr(ws), ws.numel(), stream_ptr()),
+                   "geo_vanilla_vjp")
+    return out
+
+
 def edge_lengths_vanilla_graph_device(export: VanillaDecoderExport, z: torch.Tensor, src: torch.Tensor, dst: torch.Tensor,
                                       max_workspace_bytes=None) -> torch.Tensor:
     """Vanilla-decoder HIP path on an edge list (int32 src / dst) over resident latents, no gathered copies: with the

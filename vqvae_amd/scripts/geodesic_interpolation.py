@@ -10,6 +10,11 @@ is two images of the training latents; each of their grid positions is one node 
 (geo.interpolation.interpolate_images_spatial).  The decoder runs in eval() mode.  An extension: the reference's demos
 (visualizations/interactive_knn_viz.py, demos/interactive_exploration.py) colour nodes by geodesic distance and stop there.
 
+DIR may also be an output of vqvae_amd.training.build_riemannian_codebook_legacy (the vanilla/geodesic pipeline), recognised
+by knn_graph_riemannian.npz beside a codebook.pt whose z_medoid is 2-D: its "config" is read as the builder read it
+(LegacyJob.from_config, read_latents, read_decoder), an image is one latent and a pair one node pair
+(geo.interpolation.interpolate_images_vanilla), and the artefacts below have h w = 1.
+
 Writes to OUT:
   interpolation.png   two rows of `frames` images per pair: the chord on top, the geodesic below (the grid of codebook_sampling)
   interpolation.npz   pairs i64 [M, 2]; frames_lin, frames_geo f32 [M, F, d, h, w]; images_lin, images_geo f32 [M, F, C, S, S];
@@ -64,15 +69,58 @@ def _ratio(a: float, b: float):
     return a / b if b > 0 else None
 
 
+def is_legacy_build(cb_dir: Path) -> bool:
+    """A directory written by build_riemannian_codebook_legacy: knn_graph_riemannian.npz plus codebook.pt with 2-D z_medoid."""
+    if not ((cb_dir / "knn_graph_riemannian.npz").is_file() and (cb_dir / "codebook.pt").is_file()):
+        return False
+    z_medoid = torch.load(cb_dir / "codebook.pt", map_location="cpu", weights_only=False).get("z_medoid")
+    return torch.is_tensor(z_medoid) and z_medoid.dim() == 2
+
+
+def load_legacy_build(cb_dir: Path, train_latents_path=None):
+    """(job, apply_sigmoid, W scipy CSR, z f32 [N, d], lcc rows) of a legacy build; ValueError when codes.npy, the graph, the
+    latents and z_medoid do not belong together."""
+    from scipy import sparse
+    from ..training.assign_codes_val_geodesic import lcc_rows
+    from ..training.build_riemannian_codebook_legacy import LegacyJob, read_latents
+    codebook = torch.load(cb_dir / "codebook.pt", map_location="cpu", weights_only=False)
+    job = LegacyJob.from_config(codebook["config"])
+    W = sparse.load_npz(cb_dir / "knn_graph_riemannian.npz").tocsr()
+    z = read_latents(Path(train_latents_path) if train_latents_path else job.latents)
+    rows = lcc_rows(np.load(cb_dir / "codes.npy"))
+    med = np.asarray(codebook["medoid_indices"], dtype=np.int64)
+    if z.dim() != 2 or np.load(cb_dir / "codes.npy").size != z.shape[0] or rows.size != W.shape[0] or (
+            med.size and not torch.equal(z[torch.from_numpy(rows[med])], codebook["z_medoid"].float())):
+        raise ValueError(f"{cb_dir}: codes.npy, knn_graph_riemannian.npz, codebook.pt and the latents {tuple(z.shape)} do not "
+                         "belong together")
+    vae = job.vae_config
+    apply_sigmoid = str(vae.get("recon_loss", "mse")).lower() == "bce" or bool(vae.get("mse_use_sigmoid", False))
+    return job, apply_sigmoid, W, z, rows
+
+
 def main(args) -> dict:
     from .._device import DeviceCSR, device
-    from ..geo.interpolation import interpolate_images_spatial
+    from ..geo.interpolation import interpolate_images_spatial, interpolate_images_vanilla
     from ..spatial_decoder import load_decoder_from_checkpoint
     from ..training.assign_codes_val_geodesic import lcc_rows, load_build
-    from .generate_samples import save_image
-    cb_dir, out_dir = Path(args.codebook_dir), Path(args.out_dir)
+    cb_dir = Path(args.codebook_dir)
     if (args.pairs is None) == (args.num_pairs is None):
         raise ValueError("give either --pairs i:j ... or --num_pairs N")
+    if is_legacy_build(cb_dir):
+        from ..training.build_riemannian_codebook_legacy import read_decoder
+        job, apply_sigmoid, W, z, rows = load_legacy_build(cb_dir, args.train_latents_path)
+        pairs = parse_pairs(args.pairs, z.shape[0]) if args.pairs is not None else draw_pairs(z.shape[0], args.num_pairs, args.seed)
+        dev = device()
+        out = interpolate_images_vanilla(z, rows, DeviceCSR.from_scipy(W, dev), read_decoder(job.checkpoint, job.vae_config, dev),
+                                         pairs, args.frames, args.dataset, apply_sigmoid, batch_size=args.batch_size,
+                                         relax_iters=args.relax_iters)
+        # the same artefacts with h w = 1: a position axis of one, frames as 1 x 1 grids
+        for k, v in out.items():
+            if k.startswith("frames_"):
+                out[k] = v.view(*v.shape, 1, 1)
+            elif torch.is_tensor(v) and v.dim() == 1 and not k.startswith(("curve_len_", "image_len_")):
+                out[k] = v.view(-1, 1)
+        return write_artefacts(args, out, pairs, apply_sigmoid)
     codebook, W, _ = load_build(cb_dir, args.train_latents_path)       # checks that the artefacts belong together
     cfg = codebook["config"]
     z = torch.load(args.train_latents_path or cfg["latents_path"], map_location="cpu").float()
@@ -87,7 +135,13 @@ def main(args) -> dict:
     out = interpolate_images_spatial(z, lcc_rows(np.load(cb_dir / "codes.npy")), DeviceCSR.from_scipy(W, dev), decoder,
                                      pairs, args.frames, args.dataset, apply_sigmoid, batch_size=args.batch_size,
                                      relax_iters=args.relax_iters)
+    return write_artefacts(args, out, pairs, apply_sigmoid)
 
+
+def write_artefacts(args, out: dict, pairs: np.ndarray, apply_sigmoid: bool) -> dict:
+    """interpolation.png / .npz / .json of the module docstring from an interpolate_images_* result with a position axis."""
+    from .generate_samples import save_image
+    cb_dir, out_dir = Path(args.codebook_dir), Path(args.out_dir)
     M, F = pairs.shape[0], int(args.frames)
     host = {k: out[k].cpu().numpy() for k in ("frames_lin", "frames_geo", "images_lin", "images_geo", "graph_dist", "hops",
                                                "status", "curve_len_lin", "curve_len_geo", "image_len_lin", "image_len_geo")}

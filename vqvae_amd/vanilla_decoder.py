@@ -75,6 +75,7 @@ def vanilla_kernels_cover(m: nn.Module) -> bool:
 class VanillaDecoderExport:
     """The composed front, the folded second norm and the re-laid-out convolutions of a covered decoder as f32 tensors on
     `dev`, plus the ctypes descriptor over them.  `A` [n1, d] and `c` [n1] are the composed front (n = pixel * c1 + channel).
+    `tensors` are what every entry point reads, `adjoint` the transposed packs that geo_vanilla_vjp reads besides.
     A snapshot: later changes of the module (weights, statistics, mode) are not seen."""
 
     def __init__(self, dec: nn.Module, dev: torch.device):
@@ -101,12 +102,20 @@ class VanillaDecoderExport:
             shift2 = shift2 + scale2 * f64(conv2.bias)
             w2p = pack_k_quads(_parity_taps(f64(conv2.weight)))                      # [4][4][c1 / 4][c2][4]
             w3p = _parity_taps(f64(out.weight)).permute(0, 1, 3, 2)                  # [4][4][C][c2]
+            # the transposed packs of geo_vanilla_vjp: both convolutions by kernel tap 4 ky + kx, At as a K-quad B operand
+            w2t = pack_k_quads(f64(conv2.weight).permute(2, 3, 1, 0).reshape(16, c2, c1))   # [16][c2 / 4][c1][4]
+            w3t = f64(out.weight).permute(2, 3, 1, 0).reshape(16, C, c2)                    # [16][C][c2]
+            Atn = torch.zeros(At.shape[1], (d + 31) // 32 * 32, dtype=torch.float64)
+            Atn[:, :d] = At[:d].t()
+            Atq = pack_k_quads(Atn)                                                          # [n1 / 4][dn][4]
         host = {"At": At, "c": c, "w2p": w2p, "scale2": scale2, "shift2": shift2, "w3p": w3p, "b3": f64(out.bias)}
         self.tensors = {k: f32(v, dev) for k, v in host.items()}
+        self.adjoint = {k: f32(v, dev) for k, v in {"w2t": w2t, "w3t": w3t, "Atq": Atq}.items()}
         self.latent_dim, self.out_size, self.n1 = d, 4 * s1, s1 * s1 * c1
+        self.n_out = C * (4 * s1) ** 2
         desc = _lib.VanillaDecoderDesc()
         desc.latent_dim, desc.c1, desc.c2, desc.out_channels, desc.out_size = d, c1, c2, C, 4 * s1
-        self.desc = fill_desc(desc, self.tensors)
+        self.desc = fill_desc(fill_desc(desc, self.tensors), self.adjoint)
 
     @property
     def A(self) -> torch.Tensor:
