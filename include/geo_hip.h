@@ -997,6 +997,34 @@ int geo_batch_assemble(const uint8_t *u8, int64_t N, int32_t H, int32_t W, int32
                        const int32_t *offset, const uint8_t *flip, int32_t pad, const float *mean, const float *std, float *out,
                        void *stream);
 
+/* ---- Scores of a generated sample set: kNN radii and ball membership (DESIGN.md section "Precision, recall, density,
+ * coverage") ----
+ * THE KEY of a pair of float32 rows x, y of width d is geo_knn_query's form 0 chain:
+ *   acc = 0;  for c = 0 .. d-1 in this order:  t = (double)x[c] - (double)y[c];  acc = fma(t, t, acc).
+ * It is symmetric in x and y, and no tile, slice, corpus range, workspace size or stream enters it: one sequential chain per
+ * pair, kept in a register across the dimension chunks.
+ *
+ * geo_kth_radius: a f32 [n][d] -> r2_out f64 [n]: r2_out[i] = the k-th smallest key between row i and the OTHER rows (self is
+ * left out by index: a duplicate of row i is a neighbour at key 0).  An order statistic of a multiset: no tie rule.
+ * geo_ball_count: corpus z f32 [n][d] with radii r2 f64 [n], queries q f32 [m][d] -> any of (each may be NULL)
+ *   count_out i32 [m]:  #{ i : key(q_j, z_i) <= r2[i] }  (equality counts),
+ *   near_key_out f64 [m]:  min_i key(q_j, z_i),   near_idx_out i32 [m]:  the lowest i attaining it.
+ * Limits: 1 <= d <= 1024, 1 <= n < 2^31, 0 <= m < 2^31, 1 <= k <= GEO_PRDC_MAX_K and k <= n - 1; GEO_E_ARG outside and for a
+ * null z / a / q / r2 / r2_out / ws, GEO_E_WORKSPACE below geo_prdc_min_workspace_bytes(d); both before any launch, nothing is
+ * written.  m == 0 (arguments in range) returns GEO_OK without a launch, whatever ws_bytes is.  Asynchronous, no atomics:
+ * the corpus is cut into S contiguous ranges per
+ * tile of 64 query rows, every range writes its partial (count, nearest pair, k smallest keys) to the workspace and a second
+ * kernel folds the ranges in ascending order.
+ * Workspace: geo_prdc_workspace_bytes(n, m, d) = all m query rows against n corpus rows in one slice (geo_kth_radius: m = n);
+ * geo_prdc_min_workspace_bytes(d) = one tile of 64 query rows, one range.  Anything in between means more slices of query rows
+ * or fewer ranges, never another result.  Both queries answer 0 outside the limits. */
+#define GEO_PRDC_MAX_K 64
+size_t geo_prdc_workspace_bytes(int64_t n, int64_t m, int32_t d);
+size_t geo_prdc_min_workspace_bytes(int32_t d);
+int geo_kth_radius(const float *a, int64_t n, int32_t d, int32_t k, double *r2_out, void *ws, size_t ws_bytes, void *stream);
+int geo_ball_count(const float *z, const double *r2, int64_t n, const float *q, int64_t m, int32_t d, int32_t *count_out,
+                   double *near_key_out, int32_t *near_idx_out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,10 @@ _SIGNATURES = {
     "geo_vae_elbo_backward": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, i64, i32, i32, ctypes.c_double,
                                              ctypes.c_double, ctypes.c_double, i32, c_p, c_p, c_p, c_p]),
     "geo_batch_assemble": (ctypes.c_int, [c_p, i64, i32, i32, i32, c_p, i32, c_p, c_p, i32, c_p, c_p, c_p, c_p]),
+    "geo_prdc_workspace_bytes": (sz, [i64, i64, i32]),
+    "geo_prdc_min_workspace_bytes": (sz, [i32]),
+    "geo_kth_radius": (ctypes.c_int, [c_p, i64, i32, i32, c_p, c_p, sz, c_p]),
+    "geo_ball_count": (ctypes.c_int, [c_p, c_p, i64, c_p, i64, i32, c_p, c_p, c_p, c_p, sz, c_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -33,6 +33,7 @@ const OptionName kOptionNames[] = {
     {"jvp_front_once", "GEO_JVP_FRONT_ONCE", &Options::jvp_front_once},
     {"jvp_head_stream", "GEO_JVP_HEAD_STREAM", &Options::jvp_head_stream},
     {"curve_repack", "GEO_CURVE_REPACK", &Options::curve_repack},
+    {"prdc_split", "GEO_PRDC_SPLIT", &Options::prdc_split},
 };
 Options from_environment() {
     Options o;

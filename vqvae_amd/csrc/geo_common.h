@@ -42,7 +42,8 @@ struct Options {
         jvp_start_dedup = 1 /* train-mode BatchNorm, graph edges: each chunk's start-side primal ConvT2 / ConvT3 rows once per run of equal src (0: once per slot) */,
         jvp_front_once = 1 /* on that route with the vector first layer: the tangent row once per edge, the start-side primal row once per run (0: every row of both sides) */,
         jvp_head_stream = 1 /* 16-output ConvT3 head without GroupNorm: head_stream_kernel, the next K block's rows in flight while one is converted and multiplied (0: back_mfma_kernel; same bits) */,
-        curve_repack = 0 /* geo_curve_relax: 1 = pack the decoder's weights before every evaluation, as a run_jvp call per iteration would, instead of once per slice (a measurement switch; same bits) */;
+        curve_repack = 0 /* geo_curve_relax: 1 = pack the decoder's weights before every evaluation, as a run_jvp call per iteration would, instead of once per slice (a measurement switch; same bits) */,
+        prdc_split = -1 /* geo_kth_radius / geo_ball_count: corpus ranges per query tile; -1 = enough to fill the chip, S >= 1 = S (cut to the corpus tiles, 32 and the workspace; same bits) */;
 };
 Options &options();
 
