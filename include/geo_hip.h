@@ -669,6 +669,12 @@ typedef struct geo_spatial_image_decoder_desc {
     const float *shift2;       /* [c2] */
     const float *w3p;          /* [parity][tap][C][c2] */
     const float *b3;           /* [C] */
+    /* the transposed packs of geo_spatial_vjp and the grid curves alone; geo_spatial_decode ignores them and accepts them null */
+    const float *w1t;          /* the composed first stage as [tap 4 ky + kx][c1 / 4][dn][4], dn = d rounded up to a multiple of 32:
+                                  element (tap, q, k, r) = scale1[4 q + r] * sum_c0 w_in[c0][k] w1[c0][4 q + r][ky][kx] for k < d
+                                  (in fp64, rounded once), 0 above; the bias channel has no gradient */
+    const float *w2t;          /* as in geo_vanilla_decoder_desc */
+    const float *w3t;          /* as in geo_vanilla_decoder_desc */
 } geo_spatial_image_decoder_desc;
 
 size_t geo_spatial_decode_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int64_t n);
@@ -676,6 +682,42 @@ size_t geo_spatial_decode_workspace_bytes(const geo_spatial_image_decoder_desc *
  * latter, position p of image i is table[codes[i][p]] -- how build_codebook's codes quantize a grid. */
 int geo_spatial_decode(const geo_spatial_image_decoder_desc *dec, const float *z, const float *table, const int32_t *codes,
                        int64_t n, float *logits_out, void *ws, size_t ws_bytes, void *stream);
+
+/* Vector-Jacobian product of the same decoder on whole grids: with g(z) = sigmoid(decoder(z)) of a 4 x 4
+ * grid z, flattened to nout = C S S values ([C][S][S], S = out_size; at 28 px rows and columns 2 .. 29 of the 32-px output) and
+ * J = dg/dz over the grid's 16 d coordinates,  out[i] = J(z_i)^T u_i,  z_i = z[index ? index[i] : i].
+ * z f32 [.][d][4][4], index NULL or i32 [n], u f32 [n][nout], out f64 [n][d][4][4]; the descriptor's w1t, w2t and w3t are required.
+ * The masks and sigmoid' come from a point pass of geo_spatial_decode's chains; the second and third layer are walked backwards by
+ * geo_vanilla_vjp's kernels, the first by a K-quad chain over the c1 channels of each 8 x 8 pixel (2 y - 1 + ky, 2 x - 1 + kx)
+ * inside the image, the pixels of a grid position added in fp64 in ascending (ky, kx) order.  No atomics, every value a
+ * fixed-order chain of its own item: a row's bits do not depend on n, its position, index, the pass size, the stream or earlier
+ * workspace contents; u_i = 0 gives exactly 0.  Any workspace from geo_spatial_vjp_min_workspace_bytes(dec) upwards is legal (a
+ * smaller one: GEO_E_WORKSPACE).  The queries answer 0 for a descriptor outside geo_spatial_decode's coverage and the call rejects
+ * it (GEO_E_ARG) before any launch.  n == 0 returns GEO_OK without a launch; n < 2^31.  Asynchronous on `stream`. */
+size_t geo_spatial_vjp_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int64_t n);
+size_t geo_spatial_vjp_min_workspace_bytes(const geo_spatial_image_decoder_desc *dec);
+int geo_spatial_vjp(const geo_spatial_image_decoder_desc *dec, const float *z, const int32_t *index, int64_t n, const float *u,
+                    double *out, void *ws, size_t ws_bytes, void *stream);
+
+/* Curve energy and relaxation of image curves under the whole spatial decoder: the definitions, the loop
+ * and the rules of geo_vanilla_curve_energy / geo_vanilla_curve_relax above with a frame = one grid, d := 16 d coordinates in NCHW
+ * order, g and J as for geo_spatial_vjp.  x f32 [C][F][d][4][4], 2 <= F <= 64; energy f64 [C]; seg_sq f64 [C][F-1],
+ * grad f64 [C][F][d][4][4], g_out f32 [C][F][nout], probe_out f64 [C][F] may each be null.  One rule differs, the first step: in
+ * place of the trace,
+ *   probe[f] = sum over the 16 d coordinates k, ascending, in fp64, of (J(x[f])^T s)[k]^2,
+ *   s[c][y][x] = +1 where c + y + x is even, else -1 (indices of the S x S output),
+ * a one-sample estimate of tr J J^T (not a bound), and a step_inout < 0 becomes 1 / (8 max over interior f of probe[f]), 0 where
+ * that maximum is 0 (a NaN is ignored).  The probe (one more VJP per frame) is computed only where asked for: by probe_out, or in
+ * geo_spatial_curve_relax for a slice that holds a curve with step_inout < 0.  Slices, the workspace rule, the host read of
+ * step_inout, "n iterations in one call are the bits of n calls of one" and the refusals are geo_vanilla_curve_relax's. */
+size_t geo_spatial_curve_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int64_t C, int32_t F);
+size_t geo_spatial_curve_min_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int32_t F);
+int geo_spatial_curve_energy(const geo_spatial_image_decoder_desc *dec, const float *x, int64_t C, int32_t F, double *energy_out,
+                             double *seg_sq_out, double *grad_out, float *g_out, double *probe_out, void *ws, size_t ws_bytes,
+                             void *stream);
+int geo_spatial_curve_relax(const geo_spatial_image_decoder_desc *dec, float *x_inout, int64_t C, int32_t F, int32_t n_iters,
+                            double *step_inout, double *energy0_out, double *energy_out, double *seg_sq_out, int32_t *accepted_out,
+                            void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Image encode: images -> (mu, logvar) of the encoder of either VAE with FIXED statistics

@@ -32,7 +32,8 @@ class VanillaDecoderDesc(ctypes.Structure):
 class SpatialImageDecoderDesc(ctypes.Structure):
     """geo_spatial_image_decoder_desc of include/geo_hip.h."""
     _fields_ = ([(n, i32) for n in ("latent_dim", "c1", "c2", "out_channels", "out_size")]
-                + [(n, c_p) for n in ("w1p", "scale1", "shift1", "w2p", "scale2", "shift2", "w3p", "b3")])
+                + [(n, c_p) for n in ("w1p", "scale1", "shift1", "w2p", "scale2", "shift2", "w3p", "b3", "w1t", "w2t",
+                                         "w3t")])
 
 
 class ImageEncoderDesc(ctypes.Structure):
@@ -139,6 +140,15 @@ _SIGNATURES = {
     "geo_vanilla_decode": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, c_p, c_p, sz, c_p]),
     "geo_spatial_decode_workspace_bytes": (sz, [ctypes.POINTER(SpatialImageDecoderDesc), i64]),
     "geo_spatial_decode": (ctypes.c_int, [ctypes.POINTER(SpatialImageDecoderDesc), c_p, c_p, c_p, i64, c_p, c_p, sz, c_p]),
+    "geo_spatial_vjp_workspace_bytes": (sz, [ctypes.POINTER(SpatialImageDecoderDesc), i64]),
+    "geo_spatial_vjp_min_workspace_bytes": (sz, [ctypes.POINTER(SpatialImageDecoderDesc)]),
+    "geo_spatial_vjp": (ctypes.c_int, [ctypes.POINTER(SpatialImageDecoderDesc), c_p, c_p, i64, c_p, c_p, c_p, sz, c_p]),
+    "geo_spatial_curve_workspace_bytes": (sz, [ctypes.POINTER(SpatialImageDecoderDesc), i64, i32]),
+    "geo_spatial_curve_min_workspace_bytes": (sz, [ctypes.POINTER(SpatialImageDecoderDesc), i32]),
+    "geo_spatial_curve_energy": (ctypes.c_int, [ctypes.POINTER(SpatialImageDecoderDesc), c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, sz,
+                                                c_p]),
+    "geo_spatial_curve_relax": (ctypes.c_int, [ctypes.POINTER(SpatialImageDecoderDesc), c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, sz,
+                                               c_p]),
     "geo_image_encode_workspace_bytes": (sz, [ctypes.POINTER(ImageEncoderDesc), i64]),
     "geo_image_encode": (ctypes.c_int, [ctypes.POINTER(ImageEncoderDesc), c_p, i64, c_p, c_p, c_p, sz, c_p]),
     "geo_lpips_alex_workspace_bytes": (sz, [i64]),

@@ -19,6 +19,9 @@
 // front and mid without the masks and writes the logits instead of sigmoid'.
 // The vector-Jacobian product (geo_vanilla_vjp) and the curve energy and relaxation built on it (geo_vanilla_curve_energy,
 // geo_vanilla_curve_relax) run the point pass as it is and then the three layers backwards.
+// The same for whole 4 x 4 grids under the spatial decoder (geo_spatial_vjp, geo_spatial_curve_energy, geo_spatial_curve_relax;
+// DESIGN.md section 29): the image decode's first stage with the mask bits, the two shared layers at s1 = 8, and a first-stage
+// adjoint of its own.
 //
 // ConvT2 (k4, s2, p1) is four implicit GEMMs, one per output-pixel parity: out[(2y+py, 2x+px)][co] = sum over the taps
 // (a, b) in {0,1}^2 and ci of in[(y+py-a, x+px-b)][ci] w2[ci][co][2a+1-py][2b+1-px]; M = (item, pixel) rows, K = 4 c1, N = c2, on
@@ -266,12 +269,13 @@ __global__ __launch_bounds__(512) void vj_mid_kernel(const float *__restrict__ i
 // ([pixel][c2]) in LDS.  Point pass: sigmoid' = e / (1 + e)^2, e = exp(-|logit|), to the slot.  Edge pass: both ends of one
 // edge in turn; squares summed per thread in position order, then a fixed tree over the wave and the four waves in order.
 // SQ (edge pass): len_out [2 E] takes each end's sum of squares instead of the edge's length.  G_OUT (point pass): g_out takes
-// the sigmoid itself beside sigmoid', from the same e: 1 / (1 + e) for a logit >= 0, else e / (1 + e).
+// the sigmoid itself beside sigmoid', from the same e: 1 / (1 + e) for a logit >= 0, else e / (1 + e); g_out [slot][C][So][So] is the
+// window of rows and columns crop .. S - crop - 1 (crop = 2: the spatial decoder at 28 px), sigmoid' always the whole S x S.
 template <int C2, int CO, bool TANGENT, bool SQ = false, bool G_OUT = false>
 __global__ __launch_bounds__(256) void vj_back_kernel(const float *__restrict__ in, float *__restrict__ sigp, Ends s,
                                                       int resident, int64_t slot0, int s2, const float *__restrict__ w3p,
                                                       const float *__restrict__ b3, float *__restrict__ len_out,
-                                                      float *__restrict__ g_out) {
+                                                      float *__restrict__ g_out, int crop) {
     constexpr int LD = C2 + 4;
     __shared__ __attribute__((aligned(16))) float lds[(MID_ROWS + 1) * LD];
     __shared__ float wsum[4];
@@ -321,7 +325,11 @@ __global__ __launch_bounds__(256) void vj_back_kernel(const float *__restrict__ 
                     } else {
                         const float e = expf(-fabsf(acc[c]));
                         sg[o] = e / ((1.f + e) * (1.f + e));
-                        if (G_OUT) g_out[(size_t)slot * nout + o] = acc[c] >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+                        if (G_OUT) {
+                            const int So = S - 2 * crop, oy = 2 * y + py - crop, ox = 2 * x + px - crop;
+                            if (oy >= 0 && oy < So && ox >= 0 && ox < So)
+                                g_out[((size_t)(slot * CO + c) * So + oy) * So + ox] = acc[c] >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+                        }
                     }
                 }
             }
@@ -357,11 +365,11 @@ int run_mid(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *in
 
 template <bool TANGENT, bool SQ = false, bool G_OUT = false>
 int run_back(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *in, float *sigp, const Ends &e, int resident,
-             int64_t slot0, int64_t blocks, float *len_out, hipStream_t st, float *g_out = nullptr) {
+             int64_t slot0, int64_t blocks, float *len_out, hipStream_t st, float *g_out = nullptr, int crop = 0) {
     const unsigned grid = (unsigned)blocks;
 #define VJ_BACK(C2_, CO_)                                                                                                     \
     vj_back_kernel<C2_, CO_, TANGENT, SQ, G_OUT><<<grid, 256, 0, st>>>(in, sigp, e, resident, slot0, sh.s2, dc->w3p, dc->b3,     \
-                                                                        len_out, g_out)
+                                                                        len_out, g_out, crop)
     if (sh.c2 == 64 && sh.co == 1) VJ_BACK(64, 1);
     else if (sh.c2 == 64) VJ_BACK(64, 3);
     else if (sh.co == 1) VJ_BACK(32, 1);
@@ -499,11 +507,15 @@ __global__ __launch_bounds__(256) void vj_image_kernel(const float *__restrict__
 // constant channel is 0 too, so the border sees the bias through exactly the taps it has.  Channels d+1 .. dp-1 are zero.
 // A row is a latent grid's position (z, NCHW) or a table row (table[codes[item][pixel]]): the same staged values, hence
 // the same logits.  w1p: [parity][tap][dp / 4][c1][4]; out [item][8 x 8 pixel][c1] = relu(scale1 * acc + shift1).
-template <int C1>
+// MASKS (the point pass of the grid VJP, section 29): the sign bits of pre1 go to mask1 [item][8 x 8 pixel][c1 / 32] as well, and
+// item i of a z pass is grid (index ? index[base + i] : base + i).  The image decode runs MASKS = false, index null.
+template <int C1, bool MASKS = false>
 __global__ __launch_bounds__(512) void sd_front_kernel(const float *__restrict__ z, const float *__restrict__ table,
                                                        const int32_t *__restrict__ codes, int64_t base, int64_t n_items, int d,
                                                        int dp, const float *__restrict__ w1p, const float *__restrict__ sc1,
-                                                       const float *__restrict__ sh1, float *__restrict__ out) {
+                                                       const float *__restrict__ sh1, float *__restrict__ out,
+                                                       const int32_t *__restrict__ index = nullptr,
+                                                       uint32_t *__restrict__ mask1 = nullptr) {
     constexpr int TN = C1 / 32, WPN = 8 / TN, MT = TN, P = 16, ZR = MID_ROWS;
     __shared__ __attribute__((aligned(16))) float lds[(MID_ROWS + 1) * (SD_MAX_DP + 4)];
     const int LD = dp + 4;
@@ -515,10 +527,10 @@ __global__ __launch_bounds__(512) void sd_front_kernel(const float *__restrict__
         if (k >= d || r >= live * P) lds[q] = (k == d && r < live * P) ? 1.f : 0.f;
     }
     if (z) {
-        const float *src = z + (size_t)(base + item0) * d * P;          // [item][d][pixel], contiguous over the workgroup
-        for (int q = tid; q < live * d * P; q += 512) {
-            const int g = q / (d * P), k = (q - g * d * P) / P, pix = q % P;
-            lds[(size_t)(g * P + pix) * LD + k] = src[q];
+        for (int q = tid; q < live * d * P; q += 512) {                 // [item][d][pixel]
+            const int g = q / (d * P), e = q - g * d * P, k = e / P, pix = e % P;
+            const int64_t row = MASKS && index ? (int64_t)index[base + item0 + g] : base + item0 + g;
+            lds[(size_t)(g * P + pix) * LD + k] = z[(size_t)row * d * P + e];
         }
     } else {
         for (int q = tid; q < live * P * d; q += 512) {
@@ -556,11 +568,14 @@ __global__ __launch_bounds__(512) void sd_front_kernel(const float *__restrict__
             for (int q = 0; q < 16; ++q) {
                 const int r = mfma_conv::acc_row(q, h, (m0 + m * WPN) * 32);
                 const int g = r >> 4, y = (r >> 2) & 3, x = r & 3;
-                if (g < live) {
-                    const int opix = (2 * y + py) * 8 + 2 * x + px;
-                    const float x1 = fmaf(scale, acc[m][q], shift);
-                    out[(size_t)(item0 + g) * (64 * C1) + (size_t)opix * C1 + co] = x1 > 0.f ? x1 : 0.f;
+                const int opix = (2 * y + py) * 8 + 2 * x + px;
+                const float x1 = fmaf(scale, acc[m][q], shift);
+                if (MASKS) {
+                    const unsigned long long bits = __ballot(x1 > 0.f);    // low half: the h = 0 row, high half: the h = 1 row
+                    if (g < live && j == 0)
+                        mask1[(size_t)(item0 + g) * (2 * C1) + (size_t)opix * TN + nt] = (uint32_t)(h ? bits >> 32 : bits);
                 }
+                if (g < live) out[(size_t)(item0 + g) * (64 * C1) + (size_t)opix * C1 + co] = x1 > 0.f ? x1 : 0.f;
             }
         }
     }
@@ -638,22 +653,25 @@ VjpWorkspace lay_out_vjp(geo::Arena &ar, const Shape &s, int64_t pb) {
 size_t vjp_layout_bytes(const Shape &s, int64_t pb) { return geo::measure(lay_out_vjp, s, pb); }
 
 // w3t: [tap 4 ky + kx][C][c2].  A thread owns one channel ci of c2 and keeps its 16 C weights in registers; u3 sits in LDS
-// with a border of one zero pixel, so no tap tests a bound.  One item per workgroup.
+// with a border of one zero pixel, so no tap tests a bound.  One item per workgroup.  u [.][C][So][So], So = S - 2 crop, is the
+// window of rows and columns crop .. S - crop - 1 of the output (zero outside it); row i of the pass is u + (row0 + i) u_stride
+// (u_stride = 0: one row for every item).
 template <int C2, int CO>
 __global__ __launch_bounds__(256) void vv_back_kernel(const float *__restrict__ u, const float *__restrict__ sigp,
                                                       const uint32_t *__restrict__ mask2, float *__restrict__ out, int64_t row0,
-                                                      int s2, const float *__restrict__ w3t, const float *__restrict__ sc2) {
+                                                      int s2, const float *__restrict__ w3t, const float *__restrict__ sc2,
+                                                      int crop, int64_t u_stride) {
     constexpr int NPG = 256 / C2, TN = C2 / 32;
     __shared__ float us[CO * 34 * 34];
     const int S = 2 * s2, SP = S + 2, P2 = s2 * s2, n2 = P2 * C2, nout = CO * S * S;
     const int tid = threadIdx.x;
     const int64_t it = blockIdx.x;
-    const float *ui = u + (size_t)(row0 + it) * nout, *sg = sigp + (size_t)it * nout;
+    const int So = S - 2 * crop;
+    const float *ui = u + (size_t)(row0 + it) * u_stride, *sg = sigp + (size_t)it * nout;
     for (int q = tid; q < CO * SP * SP; q += 256) {
         const int c = q / (SP * SP), rem = q - c * SP * SP, py = rem / SP, px = rem - py * SP;
-        const bool in = py >= 1 && py <= S && px >= 1 && px <= S;
-        const int o = (c * S + py - 1) * S + px - 1;
-        us[q] = in ? sg[o] * ui[o] : 0.f;
+        const bool in = py >= 1 + crop && py <= S - crop && px >= 1 + crop && px <= S - crop;
+        us[q] = in ? sg[(c * S + py - 1) * S + px - 1] * ui[(c * So + py - 1 - crop) * So + px - 1 - crop] : 0.f;
     }
     const int ci = tid % C2, pg = tid / C2;
     float w[16 * CO];
@@ -791,7 +809,8 @@ __global__ __launch_bounds__(256) void vv_sum_kernel(const double *__restrict__ 
 int run_vjp_tail(const geo_vanilla_decoder_desc *dc, const Shape &sh, const VjpWorkspace &w, const float *u, int64_t row0,
                  int64_t cnt, double *out, hipStream_t st, int F = 0) {
 #define VV_BACK(C2_, CO_)                                                                                                     \
-    vv_back_kernel<C2_, CO_><<<(unsigned)cnt, 256, 0, st>>>(u, w.pt.sigp, w.pt.mask2, w.pt.buf2, row0, sh.s2, dc->w3t, dc->scale2)
+    vv_back_kernel<C2_, CO_><<<(unsigned)cnt, 256, 0, st>>>(u, w.pt.sigp, w.pt.mask2, w.pt.buf2, row0, sh.s2, dc->w3t, dc->scale2, \
+                                                            0, (int64_t)sh.nout)
     if (sh.c2 == 64 && sh.co == 1) VV_BACK(64, 1);
     else if (sh.c2 == 64) VV_BACK(64, 3);
     else if (sh.co == 1) VV_BACK(32, 1);
@@ -968,12 +987,14 @@ int curve_check(const char *who, const geo_vanilla_decoder_desc *dc, Shape *sh, 
     return GEO_OK;
 }
 
-// the curves per slice a workspace holds: everything (up to the cap) when it fits, else the largest count that does
-int curve_slice_length(const char *who, const Shape &sh, int64_t C, int F, size_t ws_bytes, int64_t *slice) {
+// the curves per slice a workspace holds: everything (up to the cap) when it fits, else the largest count that does;
+// bytes(n_curves) measures a slice's layout
+template <typename Bytes>
+int curve_slice_length(const char *who, Bytes bytes, int64_t C, int F, size_t ws_bytes, int64_t *slice) {
     const int64_t cap = curve_slice_cap(C, F);
     *slice = cap;
-    if (ws_bytes >= curve_slice_bytes(sh, cap, F)) return GEO_OK;
-    const size_t min_bytes = curve_slice_bytes(sh, 1, F);
+    if (ws_bytes >= bytes(cap)) return GEO_OK;
+    const size_t min_bytes = bytes(1);
     if (ws_bytes < min_bytes) {
         geo::set_error("%s: workspace of %zu bytes is below the minimum of %zu", who, ws_bytes, min_bytes);
         return GEO_E_WORKSPACE;
@@ -981,7 +1002,7 @@ int curve_slice_length(const char *who, const Shape &sh, int64_t C, int F, size_
     int64_t lo = 1, hi = cap;
     while (lo < hi) {
         const int64_t mid = (lo + hi + 1) / 2;
-        if (curve_slice_bytes(sh, mid, F) <= ws_bytes) lo = mid; else hi = mid - 1;
+        if (bytes(mid) <= ws_bytes) lo = mid; else hi = mid - 1;
     }
     *slice = lo;
     return GEO_OK;
@@ -995,7 +1016,7 @@ int curve_energy(const geo_vanilla_decoder_desc *dc, const float *x, int64_t C, 
     if (C == 0) return GEO_OK;
     GEO_REQUIRE(x && energy_out && ws, "%s: null pointer", who);
     int64_t slice = 0;
-    if (const int rc = curve_slice_length(who, sh, C, F, ws_bytes, &slice)) return rc;
+    if (const int rc = curve_slice_length(who, [&](int64_t nc) { return curve_slice_bytes(sh, nc, F); }, C, F, ws_bytes, &slice)) return rc;
     for (int64_t base = 0; base < C; base += slice) {
         const int64_t nc = C - base < slice ? C - base : slice;
         geo::Arena ar(ws, ws_bytes);
@@ -1020,7 +1041,7 @@ int curve_relax(const geo_vanilla_decoder_desc *dc, float *x, int64_t C, int F, 
     if (C == 0) return GEO_OK;
     GEO_REQUIRE(x && step && energy_out && accepted_out && ws, "%s: null pointer", who);
     int64_t slice = 0;
-    if (const int rc = curve_slice_length(who, sh, C, F, ws_bytes, &slice)) return rc;
+    if (const int rc = curve_slice_length(who, [&](int64_t nc) { return curve_slice_bytes(sh, nc, F); }, C, F, ws_bytes, &slice)) return rc;
     // the trace costs d tangents per frame: only for a slice with a curve whose step the caller left to the call (one copy of the
     // steps to the host, before the first launch; nothing is read back per iteration)
     std::vector<double> step_h((size_t)C);
@@ -1050,7 +1071,351 @@ int curve_relax(const geo_vanilla_decoder_desc *dc, float *x, int64_t C, int F, 
     return GEO_OK;
 }
 
+// ================================ the spatial decoder on whole grids: VJP and curves ================================
+// geo_spatial_vjp, geo_spatial_curve_energy, geo_spatial_curve_relax: section 27 for the decoder of geo_spatial_decode.  A point is a
+// 4 x 4 grid of d-vectors (16 d coordinates, NCHW), its image the whole S x S output.  From the 8 x 8 stage on this is the 32-px
+// vanilla geometry, so the point pass and the walk backwards are the kernels above at s1 = 8; the first stage is its own:
+//   sd_front_kernel<.., true>      conv_in . ConvT1 -> mask1 bits, relu(pre1) [8 x 8][c1]
+//   vj_mid_kernel, vj_back_kernel  as in the vanilla point pass; at 28 px g is the window 2 .. 29 of the 32-px output
+//   vv_back_kernel (crop)          u lives on the window and is zero outside it
+//   vv_mid_kernel                  as it is
+//   sv_final_kernel                out[i][k][y][x] = sum over (ky, kx) of the K-quad chain over c1 of u1[(2y-1+ky, 2x-1+kx)][co] w1t
+// Fixed orders beyond section 27's: a pixel's c1 channels are one f32 K-quad chain from 0; the up to 16 pixels of a grid position
+// are added in fp64 in ascending (ky, kx) order (a pixel outside the 8 x 8 image adds 0).  No atomics; every value belongs to one
+// item.  The first step of a relaxation is the sign probe below instead of the trace.
+constexpr int SV_ITEMS = 4;                      // grids of one sv_final workgroup: two M tiles of 32 (grid, position) rows
+
+struct GridShape {
+    SpatialShape sp;
+    Shape sh;                                    // the tail at s1 = 8: n1 = 64 c1, n2 = 256 c2, nout = C 32 32 (sigmoid' is kept whole)
+    geo_vanilla_decoder_desc tail;               // what run_mid / run_back read: the second and third layer's packs
+    int dn, dz, nout;                            // d rounded up to 32; 16 d; C So So
+};
+
+bool make_grid_shape(const geo_spatial_image_decoder_desc *dc, GridShape *g) {
+    if (!make_spatial_shape(dc, &g->sp)) return false;
+    g->tail = geo_vanilla_decoder_desc{dc->latent_dim, dc->c1, dc->c2, dc->out_channels, 32, nullptr, nullptr, dc->w2p, dc->scale2,
+                                       dc->shift2, dc->w3p, dc->b3, dc->w2t, dc->w3t, nullptr};
+    if (!make_shape(&g->tail, &g->sh)) return false;
+    g->dn = (g->sp.d + 31) & ~31;
+    g->dz = 16 * g->sp.d;
+    g->nout = g->sp.co * g->sp.So * g->sp.So;
+    return true;
+}
+
+int check_grid_desc(const geo_spatial_image_decoder_desc *dc, GridShape *g, const char *who) {
+    GEO_REQUIRE(make_grid_shape(dc, g), "%s: decoder configuration not covered (see geo_hip.h)", who);
+    GEO_REQUIRE(dc->w1p && dc->scale1 && dc->shift1 && dc->w2p && dc->scale2 && dc->shift2 && dc->w3p && dc->b3,
+                "%s: null pointer in the descriptor", who);
+    GEO_REQUIRE(dc->w1t && dc->w2t && dc->w3t, "%s: null transposed pack in the descriptor", who);
+    return GEO_OK;
+}
+
+// per item of a pass: the two masks, sigmoid' (32 x 32) and the two activation buffers
+Workspace lay_out_grid(geo::Arena &ar, const GridShape &g, int64_t pb) {
+    Workspace w;
+    ar.take(w.mask1, (size_t)pb * (g.sh.n1 / 32)); ar.take(w.mask2, (size_t)pb * (g.sh.n2 / 32));
+    ar.take(w.sigp, (size_t)pb * g.sh.nout);
+    ar.take(w.buf1, (size_t)pb * g.sh.n1); ar.take(w.buf2, (size_t)pb * g.sh.n2);
+    return w;
+}
+size_t grid_layout_bytes(const GridShape &g, int64_t pb) { return geo::measure(lay_out_grid, g, pb); }
+
+// w1t: [tap 4 ky + kx][c1 / 4][dn][4], element (tap, q, k, r) = scale1[4 q + r] W[ky][kx][k][4 q + r] (conv_in composed into ConvT1,
+// the first norm's scale folded in), 0 for k >= d.  M = (grid, position) rows, N = dn, K = c1 per pixel.  A workgroup stages the u1
+// ([8 x 8 pixel][c1]) of SV_ITEMS grids in mfma_conv.h's layout; wave = (M tile, N tile), a wave past dn / 32 N tiles only stages.
+// F = 0: out = the sum.  F >= 2 (the grids are curves of F frames): twice the sum at an interior frame, 0 at the ends.
+template <int C1>
+__global__ __launch_bounds__(256) void sv_final_kernel(const float *__restrict__ u1, int64_t cnt, int d, int dn,
+                                                       const float *__restrict__ w1t, int F, double *__restrict__ out) {
+    constexpr int LD = C1 + 4, ZR = SV_ITEMS * 64;
+    __shared__ __attribute__((aligned(16))) float lds[(SV_ITEMS * 64 + 1) * LD];
+    const int tid = threadIdx.x;
+    const int64_t item0 = (int64_t)blockIdx.x * SV_ITEMS;
+    for (int g = 0; g < SV_ITEMS; ++g)
+        if (item0 + g < cnt) mfma_conv::stage_rows<C1, 256>(lds + (size_t)g * 64 * LD, u1 + (size_t)(item0 + g) * 64 * C1, 64, tid);
+    mfma_conv::fill_zero_row<256>(lds, ZR, LD, tid);
+    __syncthreads();
+
+    const int lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int mt = wave & 1, nt = wave >> 1;
+    if (nt * 32 >= dn) return;
+    const int r = mt * 32 + j, g = r >> 4, y = (r >> 2) & 3, x = r & 3;
+    const bool rv = item0 + g < cnt;
+    const int col = nt * 32 + j;
+    double sum[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sum[q] = 0.0;
+    for (int tap = 0; tap < 16; ++tap) {
+        const int ky = tap >> 2, kx = tap & 3;
+        const float *ap[1] = {mfma_conv::tap_row(lds, LD, ZR, rv, g, 2 * y - 1 + ky, 2 * x - 1 + kx, 8, 64, h)};
+        mfma_conv::f32x16 acc[1];
+        mfma_conv::clear(acc);
+        const float4 *wp = reinterpret_cast<const float4 *>(w1t) + ((size_t)tap * (C1 / 4) + h) * dn + col;
+        mfma_conv::k_chain<1, 4>(acc, ap, wp, C1 / 8, dn);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) sum[q] += (double)acc[0][q];
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int ro = mfma_conv::acc_row(q, h, mt * 32);
+        const int64_t it = item0 + (ro >> 4);
+        if (it < cnt && col < d) {
+            double s = sum[q];
+            if (F) {
+                const int f = (int)(it % F);
+                s = f > 0 && f < F - 1 ? 2.0 * s : 0.0;
+            }
+            out[((size_t)it * d + col) * 16 + (ro & 15)] = s;
+        }
+    }
+}
+
+// The point pass over grids base .. base + cnt of z (through index, if given): masks and sigmoid' to slots 0 .. cnt - 1; g_out (may
+// be null): the sigmoids [slot][nout].
+int run_grid_point_pass(const geo_spatial_image_decoder_desc *dc, const GridShape &gs, const Workspace &w, const float *z,
+                        const int32_t *index, int64_t base, int64_t cnt, hipStream_t st, float *g_out) {
+    const unsigned grid = (unsigned)((cnt + SD_ITEMS - 1) / SD_ITEMS);
+    if (gs.sp.c1 == 128)
+        sd_front_kernel<128, true><<<grid, 512, 0, st>>>(z, nullptr, nullptr, base, cnt, gs.sp.d, gs.sp.dp, dc->w1p, dc->scale1,
+                                                         dc->shift1, w.buf1, index, w.mask1);
+    else
+        sd_front_kernel<64, true><<<grid, 512, 0, st>>>(z, nullptr, nullptr, base, cnt, gs.sp.d, gs.sp.dp, dc->w1p, dc->scale1,
+                                                        dc->shift1, w.buf1, index, w.mask1);
+    GEO_LAUNCH_CHECK();
+    const Ends none{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    int rc = run_mid<false>(gs.sh, &gs.tail, w.buf1, w.buf2, w.mask1, w.mask2, none, 0, 0, cnt, st);
+    if (rc != GEO_OK) return rc;
+    if (g_out) return run_back<false, false, true>(gs.sh, &gs.tail, w.buf2, w.sigp, none, 0, 0, cnt, nullptr, st, g_out, gs.sp.crop);
+    return run_back<false>(gs.sh, &gs.tail, w.buf2, w.sigp, none, 0, 0, cnt, nullptr, st);
+}
+
+// u f32 rows u + (row0 + i) u_stride of nout values -> out f64 [cnt][d][4][4], with the masks and sigmoid' of slots 0 .. cnt - 1.
+int run_grid_tail(const geo_spatial_image_decoder_desc *dc, const GridShape &gs, const Workspace &w, const float *u, int64_t row0,
+                  int64_t u_stride, int64_t cnt, double *out, hipStream_t st, int F = 0) {
+#define VV_BACK(C2_, CO_)                                                                                                     \
+    vv_back_kernel<C2_, CO_><<<(unsigned)cnt, 256, 0, st>>>(u, w.sigp, w.mask2, w.buf2, row0, gs.sh.s2, dc->w3t, dc->scale2,     \
+                                                            gs.sp.crop, u_stride)
+    if (gs.sh.c2 == 64 && gs.sh.co == 1) VV_BACK(64, 1);
+    else if (gs.sh.c2 == 64) VV_BACK(64, 3);
+    else if (gs.sh.co == 1) VV_BACK(32, 1);
+    else VV_BACK(32, 3);
+#undef VV_BACK
+    GEO_LAUNCH_CHECK();
+    const unsigned mid_grid = (unsigned)((cnt + VV_MID_ITEMS - 1) / VV_MID_ITEMS);
+    if (gs.sh.c1 == 128) vv_mid_kernel<128, 64><<<mid_grid, 512, 0, st>>>(w.buf2, w.buf1, w.mask1, cnt, gs.sh.s1, dc->w2t);
+    else vv_mid_kernel<64, 32><<<mid_grid, 512, 0, st>>>(w.buf2, w.buf1, w.mask1, cnt, gs.sh.s1, dc->w2t);
+    GEO_LAUNCH_CHECK();
+    const unsigned fin_grid = (unsigned)((cnt + SV_ITEMS - 1) / SV_ITEMS);
+    if (gs.sh.c1 == 128) sv_final_kernel<128><<<fin_grid, 256, 0, st>>>(w.buf1, cnt, gs.sp.d, gs.dn, dc->w1t, F, out);
+    else sv_final_kernel<64><<<fin_grid, 256, 0, st>>>(w.buf1, cnt, gs.sp.d, gs.dn, dc->w1t, F, out);
+    GEO_LAUNCH_CHECK();
+    return GEO_OK;
+}
+
+// ---- curves of grids: section 27's evaluation with d := 16 d.  The first step: instead of the trace (16 d tangents per frame), one
+// more VJP per frame with the fixed sign probe s[c][y][x] = +1 for c + y + x even, else -1 (indices of the S x S output):
+// probe[f] = sum over the 16 d coordinates, ascending, in fp64, of (J(x[f])^T s)[k]^2, a one-sample estimate of tr J J^T, not a bound.
+// It lands where curve_step_kernel reads the trace, so the step rule and the loop are curve_step.h's, unchanged.
+struct GridCurveWorkspace {
+    CurveState st;
+    Workspace pt;
+    float *g, *r, *sgn;
+};
+
+GridCurveWorkspace lay_out_grid_curve_slice(geo::Arena &ar, const GridShape &gs, int64_t n_curves, int F) {
+    GridCurveWorkspace w;
+    const int64_t n = n_curves * F;
+    lay_out_curves(ar, &w.st, n_curves, F, gs.dz);
+    w.pt = lay_out_grid(ar, gs, n);
+    ar.take(w.g, (size_t)n * gs.nout); ar.take(w.r, (size_t)n * gs.nout);
+    ar.take(w.sgn, (size_t)gs.nout);
+    return w;
+}
+size_t grid_curve_slice_bytes(const GridShape &gs, int64_t n_curves, int F) {
+    return geo::measure(lay_out_grid_curve_slice, gs, n_curves, F);
+}
+
+__global__ __launch_bounds__(256) void sv_sign_kernel(int So, int nout, float *__restrict__ s) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= nout) return;
+    const int c = o / (So * So), rem = o - c * So * So, y = rem / So, x = rem - y * So;
+    s[o] = ((c + y + x) & 1) ? -1.f : 1.f;
+}
+
+// probe[p] = sum over k ascending of v[p][k]^2, one thread per frame
+__global__ __launch_bounds__(256) void sv_probe_kernel(const double *__restrict__ v, int dz, int64_t n, double *__restrict__ probe) {
+#pragma clang fp contract(off)
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    double t = 0.0;
+    for (int k = 0; k < dz; ++k) {
+        const double a = v[(size_t)p * dz + k];
+        t += a * a;
+    }
+    probe[p] = t;
+}
+
+// Evaluate(z) over a slice of n_curves, as curve_evaluate above; probe [n] or null (through grad, which the gradient then overwrites)
+int grid_curve_evaluate(const geo_spatial_image_decoder_desc *dc, const GridShape &gs, const GridCurveWorkspace &w, const float *z,
+                        int64_t n_curves, int F, double *energy, double *seg_sq, double *grad, float *g, double *probe,
+                        hipStream_t st) {
+    const int64_t n = n_curves * F;
+    int rc = run_grid_point_pass(dc, gs, w.pt, z, nullptr, 0, n, st, g);
+    if (rc != GEO_OK) return rc;
+    vc_residual_kernel<<<(unsigned)n, 256, 0, st>>>(g, F, gs.nout, seg_sq, w.r);
+    GEO_LAUNCH_CHECK();
+    vc_energy_kernel<<<(unsigned)n_curves, 64, 0, st>>>(seg_sq, z, F, gs.dz, energy);
+    GEO_LAUNCH_CHECK();
+    if (probe) {
+        sv_sign_kernel<<<(unsigned)((gs.nout + 255) / 256), 256, 0, st>>>(gs.sp.So, gs.nout, w.sgn);
+        GEO_LAUNCH_CHECK();
+        rc = run_grid_tail(dc, gs, w.pt, w.sgn, 0, 0, n, grad, st);
+        if (rc != GEO_OK) return rc;
+        sv_probe_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(grad, gs.dz, n, probe);
+        GEO_LAUNCH_CHECK();
+    }
+    return run_grid_tail(dc, gs, w.pt, w.r, 0, gs.nout, n, grad, st, F);
+}
+
+int grid_curve_check(const char *who, const geo_spatial_image_decoder_desc *dc, GridShape *gs, int64_t C, int F) {
+    if (const int rc = check_grid_desc(dc, gs, who)) return rc;
+    GEO_REQUIRE(F >= 2 && F <= CURVE_MAX_F, "%s: F %d not in [2,%d]", who, F, CURVE_MAX_F);
+    GEO_REQUIRE(C >= 0, "%s: C %lld < 0", who, (long long)C);
+    return GEO_OK;
+}
+
+int grid_curve_energy(const geo_spatial_image_decoder_desc *dc, const float *x, int64_t C, int F, double *energy_out,
+                      double *seg_sq_out, double *grad_out, float *g_out, double *probe_out, void *ws, size_t ws_bytes,
+                      hipStream_t st) {
+    static const char who[] = "geo_spatial_curve_energy";
+    GridShape gs;
+    if (const int rc = grid_curve_check(who, dc, &gs, C, F)) return rc;
+    if (C == 0) return GEO_OK;
+    GEO_REQUIRE(x && energy_out && ws, "%s: null pointer", who);
+    int64_t slice = 0;
+    const auto bytes = [&](int64_t nc) { return grid_curve_slice_bytes(gs, nc, F); };
+    if (const int rc = curve_slice_length(who, bytes, C, F, ws_bytes, &slice)) return rc;
+    for (int64_t base = 0; base < C; base += slice) {
+        const int64_t nc = C - base < slice ? C - base : slice;
+        geo::Arena ar(ws, ws_bytes);
+        const GridCurveWorkspace w = lay_out_grid_curve_slice(ar, gs, nc, F);
+        GEO_REQUIRE_WORKSPACE("geo_spatial_curve_energy", ar, bytes(nc));
+        const size_t at = (size_t)base * F;
+        if (const int rc = grid_curve_evaluate(dc, gs, w, x + at * gs.dz, nc, F, energy_out + base,
+                                               seg_sq_out ? seg_sq_out + (size_t)base * (F - 1) : w.st.seg_ev,
+                                               grad_out ? grad_out + at * gs.dz : w.st.grad_ev, g_out ? g_out + at * gs.nout : w.g,
+                                               probe_out ? probe_out + at : nullptr, st))
+            return rc;
+    }
+    return GEO_OK;
+}
+
+int grid_curve_relax(const geo_spatial_image_decoder_desc *dc, float *x, int64_t C, int F, int n_iters, double *step,
+                     double *energy0_out, double *energy_out, double *seg_sq_out, int32_t *accepted_out, void *ws, size_t ws_bytes,
+                     hipStream_t st) {
+    static const char who[] = "geo_spatial_curve_relax";
+    GridShape gs;
+    if (const int rc = grid_curve_check(who, dc, &gs, C, F)) return rc;
+    GEO_REQUIRE(n_iters >= 0, "%s: n_iters %d < 0", who, n_iters);
+    if (C == 0) return GEO_OK;
+    GEO_REQUIRE(x && step && energy_out && accepted_out && ws, "%s: null pointer", who);
+    int64_t slice = 0;
+    const auto bytes = [&](int64_t nc) { return grid_curve_slice_bytes(gs, nc, F); };
+    if (const int rc = curve_slice_length(who, bytes, C, F, ws_bytes, &slice)) return rc;
+    // the probe costs one more VJP per frame: only for a slice with a curve whose step the caller left to the call (one copy of the
+    // steps to the host, before the first launch; nothing is read back per iteration)
+    std::vector<double> step_h((size_t)C);
+    GEO_HIP_CHECK(hipMemcpyAsync(step_h.data(), step, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost, st));
+    GEO_HIP_CHECK(hipStreamSynchronize(st));
+    const int iters = F == 2 ? 0 : n_iters;                       // no interior frame: nothing can move
+    for (int64_t base = 0; base < C; base += slice) {
+        const int64_t nc = C - base < slice ? C - base : slice;
+        geo::Arena ar(ws, ws_bytes);
+        const GridCurveWorkspace w = lay_out_grid_curve_slice(ar, gs, nc, F);
+        GEO_REQUIRE_WORKSPACE("geo_spatial_curve_relax", ar, bytes(nc));
+        bool need_probe = false;
+        for (int64_t c = base; c < base + nc; ++c) need_probe |= step_h[(size_t)c] < 0.0;
+        const CurveState &cs = w.st;
+        float *xs = x + (size_t)base * F * gs.dz;
+        double *seg_s = seg_sq_out ? seg_sq_out + (size_t)base * (F - 1) : nullptr;
+        for (int it = -1; it < iters; ++it) {                     // it = -1: the curve itself
+            if (const int rc = grid_curve_evaluate(dc, gs, w, it < 0 ? xs : cs.y, nc, F, cs.e_ev, cs.seg_ev, cs.grad_ev, w.g,
+                                                   it < 0 && need_probe ? cs.tr : nullptr, st))
+                return rc;
+            curve_step_kernel<<<(unsigned)nc, CURVE_THREADS, 0, st>>>(cs, xs, F, gs.dz, it < 0, it == iters - 1, step + base,
+                                                                      energy0_out ? energy0_out + base : nullptr, energy_out + base,
+                                                                      seg_s, accepted_out + base);
+            GEO_LAUNCH_CHECK();
+        }
+    }
+    return GEO_OK;
+}
+
 }  // namespace
+
+extern "C" size_t geo_spatial_vjp_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int64_t n) {
+    GridShape gs;
+    if (!make_grid_shape(dec, &gs) || n < 0) return 0;
+    return grid_layout_bytes(gs, n < 1 ? 1 : (n < VJP_ITEMS_PER_PASS ? n : VJP_ITEMS_PER_PASS));
+}
+
+extern "C" size_t geo_spatial_vjp_min_workspace_bytes(const geo_spatial_image_decoder_desc *dec) {
+    GridShape gs;
+    return make_grid_shape(dec, &gs) ? grid_layout_bytes(gs, 1) : 0;
+}
+
+extern "C" int geo_spatial_vjp(const geo_spatial_image_decoder_desc *dec, const float *z, const int32_t *index, int64_t n,
+                               const float *u, double *out, void *ws, size_t ws_bytes, void *stream) {
+    GridShape gs;
+    if (const int rc = check_grid_desc(dec, &gs, "geo_spatial_vjp")) return rc;
+    GEO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "geo_spatial_vjp: n %lld", (long long)n);
+    if (n == 0) return GEO_OK;
+    GEO_REQUIRE(z && u && out && ws, "geo_spatial_vjp: null pointer");
+    int64_t pb = n < VJP_ITEMS_PER_PASS ? n : VJP_ITEMS_PER_PASS;
+    while (pb >= 1 && grid_layout_bytes(gs, pb) > ws_bytes) pb = geo::shrink_pass(pb);
+    if (pb < 1) {
+        geo::set_error("geo_spatial_vjp: workspace of %zu bytes is below the minimum of %zu", ws_bytes, grid_layout_bytes(gs, 1));
+        return GEO_E_WORKSPACE;
+    }
+    geo::Arena ar(ws, ws_bytes);
+    const Workspace w = lay_out_grid(ar, gs, pb);
+    GEO_REQUIRE_WORKSPACE("geo_spatial_vjp", ar, grid_layout_bytes(gs, pb));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (int64_t p0 = 0; p0 < n; p0 += pb) {
+        const int64_t cnt = n - p0 < pb ? n - p0 : pb;
+        if (const int rc = run_grid_point_pass(dec, gs, w, z, index, p0, cnt, st, nullptr)) return rc;
+        if (const int rc = run_grid_tail(dec, gs, w, u, p0, gs.nout, cnt, out + (size_t)p0 * gs.dz, st)) return rc;
+    }
+    return GEO_OK;
+}
+
+extern "C" size_t geo_spatial_curve_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int64_t C, int32_t F) {
+    GridShape gs;
+    if (!make_grid_shape(dec, &gs) || C < 0 || F < 2 || F > CURVE_MAX_F) return 0;
+    return grid_curve_slice_bytes(gs, curve_slice_cap(C, F), F);
+}
+
+extern "C" size_t geo_spatial_curve_min_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int32_t F) {
+    GridShape gs;
+    if (!make_grid_shape(dec, &gs) || F < 2 || F > CURVE_MAX_F) return 0;
+    return grid_curve_slice_bytes(gs, 1, F);
+}
+
+extern "C" int geo_spatial_curve_energy(const geo_spatial_image_decoder_desc *dec, const float *x, int64_t C, int32_t F,
+                                        double *energy_out, double *seg_sq_out, double *grad_out, float *g_out, double *probe_out,
+                                        void *ws, size_t ws_bytes, void *stream) {
+    return grid_curve_energy(dec, x, C, F, energy_out, seg_sq_out, grad_out, g_out, probe_out, ws, ws_bytes,
+                             static_cast<hipStream_t>(stream));
+}
+
+extern "C" int geo_spatial_curve_relax(const geo_spatial_image_decoder_desc *dec, float *x_inout, int64_t C, int32_t F, int32_t n_iters,
+                                       double *step_inout, double *energy0_out, double *energy_out, double *seg_sq_out,
+                                       int32_t *accepted_out, void *ws, size_t ws_bytes, void *stream) {
+    return grid_curve_relax(dec, x_inout, C, F, n_iters, step_inout, energy0_out, energy_out, seg_sq_out, accepted_out, ws, ws_bytes,
+                            static_cast<hipStream_t>(stream));
+}
 
 extern "C" size_t geo_vanilla_curve_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t C, int32_t F) {
     Shape sh;

@@ -8,6 +8,8 @@ latent grids, decoded (decode_images), with the image-space length of both route
 interpolate_images_vanilla: the same for a vanilla pipeline's vector latents, one node pair per image pair.
 relax_iters > 0 (both): the geodesic's frames and the chord are each relaxed under the decoder's metric with the ends fixed
 (relax_curves_device) and the result with the lower energy is kept per pair: never worse than either start.
+interpolate_images_spatial(relax_metric="image") relaxes the two sequences of whole 4x4 grids under the whole decoder instead
+(relax_grid_curves_device): the energy is the image sequence's own.
 """
 from typing import Dict, Sequence, Tuple
 
@@ -16,6 +18,7 @@ import torch
 
 from .._device import DeviceCSR
 from .geo_shortest_paths import _check_frames, chord_frames_device, geodesic_paths_device, resample_paths_device
+from .grid_relaxation import relax_grid_curves_device
 from .relaxation import relax_curves_device
 from .riemannian_metric import edge_lengths_riemannian
 
@@ -30,15 +33,16 @@ def curve_lengths(decoder, frames: torch.Tensor, batch_size: int = 512) -> torch
     return total
 
 
-def relax_best(decoder, frames_geo: torch.Tensor, frames_lin: torch.Tensor, relax_iters: int) -> Dict[str, torch.Tensor]:
+def relax_best(decoder, frames_geo: torch.Tensor, frames_lin: torch.Tensor, relax_iters: int,
+               relax=relax_curves_device) -> Dict[str, torch.Tensor]:
     """Relax both starts of M curves [M, F, d] for relax_iters iterations and keep, per curve, the result with the lower final
     energy (a tie goes to the geodesic).  Returns frames_relaxed f32 [M, F, d]; relax_from i32 [M] (0 the chord, 1 the
     geodesic); energy_geo, energy_lin f64 [M] (of the starts), energy_relaxed f64 [M] (<= both); accepted_geo, accepted_lin
-    i32 [M]."""
-    geo = relax_curves_device(decoder, frames_geo, relax_iters)
-    lin = relax_curves_device(decoder, frames_lin, relax_iters)
+    i32 [M].  relax=relax_grid_curves_device: the same over curves of grids [M, F, d, 4, 4]."""
+    geo = relax(decoder, frames_geo, relax_iters)
+    lin = relax(decoder, frames_lin, relax_iters)
     from_geo = geo.energy <= lin.energy
-    return {"frames_relaxed": torch.where(from_geo.view(-1, 1, 1), geo.frames, lin.frames),
+    return {"frames_relaxed": torch.where(from_geo.view(-1, *([1] * (frames_geo.dim() - 1))), geo.frames, lin.frames),
             "relax_from": from_geo.to(torch.int32), "energy_geo": geo.energy0, "energy_lin": lin.energy0,
             "energy_relaxed": torch.where(from_geo, geo.energy, lin.energy), "accepted_geo": geo.accepted,
             "accepted_lin": lin.accepted}
@@ -156,7 +160,7 @@ def interpolate_images_vanilla(z: torch.Tensor, lcc_index, G: DeviceCSR, decoder
 
 def interpolate_images_spatial(z_grids: torch.Tensor, lcc_index, G: DeviceCSR, decoder, image_pairs: Sequence[Tuple[int, int]],
                                n_frames: int, dataset: str, apply_sigmoid: bool, *, batch_size: int = 512,
-                               relax_iters: int = 0) -> Dict:
+                               relax_iters: int = 0, relax_metric: str = "position") -> Dict:
     """Image pairs of the spatial pipeline.  z_grids f32 [N, d, 4, 4] (any h x w grid); lcc_index: the flat positions
     img * h * w + y * w + x that are nodes of G, ascending -- np.flatnonzero(codes.reshape(-1) >= 0) of a build_codebook
     output: a position's node is its rank in that list.  Pair (i, j) is h * w node pairs, position p of image i to position p
@@ -167,12 +171,22 @@ def interpolate_images_spatial(z_grids: torch.Tensor, lcc_index, G: DeviceCSR, d
     [M] (pull-back lengths summed over the positions in position order); image_len_geo, image_len_lin f64 [M].
     relax_iters > 0 relaxes every position's two curves (relax_best) and adds frames_relaxed, images_relaxed, image_len_relaxed
     and curve_len_relaxed like the other two routes', and relax_from, accepted_geo, accepted_lin i32 [M, h w], energy_geo,
-    energy_lin, energy_relaxed f64 [M, h w]; with 0 the result is what it always was."""
+    energy_lin, energy_relaxed f64 [M, h w]; with 0 the result is what it always was.
+    relax_metric="image" (needs h = w = 4; the default "position" is the above) relaxes, per pair, the two sequences of whole
+    grids frames_geo and frames_lin under the whole decoder instead (relax_grid_curves_device): the energy is the image
+    sequence's own and sees the overlap of neighbouring positions.  The relaxed fields are then per pair: frames_relaxed
+    [M, F, d, 4, 4], images_relaxed, image_len_relaxed, curve_len_relaxed as before; energy_geo, energy_lin, energy_relaxed
+    f64 [M]; accepted_geo, accepted_lin, relax_from i32 [M]."""
     from ..decode import decode_images
     F = _check_frames(n_frames)
     dev = G.indptr.device
     N, d, h, w = z_grids.shape
     hw = h * w
+    if relax_metric not in ("position", "image"):
+        raise ValueError(f"relax_metric must be 'position' or 'image', got {relax_metric!r}")
+    by_image = relax_metric == "image" and relax_iters > 0
+    if by_image and (h, w) != (4, 4):
+        raise ValueError(f"relax_metric='image' relaxes 4x4 grids, the latents are {h}x{w}")
     pairs, lcc_index = _check_pairs(image_pairs, lcc_index, N, N * hw, G)
     M = pairs.shape[0]
     flat = z_grids.to(dev, torch.float32).permute(0, 2, 3, 1).reshape(N * hw, d).contiguous()
@@ -184,13 +198,21 @@ def interpolate_images_spatial(z_grids: torch.Tensor, lcc_index, G: DeviceCSR, d
     out = {"frames_geo": None, "frames_lin": None, "graph_dist": graph_dist.view(M, hw), "hops": hops.view(M, hw),
            "status": status.view(M, hw), "fallback_positions": [np.flatnonzero(st[m] != 0).astype(np.int32) for m in range(M)]}
     routes = [("geo", frames_geo), ("lin", frames_lin)]
-    if relax_iters > 0:
+
+    def as_grids(fr):                                                        # [M hw, F, d] -> [M, F, d, h, w]
+        return fr.view(M, h, w, F, d).permute(0, 3, 4, 1, 2).contiguous()
+
+    if by_image:
+        best = relax_best(decoder, as_grids(frames_geo), as_grids(frames_lin), int(relax_iters), relax_grid_curves_device)
+        routes.append(("relaxed", best.pop("frames_relaxed").permute(0, 3, 4, 1, 2).reshape(M * hw, F, d).contiguous()))
+        out.update(best)
+    elif relax_iters > 0:
         best = relax_best(decoder, frames_geo, frames_lin, int(relax_iters))
         routes.append(("relaxed", best.pop("frames_relaxed")))
         out.update({k: v.view(M, hw) for k, v in best.items()})
     for name, fr in routes:
         out[f"curve_len_{name}"] = curve_lengths(decoder, fr, batch_size).view(M, hw).sum(dim=1)
-        grids = fr.view(M, h, w, F, d).permute(0, 3, 4, 1, 2).contiguous()   # [M, F, d, h, w]
+        grids = as_grids(fr)
         images = decode_images(decoder, grids.view(M * F, d, h, w), dataset=dataset, apply_sigmoid=apply_sigmoid)
         out[f"frames_{name}"] = grids
         out[f"images_{name}"] = images.view(M, F, *images.shape[1:])

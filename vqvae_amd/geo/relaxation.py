@@ -34,7 +34,8 @@ _BN_ERROR = ("curve energy under a train-mode BatchNorm decoder: a sample's Jaco
 class CurveEnergy:
     """energy f64 [C]; seg_sq f64 [C, F-1]; grad f64 [C, F, d] (0 at the ends); outputs f32 [C, F, p_out] (the sigmoids g);
     jac f32 [C, F, d, p_out] or None; route "native" or "torch"; trace f64 [C, F] (tr J^T J per frame) where the call was asked
-    for it on the native vanilla route, else None."""
+    for it on the native vanilla route, else None.  grid_relaxation's calls return it with frames of grids ([C, F, d, 4, 4] for
+    grad) and their sign probe in `trace`."""
     energy: object
     seg_sq: object
     grad: object

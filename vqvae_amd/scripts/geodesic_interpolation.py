@@ -2,7 +2,7 @@
 
     python -m vqvae_amd.scripts.geodesic_interpolation --codebook_dir DIR --out_dir OUT
         (--pairs i:j [i:j ...] | --num_pairs N [--seed S]) [--frames 9] [--dataset other] [--batch_size 512]
-        [--train_latents_path PATH] [--relax_iters N]
+        [--train_latents_path PATH] [--relax_iters N] [--relax_metric position|image]
 
 DIR is an output of vqvae_amd.scripts.build_codebook (spatial pipeline): codebook.pt's "config" names the checkpoint, the
 training latents and the decoder's arguments, exactly as vqvae_amd.training.assign_codes_val_geodesic reads them.  A pair i:j
@@ -31,6 +31,10 @@ decoder's metric with the ends fixed for N iterations each (geo.relaxation) and 
   interpolation.json  per pair also curve_len_relaxed, image_len_relaxed, energy_geo, energy_lin, energy_relaxed (summed over
                       the positions), relax_from and the accepted counts per position; the totals of the lengths and energies
 The relaxed curve is never worse in energy than either start, by construction.
+--relax_metric image (spatial builds with 4x4 grids, with --relax_iters N) relaxes each pair's two sequences of whole grids under
+the whole decoder instead (geo.grid_relaxation): the third row is that result, relax_from, accepted_geo, accepted_lin are i32 [M]
+and energy_geo, energy_lin, energy_relaxed f64 [M] (one curve per pair), and the JSON names "relax_metric": "image".  Without
+the flag the three artefacts are what they were.
 
 Whether the geodesic is the shorter curve under the decoder's metric is a property of the trained model; the JSON reports
 the ratio and the script asserts nothing about it.
@@ -107,6 +111,8 @@ def main(args) -> dict:
     if (args.pairs is None) == (args.num_pairs is None):
         raise ValueError("give either --pairs i:j ... or --num_pairs N")
     if is_legacy_build(cb_dir):
+        if args.relax_metric != "position":
+            raise ValueError("--relax_metric image relaxes the latent grids of a spatial build; this is a vanilla build")
         from ..training.build_riemannian_codebook_legacy import read_decoder
         job, apply_sigmoid, W, z, rows = load_legacy_build(cb_dir, args.train_latents_path)
         pairs = parse_pairs(args.pairs, z.shape[0]) if args.pairs is not None else draw_pairs(z.shape[0], args.num_pairs, args.seed)
@@ -134,7 +140,7 @@ def main(args) -> dict:
     apply_sigmoid = str(cfg.get("recon_loss", "mse")).lower() == "bce" or bool(cfg.get("mse_use_sigmoid", False))
     out = interpolate_images_spatial(z, lcc_rows(np.load(cb_dir / "codes.npy")), DeviceCSR.from_scipy(W, dev), decoder,
                                      pairs, args.frames, args.dataset, apply_sigmoid, batch_size=args.batch_size,
-                                     relax_iters=args.relax_iters)
+                                     relax_iters=args.relax_iters, relax_metric=args.relax_metric)
     return write_artefacts(args, out, pairs, apply_sigmoid)
 
 
@@ -166,7 +172,7 @@ def write_artefacts(args, out: dict, pairs: np.ndarray, apply_sigmoid: bool) -> 
             for k in relax_sums:
                 rec[k] = float(np.asarray(host[k][m], dtype=np.float64).sum())
             for k in relax_lists:
-                rec[k] = [int(v) for v in host[k][m]]
+                rec[k] = [int(v) for v in np.atleast_1d(host[k][m])]
         per_pair.append(rec)
     totals = {k: float(sum(r[k] for r in per_pair))
               for k in ("graph_dist", "curve_len_lin", "curve_len_geo", "image_len_lin", "image_len_geo")}
@@ -179,6 +185,8 @@ def write_artefacts(args, out: dict, pairs: np.ndarray, apply_sigmoid: bool) -> 
                "pairs": per_pair, "totals": totals}
     if relaxed:
         summary["relax_iters"] = int(args.relax_iters)
+        if args.relax_metric != "position":
+            summary["relax_metric"] = args.relax_metric
 
     out_dir.mkdir(parents=True, exist_ok=True)
     # [M, 2 or 3, F, C, S, S]: chord above geodesic (above the relaxed curve), per pair
@@ -196,7 +204,8 @@ def write_artefacts(args, out: dict, pairs: np.ndarray, apply_sigmoid: bool) -> 
     if relaxed:
         print(f"relaxed for {args.relax_iters} iteration(s): pull-back length {t['curve_len_relaxed']:.4f}, image-space length "
               f"{t['image_len_relaxed']:.4f}; curve energy {t['energy_relaxed']:.6g} from geodesic {t['energy_geo']:.6g} / chord "
-              f"{t['energy_lin']:.6g}; {int(sum(sum(r['relax_from']) for r in per_pair))} position(s) kept the geodesic's result")
+              f"{t['energy_lin']:.6g}; {int(sum(sum(r['relax_from']) for r in per_pair))} "
+              f"{'pair' if args.relax_metric == 'image' else 'position'}(s) kept the geodesic's result")
     print(f"Saved artifacts to: {out_dir}")
     return out
 
@@ -214,6 +223,8 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--train_latents_path", type=str, default=None)
     p.add_argument("--relax_iters", type=int, default=0,
                    help="relax geodesic and chord under the decoder's metric for this many iterations and add the better result")
+    p.add_argument("--relax_metric", choices=("position", "image"), default="position",
+                   help="image: relax each pair's sequences of whole 4x4 grids under the whole decoder (spatial builds)")
     return p
 
 

@@ -209,6 +209,9 @@ class SpatialImageDecoderExport:
     constant.  It is carried as input channel d, which the kernel holds at 1 inside the grid; outside the grid every channel,
     that one included, is 0.  `host` keeps the fp64 originals: "W" [parity][tap][d + 1][c1] (row d is the bias row),
     "scale1", "shift1" [c1] with pre1 = scale1 * sum(taps, channels) + shift1 (ConvT1's bias inside shift1).
+    `tensors` are what geo_spatial_decode reads; `adjoint` holds the transposed packs that geo_spatial_vjp and the grid curves read
+    besides: "w2t", "w3t" as in VanillaDecoderExport, "w1t" [16][c1 / 4][dn][4] the composed first stage by
+    kernel tap 4 ky + kx with scale1 folded in, latent channels only (the bias channel has no gradient), dn = d rounded up to 32.
     A snapshot: later changes of the module (weights, statistics, mode) are not seen."""
 
     def __init__(self, dec: nn.Module, dev: torch.device):
@@ -231,11 +234,19 @@ class SpatialImageDecoderExport:
             shift2 = shift2 + scale2 * f64(conv2.bias)
             w2p = pack_k_quads(_parity_taps(f64(conv2.weight)))                                            # [4][4][c1 / 4][c2][4]
             w3p = _parity_taps(f64(out.weight)).permute(0, 1, 3, 2)                                        # [4][4][C][c2]
+            # the transposed packs: every layer by kernel tap 4 ky + kx, the first as a K-quad B operand [c1][dn]
+            w1n = torch.zeros(16, c1, (d + 31) // 32 * 32, dtype=torch.float64)
+            w1n[:, :, :d] = torch.einsum("ck,coyx,o->yxok", aug[:, :d], f64(conv1.weight), scale1).reshape(16, c1, d)
+            w1t = pack_k_quads(w1n)                                                                        # [16][c1 / 4][dn][4]
+            w2t = pack_k_quads(f64(conv2.weight).permute(2, 3, 1, 0).reshape(16, c2, c1))                  # [16][c2 / 4][c1][4]
+            w3t = f64(out.weight).permute(2, 3, 1, 0).reshape(16, C, c2)                                   # [16][C][c2]
         self.host = {"W": W, "scale1": scale1, "shift1": shift1}
         packed = {"w1p": w1p, "scale1": scale1, "shift1": shift1, "w2p": w2p, "scale2": scale2, "shift2": shift2, "w3p": w3p,
                   "b3": f64(out.bias)}
         self.tensors = {k: f32(v, dev) for k, v in packed.items()}
+        self.adjoint = {k: f32(v, dev) for k, v in {"w1t": w1t, "w2t": w2t, "w3t": w3t}.items()}
         self.latent_dim, self.out_channels, self.out_size = d, C, {1: 32, 3: 28}[out.padding[0]]
+        self.n_out = C * self.out_size ** 2
         desc = _lib.SpatialImageDecoderDesc()
         desc.latent_dim, desc.c1, desc.c2, desc.out_channels, desc.out_size = d, c1, c2, C, self.out_size
-        self.desc = fill_desc(desc, self.tensors)
+        self.desc = fill_desc(fill_desc(desc, self.tensors), self.adjoint)
