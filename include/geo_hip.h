@@ -626,6 +626,43 @@ int geo_vanilla_curve_relax(const geo_vanilla_decoder_desc *dec, float *x_inout,
                             double *step_inout, double *energy0_out, double *energy_out, double *seg_sq_out, int32_t *accepted_out,
                             void *ws, size_t ws_bytes, void *stream);
 
+/* The pull-back metric tensor of the same decoder per latent: with g and J as for geo_vanilla_vjp,
+ *   G(z_i) = J(z_i)^T J(z_i),  z_i = z[index ? index[i] : i].
+ * z f32 [.][d], index NULL or i32 [n]; G_out f64 [n][d][d], required; jac_out f32 [n][d][nout], the columns J[.][k] themselves,
+ * may be null; eig_out f64 [n][d], logvol_out f64 [n], rank_out i32 [n]: all three or none (a mixed triple: GEO_E_ARG).
+ * Coverage is geo_vanilla_jvp_pairs's; the transposed packs are not read.  The columns are the unit tangents of
+ * geo_vanilla_curve_energy's trace pushed through the tangent kernels in f32; G[a][b] = sum over o of
+ * (double)J[a][o] * (double)J[b][o], exact products added in an order that depends on (d, nout) alone (outputs in chunks of
+ * 64 ascending, each chunk in groups of four on v_mfma_f64_16x16x4_f64), the lower triangle written from the upper: G == G^T
+ * bit for bit, and no bit of G, jac_out or the spectrum depends on n, a latent's position, index, the workspace size, the
+ * stream or earlier workspace contents.  The spectrum is geo_sym_spectrum's on G with p_out = nout.  Latents run in slices
+ * (pairs of latents) sized from ws_bytes: any size from geo_vanilla_metric_min_workspace_bytes(dec) -- one pair -- upwards is
+ * legal (a smaller one: GEO_E_WORKSPACE).  The queries answer 0 for a descriptor outside the coverage and the call rejects it
+ * (GEO_E_ARG, as a null required pointer) before any launch.  n == 0 returns GEO_OK without a launch; n < 2^31.
+ * Asynchronous on `stream`: no atomics, no host synchronisation. */
+size_t geo_vanilla_metric_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n);
+size_t geo_vanilla_metric_min_workspace_bytes(const geo_vanilla_decoder_desc *dec);
+int geo_vanilla_metric_tensor(const geo_vanilla_decoder_desc *dec, const float *z, const int32_t *index, int64_t n, double *G_out,
+                              float *jac_out, double *eig_out, double *logvol_out, int32_t *rank_out, void *ws, size_t ws_bytes,
+                              void *stream);
+
+/* Eigenvalues of n symmetric matrices G f64 [n][d][d], 1 <= d <= 128 (csrc/sym_spectrum.hip); only the
+ * upper triangle a <= b of each matrix is read.  eig_out f64 [n][d] ascending; with emax the largest,
+ *   rank   = #{ i : eig_i > 0 and sqrt(eig_i) > max(p_out, d) * FLT_EPSILON * sqrt(emax) },
+ *   logvol = 0.5 * sum_i log(eig_i), ascending, if every eigenvalue is > 0, else -inf
+ * (the rules of geo_decoder_metric_tensor).  G = 0 gives eig = 0, rank = 0, logvol = -inf.  One workgroup holds a matrix in LDS
+ * and runs parallel-order cyclic Jacobi on a fixed round-robin schedule until every off-diagonal entry is exactly 0 (at most
+ * geo_sym_spectrum_sweep_cap() sweeps); a matrix's results are a function of the matrix alone.  A matrix with a NaN or an inf
+ * among the entries read gives eig NaN, logvol NaN, rank 0 and leaves the other matrices' results untouched.  d outside
+ * [1,128], n < 0, p_out < 1 or (n > 0) a null pointer: GEO_E_ARG before any launch; n == 0: GEO_OK.  Asynchronous on `stream`.
+ * Diagnostics, for tests and measurements, not for pipelines: geo_sym_spectrum_sweeps is the same call and also writes the sweeps
+ * each matrix took to sweeps_out i32 [n]; geo_sym_spectrum_sweep_cap() is the kernel's sweep cap. */
+int geo_sym_spectrum(const double *G, int64_t n, int32_t d, int32_t p_out, double *eig_out, double *logvol_out, int32_t *rank_out,
+                     void *stream);
+int geo_sym_spectrum_sweeps(const double *G, int64_t n, int32_t d, int32_t p_out, double *eig_out, double *logvol_out,
+                            int32_t *rank_out, int32_t *sweeps_out, void *stream);
+int32_t geo_sym_spectrum_sweep_cap(void);
+
 /* ------------------------------------------------------------------------------------------
  * Image decode: latents or codes -> the decoder's raw output (before any sigmoid), f32 NCHW
  * [n][C][S][S].  Only the primal chain of the kernels above: no masks, no sigmoid'; the workspace is the two activation

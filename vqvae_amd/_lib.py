@@ -136,6 +136,13 @@ _SIGNATURES = {
     "geo_vanilla_curve_energy": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, sz, c_p]),
     "geo_vanilla_curve_relax": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, sz,
                                                c_p]),
+    "geo_vanilla_metric_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64]),
+    "geo_vanilla_metric_min_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc)]),
+    "geo_vanilla_metric_tensor": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, c_p, c_p, c_p, c_p, c_p, c_p, sz,
+                                                 c_p]),
+    "geo_sym_spectrum": (ctypes.c_int, [c_p, i64, i32, i32, c_p, c_p, c_p, c_p]),
+    "geo_sym_spectrum_sweeps": (ctypes.c_int, [c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p]),
+    "geo_sym_spectrum_sweep_cap": (i32, []),
     "geo_vanilla_decode_workspace_bytes": (sz, [ctypes.POINTER(VanillaDecoderDesc), i64]),
     "geo_vanilla_decode": (ctypes.c_int, [ctypes.POINTER(VanillaDecoderDesc), c_p, c_p, i64, c_p, c_p, sz, c_p]),
     "geo_spatial_decode_workspace_bytes": (sz, [ctypes.POINTER(SpatialImageDecoderDesc), i64]),

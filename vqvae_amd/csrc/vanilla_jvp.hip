@@ -22,6 +22,9 @@
 // The same for whole 4 x 4 grids under the spatial decoder (geo_spatial_vjp, geo_spatial_curve_energy, geo_spatial_curve_relax;
 // DESIGN.md section 29): the image decode's first stage with the mask bits, the two shared layers at s1 = 8, and a first-stage
 // adjoint of its own.
+// The metric tensor per latent (geo_vanilla_metric_tensor) runs the point pass and the edge pass over unit
+// tangents, keeps the columns vj_back_kernel forms and reduces them to G = J^T J in fp64 (vm_gram_kernel); its eigenvalues are
+// csrc/sym_spectrum.hip's.
 //
 // ConvT2 (k4, s2, p1) is four implicit GEMMs, one per output-pixel parity: out[(2y+py, 2x+px)][co] = sum over the taps
 // (a, b) in {0,1}^2 and ci of in[(y+py-a, x+px-b)][ci] w2[ci][co][2a+1-py][2b+1-px]; M = (item, pixel) rows, K = 4 c1, N = c2, on
@@ -271,7 +274,9 @@ __global__ __launch_bounds__(512) void vj_mid_kernel(const float *__restrict__ i
 // SQ (edge pass): len_out [2 E] takes each end's sum of squares instead of the edge's length.  G_OUT (point pass): g_out takes
 // the sigmoid itself beside sigmoid', from the same e: 1 / (1 + e) for a logit >= 0, else e / (1 + e); g_out [slot][C][So][So] is the
 // window of rows and columns crop .. S - crop - 1 (crop = 2: the spatial decoder at 28 px), sigmoid' always the whole S x S.
-template <int C2, int CO, bool TANGENT, bool SQ = false, bool G_OUT = false>
+// COLS (edge pass): g_out [2 E][nout] also takes the columns themselves, v = sigmoid' * tangent, per item (edge, end), before they
+// are squared (geo_vanilla_metric_tensor); nothing else changes.
+template <int C2, int CO, bool TANGENT, bool SQ = false, bool G_OUT = false, bool COLS = false>
 __global__ __launch_bounds__(256) void vj_back_kernel(const float *__restrict__ in, float *__restrict__ sigp, Ends s,
                                                       int resident, int64_t slot0, int s2, const float *__restrict__ w3p,
                                                       const float *__restrict__ b3, float *__restrict__ len_out,
@@ -321,6 +326,7 @@ __global__ __launch_bounds__(256) void vj_back_kernel(const float *__restrict__ 
                     const size_t o = ((size_t)c * S + (2 * y + py)) * S + 2 * x + px;
                     if (TANGENT) {
                         const float v = sg[o] * acc[c];
+                        if (COLS) g_out[(size_t)it * nout + o] = v;
                         ss = fmaf(v, v, ss);
                     } else {
                         const float e = expf(-fabsf(acc[c]));
@@ -363,12 +369,12 @@ int run_mid(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *in
     return launch_mid<64, 32, TANGENT>(sh, dc, in, out, mask1, mask2, e, resident, slot0, n_items, st);
 }
 
-template <bool TANGENT, bool SQ = false, bool G_OUT = false>
+template <bool TANGENT, bool SQ = false, bool G_OUT = false, bool COLS = false>
 int run_back(const Shape &sh, const geo_vanilla_decoder_desc *dc, const float *in, float *sigp, const Ends &e, int resident,
              int64_t slot0, int64_t blocks, float *len_out, hipStream_t st, float *g_out = nullptr, int crop = 0) {
     const unsigned grid = (unsigned)blocks;
 #define VJ_BACK(C2_, CO_)                                                                                                     \
-    vj_back_kernel<C2_, CO_, TANGENT, SQ, G_OUT><<<grid, 256, 0, st>>>(in, sigp, e, resident, slot0, sh.s2, dc->w3p, dc->b3,     \
+    vj_back_kernel<C2_, CO_, TANGENT, SQ, G_OUT, COLS><<<grid, 256, 0, st>>>(in, sigp, e, resident, slot0, sh.s2, dc->w3p, dc->b3,     \
                                                                         len_out, g_out, crop)
     if (sh.c2 == 64 && sh.co == 1) VJ_BACK(64, 1);
     else if (sh.c2 == 64) VJ_BACK(64, 3);
@@ -1353,7 +1359,168 @@ int grid_curve_relax(const geo_spatial_image_decoder_desc *dc, float *x, int64_t
     return GEO_OK;
 }
 
+// ================================ the metric tensor per latent ================================
+// geo_vanilla_metric_tensor: G(z) = J(z)^T J(z), J = d sigmoid(decoder(z)) / dz.  A slice of latents runs the point pass, then
+// the unit-tangent passes of curve_evaluate's trace branch over pseudo-edges (pair of latents, k) -- vc_unit_kernel,
+// vj_mid_kernel<.., true>, vj_back_kernel<.., true, SQ, false, COLS> -- which leave the columns J[.][k] of item (edge, end) in
+// `cols`; vm_gram_kernel reduces a latent's d columns to G in fp64 (and copies them to jac_out), and geo_sym_spectrum
+// (csrc/sym_spectrum.hip) takes the eigenvalues of all n matrices at the end.
+//
+// Gram order.  One workgroup per latent.  The outputs go through LDS in chunks of GRAM_OC = 64, o ascending (the last chunk
+// padded with zeros, which add nothing); the upper triangle of 16 x 16 tiles of G, tile t on wave t mod 4, each accumulated by
+// v_mfma_f64_16x16x4_f64 over the chunk's 16 groups of four outputs in order.  A product of two float32 values is exact in
+// fp64, so an entry is a sum of exact terms whose order is a function of (d, nout) alone: it does not depend on n, the
+// latent's position, `index`, the slice, the stream or what the workspace held.  The lower triangle is written from the upper.
+// (latent, k) tangent items of a slice at most.  The tangent kernels carry a call: at 8192 items vj_mid_kernel launches 1 600 to
+// 2 048 workgroups and vj_back_kernel 4 096 on 256 CUs, and the slice's buffers are 0.9 GB at d = 128, 32 px x 3 (they grow in
+// proportion).  The point pass and vm_gram_kernel see 8192 / d latents a slice: at d = 128 their 64 workgroups (4 for the front)
+// leave most CUs idle and cost 35 % of a call in the kernel trace of DESIGN.md section 30 -- the follow-up named there.
+constexpr int64_t METRIC_SLICE_ITEMS = 8192;
+constexpr int GRAM_OC = 64, GRAM_LD = GRAM_OC + 4;
+constexpr int GRAM_DT = MAX_D / 16, GRAM_WAVE_TILES = (GRAM_DT * (GRAM_DT + 1) / 2 + 3) / 4;
+using f64x4 = __attribute__((__vector_size__(4 * sizeof(double)))) double;
+
+struct MetricWorkspace {
+    Workspace pt;
+    int32_t *ia, *ib;
+    float *sq, *cols;
+};
+MetricWorkspace lay_out_metric(geo::Arena &ar, const Shape &s, int64_t pairs) {
+    MetricWorkspace w;
+    const int64_t ne = pairs * s.d;                           // pseudo-edges (pair, k): two items each
+    w.pt = lay_out(ar, s, 2 * pairs, ne);
+    ar.take(w.ia, (size_t)ne); ar.take(w.ib, (size_t)ne);
+    ar.take(w.sq, (size_t)2 * ne); ar.take(w.cols, (size_t)2 * ne * s.nout);
+    return w;
+}
+size_t metric_bytes(const Shape &s, int64_t pairs) { return geo::measure(lay_out_metric, s, pairs); }
+int64_t metric_pair_cap(const Shape &s, int64_t n) {
+    const int64_t cap = METRIC_SLICE_ITEMS / (2 * s.d) < 1 ? 1 : METRIC_SLICE_ITEMS / (2 * s.d), need = n < 2 ? 1 : (n + 1) / 2;
+    return need < cap ? need : cap;
+}
+
+// latent `node` of the slice: its column k is item 2 ((node / 2) d + k) + (node & 1) of cols
+__global__ __launch_bounds__(256) void vm_gram_kernel(const float *__restrict__ cols, int d, int nout, int64_t node0,
+                                                      double *__restrict__ G, float *__restrict__ jac_out) {
+    __shared__ float Js[MAX_D][GRAM_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t node = blockIdx.x, q = node >> 1;
+    const int side = (int)(node & 1);
+    const int dt = (d + 15) / 16, ntiles = dt * (dt + 1) / 2;
+    int bi[GRAM_WAVE_TILES], bj[GRAM_WAVE_TILES];
+    f64x4 acc[GRAM_WAVE_TILES];
+#pragma unroll
+    for (int ti = 0; ti < GRAM_WAVE_TILES; ++ti) {
+        int a = 0, p = wave + 4 * ti;
+        if (p >= ntiles) p = 0;                               // (not used)
+        while (p >= dt - a) p -= dt - a, ++a;
+        bi[ti] = a;
+        bj[ti] = a + p;
+        acc[ti] = f64x4{0.0, 0.0, 0.0, 0.0};
+    }
+    for (int o0 = 0; o0 < nout; o0 += GRAM_OC) {
+        __syncthreads();
+        for (int i = tid; i < dt * 16 * GRAM_OC; i += 256) {
+            const int k = i / GRAM_OC, oo = i - k * GRAM_OC, o = o0 + oo;
+            float v = 0.f;
+            if (k < d && o < nout) {
+                v = cols[(2 * ((size_t)q * d + k) + side) * nout + o];
+                if (jac_out) jac_out[((size_t)(node0 + node) * d + k) * nout + o] = v;
+            }
+            Js[k][oo] = v;
+        }
+        __syncthreads();
+        for (int kk = 0; kk < GRAM_OC / 4; ++kk) {
+            const int k = kk * 4 + (lane >> 4);               // A[i = lane & 15][k = lane >> 4], B[k][j = lane & 15]
+#pragma unroll
+            for (int ti = 0; ti < GRAM_WAVE_TILES; ++ti)
+                if (wave + 4 * ti < ntiles) {
+                    const double a = (double)Js[bi[ti] * 16 + (lane & 15)][k], b = (double)Js[bj[ti] * 16 + (lane & 15)][k];
+                    acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[ti], 0, 0, 0);
+                }
+        }
+    }
+    // f64 C/D layout: col = lane & 15, row = (lane >> 4) + 4 reg
+    double *Gn = G + (size_t)(node0 + node) * d * d;
+#pragma unroll
+    for (int ti = 0; ti < GRAM_WAVE_TILES; ++ti)
+        if (wave + 4 * ti < ntiles) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int gi = bi[ti] * 16 + (lane >> 4) + 4 * reg, gj = bj[ti] * 16 + (lane & 15);
+                if (gi <= gj && gj < d) {
+                    Gn[(size_t)gi * d + gj] = acc[ti][reg];
+                    Gn[(size_t)gj * d + gi] = acc[ti][reg];
+                }
+            }
+        }
+}
+
+int metric_tensor(const geo_vanilla_decoder_desc *dc, const float *z, const int32_t *index, int64_t n, double *G_out, float *jac_out,
+                  double *eig_out, double *logvol_out, int32_t *rank_out, void *ws, size_t ws_bytes, hipStream_t st) {
+    static const char who[] = "geo_vanilla_metric_tensor";
+    Shape sh;
+    if (const int rc = check_desc(dc, &sh, who)) return rc;
+    GEO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "%s: n %lld", who, (long long)n);
+    const bool spectrum = eig_out || logvol_out || rank_out;
+    GEO_REQUIRE(!spectrum || (eig_out && logvol_out && rank_out), "%s: eig_out, logvol_out and rank_out go together", who);
+    if (n == 0) return GEO_OK;
+    GEO_REQUIRE(z && G_out && ws, "%s: null pointer", who);
+    // the pairs of latents per slice: everything (up to the cap) when it fits, else the largest count that does
+    int64_t pairs = metric_pair_cap(sh, n);
+    if (ws_bytes < metric_bytes(sh, pairs)) {
+        if (ws_bytes < metric_bytes(sh, 1)) {
+            geo::set_error("%s: workspace of %zu bytes is below the minimum of %zu", who, ws_bytes, metric_bytes(sh, 1));
+            return GEO_E_WORKSPACE;
+        }
+        int64_t lo = 1, hi = pairs;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) / 2;
+            if (metric_bytes(sh, mid) <= ws_bytes) lo = mid; else hi = mid - 1;
+        }
+        pairs = lo;
+    }
+    for (int64_t base = 0; base < n; base += 2 * pairs) {
+        const int64_t ns = n - base < 2 * pairs ? n - base : 2 * pairs, np = (ns + 1) / 2, ne = np * sh.d;
+        geo::Arena ar(ws, ws_bytes);
+        const MetricWorkspace w = lay_out_metric(ar, sh, np);
+        GEO_REQUIRE_WORKSPACE("geo_vanilla_metric_tensor", ar, metric_bytes(sh, np));
+        const Ends e{z, z, index, nullptr, base, (int)ns};
+        int rc = run_point_pass(dc, sh, w.pt, e, ns, 0, st);
+        if (rc != GEO_OK) return rc;
+        vc_unit_kernel<<<(unsigned)ne, 256, 0, st>>>(dc->At, sh.d, sh.n1, 0, ns, w.pt.buf1, w.ia, w.ib);
+        GEO_LAUNCH_CHECK();
+        const Ends t{z, z, w.ia, w.ib, 0, (int)ne};
+        rc = run_mid<true>(sh, dc, w.pt.buf1, w.pt.buf2, w.pt.mask1, w.pt.mask2, t, 1, 0, 2 * ne, st);
+        if (rc != GEO_OK) return rc;
+        rc = run_back<true, true, false, true>(sh, dc, w.pt.buf2, w.pt.sigp, t, 1, 0, ne, w.sq, st, w.cols);
+        if (rc != GEO_OK) return rc;
+        vm_gram_kernel<<<(unsigned)ns, 256, 0, st>>>(w.cols, sh.d, sh.nout, base, G_out, jac_out);
+        GEO_LAUNCH_CHECK();
+    }
+    if (!spectrum) return GEO_OK;
+    return geo_sym_spectrum(G_out, n, sh.d, sh.nout, eig_out, logvol_out, rank_out, st);
+}
+
 }  // namespace
+
+extern "C" size_t geo_vanilla_metric_workspace_bytes(const geo_vanilla_decoder_desc *dec, int64_t n) {
+    Shape sh;
+    if (!make_shape(dec, &sh) || n < 0) return 0;
+    return metric_bytes(sh, metric_pair_cap(sh, n));
+}
+
+extern "C" size_t geo_vanilla_metric_min_workspace_bytes(const geo_vanilla_decoder_desc *dec) {
+    Shape sh;
+    return make_shape(dec, &sh) ? metric_bytes(sh, 1) : 0;
+}
+
+extern "C" int geo_vanilla_metric_tensor(const geo_vanilla_decoder_desc *dec, const float *z, const int32_t *index, int64_t n,
+                                         double *G_out, float *jac_out, double *eig_out, double *logvol_out, int32_t *rank_out,
+                                         void *ws, size_t ws_bytes, void *stream) {
+    return metric_tensor(dec, z, index, n, G_out, jac_out, eig_out, logvol_out, rank_out, ws, ws_bytes,
+                         static_cast<hipStream_t>(stream));
+}
 
 extern "C" size_t geo_spatial_vjp_workspace_bytes(const geo_spatial_image_decoder_desc *dec, int64_t n) {
     GridShape gs;

@@ -14,6 +14,7 @@ has no kernel: it is differentiated by autograd on the decoder's own device.
 """
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -213,12 +214,14 @@ _GRAM_LOOP_MAX_OUTPUTS = 256    # up to this many outputs the generic Gram is ac
 @dataclass
 class PullbackMetric:
     """G fp64 [n, d, d] (or [N, H, W, d, d] for a latent grid); eig fp64 [..., d] ascending, logvol fp64 [...] = 0.5 log det G
-    (-inf unless every eigenvalue is > 0), rank int32 [...] -- None with spectrum=False; route "native" or "autograd"."""
+    (-inf unless every eigenvalue is > 0), rank int32 [...] -- None with spectrum=False; route "native" or "autograd"; J the
+    columns themselves, f32 [..., d, nout] (J[k] = d sigmoid(decoder(z)) / dz_k, flattened), only with jacobian=True."""
     G: object
     eig: object
     logvol: object
     rank: object
     route: str
+    J: object = None
 
 
 def native_metric_covers(decoder) -> bool:
@@ -239,6 +242,13 @@ def native_metric_covers(decoder) -> bool:
     tiles = (seq[6].out_channels * s_out * s_out + 31) // 32
     return (fixed and decoder.conv_in.in_channels <= 16 and seq[0].out_channels in (32, 64, 128) and seq[3].out_channels == 64
             and tiles in (1, 6))
+
+
+def native_vanilla_metric_covers(decoder) -> bool:
+    """Whether geo_vanilla_metric_tensor computes this decoder's metric tensor: exactly
+    vanilla_kernels_cover(decoder) -- the vanilla decoder with eval-mode BatchNorm or no norm, 1 <= latent_dim <= 128,
+    dec_channels[1:] (128, 64) or (64, 32), 1 or 3 channels of 28 or 32 px.  native_metric_covers stays False for it."""
+    return vanilla_kernels_cover(decoder)
 
 
 def _has_train_batchnorm(decoder) -> bool:
@@ -262,8 +272,9 @@ def metric_spectrum_fields(G: torch.Tensor, eig: torch.Tensor, p_out: int):
     return logvol, rank
 
 
-def _generic_metric(decoder, z: torch.Tensor, spectrum: bool):
-    """The generic route on the decoder's own device: (G, eig, logvol, rank) for z [n, d]."""
+def _generic_metric(decoder, z: torch.Tensor, spectrum: bool, jacobian: bool = False):
+    """The generic route on the decoder's own device: (G, eig, logvol, rank, J) for z [n, d]; J f32 [n, d, p_out] is jacfwd's,
+    transposed, with `jacobian`, else None."""
     dec_dev = next(decoder.parameters()).device
     first = next(decoder.children())
     flat_input = hasattr(first, "in_features")
@@ -276,9 +287,13 @@ def _generic_metric(decoder, z: torch.Tensor, spectrum: bool):
     n, d = z.shape
     G = torch.empty(n, d, d, dtype=torch.float64, device=dec_dev)
     p_out = 0
+    cols = []
     for lo in range(0, n, _GENERIC_BATCH):
         with torch.no_grad():
-            J = torch.func.vmap(torch.func.jacfwd(image))(z[lo:lo + _GENERIC_BATCH]).double()      # [b, p_out, d]
+            J = torch.func.vmap(torch.func.jacfwd(image))(z[lo:lo + _GENERIC_BATCH])               # [b, p_out, d]
+        if jacobian:
+            cols.append(J.transpose(1, 2).contiguous())
+        J = J.double()
         p_out = J.shape[1]
         if p_out <= _GRAM_LOOP_MAX_OUTPUTS:
             g = torch.zeros(J.shape[0], d, d, dtype=torch.float64, device=dec_dev)
@@ -288,11 +303,14 @@ def _generic_metric(decoder, z: torch.Tensor, spectrum: bool):
             g = torch.bmm(J.transpose(1, 2), J)
             g = torch.triu(g) + torch.triu(g, 1).transpose(1, 2)
         G[lo:lo + _GENERIC_BATCH] = g
+    Jt = None
+    if jacobian:
+        Jt = torch.cat(cols) if cols else torch.empty(0, d, 0, dtype=torch.float32, device=dec_dev)
     if not spectrum:
-        return G, None, None, None
+        return G, None, None, None, Jt
     eig = torch.linalg.eigvalsh(G) if n else torch.empty(0, d, dtype=torch.float64, device=dec_dev)
     logvol, rank = metric_spectrum_fields(G, eig, p_out)
-    return G, eig, logvol, rank
+    return G, eig, logvol, rank, Jt
 
 
 def _native_metric(export: DecoderExport, z: torch.Tensor, spectrum: bool, max_workspace_bytes):
@@ -310,18 +328,59 @@ def _native_metric(export: DecoderExport, z: torch.Tensor, spectrum: bool, max_w
                               "geo_metric_tensor_workspace_bytes: decoder")
         _lib.check(lib.geo_decoder_metric_tensor(export.desc, ptr(z), n, ptr(G), ptr(eig), ptr(logvol), ptr(rank), ptr(ws),
                                                  ws.numel(), stream_ptr()), "geo_decoder_metric_tensor")
-    return G, eig, logvol, rank
+    return G, eig, logvol, rank, None
 
 
-def pullback_metric_device(decoder_or_export, z: torch.Tensor, *, spectrum: bool = True,
-                           max_workspace_bytes=None) -> PullbackMetric:
+def _native_vanilla_metric(export: VanillaDecoderExport, z: torch.Tensor, spectrum: bool, jacobian: bool, max_workspace_bytes):
+    lib = _lib.load()
+    dev = z.device
+    n, d = z.shape
+    G = torch.empty(n, d, d, dtype=torch.float64, device=dev)
+    J = torch.empty(n, d, export.n_out, dtype=torch.float32, device=dev) if jacobian else None
+    eig = torch.empty(n, d, dtype=torch.float64, device=dev) if spectrum else None
+    logvol = torch.empty(n, dtype=torch.float64, device=dev) if spectrum else None
+    rank = torch.empty(n, dtype=torch.int32, device=dev) if spectrum else None
+    if n == 0:
+        return G, eig, logvol, rank, J
+    with torch.cuda.device(dev):
+        ws = capped_workspace(lib.geo_vanilla_metric_workspace_bytes(export.desc, n), max_workspace_bytes, dev,
+                              "geo_vanilla_metric_workspace_bytes: decoder")
+        _lib.check(lib.geo_vanilla_metric_tensor(export.desc, ptr(z), None, n, ptr(G), ptr(J), ptr(eig), ptr(logvol), ptr(rank),
+                                                 ptr(ws), ws.numel(), stream_ptr()), "geo_vanilla_metric_tensor")
+    return G, eig, logvol, rank, J
+
+
+def sym_spectrum_device(G: torch.Tensor, p_out: int):
+    """(eig f64 [n, d] ascending, logvol f64 [n], rank int32 [n]) of symmetric matrices G, a CUDA fp64 tensor [n, d, d] with
+    1 <= d <= 128, by geo_sym_spectrum (csrc/sym_spectrum.hip): only the upper triangles are read; the rank and logvol rules of
+    metric_spectrum_fields with `p_out` outputs.  A matrix with a NaN or an inf gives eig NaN, logvol NaN, rank 0."""
+    if G.ndim != 3 or G.shape[1] != G.shape[2] or G.dtype != torch.float64 or G.device.type != "cuda":
+        raise ValueError(f"G must be a CUDA float64 tensor [n, d, d], got {G.dtype} {tuple(G.shape)} on {G.device}")
+    lib = _lib.load()
+    G = G.contiguous()
+    n, d = int(G.shape[0]), int(G.shape[1])
+    eig = torch.empty(n, d, dtype=torch.float64, device=G.device)
+    logvol = torch.empty(n, dtype=torch.float64, device=G.device)
+    rank = torch.empty(n, dtype=torch.int32, device=G.device)
+    with torch.cuda.device(G.device):
+        _lib.check(lib.geo_sym_spectrum(ptr(G), n, d, int(p_out), ptr(eig), ptr(logvol), ptr(rank), stream_ptr()),
+                   "geo_sym_spectrum")
+    return eig, logvol, rank
+
+
+def pullback_metric_device(decoder_or_export, z: torch.Tensor, *, spectrum: bool = True, max_workspace_bytes=None,
+                           jacobian: bool = False) -> PullbackMetric:
     """The pull-back metric tensor G = J^T J of every latent, J = d sigmoid(decoder(z)) / dz on a 1x1 latent, with (spectrum)
     its eigenvalues, logvol = 0.5 log det G and numerical rank.  z: [n, d], or a latent grid [N, d, H, W], which is flattened
     in build_codebook's (n, h, w) row order and gives fields shaped [N, H, W, ...].  The tensors live on z's device.
     A decoder with native_metric_covers and z on a GPU run geo_decoder_metric_tensor (a DecoderExport always does;
     `max_workspace_bytes` caps its workspace, not below geo_metric_tensor_min_workspace_bytes, and changes no bit); anything
     else takes the generic autograd route on the decoder's device.  Train-mode BatchNorm raises ValueError on both routes: a
-    sample's Jacobian there depends on the batch it is in."""
+    sample's Jacobian there depends on the batch it is in.
+    A vanilla decoder with native_vanilla_metric_covers and z [n, d] on a GPU run geo_vanilla_metric_tensor (a
+    VanillaDecoderExport always does), d up to 128; its workspace is capped the same way.  `jacobian`: the result also carries
+    the columns J f32 [n, d, nout] (the spatial decoder's native route has none to give: ValueError for a DecoderExport and for a
+    module that would take that route)."""
     grid = None
     if z.ndim == 4:
         N, d, H, W = z.shape
@@ -330,7 +389,15 @@ def pullback_metric_device(decoder_or_export, z: torch.Tensor, *, spectrum: bool
     if z.ndim != 2:
         raise ValueError(f"z must be [n, d] or [N, d, H, W], got {tuple(z.shape)}")
     out_dev = z.device
-    if isinstance(decoder_or_export, DecoderExport):
+    if isinstance(decoder_or_export, VanillaDecoderExport):
+        if z.shape[1] != decoder_or_export.latent_dim:
+            raise ValueError(f"z has {z.shape[1]} latent dimensions, the decoder {decoder_or_export.latent_dim}")
+        fields = _native_vanilla_metric(decoder_or_export, z.detach().to(torch.float32).contiguous(), spectrum, jacobian,
+                                        max_workspace_bytes)
+        route = "native"
+    elif isinstance(decoder_or_export, DecoderExport):
+        if jacobian:
+            raise ValueError("jacobian=True: geo_decoder_metric_tensor does not return its columns")
         if decoder_or_export.desc.norm == 1 and decoder_or_export.desc.bn_train:
             raise ValueError("pull-back metric tensor of a train-mode BatchNorm decoder: a sample's Jacobian depends on its "
                              "batch; put the decoder in eval()")
@@ -341,27 +408,37 @@ def pullback_metric_device(decoder_or_export, z: torch.Tensor, *, spectrum: bool
         if _has_train_batchnorm(decoder):
             raise ValueError("pull-back metric tensor of a train-mode BatchNorm decoder: a sample's Jacobian depends on its "
                              "batch; put the decoder in eval()")
-        if native_metric_covers(decoder) and out_dev.type == "cuda":
+        if native_vanilla_metric_covers(decoder) and out_dev.type == "cuda" and grid is None:
+            export = VanillaDecoderExport(decoder, out_dev)
+            if z.shape[1] != export.latent_dim:
+                raise ValueError(f"z has {z.shape[1]} latent dimensions, the decoder {export.latent_dim}")
+            fields = _native_vanilla_metric(export, z.detach().to(torch.float32).contiguous(), spectrum, jacobian,
+                                            max_workspace_bytes)
+            route = "native"
+        elif native_metric_covers(decoder) and out_dev.type == "cuda":
+            if jacobian:
+                raise ValueError("jacobian=True: geo_decoder_metric_tensor does not return its columns")
             if z.shape[1] != decoder.conv_in.in_channels:
                 raise ValueError(f"z has {z.shape[1]} latent dimensions, the decoder {decoder.conv_in.in_channels}")
             fields = _native_metric(DecoderExport(decoder, out_dev), z.detach().to(torch.float32).contiguous(), spectrum,
                                     max_workspace_bytes)
             route = "native"
         else:
-            fields = tuple(None if t is None else t.to(out_dev) for t in _generic_metric(decoder, z, spectrum))
+            fields = tuple(None if t is None else t.to(out_dev) for t in _generic_metric(decoder, z, spectrum, jacobian))
             route = "autograd"
     if grid is not None:
         fields = tuple(None if t is None else t.reshape(*grid, *t.shape[1:]) for t in fields)
-    return PullbackMetric(*fields, route=route)
+    return PullbackMetric(*fields[:4], route=route, J=fields[4])
 
 
-def pullback_metric(decoder, z) -> PullbackMetric:
+def pullback_metric(decoder, z, *, jacobian: bool = False) -> PullbackMetric:
     """pullback_metric_device on host arrays: z a numpy array ([n, d] or [N, d, H, W]), the fields numpy arrays.  A covered decoder
     runs natively (on its own GPU, or on this process's when it lives on the CPU and there is one); any other on its own device."""
     dec_dev = next(decoder.parameters()).device
     dev = dec_dev
-    if native_metric_covers(decoder) and dec_dev.type != "cuda" and torch.cuda.is_available():
+    covered = native_metric_covers(decoder) or (native_vanilla_metric_covers(decoder) and np.ndim(z) == 2)
+    if covered and dec_dev.type != "cuda" and torch.cuda.is_available():
         dev = device()
-    res = pullback_metric_device(decoder, torch.as_tensor(z, dtype=torch.float32).to(dev))
+    res = pullback_metric_device(decoder, torch.as_tensor(z, dtype=torch.float32).to(dev), jacobian=jacobian)
     return PullbackMetric(*(None if t is None else t.cpu().numpy() for t in (res.G, res.eig, res.logvol, res.rank)),
-                          route=res.route)
+                          route=res.route, J=None if res.J is None else res.J.cpu().numpy())

@@ -66,12 +66,49 @@ def _quantiles(x: np.ndarray):
     return {f"{q:g}": float(np.quantile(x, q)) for q in QUANTILES} if x.size else None
 
 
-def main(args):
-    from ..geo.riemannian_metric import pullback_metric_device
-    from ..spatial_decoder import load_decoder_from_checkpoint
+def summarise(logvol, eig_min, eig_max, rank, d: int, n_total: int, route: str, codes=None) -> dict:
+    """metric_map.json of a map (shared with vanilla_metric_map): counts, the quantiles of logvol over the full-rank latents and
+    of eig_max / eig_min, the `note` for an ill-conditioned map, and per-code statistics where `codes` (one per latent of the
+    map) is given."""
+    full = rank == d
+    finite = np.isfinite(logvol)
+    cond = eig_max[eig_min > 0] / eig_min[eig_min > 0]
+    summary = {"n": int(len(logvol)), "n_total": int(n_total), "latent_dim": int(d), "n_rank_deficient": int((~full).sum()),
+               "route": route, "decoder_mode": "eval",
+               "logvol_quantiles_full_rank": _quantiles(logvol[full & finite]),
+               "eig_ratio_quantiles": _quantiles(cond)}
+    if cond.size and cond.max() > ILL_CONDITIONED:
+        summary["note"] = NOTE.format(cond=float(cond.max()))
+        print("Note: " + summary["note"])
+    if codes is not None:
+        summary["per_code"] = per_code_stats(codes, logvol)
+    return summary
+
+
+def plot_map(logvol, eig_min, eig_max, path):
+    """metric_map.png (shared with vanilla_metric_map): the histogram of logvol and logvol against the anisotropy."""
     import matplotlib
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt
+    finite = np.isfinite(logvol)
+    fig, (ax1, ax2) = plt.subplots(1, 2, figsize=(10, 5))
+    ax1.hist(logvol[finite], bins=50)
+    ax1.set_xlabel("logvol = 0.5 log det G")
+    ax1.set_ylabel("Count")
+    ax1.set_title("Volume element of the pull-back metric (eval-mode decoder)")
+    both = finite & (eig_min > 0)
+    ax2.scatter(np.log10(eig_max[both] / eig_min[both]), logvol[both], s=6, alpha=0.6)
+    ax2.set_xlabel("log10(eig_max / eig_min)")
+    ax2.set_ylabel("logvol")
+    ax2.set_title("Volume element against anisotropy")
+    plt.tight_layout()
+    plt.savefig(path, dpi=150)
+    plt.close(fig)
+
+
+def main(args):
+    from ..geo.riemannian_metric import pullback_metric_device
+    from ..spatial_decoder import load_decoder_from_checkpoint
 
     out_dir = Path(args.out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -99,37 +136,16 @@ def main(args):
         arrays["G"] = G
     np.savez(out_dir / "metric_map.npz", **arrays)
 
-    full = rank == d
-    finite = np.isfinite(logvol)
-    cond = eig_max[eig_min > 0] / eig_min[eig_min > 0]
-    summary = {"n": int(len(index)), "n_total": int(n_all), "latent_dim": int(d), "n_rank_deficient": int((~full).sum()),
-               "route": res.route, "decoder_mode": "eval",
-               "logvol_quantiles_full_rank": _quantiles(logvol[full & finite]),
-               "eig_ratio_quantiles": _quantiles(cond)}
-    if cond.size and cond.max() > ILL_CONDITIONED:
-        summary["note"] = NOTE.format(cond=float(cond.max()))
-        print("Note: " + summary["note"])
+    codes = None
     if args.codes:
         codes = np.load(args.codes).reshape(-1)
         if codes.shape[0] != n_all:
             raise ValueError(f"--codes has {codes.shape[0]} entries, the latents {n_all}")
-        summary["per_code"] = per_code_stats(codes[index], logvol)
+        codes = codes[index]
+    summary = summarise(logvol, eig_min, eig_max, rank, d, n_all, res.route, codes)
     with open(out_dir / "metric_map.json", "w") as f:
         json.dump(summary, f, indent=1)
-
-    fig, (ax1, ax2) = plt.subplots(1, 2, figsize=(10, 5))
-    ax1.hist(logvol[finite], bins=50)
-    ax1.set_xlabel("logvol = 0.5 log det G")
-    ax1.set_ylabel("Count")
-    ax1.set_title("Volume element of the pull-back metric (eval-mode decoder)")
-    both = finite & (eig_min > 0)
-    ax2.scatter(np.log10(eig_max[both] / eig_min[both]), logvol[both], s=6, alpha=0.6)
-    ax2.set_xlabel("log10(eig_max / eig_min)")
-    ax2.set_ylabel("logvol")
-    ax2.set_title("Volume element against anisotropy")
-    plt.tight_layout()
-    plt.savefig(out_dir / "metric_map.png", dpi=150)
-    plt.close(fig)
+    plot_map(logvol, eig_min, eig_max, out_dir / "metric_map.png")
     print(f"route {res.route}: {summary['n_rank_deficient']} of {summary['n']} latents rank deficient; saved to {out_dir}")
     return summary
 
